@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- flat-scan top-10, d=768, fp16 corpus, batch 1024 (BASELINE.json configs[1] on one GPU, configs[3] on N > 1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given and prints
+the result line.  Everything else -- the parity self-check, the N > 1 merge check and step split, the host-API leg, the
+secondary measurements (`extras`) and the CPU baseline -- runs only under `--full` (where --no-extras / --no-cpu-baseline
+still drop parts of it).  `--sweep` is its own opt-in and runs whenever it is given.
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step returned (rank 0; the merged lists when N > 1) is
+written as DIR/ids.npy (float64) and DIR/scores.npy (float32), shape [batch, k].  Inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process NEVER touches the GPU; it starts N ranks of
 itself (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set) and waits for them.
@@ -62,7 +71,13 @@ def parse():
     ap.add_argument("--no-verify-merge", action="store_true", help="N>1: skip the merged == unsharded check of the first step")
     ap.add_argument("--sweep", default="", help="comma list of extra batch sizes to time (N=1 only), e.g. 1,16,64,256")
     ap.add_argument("--dry-launch", action="store_true", help="start the ranks, rendezvous over gloo on the CPU, exchange one tensor, exit (no GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run the checks and secondary measurements (parity, merge check, step split, "
+                                                        "host API, extras, CPU baseline); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's ids / scores as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ launcher (no GPU touched)
@@ -394,6 +409,24 @@ def config0_plumbing(nvdb_amd, args):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ids, scores):
+    """ids.npy (float64: every row id below 2**53 is exact) and scores.npy (float32), one row per query.  A batch whose two
+    arrays would pass DUMP_LIMIT_BYTES is sampled: a fixed, seeded choice of query rows, listed in query_rows.npy."""
+    ids = ids.cpu().numpy().astype(np.float64)
+    scores = scores.cpu().numpy().astype(np.float32)
+    rows_max = max(1, DUMP_LIMIT_BYTES // (ids.shape[1] * 12 + 8))
+    os.makedirs(out_dir, exist_ok=True)
+    if ids.shape[0] > rows_max:
+        pick = np.sort(np.random.RandomState(SEED).choice(ids.shape[0], rows_max, replace=False))
+        ids, scores = ids[pick], scores[pick]
+        np.save(os.path.join(out_dir, "query_rows.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, "ids.npy"), ids)
+    np.save(os.path.join(out_dir, "scores.npy"), scores)
+
+
 # ------------------------------------------------------------------------------------------ the benchmark
 def main():
     args = parse()
@@ -503,8 +536,8 @@ def main():
         step(i)
     torch.cuda.synchronize()
     ctx.search_check()                                         # raises on overflow / bound violation in any warm-up step
-    parity = "skipped"
-    if rank == 0:
+    parity = "skipped" if args.full else "not checked (--full checks it)"
+    if rank == 0 and args.full:
         # Self-check without the oracle (the oracle only serves the cpu_baseline leg here; tests/ pin the exact
         # fp32 kernel against it, and compare ALL queries at 10M and 100M rows): the MFMA filter path must reproduce
         # the exact fp32-order kernel bit for bit.  Local search only -- no collective in this branch.
@@ -528,7 +561,7 @@ def main():
     # ---- N > 1: the merged lists of one step against the unsharded corpus on rank 0 -------------------------
     merge_check = None
     one_gpu_ms = None
-    if use_dist and not args.no_verify_merge:
+    if use_dist and args.full and not args.no_verify_merge:
         step(0)
         torch.cuda.synchronize()
         if rank == 0:
@@ -568,11 +601,14 @@ def main():
 
     qps = args.steps * B / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (timed_steps ended in a device synchronise)
+        dump_outputs(args.dump_outputs, m_ids if use_dist else out_ids, m_sc if use_dist else out_sc)
 
     # ---- N > 1: where a step's time goes (events on the bench stream around search / all-gather / merge; a few extra, untimed
     # steps after the timed region; per phase the MAX over ranks of the per-rank mean) ---------------------------------------
     step_split = None
-    if use_dist and not share_gpu:
+    if use_dist and not share_gpu and args.full:
         nsp = max(2, min(args.steps, 8))
         evs = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(nsp)]
         barrier()
@@ -651,7 +687,7 @@ def main():
         out["roofline"] = None
 
     # ---- the same step through the host API of the C ABI (PCIe-inclusive; never `value`) --------------------------
-    if world == 1:
+    if world == 1 and args.full:
         reps = max(2, min(args.steps, 8))
         ctx.search_batch(qhost[:B], K)
         t0 = time.perf_counter()
@@ -662,7 +698,7 @@ def main():
                            "qps": B / el, "ms_per_step": el * 1e3, "overhead_vs_device_resident_ms": el * 1e3 - ms_per_step}
 
     # ---- N > 1: the 10M-row corpus of configs[1] sharded the same way (small shards: fixed costs weigh more) -----------
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         lo2, hi2 = shard_range(ROWS_1GPU, rank, world)
         ctx.generate_corpus(SEED, hi2 - lo2, D, dt, row_base=lo2)
         for i in range(2):
@@ -690,7 +726,7 @@ def main():
         out["sweep"] = sweep
 
     # ---- secondary measurements (N=1 only; the headline `value` above is unaffected) ------------------------
-    if rank == 0 and world == 1 and not args.no_extras and args.dtype == "f16":
+    if rank == 0 and world == 1 and args.full and not args.no_extras and args.dtype == "f16":
         extras = {}
         try:
             def timed_passes(c, b, reps=6):
@@ -844,7 +880,7 @@ def main():
             extras["error"] = repr(e)
         out["extras"] = extras
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(ctx, args, nvdb_amd, N)
         except Exception as e:                                   # never let the baseline leg kill the bench line

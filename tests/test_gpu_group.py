@@ -205,7 +205,7 @@ def test_bench_rccl_branch_with_one_rank():
     env = dict(os.environ, NVDB_BENCH_FORCE_COLLECTIVE="1", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "2000000",
-                        "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                        "--full", "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["merge_check"] is True, line

@@ -6,7 +6,7 @@ TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --no-cpu-baseline --no-extras $*"
+B="$R/bench.py --full --no-cpu-baseline --no-extras $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_kt -- python3 $B --steps 4 --warmup 1 > $O/${TAG}_kt.log 2>&1
 python3 $R/tools_dev/summarize_prof.py $O/${TAG}_kt $O/${TAG}_kernel_trace_stats.txt > /dev/null
 echo "kernel trace done"
