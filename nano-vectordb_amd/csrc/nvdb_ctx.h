@@ -119,6 +119,7 @@ struct nvdb_hip_ctx {
   bool status_by_kernel = false;                   // last search_core: its final kernel wrote the status words to the caller's pinned block
   size_t q32_dirty = 0;                            // bytes of q32 (from its start) that may hold old queries: beyond them the buffer is zero
   DevBuf rq, rcand, rout_ids, rout_dist;           // refine
+  DevBuf rdbg;                                     // refine phase stamps: 3 x uint64 per sampled query (option refine_dbg_q)
   DevBuf xcdw;                                     // XCD balance: 8 speed weights + 16 accumulators (kernels_filter.h ScatterArgs::xcdw)
   int64_t opt_xcd_balance = 1;
   int64_t opt_i8_lo_bits = 7;                      // int8: bits of a quantised query's lo plane (ScatterArgs::lo_bits)
@@ -127,6 +128,7 @@ struct nvdb_hip_ctx {
   int64_t dbg_rows = 0;                            // developer build: rows the stamped launches of nvdb_hip_debug_clock_i8 cover (0: the corpus)
   DevBuf lk_scores, lk_sel, lk_hist, lk_state;     // any-k path (kernels_largek.h): score matrix of a query sub-batch, selected keys, radix state
   int64_t opt_refine_pinned = 0;                   // refine host call: stage queries / candidates / results through pinned host buffers (reference CUDA_PINNED)
+  int64_t opt_refine_dbg_q = 0;                    // refine host call with a timing struct: the first min(this, Q) queries run the stamped twin kernel (reference CUDA_DBG_TIMING / CUDA_DBG_Q); 0 = off
   void* rpinned = nullptr;                         // ... [queries | candidates | out ids | out dist]
   size_t rpinned_bytes = 0;
   int64_t opt_largek_budget_mb = 8192;             // HBM the any-k path may use for its score matrix

@@ -15,20 +15,32 @@ static nvdb_status refine_args(nvdb_hip_ctx* c, const void* q, const void* cand,
   return NVDB_OK;
 }
 
+static nvdb_status raise_lds_limit(nvdb_hip_ctx* c, const void* fn, size_t lds) {
+  if (!c->lds_attr_set.count(fn)) {
+    HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    c->lds_attr_set.insert(fn);
+  }
+  return NVDB_OK;
+}
+
+// dbg != nullptr: the stamped twin of the kernel chosen below (same arithmetic, same results; wave 0 of the first dbg_q
+// workgroups writes its phase cycles to dbg[3q ..]).
 static nvdb_status launch_refine(nvdb_hip_ctx* c, hipStream_t s, const float* dq, const uint32_t* dc, uint32_t Q, uint32_t R,
-                                 uint32_t K, uint32_t* doi, float* dod) {
+                                 uint32_t K, uint32_t* doi, float* dod, uint64_t* dbg = nullptr, uint32_t dbg_q = 0) {
   const bool al = aligned_rows(c->dtype, c->dim);
+  nvdb_status st;
   // v3 (whole rows per request, four lanes per row): fp16 rows of 512 / 1024 / 1536 bytes
   if (c->opt_refine_v2 >= 2 && c->dtype == NVDB_DTYPE_F16 && refine3_dim(c->dim)) {
 #define NVDB_REFINE3(D)                                                                                                        \
     {                                                                                                                          \
       constexpr size_t lds = static_cast<size_t>(REFINE3_WAVES) * refine3_slot_bytes<D>();                                      \
-      const void* fn = reinterpret_cast<const void*>(refine_l2_rows_kernel<D>);                                                 \
-      if (!c->lds_attr_set.count(fn)) {                                                                                        \
-        HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));                 \
-        c->lds_attr_set.insert(fn);                                                                                            \
+      if (dbg) {                                                                                                               \
+        if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(refine_dbg_rows_kernel<D>), lds))) return st;               \
+        refine_dbg_rows_kernel<D><<<Q, 64 * REFINE3_WAVES, lds, s>>>(c->rows, c->n, dq, dc, R, K, doi, dod, dbg, dbg_q);        \
+      } else {                                                                                                                 \
+        if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(refine_l2_rows_kernel<D>), lds))) return st;                \
+        refine_l2_rows_kernel<D><<<Q, 64 * REFINE3_WAVES, lds, s>>>(c->rows, c->n, dq, dc, R, K, doi, dod);                     \
       }                                                                                                                        \
-      refine_l2_rows_kernel<D><<<Q, 64 * REFINE3_WAVES, lds, s>>>(c->rows, c->n, dq, dc, R, K, doi, dod);                       \
     }
     if (c->dim == 768) NVDB_REFINE3(768) else if (c->dim == 512) NVDB_REFINE3(512) else if (c->dim == 384) NVDB_REFINE3(384) else NVDB_REFINE3(256)
 #undef NVDB_REFINE3
@@ -38,18 +50,29 @@ static nvdb_status launch_refine(nvdb_hip_ctx* c, hipStream_t s, const float* dq
   // v2 (coalesced gather through LDS): whole 16-byte steps only (f16: dim % 8 == 0, f32: dim % 4 == 0)
   if (al && c->opt_refine_v2 && static_cast<uint64_t>(c->dim) * bpe_of(c->dtype) >= 256) {
     constexpr size_t lds = 4 * 2 * 64 * 256;
-    const void* fn = c->dtype == NVDB_DTYPE_F16 ? reinterpret_cast<const void*>(refine_l2_lds_kernel<DT_F16>)
-                                                : reinterpret_cast<const void*>(refine_l2_lds_kernel<DT_F32>);
-    if (!c->lds_attr_set.count(fn)) {
-      HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      c->lds_attr_set.insert(fn);
+    const bool f16 = c->dtype == NVDB_DTYPE_F16;
+    const void* fn = dbg ? (f16 ? reinterpret_cast<const void*>(refine_dbg_lds_kernel<DT_F16>) : reinterpret_cast<const void*>(refine_dbg_lds_kernel<DT_F32>))
+                         : (f16 ? reinterpret_cast<const void*>(refine_l2_lds_kernel<DT_F16>) : reinterpret_cast<const void*>(refine_l2_lds_kernel<DT_F32>));
+    if ((st = raise_lds_limit(c, fn, lds))) return st;
+    if (dbg) {
+      if (f16) refine_dbg_lds_kernel<DT_F16><<<Q, 256, lds, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
+      else refine_dbg_lds_kernel<DT_F32><<<Q, 256, lds, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
+    } else {
+      if (f16) refine_l2_lds_kernel<DT_F16><<<Q, 256, lds, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
+      else refine_l2_lds_kernel<DT_F32><<<Q, 256, lds, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
     }
-    if (c->dtype == NVDB_DTYPE_F16) refine_l2_lds_kernel<DT_F16><<<Q, 256, lds, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
-    else refine_l2_lds_kernel<DT_F32><<<Q, 256, lds, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
     HIPCHK(c, hipGetLastError());
     return NVDB_OK;
   }
-  if (c->dtype == NVDB_DTYPE_F16) {
+  if (dbg) {
+    if (c->dtype == NVDB_DTYPE_F16) {
+      if (al) refine_dbg_kernel<DT_F16, true><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
+      else refine_dbg_kernel<DT_F16, false><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
+    } else {
+      if (al) refine_dbg_kernel<DT_F32, true><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
+      else refine_dbg_kernel<DT_F32, false><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
+    }
+  } else if (c->dtype == NVDB_DTYPE_F16) {
     if (al) refine_l2_kernel<DT_F16, true><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
     else refine_l2_kernel<DT_F16, false><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
   } else {
@@ -82,6 +105,13 @@ nvdb_status nvdb_hip_refine_l2_topk(nvdb_hip_ctx* c, const float* queries, const
   if ((st = ensure(c, c->rcand, cb))) return st;
   if ((st = ensure(c, c->rout_ids, ob))) return st;
   if ((st = ensure(c, c->rout_dist, ob))) return st;
+  // phase stamps (reference CUDA_DBG_TIMING / CUDA_DBG_Q, cuda_refine.cu:863-872): only with a timing struct to report them in
+  const uint32_t dbg_q = (timing && c->opt_refine_dbg_q > 0) ? static_cast<uint32_t>(std::min<int64_t>(c->opt_refine_dbg_q, Q)) : 0u;
+  const size_t dbgb = static_cast<size_t>(dbg_q) * 3 * sizeof(uint64_t);
+  if (dbg_q) {
+    if ((st = ensure(c, c->rdbg, dbgb))) return st;
+    HIPCHK(c, hipMemsetAsync(c->rdbg.p, 0, dbgb, s));
+  }
   hipEvent_t e0 = get_event(c, 56), e1 = get_event(c, 57), e2 = get_event(c, 58), e3 = get_event(c, 59);
   // optional pinned staging (reference: CUDA_PINNED, src/cuda_refine.cu:875, 902-914): inputs are packed into pinned host
   // buffers BEFORE the timed region, the asynchronous copies then run at the link's rate instead of through the runtime's
@@ -108,7 +138,8 @@ nvdb_status nvdb_hip_refine_l2_topk(nvdb_hip_ctx* c, const float* queries, const
   HIPCHK(c, hipMemcpyAsync(c->rcand.p, h_c, cb, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipEventRecord(e1, s));
   if ((st = launch_refine(c, s, static_cast<const float*>(c->rq.p), static_cast<const uint32_t*>(c->rcand.p), Q, R, K,
-                          static_cast<uint32_t*>(c->rout_ids.p), out_dist ? static_cast<float*>(c->rout_dist.p) : nullptr)))
+                          static_cast<uint32_t*>(c->rout_ids.p), out_dist ? static_cast<float*>(c->rout_dist.p) : nullptr,
+                          dbg_q ? static_cast<uint64_t*>(c->rdbg.p) : nullptr, dbg_q)))
     return st;
   HIPCHK(c, hipEventRecord(e2, s));
   HIPCHK(c, hipMemcpyAsync(h_oi, c->rout_ids.p, ob, hipMemcpyDeviceToHost, s));
@@ -128,6 +159,22 @@ nvdb_status nvdb_hip_refine_l2_topk(nvdb_hip_ctx* c, const float* queries, const
     timing->threads = rows_kernel ? 64 * REFINE3_WAVES : 256; timing->nwarps = rows_kernel ? REFINE3_WAVES : 4; timing->K = K; timing->R = R;
     timing->shmem_bytes = rows_kernel ? static_cast<size_t>(REFINE3_WAVES) * (c->dim == 768 ? refine3_slot_bytes<768>() : c->dim == 512 ? refine3_slot_bytes<512>() : c->dim == 384 ? refine3_slot_bytes<384>() : refine3_slot_bytes<256>())
                                       : (c->opt_refine_v2 ? 4 * 2 * 64 * 256 : 4 * 64 * 8 + 16);
+  }
+  if (dbg_q) {                                   // after the events: h2d / kernel / d2h keep their meaning (cuda_refine.cu:1116-1144)
+    std::vector<uint64_t> h(static_cast<size_t>(dbg_q) * 3);
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->rdbg.p, dbgb, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    double sum[3] = {0.0, 0.0, 0.0};
+    for (uint32_t i = 0; i < dbg_q; ++i)
+      for (int p = 0; p < 3; ++p) sum[p] += static_cast<double>(h[static_cast<size_t>(i) * 3 + p]);
+    timing->dbg_q = dbg_q;
+    timing->dbg_dist_cycles_avg = sum[0] / dbg_q;
+    timing->dbg_write_cycles_avg = sum[1] / dbg_q;
+    timing->dbg_merge_cycles_avg = sum[2] / dbg_q;
+    const double tot = timing->dbg_dist_cycles_avg + timing->dbg_write_cycles_avg + timing->dbg_merge_cycles_avg;
+    timing->dbg_dist_pct = tot > 0.0 ? timing->dbg_dist_cycles_avg / tot : 0.0;     // fractions, like the reference's *_pct
+    timing->dbg_write_pct = tot > 0.0 ? timing->dbg_write_cycles_avg / tot : 0.0;
+    timing->dbg_merge_pct = tot > 0.0 ? timing->dbg_merge_cycles_avg / tot : 0.0;
   }
   return NVDB_OK;
 }

@@ -9,6 +9,9 @@
 //   nvdb_cuda_refine_eval <base.vecbin> <query.vecbin> <k>
 //   env: REFINE_K (default 1024)   CAND_PATH (raw uint32[Q*REFINE_K]; default: synthetic, see below)
 //        CUDA_REFINE_WARMUP (1)    CUDA_RETURN_DIST (1)   CUDA_PINNED (0)   GIT_SHA
+//        CUDA_DBG_TIMING (0)  CUDA_DBG_Q (32)  CUDA_DBG_DIR (./results_dbg)  CUDA_SHMEM_OPTIN (0, file name only)
+// With CUDA_DBG_TIMING set, the measured call's phase split goes to a one-row TSV in CUDA_DBG_DIR with the columns and file
+// name of the reference's eval app (apps/nvdb_ivf_eval.cpp:47-126; nprobe = 0: no IVF stage here) and two lines before RESULT.
 // Synthetic candidates (FAISS absent): per query the exact top-min(64,REFINE_K) by dot (== L2 for
 // normalised data) found with the GPU flat scan, filled up to REFINE_K with distinct pseudo-random ids,
 // shuffled with a seeded generator; 1 % of the slots are set to 0xFFFFFFFF to exercise the skip path.
@@ -16,11 +19,13 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
 #include <fstream>
 #include <iomanip>
 #include <iostream>
 #include <queue>
 #include <random>
+#include <sstream>
 #include <string>
 #include <unordered_set>
 #include <vector>
@@ -32,6 +37,36 @@
 
 static int env_int(const char* k, int d) { const char* v = std::getenv(k); return v ? std::atoi(v) : d; }
 static std::string env_str(const char* k, const char* d) { const char* v = std::getenv(k); return v ? v : d; }
+
+// CUDA_DBG_TIMING: the single-row phase-split TSV (cycles with 3 decimals, fractions with 6), then its summary lines
+static void write_dbg_tsv(const nvdb::CudaRefineTiming& t, int k, uint64_t Q, uint32_t R, const std::string& kernel_mode) {
+  if (!env_int("CUDA_DBG_TIMING", 0) || t.dbg_q == 0) return;
+  const std::string dir = env_str("CUDA_DBG_DIR", "./results_dbg");
+  const int optin = env_int("CUDA_SHMEM_OPTIN", 0), pinned = env_int("CUDA_PINNED", 0), ret = env_int("CUDA_RETURN_DIST", 1);
+  const std::string git = env_str("GIT_SHA", "NA");
+  std::ostringstream name;
+  name << "dbg_K" << k << "_Q" << Q << "_R" << R << "_th" << t.threads << "_mode=" << kernel_mode << "_optin=" << optin
+       << "_pinned=" << pinned << "_ret=" << ret << "_git=" << git << ".tsv";
+  std::error_code ec;
+  std::filesystem::create_directories(dir, ec);
+  const std::string path = dir + "/" + name.str();
+  std::ofstream f(path, std::ios::trunc);
+  if (!f) { std::cerr << "[WARN] cannot write DBG TSV: " << path << "\n"; return; }
+  f << "k\tQ\tR\tnprobe\trefine_k\tkernel_mode\tcuda_threads\tcuda_nwarps\tcuda_shmem_bytes\tcuda_shmem_optin\t"
+       "cuda_pinned\tcuda_return_dist\tgit_rev\tdbg_q\tdbg_dist_cycles_avg\tdbg_write_cycles_avg\tdbg_merge_cycles_avg\t"
+       "dbg_dist_pct\tdbg_write_pct\tdbg_merge_pct\n";
+  f << k << '\t' << Q << '\t' << R << '\t' << 0 << '\t' << R << '\t' << kernel_mode << '\t' << t.threads << '\t' << t.nwarps << '\t'
+    << t.shmem_bytes << '\t' << optin << '\t' << pinned << '\t' << ret << '\t' << git << '\t' << t.dbg_q << '\t' << std::fixed
+    << std::setprecision(3) << t.dbg_dist_cycles_avg << '\t' << t.dbg_write_cycles_avg << '\t' << t.dbg_merge_cycles_avg << '\t'
+    << std::setprecision(6) << t.dbg_dist_pct << '\t' << t.dbg_write_pct << '\t' << t.dbg_merge_pct << '\n';
+  f.close();
+  std::ostringstream out;
+  out << std::fixed << std::setprecision(3) << "DBG_TSV=" << path << " dbg_q=" << t.dbg_q << " dist%=" << t.dbg_dist_pct * 100.0
+      << " write%=" << t.dbg_write_pct * 100.0 << " merge%=" << t.dbg_merge_pct * 100.0 << "\n";
+  out << std::setprecision(6) << "dbg_q=" << t.dbg_q << " dbg_merge_pct=" << t.dbg_merge_pct << " dbg_write_pct=" << t.dbg_write_pct
+      << " dbg_dist_pct=" << t.dbg_dist_pct << "\n";
+  std::cout << out.str();
+}
 
 int main(int argc, char** argv) {
   if (argc < 4) { std::cerr << "Usage: nvdb_cuda_refine_eval <base.vecbin> <query.vecbin> <k>\n"; return 1; }
@@ -120,6 +155,7 @@ int main(int argc, char** argv) {
   }
   std::cout << std::fixed << std::setprecision(6);
   std::cout << "refine_recall_gpu_vs_cpu=" << recall_sum / double(Q) << " identical_rows=" << exact_rows << "/" << Q << " cpu_refine_ms_total=" << cpu_ms << "\n";
+  write_dbg_tsv(t, k, Q, R, "wave64");          // t: the measured call's timing, not the warm-up's
   std::cout << "RESULT refine_k=" << refine_k << " Q=" << Q << " k=" << k << " cuda_refine=1 refine_enabled=1 refine_backend=cuda"
             << " refine_ms_total=" << t.total_ms << " refine_ms_per_q=" << t.total_ms / double(Q)
             << " kernel_mode=wave64 cuda_pinned=" << env_int("CUDA_PINNED", 0) << " cuda_return_dist=" << env_int("CUDA_RETURN_DIST", 1) << " git_rev=" << env_str("GIT_SHA", "NA")

@@ -41,6 +41,15 @@ void cuda_l2_topk_batch(const void* base_ptr, uint32_t base_dtype, uint64_t N, u
   }
   const char* pn = std::getenv("CUDA_PINNED");                                  // :875 pinned host staging of the call's buffers
   if (nvdb_hip_set_option(g.ctx, "refine_pinned", (pn && std::atoi(pn) != 0) ? 1 : 0) != NVDB_OK) die("set_option", 1);
+  // in-kernel phase split (:863-868): CUDA_DBG_TIMING != 0 samples the first CUDA_DBG_Q (default 32, at most Q) queries
+  const char* dt = std::getenv("CUDA_DBG_TIMING");
+  uint32_t dbg_q = 0;
+  if (dt && std::atoi(dt) != 0) {
+    const char* dq = std::getenv("CUDA_DBG_Q");
+    dbg_q = dq ? static_cast<uint32_t>(std::atoi(dq)) : 32u;
+    if (dbg_q > Q) dbg_q = Q;
+  }
+  if (nvdb_hip_set_option(g.ctx, "refine_dbg_q", dbg_q) != NVDB_OK) die("set_option", 1);
   const char* rd = std::getenv("CUDA_RETURN_DIST");
   const bool want_dist = !(rd && std::atoi(rd) == 0);
   out_ids.assign(static_cast<size_t>(Q) * K, 0xFFFFFFFFu);
@@ -52,6 +61,9 @@ void cuda_l2_topk_batch(const void* base_ptr, uint32_t base_dtype, uint64_t N, u
     *timing = {};
     timing->h2d_ms = t.h2d_ms; timing->kernel_ms = t.kernel_ms; timing->d2h_ms = t.d2h_ms; timing->total_ms = t.total_ms;
     timing->threads = t.threads; timing->nwarps = t.nwarps; timing->K = t.K; timing->R = t.R; timing->shmem_bytes = t.shmem_bytes;
+    timing->dbg_q = t.dbg_q;
+    timing->dbg_dist_cycles_avg = t.dbg_dist_cycles_avg; timing->dbg_write_cycles_avg = t.dbg_write_cycles_avg; timing->dbg_merge_cycles_avg = t.dbg_merge_cycles_avg;
+    timing->dbg_dist_pct = t.dbg_dist_pct; timing->dbg_write_pct = t.dbg_write_pct; timing->dbg_merge_pct = t.dbg_merge_pct;
   }
 }
 
