@@ -68,7 +68,7 @@ typedef struct nvdb_hip_timing {
 
 /* What the last flat search did (for tests, bench.py and the roofline arithmetic). */
 typedef struct nvdb_hip_scan_stats {
-  uint32_t path;               /* 1 = exact fp32 scan, 2 = MFMA filter + exact rescore (k <= 1024), 3 = any-k (k > 64 off the filter path) */
+  uint32_t path;               /* 1 = exact fp32 scan, 2 = MFMA filter + exact rescore (k <= 1024), 3 = any-k (k > 64 off the filter path), 4 = partitioned probe search */
   uint32_t chunks;             /* corpus chunks (kernel launches of the dominant kernel)          */
   uint64_t rows_scanned;       /* rows x query-tiles streamed by the dominant kernel              */
   uint64_t candidates;         /* (query,row) pairs that reached the exact rescore                */
@@ -214,6 +214,43 @@ nvdb_status nvdb_hip_group_set_option(nvdb_hip_group* group, const char* key, in
 nvdb_status nvdb_hip_group_search_batch(nvdb_hip_group* group, const float* queries, uint32_t nq, uint32_t k,
                                         uint64_t* out_ids, float* out_scores, uint32_t* out_k_eff,
                                         nvdb_hip_group_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * partitioned probe search: exact top-k over a per-query CHOICE of contiguous row partitions -- the inverted-list probe of
+ * the reference's IVF evaluation (apps/nvdb_ivf_eval.cpp, done there through FAISS) over a list-ordered corpus, and the
+ * tenant / namespace filter of a multi-tenant corpus.  Queries that probe the same partition share one read of it.
+ * ------------------------------------------------------------------------------------------- */
+
+/* partition p = local rows [offsets[p], offsets[p+1]); offsets[0] == 0, non-decreasing, offsets[nparts] == n (nparts >= 1).
+ * Empty partitions are legal.  The table is copied.  Any upload / adopt / generate of a corpus drops it (and the centroids);
+ * a new table drops the centroids of the old one. */
+nvdb_status nvdb_hip_set_partitions(nvdb_hip_ctx* ctx, const uint64_t* offsets, uint32_t nparts);
+
+/* Optional coarse quantiser: one f32 centroid per partition, [nparts][dim] (host memory, copied); requires partitions. */
+nvdb_status nvdb_hip_set_centroids(nvdb_hip_ctx* ctx, const float* centroids);
+
+/* probe[nq][nprobe] (host): partition numbers; 0xFFFFFFFF = empty slot; a partition named twice by one query counts once;
+ * any other entry >= nparts -> NVDB_ERR_INVALID before anything is launched.
+ * Result per query: exact top-k by dot product over the union of its probed partitions, the same score bits and the same
+ * (score desc, global id asc) order as nvdb_hip_search_batch.  out_ids[nq][k], out_scores[nq][k] as there.
+ * out_counts[q] (optional) = min(k, rows in the union); slots beyond it hold id UINT64_MAX / -inf.
+ * k == 0 or nq == 0 -> NVDB_OK, nothing written.  k > 64 -> NVDB_ERR_UNSUPPORTED: the lists are wavefront-resident (entry j
+ * in lane j).  nprobe == 0 -> every count 0, outputs all padding.  No partition table -> NVDB_ERR_INVALID.
+ * Non-finite query or corpus values: no fault, no hang, order unspecified.
+ * timing (optional): h2d / kernel / d2h / total as on the flat path.  nvdb_hip_get_stats afterwards: path = 4, chunks = scan
+ * launches, rows_scanned = rows read (summed over the work items), candidates = candidate slots. */
+nvdb_status nvdb_hip_search_partitions(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t k,
+                                       const uint32_t* probe, uint32_t nprobe,
+                                       uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                       nvdb_hip_timing* timing);
+
+/* IVF-Flat convenience: probe = the nprobe centroids with the largest dot product (reference fp32 order, ties by partition
+ * number; ranked by the flat search over the centroids), then as above.  nprobe > nparts clamps to nparts.  out_probe
+ * (optional, [nq][nprobe]) returns the chosen partitions, best first (slots beyond the clamp: 0xFFFFFFFF).
+ * Without centroids -> NVDB_ERR_INVALID. */
+nvdb_status nvdb_hip_search_ivf(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+                                uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                uint32_t* out_probe, nvdb_hip_timing* timing);
 
 /* Tunables (defaults are what bench.py measures; the table with meanings is in INTEGRATION.md section 4b):
  * "path" (0 auto, 1 exact, 2 mfma-filter), "chunk0_rows", "chunk_growth", "cand_cap", "min_filter_batch", "mfma_boot", "waves8",

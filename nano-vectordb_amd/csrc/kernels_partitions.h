@@ -1,0 +1,166 @@
+// kernels_partitions.h -- gfx950 kernels of the partitioned probe search (nvdb_hip_search_partitions / nvdb_hip_search_ivf).
+//
+//  * scan_parts_kernel   : one workgroup per work item = (a segment of contiguous rows, a group of <= PART_WAVES*QW queries that all
+//                          probe the partition the segment belongs to).  The queries are gathered BY INDEX into LDS once; the
+//                          segment is walked in tiles of 64 rows; one lane = one row (the reference order of exact_scores<> is a
+//                          strict chain over the row); the waves score the SAME 64 rows, each against its own QW queries,
+//                          so a wave owns its queries' top-k lists outright and nothing is merged across waves.
+//                          STAGED: the tile's rows are contiguous bytes -- the workgroup fetches them with coalesced 16-byte
+//                          global loads (the next tile's loads are in flight, in registers, while this tile is scored), stores
+//                          them into LDS at a row pitch that is an ODD number of 16-byte slots, and every lane reads its row
+//                          back with conflict-free ds_read_b128.  Otherwise (rows that are no multiple of 16 bytes, or too long
+//                          for the LDS) the lanes read their rows from global memory directly.
+//                          Each (item, query) owns a slot of min(k, segment rows) Cand entries that the host placed: no atomics,
+//                          no counters, no overflow path.
+//  * select_parts_kernel : one wave per query reduces the query's slots to the k best by (score desc, row asc), adds the global
+//                          row base and pads.
+//
+// Scores: exact_scores<> of kernels_exact.h, i.e. the bits of nvdb_hip_search_batch.  Non-finite scores: no fault, no hang,
+// order unspecified.
+#pragma once
+#include "kernels_exact.h"
+
+namespace nvdbhip {
+
+constexpr uint32_t PART_TILE_ROWS = 64;        // rows per tile = lanes per wave
+constexpr uint32_t PART_WAVES = 8;             // waves per workgroup (two per SIMD: one hides the other's LDS latency)
+constexpr uint32_t PART_THREADS = 64 * PART_WAVES;
+constexpr uint32_t PART_STAGE_MAX_ROW_BYTES = 1536;
+constexpr uint32_t PART_MAX_CHUNKS = PART_TILE_ROWS * PART_STAGE_MAX_ROW_BYTES / 16u / PART_THREADS;   // 16-byte chunks of a tile one thread prefetches
+constexpr uint32_t PART_QW_MAX = 4;            // queries per wave -> groups of at most PART_WAVES * 4 queries
+constexpr uint32_t PART_SEG_ROWS = 2048;       // a partition is cut into segments of at most this many rows
+
+// one workgroup's work; qoff indexes qidx[], doff indexes dst[] (both: one entry per query of the group)
+struct PartItem { uint32_t row_lo, row_hi, qoff, doff, nqg, pad; };
+
+// LDS row pitch of a staged tile: the smallest odd multiple of 16 bytes >= row_bytes.  A ds_read_b128 is served in groups of 16
+// lanes whose lane numbers cover every residue mod 16; with an odd pitch (in 16-byte slots) lane L's slot is L * pitch mod 16,
+// a bijection of the residues: the 16 lanes of a group touch 16 different 16-byte slots of the 256-byte bank window.
+__host__ __device__ inline uint32_t part_pitch(uint32_t row_bytes) { return ((row_bytes >> 4) | 1u) << 4; }
+
+template <int DT, int QW, bool ALIGNED, bool STAGED>
+__global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
+    const void* __restrict__ rows, const float* __restrict__ scales, uint32_t dim, const PartItem* __restrict__ items,
+    const uint32_t* __restrict__ qidx, const uint32_t* __restrict__ dst, const float* __restrict__ q32, uint32_t k,
+    Cand* __restrict__ cand) {
+  constexpr uint32_t BPE = (DT == DT_F32) ? 4 : (DT == DT_F16 ? 2 : 1);
+  constexpr uint32_t QG = PART_WAVES * QW;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const PartItem it = items[blockIdx.x];
+  const uint32_t tid = threadIdx.x;
+  const int lane = tid & 63;
+  const uint32_t wave = tid >> 6;
+  const uint32_t qstride = (dim + 3u) & ~3u;
+  float* q_lds = reinterpret_cast<float*>(smem_raw);                     // [QG][qstride]
+  char* tile = smem_raw + static_cast<size_t>(QG) * qstride * 4;         // STAGED: [64][pitch]
+
+  // gather the group's queries by index; slots beyond the group repeat its first query (scored, never kept)
+  for (uint32_t g = 0; g < QG; ++g) {
+    const uint32_t qi = qidx[it.qoff + (g < it.nqg ? g : 0u)];
+    const float* src = q32 + static_cast<uint64_t>(qi) * dim;
+    for (uint32_t j = tid; j < qstride; j += PART_THREADS) q_lds[g * qstride + j] = (j < dim) ? src[j] : 0.f;
+  }
+
+  const uint32_t row_bytes = dim * BPE;
+  const uint32_t pitch = part_pitch(row_bytes), cpr = row_bytes >> 4;     // (STAGED) 16-byte chunks per row
+  // chunk c of a tile = tid + PART_THREADS * i: global address tile_base + 16 * c (the rows are contiguous), LDS row c / cpr, slot c % cpr
+  const uint32_t r_step = PART_THREADS / (cpr ? cpr : 1u), ch_step = PART_THREADS % (cpr ? cpr : 1u);
+  uint4 pre[PART_MAX_CHUNKS];
+  // (macros, not lambdas: behind a closure the array stayed in scratch memory)
+  // issue the loads of the tile that starts at row T
+#define NVDB_PART_FETCH(T)                                                                                                     \
+  {                                                                                                                            \
+    const uint32_t nrows_ = (it.row_hi - (T) < PART_TILE_ROWS) ? it.row_hi - (T) : PART_TILE_ROWS;                             \
+    const uint32_t nch_ = nrows_ * cpr;                                                                                        \
+    const uint4* src_ = reinterpret_cast<const uint4*>(static_cast<const char*>(rows) + static_cast<uint64_t>(T) * row_bytes); \
+    _Pragma("unroll") for (uint32_t i_ = 0; i_ < PART_MAX_CHUNKS; ++i_) {                                                      \
+      const uint32_t c_ = tid + PART_THREADS * i_;                                                                                     \
+      pre[i_] = (c_ < nch_) ? src_[c_] : uint4{0u, 0u, 0u, 0u};                                                                \
+    }                                                                                                                          \
+  }
+  // ... and put them into the LDS tile
+#define NVDB_PART_STASH(T)                                                                                                     \
+  {                                                                                                                            \
+    const uint32_t nrows_ = (it.row_hi - (T) < PART_TILE_ROWS) ? it.row_hi - (T) : PART_TILE_ROWS;                             \
+    const uint32_t nch_ = nrows_ * cpr;                                                                                        \
+    uint32_t r_ = tid / cpr, ch_ = tid % cpr;                                                                                  \
+    _Pragma("unroll") for (uint32_t i_ = 0; i_ < PART_MAX_CHUNKS; ++i_) {                                                      \
+      const uint32_t c_ = tid + PART_THREADS * i_;                                                                                     \
+      if (c_ < nch_) *reinterpret_cast<uint4*>(tile + r_ * pitch + ch_ * 16u) = pre[i_];                                       \
+      r_ += r_step; ch_ += ch_step;                                                                                            \
+      if (ch_ >= cpr) { ch_ -= cpr; ++r_; }                                                                                    \
+    }                                                                                                                          \
+  }
+  if constexpr (STAGED) { NVDB_PART_FETCH(it.row_lo) NVDB_PART_STASH(it.row_lo) }
+  __syncthreads();
+
+  const float* qptr = q_lds + wave * QW * qstride;
+  const bool wave_live = wave * QW < it.nqg;                               // this wave owns at least one query of the group
+  WaveTopK tk[QW];
+#pragma unroll
+  for (int g = 0; g < QW; ++g) wtk_init(tk[g]);
+
+  for (uint32_t t_lo = it.row_lo; t_lo < it.row_hi; t_lo += PART_TILE_ROWS) {
+    const bool more = t_lo + PART_TILE_ROWS < it.row_hi;
+    if constexpr (STAGED) { if (more) NVDB_PART_FETCH(t_lo + PART_TILE_ROWS) }
+    if (wave_live) {
+      const uint32_t row = t_lo + lane;
+      const bool valid = row < it.row_hi;
+      const uint32_t rrow = valid ? row : (it.row_hi - 1);
+      const float scale = (DT == DT_I8) ? scales[rrow] : 1.f;
+      float sc[QW];
+      if constexpr (STAGED) exact_scores<DT, QW, ALIGNED>(tile + static_cast<uint32_t>(lane) * pitch, qptr, qstride, dim, scale, sc);
+      else exact_scores<DT, QW, ALIGNED>(row_ptr<DT>(rows, rrow, dim), qptr, qstride, dim, scale, sc);
+#pragma unroll
+      for (int g = 0; g < QW; ++g) {
+        const bool pass = valid && wave * QW + g < it.nqg && wtk_accepts(tk[g], k, sc[g], row);
+        wtk_offer(tk[g], k, pass, sc[g], row, lane);
+      }
+    }
+    if constexpr (STAGED) {
+      if (more) {                                                          // (uniform over the workgroup)
+        __syncthreads();                                                   // every wave has read this tile
+        NVDB_PART_STASH(t_lo + PART_TILE_ROWS)
+        __syncthreads();
+      }
+    }
+  }
+
+  const uint32_t seg = it.row_hi - it.row_lo, slot = seg < k ? seg : k;    // entries of this (item, query): every row was offered
+#pragma unroll
+  for (int g = 0; g < QW; ++g) {
+    const uint32_t gi = wave * QW + g;
+    if (gi < it.nqg && static_cast<uint32_t>(lane) < slot) {
+      const uint32_t d = dst[it.doff + gi];
+      cand[static_cast<uint64_t>(d) + lane] = (static_cast<uint32_t>(lane) < tk[g].cnt) ? Cand{tk[g].s, tk[g].id} : Cand{NEG_INF, 0xFFFFFFFFu};
+    }
+  }
+}
+
+#undef NVDB_PART_FETCH
+#undef NVDB_PART_STASH
+
+// grid = nq, block = 64: the query's slots are cand[cbeg[q] .. cbeg[q+1])
+static __global__ __launch_bounds__(64) void select_parts_kernel(
+    const Cand* __restrict__ cand, const uint32_t* __restrict__ cbeg, uint32_t k, uint64_t row_base,
+    unsigned long long* __restrict__ out_ids, float* __restrict__ out_scores) {
+  const uint32_t q = blockIdx.x;
+  const int lane = threadIdx.x;
+  const uint32_t lo = cbeg[q], hi = cbeg[q + 1];
+  WaveTopK tk;
+  wtk_init(tk);
+  for (uint32_t base = lo; base < hi; base += 64) {
+    const uint32_t i = base + lane;
+    const bool have = i < hi;
+    const Cand c = have ? cand[i] : Cand{NEG_INF, 0xFFFFFFFFu};
+    const bool pass = have && c.row != 0xFFFFFFFFu && wtk_accepts(tk, k, c.score, c.row);
+    wtk_offer(tk, k, pass, c.score, c.row, lane);
+  }
+  if (static_cast<uint32_t>(lane) < k) {
+    const bool have = static_cast<uint32_t>(lane) < tk.cnt;
+    out_ids[static_cast<uint64_t>(q) * k + lane] = have ? (row_base + tk.id) : ~0ull;
+    out_scores[static_cast<uint64_t>(q) * k + lane] = have ? tk.s : NEG_INF;
+  }
+}
+
+}  // namespace nvdbhip

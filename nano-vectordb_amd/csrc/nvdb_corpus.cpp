@@ -18,6 +18,7 @@ void free_corpus(nvdb_hip_ctx* c) {
   c->rows = nullptr; c->scales = nullptr; c->owned = false; c->n = 0; c->dim = 0; c->fdim = 0; c->dtype = 0; c->max_norm = 0.f;
   c->cap_hint = 0;
   c->q8shadow = false; c->resid_max = 0.f; c->filter_max_norm = 0.f;
+  parts_drop(c);                                   // a partition table describes the rows it was set for
 }
 
 nvdb_status compute_max_norm(nvdb_hip_ctx* c) {
@@ -225,6 +226,7 @@ void nvdb_hip_destroy(nvdb_hip_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   free_corpus(c);
+  parts_destroy(c);
   if (c->hostblock.p) c->misc.p = nullptr;         // (misc lives inside the host API's result block)
   for (DevBuf* b : {&c->q32, &c->q16, &c->qscale, &c->qinv, &c->ebound, &c->slack, &c->thr, &c->cnt, &c->overflow, &c->cand,
                     &c->out_ids, &c->out_scores, &c->misc, &c->hostblock, &c->hitlog, &c->prog, &c->qdelta, &c->rq, &c->rcand, &c->rout_ids, &c->rout_dist, &c->rdbg, &c->lk_scores, &c->lk_sel, &c->lk_hist, &c->lk_state, &c->xcdw, &c->tickets})

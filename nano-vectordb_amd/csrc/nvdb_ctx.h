@@ -7,6 +7,7 @@
 //   nvdb_launch_i8.cpp     ... of the int8 kernels (kernels_filter.h, kernels_filter_i8s.h)
 //   nvdb_launch_exact.cpp  ... of the exact fp32-order kernels, select / rescore / merge, the any-k path (kernels_exact*.h, kernels_largek.h)
 //   nvdb_refine.cpp        exact-L2 refine (kernels_refine.h)
+//   nvdb_partitions.cpp    partitioned probe search: partition table, coarse quantiser, work list, launches (kernels_partitions.h)
 //   nvdb_debug.cpp         developer entry points (libnvdb_hip_dev.so only)
 //   nvdb_group.cpp         device group, layered on the public ABI (does not include this header)
 // There is NO CPU fallback anywhere in these files: without a working HIP device every entry point that computes returns
@@ -57,6 +58,8 @@ struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
 };
+
+struct PartState;                             // nvdb_partitions.cpp: partition table, centroids and workspace of the probe search
 
 }  // namespace nvdbhip
 
@@ -153,6 +156,7 @@ struct nvdb_hip_ctx {
   int64_t opt_refine_v2 = 2;                       // refine kernel: 0 lane per row, 1 column chunks through LDS, 2 whole rows through LDS (fp16 d = 256/384/512/768; else 1)
   int64_t opt_mfma16 = 1;                          // 1: use the 16x16x32 MFMA build for 256-query tiles
   std::set<const void*> lds_attr_set;              // kernels whose dynamic-LDS limit was raised on this device
+  nvdbhip::PartState* parts = nullptr;             // partitioned probe search (created by nvdb_hip_set_partitions)
 };
 
 #define HIPCHK(ctx, call)                                                                        \
@@ -244,6 +248,9 @@ nvdb_status launch_filter_f16(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, u
 nvdb_status launch_filter_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint32_t row_hi, uint32_t nq, uint32_t QT, uint32_t cap);
 nvdb_status launch_boot_f16(nvdb_hip_ctx* c, hipStream_t s, uint32_t n0, uint32_t nq, uint32_t QT, uint32_t cap, uint32_t nb);
 nvdb_status launch_boot_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t n0, uint32_t nq, uint32_t QT, uint32_t cap);
+// nvdb_partitions.cpp
+void parts_drop(nvdb_hip_ctx* c);        // the corpus changes: forget the partition table and the centroids (the workspace stays)
+void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace
 // nvdb_search.cpp
 nvdb_status next_prog_region(nvdb_hip_ctx* c, hipStream_t s, uint32_t nwg, uint32_t** out);
 ScatterArgs scatter_args(nvdb_hip_ctx* c, uint32_t cap, uint32_t trows = 0);

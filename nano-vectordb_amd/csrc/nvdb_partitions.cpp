@@ -1,0 +1,370 @@
+// nvdb_partitions.cpp -- partitioned probe search: the partition table and the optional coarse quantiser of a context, the
+// host-side work list, the launches of kernels_partitions.h, and the entry points nvdb_hip_set_partitions / set_centroids /
+// search_partitions / search_ivf (include/nvdb_hip.h).
+//
+// Work list (built per call from the probe table, all on the host):
+//   1. every query's probes are de-duplicated; a counting sort by partition gives, per probed partition, the ascending list of
+//      the queries that probe it (qidx);
+//   2. that list is cut into groups of at most PART_WAVES * QW queries, the partition into balanced segments of at most PART_SEG_ROWS
+//      rows; one work item = (segment, group): a partition probed by 8 queries is read once per segment, not 8 times;
+//   3. every (item, query) gets a slot of min(k, segment rows) candidates inside the query's block of the candidate buffer
+//      (dst); the blocks are laid out by a prefix sum (cbeg), so the capacity is exact and nothing can overflow.
+// Items are sorted by group size into classes (<= 8, <= 16, <= 32 queries) that run the QW = 1, 2, 4 builds of the kernel (the
+// widest one the LDS has room for): a remainder group of three queries does not pay for sixteen.
+#include "nvdb_ctx.h"
+#include "kernels_partitions.h"
+
+namespace nvdbhip {
+
+struct PartState {
+  std::vector<uint64_t> offsets;                   // nparts + 1; empty: no table
+  nvdb_hip_ctx* coarse = nullptr;                  // child context that holds the centroids as an f32 corpus (same device)
+  bool have_centroids = false;
+  // grow-only workspace
+  DevBuf meta, cand, q, out_ids, out_scores;
+  void* pin = nullptr;                             // pinned staging of the work list
+  size_t pin_bytes = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  // host scratch, reused across calls
+  std::vector<uint32_t> uniq, ucount, pcount, pstart, cursor, qidx, dst, cbeg, psum, probe_tmp;
+  std::vector<uint64_t> coarse_ids;
+  std::vector<float> coarse_scores;
+  std::vector<PartItem> items[3];
+};
+
+void parts_drop(nvdb_hip_ctx* c) {
+  PartState* ps = c->parts;
+  if (!ps) return;
+  ps->offsets.clear();
+  ps->have_centroids = false;
+  if (ps->coarse) { nvdb_hip_destroy(ps->coarse); ps->coarse = nullptr; }
+}
+
+void parts_destroy(nvdb_hip_ctx* c) {
+  PartState* ps = c->parts;
+  if (!ps) return;
+  parts_drop(c);
+  for (DevBuf* b : {&ps->meta, &ps->cand, &ps->q, &ps->out_ids, &ps->out_scores}) if (b->p) (void)hipFree(b->p);
+  if (ps->pin) (void)hipHostFree(ps->pin);
+  for (hipEvent_t e : ps->ev) if (e) (void)hipEventDestroy(e);
+  delete ps;
+  c->parts = nullptr;
+}
+
+namespace {
+
+constexpr size_t PART_LDS_LIMIT = 160 * 1024;
+
+size_t parts_lds(uint32_t dim, uint32_t row_bytes, uint32_t qw, bool staged) {
+  const size_t qstride = (dim + 3u) & ~3u;
+  return PART_WAVES * qw * qstride * 4 + (staged ? static_cast<size_t>(PART_TILE_ROWS) * part_pitch(row_bytes) : 0);
+}
+
+nvdb_status raise_lds(nvdb_hip_ctx* c, const void* fn, size_t lds) {
+  if (lds > 64 * 1024 && !c->lds_attr_set.count(fn)) {
+    HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(PART_LDS_LIMIT)));
+    c->lds_attr_set.insert(fn);
+  }
+  return NVDB_OK;
+}
+
+template <int DT, int QW, bool AL, bool ST>
+nvdb_status launch_one(nvdb_hip_ctx* c, hipStream_t s, const PartItem* items, uint32_t nitems, const uint32_t* qidx, const uint32_t* dst,
+                       const float* q32, uint32_t k, Cand* cand) {
+  const size_t lds = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), QW, ST);
+  nvdb_status st = raise_lds(c, reinterpret_cast<const void*>(scan_parts_kernel<DT, QW, AL, ST>), lds);
+  if (st) return st;
+  scan_parts_kernel<DT, QW, AL, ST><<<nitems, PART_THREADS, lds, s>>>(c->rows, c->scales, c->dim, items, qidx, dst, q32, k, cand);
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+template <int DT, int QW>
+nvdb_status launch_qw(nvdb_hip_ctx* c, hipStream_t s, bool staged, const PartItem* items, uint32_t nitems, const uint32_t* qidx,
+                      const uint32_t* dst, const float* q32, uint32_t k, Cand* cand) {
+  if (staged) return launch_one<DT, QW, true, true>(c, s, items, nitems, qidx, dst, q32, k, cand);
+  if (aligned_rows(c->dtype, c->dim)) return launch_one<DT, QW, true, false>(c, s, items, nitems, qidx, dst, q32, k, cand);
+  return launch_one<DT, QW, false, false>(c, s, items, nitems, qidx, dst, q32, k, cand);
+}
+
+template <int DT>
+nvdb_status launch_dt(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const PartItem* items, uint32_t nitems, const uint32_t* qidx,
+                      const uint32_t* dst, const float* q32, uint32_t k, Cand* cand) {
+  if (qw == 4) return launch_qw<DT, 4>(c, s, staged, items, nitems, qidx, dst, q32, k, cand);
+  if (qw == 2) return launch_qw<DT, 2>(c, s, staged, items, nitems, qidx, dst, q32, k, cand);
+  return launch_qw<DT, 1>(c, s, staged, items, nitems, qidx, dst, q32, k, cand);
+}
+
+nvdb_status launch_scan_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const PartItem* items, uint32_t nitems,
+                              const uint32_t* qidx, const uint32_t* dst, const float* q32, uint32_t k, Cand* cand) {
+  if (c->dtype == NVDB_DTYPE_F32) return launch_dt<DT_F32>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand);
+  if (c->dtype == NVDB_DTYPE_F16) return launch_dt<DT_F16>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand);
+  return launch_dt<DT_I8>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand);
+}
+
+nvdb_status parts_args(nvdb_hip_ctx* c, const char* who) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
+  if (!c->parts || c->parts->offsets.empty()) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no partition table (nvdb_hip_set_partitions)");
+  return NVDB_OK;
+}
+
+// the search proper; the caller has validated the context, the table, nq > 0 and 0 < k <= 64
+nvdb_status parts_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe, uint32_t nprobe,
+                         uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
+  PartState* ps = c->parts;
+  const uint32_t nparts = static_cast<uint32_t>(ps->offsets.size() - 1);
+  const uint64_t* off = ps->offsets.data();
+  const uint32_t row_bytes = c->dim * static_cast<uint32_t>(bpe_of(c->dtype));
+
+  // kernel build: staged through LDS where the rows are whole 16-byte chunks and a tile fits beside the queries
+  const bool can_stage = row_bytes % 16 == 0 && row_bytes <= PART_STAGE_MAX_ROW_BYTES && reinterpret_cast<uintptr_t>(c->rows) % 16 == 0;
+  uint32_t qw_max = 0;
+  bool staged = false;
+  for (int pass = 0; pass < 2 && !qw_max; ++pass) {
+    if (pass == 0 && !can_stage) continue;
+    for (uint32_t qw : {4u, 2u, 1u})
+      if (parts_lds(c->dim, row_bytes, qw, pass == 0) <= PART_LDS_LIMIT) { qw_max = qw; staged = pass == 0; break; }
+  }
+  if (!qw_max) return fail(c, NVDB_ERR_UNSUPPORTED, "search_partitions: dim too large for the query staging");
+  const uint32_t qg_max = PART_WAVES * qw_max;
+
+  // 1. de-duplicated probes, per-partition query counts
+  ps->uniq.resize(static_cast<size_t>(nq) * nprobe);
+  ps->ucount.assign(nq, 0);
+  ps->pcount.assign(nparts, 0);
+  for (uint32_t q = 0; q < nq; ++q) {
+    uint32_t* u = ps->uniq.data() + static_cast<size_t>(q) * nprobe;
+    uint32_t m = 0;
+    for (uint32_t j = 0; j < nprobe; ++j) {
+      const uint32_t p = probe[static_cast<size_t>(q) * nprobe + j];
+      if (p == 0xFFFFFFFFu) continue;
+      if (p >= nparts) return fail(c, NVDB_ERR_INVALID, "search_partitions: probe entry names a partition >= nparts");
+      u[m++] = p;
+    }
+    std::sort(u, u + m);
+    m = static_cast<uint32_t>(std::unique(u, u + m) - u);
+    ps->ucount[q] = m;
+    for (uint32_t j = 0; j < m; ++j) ++ps->pcount[u[j]];
+  }
+  // 2. counting sort: the queries of every partition, ascending
+  ps->pstart.assign(nparts + 1, 0);
+  for (uint32_t p = 0; p < nparts; ++p) ps->pstart[p + 1] = ps->pstart[p] + ps->pcount[p];
+  const uint32_t npairs = ps->pstart[nparts];
+  ps->qidx.resize(npairs);
+  ps->cursor.assign(ps->pstart.begin(), ps->pstart.end() - 1);
+  for (uint32_t q = 0; q < nq; ++q) {
+    const uint32_t* u = ps->uniq.data() + static_cast<size_t>(q) * nprobe;
+    for (uint32_t j = 0; j < ps->ucount[q]; ++j) ps->qidx[ps->cursor[u[j]]++] = q;
+  }
+  // 3. candidate slots a probe of partition p costs a query; the queries' blocks
+  auto nseg_of = [](uint64_t size) { return static_cast<uint32_t>((size + PART_SEG_ROWS - 1) / PART_SEG_ROWS); };
+  ps->psum.assign(nparts, 0);
+  for (uint32_t p = 0; p < nparts; ++p) {
+    const uint64_t size = off[p + 1] - off[p];
+    if (!ps->pcount[p] || !size) continue;
+    const uint32_t nseg = nseg_of(size);
+    uint64_t sum = 0;
+    for (uint32_t sg = 0; sg < nseg; ++sg) sum += std::min<uint64_t>(k, size * (sg + 1) / nseg - size * sg / nseg);
+    ps->psum[p] = static_cast<uint32_t>(sum);
+  }
+  ps->cbeg.assign(nq + 1, 0);
+  uint64_t total = 0;
+  for (uint32_t q = 0; q < nq; ++q) {
+    const uint32_t* u = ps->uniq.data() + static_cast<size_t>(q) * nprobe;
+    uint64_t rows_union = 0;
+    for (uint32_t j = 0; j < ps->ucount[q]; ++j) { total += ps->psum[u[j]]; rows_union += off[u[j] + 1] - off[u[j]]; }
+    if (total >= 0xFFFFFFFFull) return fail(c, NVDB_ERR_UNSUPPORTED, "search_partitions: more than 2^32 candidate slots in one call (split the batch)");
+    ps->cbeg[q + 1] = static_cast<uint32_t>(total);
+    if (out_counts) out_counts[q] = static_cast<uint32_t>(std::min<uint64_t>(k, rows_union));
+  }
+  // 4. work items, by class of group size
+  for (auto& v : ps->items) v.clear();
+  ps->dst.clear();
+  ps->cursor.assign(ps->cbeg.begin(), ps->cbeg.end() - 1);
+  uint64_t rows_read = 0;
+  for (uint32_t p = 0; p < nparts; ++p) {
+    const uint64_t size = off[p + 1] - off[p];
+    const uint32_t cnt = ps->pcount[p];
+    if (!cnt || !size) continue;
+    const uint32_t nseg = nseg_of(size);
+    for (uint32_t g0 = 0; g0 < cnt; g0 += qg_max) {
+      const uint32_t nqg = std::min(qg_max, cnt - g0);
+      const int cl = nqg <= PART_WAVES ? 0 : (nqg <= 2 * PART_WAVES ? 1 : 2);
+      for (uint32_t sg = 0; sg < nseg; ++sg) {
+        const uint32_t lo = static_cast<uint32_t>(off[p] + size * sg / nseg), hi = static_cast<uint32_t>(off[p] + size * (sg + 1) / nseg);
+        ps->items[cl].push_back(PartItem{lo, hi, ps->pstart[p] + g0, static_cast<uint32_t>(ps->dst.size()), nqg, 0u});
+        const uint32_t slot = std::min<uint32_t>(k, hi - lo);
+        for (uint32_t g = 0; g < nqg; ++g) { uint32_t& cur = ps->cursor[ps->qidx[ps->pstart[p] + g0 + g]]; ps->dst.push_back(cur); cur += slot; }
+        rows_read += hi - lo;
+      }
+    }
+  }
+  const size_t nitems = ps->items[0].size() + ps->items[1].size() + ps->items[2].size();
+
+  // device workspace (grow-only) and the pinned image of the work list: [items | qidx | dst | cbeg]
+  const size_t w_items = nitems * (sizeof(PartItem) / 4), w_qidx = npairs, w_dst = ps->dst.size(), w_cbeg = nq + 1;
+  const size_t meta_bytes = (w_items + w_qidx + w_dst + w_cbeg) * 4;
+  const size_t qbytes = static_cast<size_t>(nq) * c->dim * 4, ob_ids = static_cast<size_t>(nq) * k * 8, ob_sc = static_cast<size_t>(nq) * k * 4;
+  nvdb_status st;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((st = ensure(c, ps->meta, meta_bytes))) return st;
+  if ((st = ensure(c, ps->cand, std::max<size_t>(total, 1) * sizeof(Cand)))) return st;
+  if ((st = ensure(c, ps->q, qbytes))) return st;
+  if ((st = ensure(c, ps->out_ids, ob_ids))) return st;
+  if ((st = ensure(c, ps->out_scores, ob_sc))) return st;
+  if (ps->pin_bytes < meta_bytes) {
+    if (ps->pin) (void)hipHostFree(ps->pin);
+    ps->pin = nullptr; ps->pin_bytes = 0;
+    HIPCHK(c, hipHostMalloc(&ps->pin, meta_bytes + meta_bytes / 2, hipHostMallocDefault));
+    ps->pin_bytes = meta_bytes + meta_bytes / 2;
+  }
+  for (hipEvent_t& e : ps->ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+  uint32_t* pin = static_cast<uint32_t*>(ps->pin);
+  {
+    uint32_t* w = pin;
+    for (int cl = 2; cl >= 0; --cl) {                                     // the widest groups first: the longest items start early
+      if (!ps->items[cl].empty()) std::memcpy(w, ps->items[cl].data(), ps->items[cl].size() * sizeof(PartItem));
+      w += ps->items[cl].size() * (sizeof(PartItem) / 4);
+    }
+    if (w_qidx) std::memcpy(w, ps->qidx.data(), w_qidx * 4);
+    w += w_qidx;
+    if (w_dst) std::memcpy(w, ps->dst.data(), w_dst * 4);
+    w += w_dst;
+    std::memcpy(w, ps->cbeg.data(), w_cbeg * 4);
+  }
+  hipStream_t s = c->stream;
+  uint32_t* dmeta = static_cast<uint32_t*>(ps->meta.p);
+  const PartItem* d_items = reinterpret_cast<const PartItem*>(dmeta);
+  const uint32_t* d_qidx = dmeta + w_items;
+  const uint32_t* d_dst = d_qidx + w_qidx;
+  const uint32_t* d_cbeg = d_dst + w_dst;
+  if (timing) HIPCHK(c, hipEventRecord(ps->ev[0], s));
+  HIPCHK(c, hipMemcpyAsync(ps->meta.p, pin, meta_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(ps->q.p, queries, qbytes, hipMemcpyHostToDevice, s));
+  if (timing) HIPCHK(c, hipEventRecord(ps->ev[1], s));
+  uint32_t launches = 0;
+  {
+    const PartItem* it = d_items;
+    for (int cl = 2; cl >= 0; --cl) {
+      const uint32_t n_cl = static_cast<uint32_t>(ps->items[cl].size());
+      if (!n_cl) continue;
+      const uint32_t qw = std::min<uint32_t>(qw_max, 1u << cl);
+      if ((st = launch_scan_parts(c, s, qw, staged, it, n_cl, d_qidx, d_dst, static_cast<const float*>(ps->q.p), k, static_cast<Cand*>(ps->cand.p)))) return st;
+      it += n_cl;
+      ++launches;
+    }
+  }
+  select_parts_kernel<<<nq, 64, 0, s>>>(static_cast<const Cand*>(ps->cand.p), d_cbeg, k, c->row_base,
+                                         static_cast<unsigned long long*>(ps->out_ids.p), static_cast<float*>(ps->out_scores.p));
+  HIPCHK(c, hipGetLastError());
+  if (timing) HIPCHK(c, hipEventRecord(ps->ev[2], s));
+  HIPCHK(c, hipMemcpyAsync(out_ids, ps->out_ids.p, ob_ids, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(out_scores, ps->out_scores.p, ob_sc, hipMemcpyDeviceToHost, s));
+  if (timing) HIPCHK(c, hipEventRecord(ps->ev[3], s));
+  HIPCHK(c, hipStreamSynchronize(s));
+
+  c->stats = nvdb_hip_scan_stats{};
+  c->stats.path = 4;
+  c->stats.chunks = launches;
+  c->stats.rows_scanned = rows_read;
+  c->stats.candidates = total;
+  c->stats_lazy = false;
+  c->last_filter = false;
+  if (timing) {
+    float h2d = 0.f, ker = 0.f, d2h = 0.f;
+    (void)hipEventElapsedTime(&h2d, ps->ev[0], ps->ev[1]);
+    (void)hipEventElapsedTime(&ker, ps->ev[1], ps->ev[2]);
+    (void)hipEventElapsedTime(&d2h, ps->ev[2], ps->ev[3]);
+    timing->h2d_ms += h2d; timing->kernel_ms += ker; timing->d2h_ms += d2h;
+    timing->total_ms = timing->h2d_ms + timing->kernel_ms + timing->d2h_ms;
+    timing->threads = PART_THREADS; timing->nwarps = PART_WAVES; timing->K = k;
+    timing->shmem_bytes = parts_lds(c->dim, row_bytes, qw_max, staged);
+  }
+  return NVDB_OK;
+}
+
+void pad_outputs(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+  for (size_t i = 0; i < static_cast<size_t>(nq) * k; ++i) { out_ids[i] = ~0ull; out_scores[i] = NEG_INF; }
+  if (out_counts) for (uint32_t q = 0; q < nq; ++q) out_counts[q] = 0;
+}
+
+}  // namespace
+}  // namespace nvdbhip
+
+extern "C" {
+
+nvdb_status nvdb_hip_set_partitions(nvdb_hip_ctx* c, const uint64_t* offsets, uint32_t nparts) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
+  if (!offsets || nparts == 0 || nparts == 0xFFFFFFFFu) return fail(c, NVDB_ERR_INVALID, "set_partitions: null table or no partitions");
+  if (c->n > 0xFFFFFF00ull) return fail(c, NVDB_ERR_UNSUPPORTED, "set_partitions: corpus shard too large");
+  if (offsets[0] != 0 || offsets[nparts] != c->n) return fail(c, NVDB_ERR_INVALID, "set_partitions: offsets[0] must be 0 and offsets[nparts] the row count");
+  for (uint32_t p = 0; p < nparts; ++p)
+    if (offsets[p + 1] < offsets[p]) return fail(c, NVDB_ERR_INVALID, "set_partitions: offsets must be non-decreasing");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->parts) c->parts = new PartState();
+  parts_drop(c);                                   // a new table: the old centroids no longer describe it
+  c->parts->offsets.assign(offsets, offsets + nparts + 1);
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_set_centroids(nvdb_hip_ctx* c, const float* centroids) {
+  nvdb_status st = parts_args(c, "set_centroids");
+  if (st) return st;
+  if (!centroids) return fail(c, NVDB_ERR_INVALID, "set_centroids: null centroids");
+  PartState* ps = c->parts;
+  ps->have_centroids = false;
+  if (!ps->coarse) {
+    if ((st = nvdb_hip_create(c->device, &ps->coarse))) return fail(c, st, std::string("set_centroids: ") + nvdb_hip_last_error(nullptr));
+  }
+  const uint32_t nparts = static_cast<uint32_t>(ps->offsets.size() - 1);
+  if ((st = nvdb_hip_upload_corpus(ps->coarse, centroids, nullptr, nparts, c->dim, NVDB_DTYPE_F32, 0)))
+    return fail(c, st, std::string("set_centroids: ") + nvdb_hip_last_error(ps->coarse));
+  ps->have_centroids = true;
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_search_partitions(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe,
+                                       uint32_t nprobe, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                       nvdb_hip_timing* timing) {
+  nvdb_status st = parts_args(c, "search_partitions");
+  if (st) return st;
+  if (timing) std::memset(timing, 0, sizeof(*timing));
+  if (nq == 0 || k == 0) return NVDB_OK;
+  if (k > WAVE_KMAX) return fail(c, NVDB_ERR_UNSUPPORTED, "search_partitions: k <= 64 (wavefront-resident lists)");
+  if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
+  if (nprobe == 0) { pad_outputs(nq, k, out_ids, out_scores, out_counts); return NVDB_OK; }
+  if (!probe) return fail(c, NVDB_ERR_INVALID, "search_partitions: null probe table");
+  return parts_search(c, queries, nq, k, probe, nprobe, out_ids, out_scores, out_counts, timing);
+}
+
+nvdb_status nvdb_hip_search_ivf(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
+                                float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
+  nvdb_status st = parts_args(c, "search_ivf");
+  if (st) return st;
+  PartState* ps = c->parts;
+  if (!ps->have_centroids) return fail(c, NVDB_ERR_INVALID, "search_ivf: no centroids (nvdb_hip_set_centroids)");
+  if (timing) std::memset(timing, 0, sizeof(*timing));
+  if (nq == 0 || k == 0) return NVDB_OK;
+  if (k > WAVE_KMAX) return fail(c, NVDB_ERR_UNSUPPORTED, "search_ivf: k <= 64 (wavefront-resident lists)");
+  if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
+  if (nprobe == 0) { pad_outputs(nq, k, out_ids, out_scores, out_counts); return NVDB_OK; }
+  const uint32_t nparts = static_cast<uint32_t>(ps->offsets.size() - 1);
+  const uint32_t np = std::min(nprobe, nparts);                            // the clamp; out_probe keeps the caller's row length
+  // coarse step: the flat search over the centroids (its order: score desc, partition number asc)
+  ps->coarse_ids.resize(static_cast<size_t>(nq) * np);
+  ps->coarse_scores.resize(static_cast<size_t>(nq) * np);
+  nvdb_hip_timing ct;
+  if ((st = nvdb_hip_search_batch(ps->coarse, queries, nq, np, ps->coarse_ids.data(), ps->coarse_scores.data(), nullptr, timing ? &ct : nullptr)))
+    return fail(c, st, std::string("search_ivf (coarse step): ") + nvdb_hip_last_error(ps->coarse));
+  ps->probe_tmp.resize(static_cast<size_t>(nq) * np);
+  for (size_t i = 0; i < ps->probe_tmp.size(); ++i) ps->probe_tmp[i] = static_cast<uint32_t>(ps->coarse_ids[i]);
+  if (out_probe)
+    for (uint32_t q = 0; q < nq; ++q)
+      for (uint32_t j = 0; j < nprobe; ++j) out_probe[static_cast<size_t>(q) * nprobe + j] = j < np ? ps->probe_tmp[static_cast<size_t>(q) * np + j] : 0xFFFFFFFFu;
+  if (timing) { timing->h2d_ms = ct.h2d_ms; timing->kernel_ms = ct.kernel_ms; timing->d2h_ms = ct.d2h_ms; }
+  return parts_search(c, queries, nq, k, ps->probe_tmp.data(), np, out_ids, out_scores, out_counts, timing);
+}
+
+}  // extern "C"

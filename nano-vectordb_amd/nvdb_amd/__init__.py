@@ -31,6 +31,7 @@ EXPORTS = [
     "nvdb_hip_group_create", "nvdb_hip_group_destroy", "nvdb_hip_group_last_error", "nvdb_hip_group_size", "nvdb_hip_group_ctx",
     "nvdb_hip_group_exchange", "nvdb_hip_group_upload_corpus", "nvdb_hip_group_generate_corpus", "nvdb_hip_group_set_option",
     "nvdb_hip_group_search_batch",
+    "nvdb_hip_set_partitions", "nvdb_hip_set_centroids", "nvdb_hip_search_partitions", "nvdb_hip_search_ivf",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_filter_variant", "nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges"]
@@ -145,6 +146,10 @@ def _bind(L, dev):
     L.nvdb_hip_group_generate_corpus.argtypes = [vp, u64, u64, u32, u32]
     L.nvdb_hip_group_set_option.argtypes = [vp, C.c_char_p, i64]
     L.nvdb_hip_group_search_batch.argtypes = [vp, vp, u32, u32, vp, vp, C.POINTER(u32), C.POINTER(GroupStats)]
+    L.nvdb_hip_set_partitions.argtypes = [vp, vp, u32]
+    L.nvdb_hip_set_centroids.argtypes = [vp, vp]
+    L.nvdb_hip_search_partitions.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_search_ivf.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, C.POINTER(Timing)]
     for name in EXPORTS:
         getattr(L, name)
     if dev:
@@ -331,6 +336,43 @@ class HipContext:
                                stream=None):
         self._chk(self.lib.nvdb_hip_merge_topk_strided_dev(self.h, dev_ids, dev_scores, stride_ids, stride_scores, nshards, nq, k,
                                                            dev_out_ids, dev_out_scores, stream))
+
+    # -- partitioned probe search
+    def set_partitions(self, offsets):
+        """offsets: nparts + 1 local row numbers, offsets[0] == 0, non-decreasing, offsets[-1] == n."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self._chk(self.lib.nvdb_hip_set_partitions(self.h, offsets.ctypes.data, max(offsets.size, 1) - 1))
+
+    def set_centroids(self, centroids):
+        centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+        self._chk(self.lib.nvdb_hip_set_centroids(self.h, centroids.ctypes.data))
+
+    def _probe_outputs(self, queries, k):
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        nq = queries.shape[0]
+        ids = np.full((nq, k), np.iinfo(np.uint64).max, dtype=np.uint64)
+        scores = np.full((nq, k), -np.inf, dtype=np.float32)
+        return queries, nq, ids, scores, np.zeros(nq, dtype=np.uint32)
+
+    def search_partitions(self, queries, k, probe, want_timing=False):
+        """probe: [nq, nprobe] partition numbers (0xFFFFFFFF = empty slot) -> (ids [nq, k], scores [nq, k], counts [nq])."""
+        queries, nq, ids, scores, counts = self._probe_outputs(queries, k)
+        probe = np.ascontiguousarray(probe, dtype=np.uint32).reshape(nq, -1)
+        t = Timing()
+        self._chk(self.lib.nvdb_hip_search_partitions(self.h, queries.ctypes.data, nq, k, probe.ctypes.data, probe.shape[1],
+                                                      ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
+                                                      C.byref(t) if want_timing else None))
+        return (ids, scores, counts, t) if want_timing else (ids, scores, counts)
+
+    def search_ivf(self, queries, k, nprobe, want_probe=False):
+        """IVF-Flat: the nprobe partitions with the best centroids, then search_partitions; (ids, scores, counts[, probe])."""
+        queries, nq, ids, scores, counts = self._probe_outputs(queries, k)
+        probe = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
+        self._chk(self.lib.nvdb_hip_search_ivf(self.h, queries.ctypes.data, nq, k, nprobe, ids.ctypes.data, scores.ctypes.data,
+                                               counts.ctypes.data, probe.ctypes.data if want_probe else None, None))
+        return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
     # -- refine
     def refine_l2_topk(self, queries, cand_ids, K, want_dist=True, want_timing=False):
