@@ -286,6 +286,7 @@ __device__ __forceinline__ void glds16_v(const void* gptr, uint32_t lds_off) {
                : "=&s"(keep) : "v"(gptr), "s"(lds_off) : "memory");
 }
 
+template <int DIM> constexpr size_t filter_f16_lds_bytes() { return static_cast<size_t>(FILTER_STAGES) * FILTER_ROWS * DIM * 2; }   // dynamic LDS of filter_f16_kernel
 template <int DIM, int NB, int VAR = 0, int RING = 6>
 __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
     const _Float16* __restrict__ rows, uint32_t row_lo, uint32_t row_hi, const _Float16* __restrict__ q16,
@@ -306,6 +307,7 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
   static_assert(DIM % 128 == 0, "swizzle assumes row stride is a multiple of 256 bytes");
   static_assert(PIECES % 4 == 0, "pieces must split evenly over 4 waves");
   static_assert(KSTEPS <= 64, "query block 0 must fit the AGPR-resident fragments");
+  static_assert(FILTER_STAGES * STAGE_BYTES == filter_f16_lds_bytes<DIM>(), "the launchers size the dynamic LDS with filter_f16_lds_bytes");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -578,6 +580,7 @@ __device__ __forceinline__ void sibling_rendezvous(uint32_t* myprog, uint32_t qt
 // registers either way (384 at the two corners), and a stage stays 48 KB.
 // WPB = waves per workgroup: 4 (one per SIMD, 512 registers each) or 8 (two per SIMD, 256 registers each, NQB = 2:
 // the second wave of a SIMD fills the gaps the first leaves at tile boundaries; twice the LDS reads per MFMA)
+template <int DIM, int MB = 2> constexpr size_t filter_f16_m16_lds_bytes() { return static_cast<size_t>(FILTER_STAGES) * 16 * MB * DIM * 2; }   // dynamic LDS of filter_f16_m16_kernel
 template <int DIM, int RING = 6, bool SYNC = false, bool STAMP = false, int VAR = 0, int MB = 2, int NQB = 4, int WPB = 4>
 __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
     const _Float16* __restrict__ rows, uint32_t row_lo, uint32_t row_hi, const _Float16* __restrict__ q16,
@@ -595,6 +598,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
   constexpr int NREAD = MB * KS;                   // A fragments per tile (MB row blocks x KS)
   static_assert(DIM % 128 == 0 && PIECES % WPB == 0 && NREAD % PPW == 0 && (WPB == 4 || WPB == 8), "shape");
   static_assert((MB == 1 || MB == 2 || MB == 4) && (NQB == 1 || NQB == 2 || NQB == 4) && NQB * KS * 4 <= 384 && STAGE_BYTES * FILTER_STAGES <= 160 * 1024, "registers / LDS");
+  static_assert(FILTER_STAGES * STAGE_BYTES == filter_f16_m16_lds_bytes<DIM, MB>(), "the launchers size the dynamic LDS with filter_f16_m16_lds_bytes");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -795,6 +799,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
 // A fragment read: LDS-bound at about half the MFMA rate of the 768 build, 64 queries per workgroup -- still far from
 // the fp32 VALU path these dims would otherwise take.  Same logging / scatter / rendezvous as filter_f16_m16_kernel.
 // ------------------------------------------------------------------------------------------------
+template <int DIM> constexpr size_t filter_f16_k2_lds_bytes() { return static_cast<size_t>(FILTER_STAGES) * 16 * (DIM / 2) * 2; }   // dynamic LDS of filter_f16_k2_kernel: half-K stages
 template <int DIM, bool SYNC = false>
 __global__ __launch_bounds__(256, 1) void filter_f16_k2_kernel(
     const _Float16* __restrict__ rows, uint32_t row_lo, uint32_t row_hi, const _Float16* __restrict__ q16,
@@ -811,6 +816,7 @@ __global__ __launch_bounds__(256, 1) void filter_f16_k2_kernel(
   constexpr int CPR = SROW / 16;                   // 16-byte chunks per stage row
   constexpr int NFRAG = 2 * KS, NFRAG_A = NFRAG < 64 ? NFRAG : 64, NFRAG_V = NFRAG - NFRAG_A;
   static_assert(DIMS % 128 == 0 && PIECES % 4 == 0 && KS % PPW == 0 && NFRAG * 4 <= 384 && STAGE_BYTES * FILTER_STAGES <= 160 * 1024, "shape");
+  static_assert(FILTER_STAGES * STAGE_BYTES == filter_f16_k2_lds_bytes<DIM>(), "the launchers size the dynamic LDS with filter_f16_k2_lds_bytes");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1051,6 +1057,7 @@ template <int ROW_BYTES> __device__ inline uint32_t a_addr_i8(uint32_t a_base, i
 
 // BOOT = true: bootstrap build (see filter_f16_kernel VAR 7): best (score,row) per tile and query -> cand lists
 // (hitlog then points at the candidate lists, aux is their stride).
+template <int DIM> constexpr size_t filter_i8_lds_bytes() { return static_cast<size_t>(FILTER_STAGES_I8) * (FILTER_ROWS * DIM + 4 * 1024); }   // dynamic LDS of filter_i8_kernel
 template <int DIM, bool BOOT = false, int RING = 6, bool SYNC = false>
 __global__ __launch_bounds__(256, 1) void filter_i8_kernel(
     const signed char* __restrict__ rows, const float* __restrict__ scales, uint32_t row_lo, uint32_t row_hi,
@@ -1066,6 +1073,7 @@ __global__ __launch_bounds__(256, 1) void filter_i8_kernel(
   constexpr int CHUNKS_PER_ROW = ROW_BYTES / 16;
   static_assert(DIM % 128 == 0, "int8 row stride: a multiple of 128 bytes (swz_chunk)");
   static_assert(PIECES % 4 == 0 && KSTEPS % PPW == 0 && 2 * KSTEPS <= 64, "shape");
+  static_assert(FILTER_STAGES_I8 * STAGE_BYTES == filter_i8_lds_bytes<DIM>(), "the launchers size the dynamic LDS with filter_i8_lds_bytes");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1266,6 +1274,10 @@ __device__ __forceinline__ int imax3(int a, int b, int c) {
 // STAMP / VAR: diagnostic builds only (libnvdb_hip_dev.so, nvdb_hip_debug_clock_i8; results are wrong for VAR != 0):
 // STAMP = s_memtime / s_memrealtime around the tile loop (written behind the rendezvous counters); VAR 1 = never run
 // stage 2 (no lo-plane pass), 2 = no stage-1 test either (MFMAs + stream only), 3 = 2 + no per-tile barrier.
+// dynamic LDS of filter_i8w_kernel: its stages, and behind them (64-row tiles) 1 KB of lo-plane scratch per wave
+template <int DIM, int MB = 2> constexpr size_t filter_i8w_lds_bytes() {
+  return static_cast<size_t>((MB == 2 || DIM > 768) ? 3 : FILTER_STAGES_I8) * (FILTER_ROWS * MB * DIM + 4 * 1024) + (MB == 2 ? 4 * 1024 : 0);
+}
 template <int DIM, int NB = 2, int RING = 6, bool SYNC = false, int MB = 2, bool STAMP = false, int VAR = 0>
 __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
     const signed char* __restrict__ rows, const float* __restrict__ scales, uint32_t row_lo, uint32_t row_hi,
@@ -1373,6 +1385,7 @@ __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
   // (row, query) pair is 4 x v_dot4_i32_i8 per lane and a wave reduction.  Same integer, same float expression, same
   // hit as the block path below.
   constexpr bool DEFER = (MB == 2) && (NSTAGE * STAGE_BYTES + 4096 <= 160 * 1024) && (DIM % 16 == 0) && (DIM / 16 <= 64);
+  static_assert(NSTAGE * STAGE_BYTES + (MB == 2 ? 4 * 1024 : 0) == filter_i8w_lds_bytes<DIM, MB>(), "the launchers size the dynamic LDS with filter_i8w_lds_bytes");
   char* scratch = smem + NSTAGE * STAGE_BYTES + wave * 1024;
   const uint32_t lds_scratch = lds_base + NSTAGE * STAGE_BYTES + wave * 1024;
   bool pend = false;                               // uniform
@@ -1661,6 +1674,10 @@ __device__ __forceinline__ void verify_and_scatter_i8(const Hit* mylog, uint32_t
 // LDS-DMA issue, ring priming, barrier waits and rare path run beside its SIMD partner's MFMAs.
 // DEFER = false (the default build): a value that passes the first stage is only logged in the loop and finished after the stream
 // (verify_and_scatter_i8); DEFER = true: the in-loop second stage (deferred v_dot4 slots, lo-plane MFMAs for dense blocks).
+// dynamic LDS of filter_i8p_kernel: three stages (tile + scale copies), and per wave the lo-plane rows of its deferred values
+template <int DIM, int WPB = 4, bool DEFER = true> constexpr size_t filter_i8p_lds_bytes() {
+  return static_cast<size_t>(3) * (2 * FILTER_ROWS * DIM + (WPB == 4 ? 4 : 1) * 256) + (DEFER ? WPB * (16 / WPB) * DIM : 0);
+}
 template <int DIM, bool SYNC = false, bool STAMP = false, int RING = 6, int VAR = 0, int WPB = 4, bool DEFER = true>
 __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
     const signed char* __restrict__ rows, const float* __restrict__ scales, uint32_t row_lo, uint32_t row_hi,
@@ -1685,6 +1702,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
   static_assert(DIM % 128 == 0 && DIM <= 768, "row stride multiple of 128 bytes (swz_chunk); int32 range of 128*H + L");
   static_assert(PIECES % WPB == 0 && KSTEPS % PPW == 0 && KSTEPS % 2 == 0 && KSTEPS >= 8, "shape");
   static_assert(NSTAGE * STAGE_BYTES + WPB * SCRATCH_BYTES <= 160 * 1024 && PPW + 1 < 64 && DIM % 16 == 0 && DIM / 16 <= 64, "LDS / vmcnt range");
+  static_assert(NSTAGE * STAGE_BYTES + WPB * SCRATCH_BYTES == filter_i8p_lds_bytes<DIM, WPB, DEFER>(), "the launchers size the dynamic LDS with filter_i8p_lds_bytes");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);

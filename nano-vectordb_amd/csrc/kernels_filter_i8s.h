@@ -29,6 +29,7 @@ typedef int intx4_t __attribute__((ext_vector_type(4)));
 // 3 = structure alone without the in-loop LDS-DMA issue (the stages keep the first tiles), 4 = structure alone without the A-fragment LDS reads.
 // WPB = 8: the same 256 queries per workgroup on 8 waves of 32 (two waves per SIMD, 128 + 128 registers each): a wave's LDS-DMA issue,
 // ring priming and barrier waits run beside its SIMD partner's MFMAs.
+template <int DIM, int WPB = 4> constexpr size_t filter_i8s_lds_bytes() { return static_cast<size_t>(3) * (2 * FILTER_ROWS * DIM + WPB * 256); }   // dynamic LDS of filter_i8s_kernel
 template <int DIM, bool SYNC = false, bool STAMP = false, int RING = 6, int VAR = 0, int WPB = 4>
 __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
     const signed char* __restrict__ rows, const float* __restrict__ scales, uint32_t row_lo, uint32_t row_hi,
@@ -52,6 +53,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
   constexpr int NFRAG = 2 * KS;                              // A fragments per 32-row block
   static_assert(DIM % 128 == 0 && DIM <= 768, "row stride multiple of 128 bytes (swz_chunk); 64 queries x DIM bytes = 192 AGPRs at most");
   static_assert(PIECES % WPB == 0 && PPW % 2 == 0 && NSTAGE * STAGE_BYTES <= 160 * 1024 && PPW + 1 < 64 && NFRAG >= RING, "shape / LDS / vmcnt range");
+  static_assert(NSTAGE * STAGE_BYTES == filter_i8s_lds_bytes<DIM, WPB>(), "the launchers size the dynamic LDS with filter_i8s_lds_bytes");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -34,6 +34,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "kernels_exact.h"       // Cand, FinalSelect
@@ -192,11 +193,25 @@ inline bool aligned_rows(uint32_t dtype, uint32_t dim) {
 }
 
 // dims the fp16 MFMA kernels are instantiated for: multiples of 128 up to 768 (64 queries per wave: their fragments fill
-// 384 registers at 768), 1024 / 1536 on the 16-row-tile build (32 queries per wave), 2048 / 3072 on the K-split build
-// (16 queries per wave, a tile streamed as two half-K stages)
+// 384 registers at 768), up to 1536 on the 16-row-tile build (32 queries per wave), 2048 / 2560 / 3072 on the K-split build
+// (16 queries per wave, a tile streamed as two half-K stages); int8 rows: every multiple of 128 bytes from 256 (swz_chunk's
+// two families), beyond 768 on 32-row tiles.  The launchers dispatch from these lists and the predicates are read off them.
+template <int... D> struct DimList {};
+using F16Dims = DimList<768, 640, 512, 384, 256, 128>;
+using F16Dims16 = DimList<896, 1024, 1152, 1280, 1408, 1536>;
+using F16DimsK2 = DimList<2048, 2560, 3072>;
+using I8Dims = DimList<768, 640, 512, 384, 256>;
+using I8DimsBig = DimList<896, 1024, 1152, 1280, 1408, 1536>;
 
-inline bool f16_filter_dim(uint32_t dim) { return dim == 768 || dim == 640 || dim == 512 || dim == 384 || dim == 256 || dim == 128 || dim == 896 || dim == 1024 || dim == 1152 || dim == 1280 || dim == 1408 || dim == 1536 || dim == 2048 || dim == 2560 || dim == 3072; }
-inline bool i8_filter_dim(uint32_t dim) { return dim % 128 == 0 && dim >= 256 && dim <= 1536; }   // int8 rows: every multiple of 128 bytes from 256 (swz_chunk's two families)
+// st = f(std::integral_constant<int, D>) for the D of the list that equals dim; false: the list does not hold dim
+template <int... D, typename F>
+bool dispatch_dim(DimList<D...>, uint32_t dim, nvdb_status& st, F&& f) {
+  return ((dim == static_cast<uint32_t>(D) && ((st = f(std::integral_constant<int, D>{})), true)) || ...);
+}
+template <int... D> bool has_dim(DimList<D...>, uint32_t dim) { return ((dim == static_cast<uint32_t>(D)) || ...); }
+
+inline bool f16_filter_dim(uint32_t dim) { return has_dim(F16Dims{}, dim) || has_dim(F16Dims16{}, dim) || has_dim(F16DimsK2{}, dim); }
+inline bool i8_filter_dim(uint32_t dim) { return has_dim(I8Dims{}, dim) || has_dim(I8DimsBig{}, dim); }
 inline bool refine3_dim(uint32_t dim) { return dim == 768 || dim == 512 || dim == 384 || dim == 256; }   // fp16 dims of the whole-row refine kernel
 
 // what the fp16 MFMA kernels stream: the corpus itself, or the fp16 shadow of an fp32 corpus
@@ -254,5 +269,82 @@ void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace
 // nvdb_search.cpp
 nvdb_status next_prog_region(nvdb_hip_ctx* c, hipStream_t s, uint32_t nwg, uint32_t** out);
 ScatterArgs scatter_args(nvdb_hip_ctx* c, uint32_t cap, uint32_t trows = 0);
+
+// ---- launching a filter kernel (nvdb_launch_f16.cpp, nvdb_launch_i8.cpp, nvdb_debug.cpp) ----------------------------
+// the dynamic-LDS limit of a kernel, raised once per kernel and device
+inline nvdb_status raise_lds_limit(nvdb_hip_ctx* c, const void* fn, size_t bytes) {
+  if (c->lds_attr_set.count(fn)) return NVDB_OK;
+  HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
+  c->lds_attr_set.insert(fn);
+  return NVDB_OK;
+}
+
+// workgroups of a filter launch: one per CU, rounded down to whole groups of QT (the QT query tiles of a row stream)
+inline uint32_t filter_grid(const nvdb_hip_ctx* c, uint32_t QT) {
+  const uint32_t nwg = (static_cast<uint32_t>(c->num_cu) / QT) * QT;
+  return nwg ? nwg : QT;
+}
+
+// the kernels' XCD-aware mapping is active: the QT workgroups of a row stream share an XCD label
+inline bool xcd_aware_grid(uint32_t QT, uint32_t nwg) { return (nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0; }
+// ... only then, and with siblings to keep in step, does the rendezvous apply
+inline bool sibling_sync_grid(const nvdb_hip_ctx* c, uint32_t QT, uint32_t nwg) { return c->opt_sibling_sync && QT > 1 && QT <= 8 && xcd_aware_grid(QT, nwg); }
+
+// rendezvous arguments of a filter kernel: counters (unused / not-yet-started slots read 0xFFFFFFFF = "far ahead"),
+// period mask, allowed lead; prog == nullptr: the SYNC = false build runs
+struct SyncArgs { uint32_t* prog = nullptr; uint32_t mask = 0, lead = 0; };
+inline nvdb_status sibling_sync_args(nvdb_hip_ctx* c, hipStream_t s, uint32_t QT, uint32_t nwg, SyncArgs& out) {
+  out = SyncArgs{};
+  if (!sibling_sync_grid(c, QT, nwg)) return NVDB_OK;
+  out.mask = static_cast<uint32_t>(c->opt_sync_every - 1);
+  out.lead = static_cast<uint32_t>(c->opt_sync_lead);
+  return next_prog_region(c, s, nwg, &out.prog);
+}
+
+// one filter pass as its caller describes it
+struct FilterCall { hipStream_t s; uint32_t row_lo, row_hi, nq, QT, cap; const float* thr; };
+// ... and as one kernel build wants it launched; log_waves: waves per workgroup the survivor log is sized for (0: the
+// build writes no log); timed: the context's launch events attach (hipExtLaunchKernelGGL)
+struct FilterGeom { uint32_t block; size_t lds; uint32_t log_waves; bool timed; };
+
+// A DevBuf* in a kernel's argument list stands for the Hit* it holds at launch time: the survivor log may move when
+// launch_filter_kernel grows it, after the caller has evaluated the arguments.
+template <typename T> inline T launch_arg(T a) { return a; }
+inline Hit* launch_arg(DevBuf* b) { return static_cast<Hit*>(b->p); }
+
+template <typename... KA, typename... A>
+nvdb_status launch_filter_kernel(nvdb_hip_ctx* c, hipStream_t s, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, A... args) {
+  nvdb_status st;
+  if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(kern), g.lds))) return st;
+  if (g.log_waves && (st = ensure(c, c->hitlog, static_cast<size_t>(nwg) * g.log_waves * FILTER_LOGCAP * sizeof(Hit)))) return st;
+  if (g.timed) hipExtLaunchKernelGGL(kern, dim3(nwg), dim3(g.block), g.lds, s, c->launch_e0, c->launch_e1, 0, launch_arg(args)...);
+  else kern<<<nwg, g.block, g.lds, s>>>(launch_arg(args)...);
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+// the arguments every fp16 build starts with (rows, range, queries, thresholds, log, scatter arguments); rest: what one
+// build adds (the rendezvous arguments, or filter_f16_kernel's aux word)
+template <typename... KA, typename... Rest>
+nvdb_status launch_filter_f16_kernel(nvdb_hip_ctx* c, const FilterCall& f, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, DevBuf* log,
+                                     uint32_t trows, Rest... rest) {
+  return launch_filter_kernel(c, f.s, kern, nwg, g, filter_rows_f16(c), f.row_lo, f.row_hi, static_cast<const _Float16*>(c->q16.p), f.nq, f.QT, f.thr,
+                              static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p), log, scatter_args(c, f.cap, trows), rest...);
+}
+
+// ... every int8 build (rows, scales, range, the two query planes -- the lo plane qlo_off bytes behind the hi plane --, thresholds)
+template <typename... KA, typename... Rest>
+nvdb_status launch_filter_i8_kernel(nvdb_hip_ctx* c, const FilterCall& f, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, size_t qlo_off, Rest... rest) {
+  const signed char* qhi = static_cast<const signed char*>(c->q16.p);
+  return launch_filter_kernel(c, f.s, kern, nwg, g, filter_rows_i8(c), filter_scales_i8(c), f.row_lo, f.row_hi, qhi, qhi + qlo_off, f.nq, f.QT, f.thr,
+                              static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p), rest...);
+}
+// ... and what the two-stage builds (filter_i8w / i8p / i8s_kernel) add: qdelta, log, scatter arguments, rendezvous, stage counts (misc[4], [5]: tiles past stage 0 / stage 1)
+template <typename... KA>
+nvdb_status launch_filter_i8w_kernel(nvdb_hip_ctx* c, const FilterCall& f, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, size_t qlo_off,
+                                     uint32_t trows, const SyncArgs& sy) {
+  return launch_filter_i8_kernel(c, f, kern, nwg, g, qlo_off, static_cast<const float*>(c->qdelta.p), &c->hitlog, scatter_args(c, f.cap, trows), sy.prog,
+                                 sy.mask, sy.lead, static_cast<uint32_t*>(c->misc.p) + 4);
+}
 
 }  // namespace nvdbhip

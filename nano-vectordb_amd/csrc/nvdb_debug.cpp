@@ -27,36 +27,32 @@ nvdb_status nvdb_hip_debug_filter_variant(nvdb_hip_ctx* c, int variant, uint32_t
   nvdb_status st = ensure(c, inf, nq_pad * 4);
   if (st) return st;
   fill_u32_kernel<<<(nq_pad + 255) / 256, 256, 0, c->stream>>>(static_cast<uint32_t*>(inf.p), 0x7F800000u, nq_pad);
-  constexpr size_t lds = static_cast<size_t>(FILTER_STAGES) * FILTER_ROWS * 768 * 2;
   const uint32_t n_al = static_cast<uint32_t>(c->n / FILTER_ROWS * FILTER_ROWS);
-  uint32_t nwg = (static_cast<uint32_t>(c->num_cu) / QT) * QT;
+  const uint32_t nwg = filter_grid(c, QT);
+  const FilterCall f{c->stream, 0, n_al, nq, QT, c->last_cap, static_cast<const float*>(inf.p)};
   hipEvent_t e0, e1;
   HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-#define NVDB_DBG_LAUNCH(V, RG)                                                                                                 \
-  {                                                                                                                            \
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(filter_f16_kernel<768, 2, V, RG>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds))); \
-    for (uint32_t r = 0; r <= reps; ++r) {                                                                                     \
-      if (r == 1) HIPCHK(c, hipEventRecord(e0, c->stream));                                                                    \
-      filter_f16_kernel<768, 2, V, RG><<<nwg, 256, lds, c->stream>>>(static_cast<const _Float16*>(c->rows), 0, n_al, static_cast<const _Float16*>(c->q16.p), nq, QT, \
-          static_cast<const float*>(inf.p), static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p), static_cast<Hit*>(c->hitlog.p),     \
-          scatter_args(c, c->last_cap), 0u);                                                                                   \
-    }                                                                                                                          \
-  }
+  auto run = [&](auto kern) -> nvdb_status {       // one untimed launch, then `reps` timed ones (tiles in identity order)
+    for (uint32_t r = 0; r <= reps; ++r) {
+      if (r == 1) HIPCHK(c, hipEventRecord(e0, c->stream));
+      if ((st = launch_filter_f16_kernel(c, f, kern, nwg, FilterGeom{256, filter_f16_lds_bytes<768>(), 4, false}, &c->hitlog, 0, 0u))) return st;
+    }
+    return NVDB_OK;
+  };
   switch (variant) {
-    case 0: NVDB_DBG_LAUNCH(0, 4) break;
-    case 1: NVDB_DBG_LAUNCH(1, 4) break;
-    case 2: NVDB_DBG_LAUNCH(2, 4) break;
-    case 3: NVDB_DBG_LAUNCH(3, 4) break;
-    case 5: NVDB_DBG_LAUNCH(5, 4) break;
-    case 6: NVDB_DBG_LAUNCH(0, 6) break;
-    case 10: NVDB_DBG_LAUNCH(6, 6) break;
-    case 7: NVDB_DBG_LAUNCH(0, 8) break;
-    case 8: NVDB_DBG_LAUNCH(0, 3) break;
-    case 9: NVDB_DBG_LAUNCH(0, 12) break;
+    case 0: st = run(filter_f16_kernel<768, 2, 0, 4>); break;
+    case 1: st = run(filter_f16_kernel<768, 2, 1, 4>); break;
+    case 2: st = run(filter_f16_kernel<768, 2, 2, 4>); break;
+    case 3: st = run(filter_f16_kernel<768, 2, 3, 4>); break;
+    case 5: st = run(filter_f16_kernel<768, 2, 5, 4>); break;
+    case 6: st = run(filter_f16_kernel<768, 2, 0, 6>); break;
+    case 10: st = run(filter_f16_kernel<768, 2, 6, 6>); break;
+    case 7: st = run(filter_f16_kernel<768, 2, 0, 8>); break;
+    case 8: st = run(filter_f16_kernel<768, 2, 0, 3>); break;
+    case 9: st = run(filter_f16_kernel<768, 2, 0, 12>); break;
     default: return fail(c, NVDB_ERR_INVALID, "debug: unknown variant");
   }
-#undef NVDB_DBG_LAUNCH
-  HIPCHK(c, hipGetLastError());
+  if (st) return st;
   HIPCHK(c, hipEventRecord(e1, c->stream));
   HIPCHK(c, hipEventSynchronize(e1));
   float ms = 0.f;
@@ -73,61 +69,43 @@ nvdb_status nvdb_hip_debug_clock(nvdb_hip_ctx* c, int variant, uint32_t nq, floa
   if (nq <= 128 || nq > (c->last_nq + 255u) / 256u * 256u) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: 128 < nq <= the last search's padded batch");
   HIPCHK(c, hipSetDevice(c->device));
   const uint32_t QT = (nq + 255) / 256, nq_pad = QT * 256;
-  const uint32_t nwg = (static_cast<uint32_t>(c->num_cu) / QT) * QT;
-  if (nwg == 0 || (nwg & 7u) || ((nwg >> 3) % QT)) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: batch does not map onto the XCD-aware grid");
+  const uint32_t nwg = filter_grid(c, QT);
+  if (!xcd_aware_grid(QT, nwg)) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: batch does not map onto the XCD-aware grid");
   DevBuf inf;
   nvdb_status st = ensure(c, inf, nq_pad * 4);
   if (st) return st;
   fill_u32_kernel<<<(nq_pad + 255) / 256, 256, 0, c->stream>>>(static_cast<uint32_t*>(inf.p), 0x7F800000u, nq_pad);
   const size_t prog_bytes = static_cast<size_t>(nwg) * 8 * 4, stamp_bytes = static_cast<size_t>(nwg) * 16;
   if ((st = ensure(c, c->prog, prog_bytes + stamp_bytes))) return st;
-  if ((st = ensure(c, c->hitlog, static_cast<size_t>(nwg) * 4 * FILTER_LOGCAP * sizeof(Hit)))) return st;
-  constexpr size_t lds = static_cast<size_t>(FILTER_STAGES) * FILTER_ROWS * 768 * 2;
   const uint32_t n_al = static_cast<uint32_t>(c->n / FILTER_ROWS * FILTER_ROWS);
+  const FilterCall f{c->stream, 0, n_al, nq, QT, c->last_cap, static_cast<const float*>(inf.p)};
   hipEvent_t e0, e1;
   HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
   const auto t_start = std::chrono::steady_clock::now();
   float ms = 0.f;
   const uint32_t burst = 8;
-#define NVDB_CLK_LAUNCH(V)                                                                                                       \
-  {                                                                                                                              \
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(filter_f16_m16_kernel<768, 6, true, true, V>),                   \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));                           \
-    for (uint32_t r = 0; r < burst; ++r) {                                                                                       \
-      HIPCHK(c, hipMemsetAsync(c->prog.p, 0xFF, prog_bytes, c->stream));                                                         \
-      filter_f16_m16_kernel<768, 6, true, true, V><<<nwg, 256, lds, c->stream>>>(                                                \
-          static_cast<const _Float16*>(c->rows), 0, n_al, static_cast<const _Float16*>(c->q16.p), nq, QT,                        \
-          static_cast<const float*>(inf.p), static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p),        \
-          static_cast<Hit*>(c->hitlog.p), scatter_args(c, c->last_cap), static_cast<uint32_t*>(c->prog.p),                       \
-          static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead));                                \
-    }                                                                                                                            \
-  }
+  auto burst_of = [&](auto kern, uint32_t waves) -> nvdb_status {      // stamped builds on `waves` waves per workgroup (tiles in identity order)
+    for (uint32_t r = 0; r < burst; ++r) {
+      HIPCHK(c, hipMemsetAsync(c->prog.p, 0xFF, prog_bytes, c->stream));
+      if ((st = launch_filter_f16_kernel(c, f, kern, nwg, FilterGeom{64 * waves, filter_f16_m16_lds_bytes<768>(), waves, false}, &c->hitlog, 0,
+                                         static_cast<uint32_t*>(c->prog.p), static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead)))) return st;
+    }
+    return NVDB_OK;
+  };
   for (;;) {                                       // back-to-back launches until `seconds` have passed, the last 8 timed
     const bool last = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_start).count() >= seconds;
     if (last) HIPCHK(c, hipEventRecord(e0, c->stream));
     switch (variant) {
-      case 0: NVDB_CLK_LAUNCH(0) break;
-      case 1: NVDB_CLK_LAUNCH(1) break;
-      case 5: NVDB_CLK_LAUNCH(5) break;
-      case 15: NVDB_CLK_LAUNCH(15) break;
-      case 16: NVDB_CLK_LAUNCH(16) break;
-      case 17: NVDB_CLK_LAUNCH(17) break;
-      case 20: {                                  // the 8-wave production build (two waves per SIMD, 32 queries each), stamped
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(filter_f16_m16_kernel<768, 4, true, true, 0, 2, 2, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        if ((st = ensure(c, c->hitlog, static_cast<size_t>(nwg) * 8 * FILTER_LOGCAP * sizeof(Hit)))) return st;
-        for (uint32_t r = 0; r < burst; ++r) {
-          HIPCHK(c, hipMemsetAsync(c->prog.p, 0xFF, prog_bytes, c->stream));
-          filter_f16_m16_kernel<768, 4, true, true, 0, 2, 2, 8><<<nwg, 512, lds, c->stream>>>(
-              static_cast<const _Float16*>(c->rows), 0, n_al, static_cast<const _Float16*>(c->q16.p), nq, QT,
-              static_cast<const float*>(inf.p), static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p),
-              static_cast<Hit*>(c->hitlog.p), scatter_args(c, c->last_cap), static_cast<uint32_t*>(c->prog.p),
-              static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead));
-        }
-      } break;
+      case 0: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 0>, 4); break;
+      case 1: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 1>, 4); break;
+      case 5: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 5>, 4); break;
+      case 15: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 15>, 4); break;
+      case 16: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 16>, 4); break;
+      case 17: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 17>, 4); break;
+      case 20: st = burst_of(filter_f16_m16_kernel<768, 4, true, true, 0, 2, 2, 8>, 8); break;   // the 8-wave production build (two waves per SIMD, 32 queries each), stamped
       default: return fail(c, NVDB_ERR_INVALID, "debug: unknown variant");
     }
-    HIPCHK(c, hipGetLastError());
+    if (st) return st;
     if (last) {
       HIPCHK(c, hipEventRecord(e1, c->stream));
       HIPCHK(c, hipEventSynchronize(e1));
@@ -137,7 +115,6 @@ nvdb_status nvdb_hip_debug_clock(nvdb_hip_ctx* c, int variant, uint32_t nq, floa
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-#undef NVDB_CLK_LAUNCH
   std::vector<uint64_t> stamps(static_cast<size_t>(nwg) * 2);
   HIPCHK(c, hipMemcpy(stamps.data(), static_cast<const char*>(c->prog.p) + prog_bytes, stamp_bytes, hipMemcpyDeviceToHost));
   std::vector<float> ghz;
@@ -172,90 +149,55 @@ nvdb_status nvdb_hip_debug_clock_i8(nvdb_hip_ctx* c, int variant, uint32_t nq, f
   if (nq <= 128 || nq > (c->last_nq + 255u) / 256u * 256u) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: 128 < nq <= the last search's padded batch");
   HIPCHK(c, hipSetDevice(c->device));
   const uint32_t QT = (nq + 255) / 256, nq_pad = QT * 256;
-  const uint32_t nwg = (static_cast<uint32_t>(c->num_cu) / QT) * QT;
-  if (nwg == 0 || (nwg & 7u) || ((nwg >> 3) % QT)) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: batch does not map onto the XCD-aware grid");
+  const uint32_t nwg = filter_grid(c, QT);
+  if (!xcd_aware_grid(QT, nwg)) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: batch does not map onto the XCD-aware grid");
   // thresholds: the ones the last search ended with (realistic stage-1 / stage-2 rates for the production variant)
   const size_t prog_bytes = static_cast<size_t>(nwg) * 8 * 4, stamp_bytes = static_cast<size_t>(nwg) * 16;
   nvdb_status st;
   if ((st = ensure(c, c->prog, std::max(prog_bytes + stamp_bytes, static_cast<size_t>(PROG_SLOTS) * c->num_cu * 8 * 4)))) return st;
-  if ((st = ensure(c, c->hitlog, static_cast<size_t>(nwg) * 8 * FILTER_LOGCAP * sizeof(Hit)))) return st;
-  constexpr size_t lds = static_cast<size_t>(3) * (I8W_TILE_ROWS * 768 + 4 * 1024) + 4096;
   const uint64_t n_dbg = c->dbg_rows > 0 ? std::min<uint64_t>(c->n, static_cast<uint64_t>(c->dbg_rows)) : c->n;
   const uint32_t n_al = static_cast<uint32_t>(n_dbg / I8W_TILE_ROWS * I8W_TILE_ROWS);
-  const signed char* qhi = static_cast<const signed char*>(c->q16.p);
-  const signed char* qlo = qhi + static_cast<size_t>(nq_pad) * 768;
+  const FilterCall f{c->stream, 0, n_al, nq, QT, c->last_cap, static_cast<const float*>(c->thr.p)};
+  const SyncArgs sy{static_cast<uint32_t*>(c->prog.p), static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead)};
   hipEvent_t e0, e1;
   HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
   const auto t_start = std::chrono::steady_clock::now();
   float ms = 0.f;
   const uint32_t burst = 8;
-#define NVDB_CLK_I8(V)                                                                                                           \
-  {                                                                                                                              \
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(filter_i8w_kernel<768, 2, 6, true, 2, true, V>),                 \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));                           \
-    for (uint32_t r = 0; r < burst; ++r) {                                                                                       \
-      HIPCHK(c, hipMemsetAsync(c->prog.p, 0xFF, prog_bytes, c->stream));                                                         \
-      filter_i8w_kernel<768, 2, 6, true, 2, true, V><<<nwg, 256, lds, c->stream>>>(                                              \
-          filter_rows_i8(c), filter_scales_i8(c), 0, n_al, qhi, qlo, nq, QT, static_cast<const float*>(c->thr.p),                \
-          static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p), static_cast<const float*>(c->qdelta.p),  \
-          static_cast<Hit*>(c->hitlog.p), scatter_args(c, c->last_cap, I8W_TILE_ROWS), static_cast<uint32_t*>(c->prog.p),        \
-          static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead), static_cast<uint32_t*>(c->misc.p) + 4);  \
-    }                                                                                                                            \
-  }
+  auto burst_of = [&](auto kern, uint32_t waves, size_t lds) -> nvdb_status {      // stamped builds (the log sized for 8 waves per workgroup, as the product's launches)
+    for (uint32_t r = 0; r < burst; ++r) {
+      HIPCHK(c, hipMemsetAsync(c->prog.p, 0xFF, prog_bytes, c->stream));
+      if ((st = launch_filter_i8w_kernel(c, f, kern, nwg, FilterGeom{64 * waves, lds, 8, false}, static_cast<size_t>(nq_pad) * 768, I8W_TILE_ROWS, sy))) return st;
+    }
+    return NVDB_OK;
+  };
   for (;;) {
     const bool last = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_start).count() >= seconds;
     if (last) { HIPCHK(c, hipMemsetAsync(static_cast<uint32_t*>(c->misc.p) + 4, 0, 8, c->stream)); HIPCHK(c, hipEventRecord(e0, c->stream)); }
     switch (variant) {
-      case 0: NVDB_CLK_I8(0) break;
-      case 1: NVDB_CLK_I8(1) break;
-      case 2: NVDB_CLK_I8(2) break;
-      case 3: NVDB_CLK_I8(3) break;
-#define NVDB_CLK_I8P(V, DF)                                                                                                      \
-      {                                                                                                                          \
-        constexpr size_t ldsp = static_cast<size_t>(3) * (I8W_TILE_ROWS * 768 + 4 * 256) + (DF ? 16 * 768 : 0);                  \
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(filter_i8p_kernel<768, true, true, 6, V, 4, DF>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsp))); \
-        for (uint32_t r = 0; r < burst; ++r) {                                                                                   \
-          HIPCHK(c, hipMemsetAsync(c->prog.p, 0xFF, prog_bytes, c->stream));                                                     \
-          filter_i8p_kernel<768, true, true, 6, V, 4, DF><<<nwg, 256, ldsp, c->stream>>>(                                               \
-              filter_rows_i8(c), filter_scales_i8(c), 0, n_al, qhi, qlo, nq, QT, static_cast<const float*>(c->thr.p),            \
-              static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p), static_cast<const float*>(c->qdelta.p), \
-              static_cast<Hit*>(c->hitlog.p), scatter_args(c, c->last_cap, I8W_TILE_ROWS), static_cast<uint32_t*>(c->prog.p),    \
-              static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead), static_cast<uint32_t*>(c->misc.p) + 4); \
-        }                                                                                                                        \
-      }
-      case 10: NVDB_CLK_I8P(0, true) break;             // the software-pipelined production build, stamped
-      case 11: NVDB_CLK_I8P(1, true) break;             // ... its structure alone: no test, no rare path
-      case 12: NVDB_CLK_I8P(2, true) break;             // ... test in the MFMA shadow, rare path never taken
-      case 13: NVDB_CLK_I8P(3, true) break;             // ... rare path, deferred values never consumed
-      case 14: NVDB_CLK_I8P(4, true) break;             // ... rare path entered and left at once
-      case 15: NVDB_CLK_I8P(5, true) break;             // ... production loop, cycles inside rare_path / consume_slots (wave 0 of every workgroup)
-#define NVDB_CLK_I8S(V) NVDB_CLK_I8SW(V, 4)
-#define NVDB_CLK_I8SW(V, W)                                                                                                      \
-      {                                                                                                                          \
-        constexpr size_t ldss = static_cast<size_t>(3) * (I8W_TILE_ROWS * 768 + W * 256);                                        \
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(filter_i8s_kernel<768, true, true, 6, V, W>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldss))); \
-        for (uint32_t r = 0; r < burst; ++r) {                                                                                   \
-          HIPCHK(c, hipMemsetAsync(c->prog.p, 0xFF, prog_bytes, c->stream));                                                     \
-          filter_i8s_kernel<768, true, true, 6, V, W><<<nwg, 64 * W, ldss, c->stream>>>(                                         \
-              filter_rows_i8(c), filter_scales_i8(c), 0, n_al, qhi, qlo, nq, QT, static_cast<const float*>(c->thr.p),            \
-              static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p), static_cast<const float*>(c->qdelta.p), \
-              static_cast<Hit*>(c->hitlog.p), scatter_args(c, c->last_cap, I8W_TILE_ROWS), static_cast<uint32_t*>(c->prog.p),    \
-              static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead), static_cast<uint32_t*>(c->misc.p) + 4); \
-        }                                                                                                                        \
-      }
-      case 30: NVDB_CLK_I8S(0) break;                // the 16x16x64 build (kernels_filter_i8s.h), stamped
-      case 31: NVDB_CLK_I8S(1) break;                // ... its structure alone: no test, nothing logged
-      case 32: NVDB_CLK_I8S(2) break;                // ... test, nothing logged
-      case 33: NVDB_CLK_I8S(3) break;                // ... structure alone without the in-loop LDS-DMA issue
-      case 34: NVDB_CLK_I8S(4) break;                // ... structure alone without the A-fragment LDS reads
-      case 35: NVDB_CLK_I8SW(0, 8) break;            // the 8-wave 16x16x64 build, stamped
-      case 36: NVDB_CLK_I8SW(1, 8) break;            // ... its structure alone
-      case 20: NVDB_CLK_I8P(0, false) break;         // the default build (first-stage survivors logged, finished after the stream), stamped
-      case 22: NVDB_CLK_I8P(2, false) break;         // ... test, nothing logged
-      case 24: NVDB_CLK_I8P(4, false) break;         // ... logging entered and left at once
+      case 0: st = burst_of(filter_i8w_kernel<768, 2, 6, true, 2, true, 0>, 4, filter_i8w_lds_bytes<768, 2>()); break;
+      case 1: st = burst_of(filter_i8w_kernel<768, 2, 6, true, 2, true, 1>, 4, filter_i8w_lds_bytes<768, 2>()); break;
+      case 2: st = burst_of(filter_i8w_kernel<768, 2, 6, true, 2, true, 2>, 4, filter_i8w_lds_bytes<768, 2>()); break;
+      case 3: st = burst_of(filter_i8w_kernel<768, 2, 6, true, 2, true, 3>, 4, filter_i8w_lds_bytes<768, 2>()); break;
+      case 10: st = burst_of(filter_i8p_kernel<768, true, true, 6, 0, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // the software-pipelined production build, stamped
+      case 11: st = burst_of(filter_i8p_kernel<768, true, true, 6, 1, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // ... its structure alone: no test, no rare path
+      case 12: st = burst_of(filter_i8p_kernel<768, true, true, 6, 2, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // ... test in the MFMA shadow, rare path never taken
+      case 13: st = burst_of(filter_i8p_kernel<768, true, true, 6, 3, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // ... rare path, deferred values never consumed
+      case 14: st = burst_of(filter_i8p_kernel<768, true, true, 6, 4, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // ... rare path entered and left at once
+      case 15: st = burst_of(filter_i8p_kernel<768, true, true, 6, 5, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // ... production loop, cycles inside rare_path / consume_slots (wave 0 of every workgroup)
+      case 30: st = burst_of(filter_i8s_kernel<768, true, true, 6, 0, 4>, 4, filter_i8s_lds_bytes<768, 4>()); break;   // the 16x16x64 build (kernels_filter_i8s.h), stamped
+      case 31: st = burst_of(filter_i8s_kernel<768, true, true, 6, 1, 4>, 4, filter_i8s_lds_bytes<768, 4>()); break;   // ... its structure alone: no test, nothing logged
+      case 32: st = burst_of(filter_i8s_kernel<768, true, true, 6, 2, 4>, 4, filter_i8s_lds_bytes<768, 4>()); break;   // ... test, nothing logged
+      case 33: st = burst_of(filter_i8s_kernel<768, true, true, 6, 3, 4>, 4, filter_i8s_lds_bytes<768, 4>()); break;   // ... structure alone without the in-loop LDS-DMA issue
+      case 34: st = burst_of(filter_i8s_kernel<768, true, true, 6, 4, 4>, 4, filter_i8s_lds_bytes<768, 4>()); break;   // ... structure alone without the A-fragment LDS reads
+      case 35: st = burst_of(filter_i8s_kernel<768, true, true, 6, 0, 8>, 8, filter_i8s_lds_bytes<768, 8>()); break;   // the 8-wave 16x16x64 build, stamped
+      case 36: st = burst_of(filter_i8s_kernel<768, true, true, 6, 1, 8>, 8, filter_i8s_lds_bytes<768, 8>()); break;   // ... its structure alone
+      case 20: st = burst_of(filter_i8p_kernel<768, true, true, 6, 0, 4, false>, 4, filter_i8p_lds_bytes<768, 4, false>()); break;   // the default build (first-stage survivors logged, finished after the stream), stamped
+      case 22: st = burst_of(filter_i8p_kernel<768, true, true, 6, 2, 4, false>, 4, filter_i8p_lds_bytes<768, 4, false>()); break;   // ... test, nothing logged
+      case 24: st = burst_of(filter_i8p_kernel<768, true, true, 6, 4, 4, false>, 4, filter_i8p_lds_bytes<768, 4, false>()); break;   // ... logging entered and left at once
       default: return fail(c, NVDB_ERR_INVALID, "debug: unknown variant");
     }
-    HIPCHK(c, hipGetLastError());
+    if (st) return st;
     if (last) {
       HIPCHK(c, hipEventRecord(e1, c->stream));
       HIPCHK(c, hipEventSynchronize(e1));
@@ -265,10 +207,6 @@ nvdb_status nvdb_hip_debug_clock_i8(nvdb_hip_ctx* c, int variant, uint32_t nq, f
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-#undef NVDB_CLK_I8
-#undef NVDB_CLK_I8P
-#undef NVDB_CLK_I8S
-#undef NVDB_CLK_I8SW
   std::vector<uint64_t> stamps(static_cast<size_t>(nwg) * 2);
   HIPCHK(c, hipMemcpy(stamps.data(), static_cast<const char*>(c->prog.p) + prog_bytes, stamp_bytes, hipMemcpyDeviceToHost));
   std::vector<float> ghz;

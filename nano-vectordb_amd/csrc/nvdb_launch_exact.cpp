@@ -59,10 +59,7 @@ nvdb_status launch_scan_exact_mfma(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_
       uint32_t P = std::max<uint32_t>(1, (static_cast<uint32_t>(c->opt_exact_wgs) * static_cast<uint32_t>(c->num_cu)) / gy);                                  \
       P = std::max<uint32_t>(1, std::min(std::min(P, std::max<uint32_t>(1, tiles / 8)), pmax));                                    \
       const void* fn = reinterpret_cast<const void*>(exact_mfma_lds_kernel<DT, D, false>);                                         \
-      if (!c->lds_attr_set.count(fn)) {                                                                                            \
-        HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, exact_lds_bytes<DT, D>()));                  \
-        c->lds_attr_set.insert(fn);                                                                                                \
-      }                                                                                                                            \
+      if (nvdb_status ls = raise_lds_limit(c, fn, exact_lds_bytes<DT, D>())) return ls;                                            \
       exact_mfma_lds_kernel<DT, D, false><<<dim3(P, gy), 256, exact_lds_bytes<DT, D>(), s>>>(c->rows, c->scales, row_lo, row_hi, q32, gy * 64, k, thr, \
                                                                                              cand, cnt, cap, ovf, nullptr, 0);     \
       HIPCHK(c, hipGetLastError());                                                                                                \
@@ -78,10 +75,7 @@ nvdb_status launch_scan_exact_mfma(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_
       uint32_t P = std::max<uint32_t>(1, (static_cast<uint32_t>(c->opt_exact_wgs) * static_cast<uint32_t>(c->num_cu)) / gy);                                  \
       P = std::max<uint32_t>(1, std::min(std::min(P, std::max<uint32_t>(1, tiles / 8)), pmax));                                    \
       const void* fn = reinterpret_cast<const void*>(exact_mfma_img_kernel<DT, D, false>);                                         \
-      if (!c->lds_attr_set.count(fn)) {                                                                                            \
-        HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, exact_img_bytes<DT, D>()));                  \
-        c->lds_attr_set.insert(fn);                                                                                                \
-      }                                                                                                                            \
+      if (nvdb_status ls = raise_lds_limit(c, fn, exact_img_bytes<DT, D>())) return ls;                                            \
       exact_mfma_img_kernel<DT, D, false><<<dim3(P, gy), 256, exact_img_bytes<DT, D>(), s>>>(c->rows, c->scales, row_lo, row_hi, q32, gy * 64, k, thr, \
                                                                                              cand, cnt, cap, ovf, nullptr, 0);     \
       HIPCHK(c, hipGetLastError());                                                                                                \
@@ -150,10 +144,7 @@ nvdb_status launch_scan_exact(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, u
 nvdb_status launch_select(nvdb_hip_ctx* c, hipStream_t s, uint32_t nq, uint32_t cap, uint32_t k, const float* slack,
                           int mode, uint64_t* out_ids, float* out_scores, uint32_t out_k) {
   const void* fn = reinterpret_cast<const void*>(select_kernel);
-  if (!c->lds_attr_set.count(fn)) {
-    HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SELECT_MAX_CAP * sizeof(Cand)));
-    c->lds_attr_set.insert(fn);
-  }
+  if (nvdb_status ls = raise_lds_limit(c, fn, SELECT_MAX_CAP * sizeof(Cand))) return ls;
   // the bitonic branch pads a list to the next power of two >= its length (<= cap): size the LDS for that
   uint32_t cap2 = 1;
   while (cap2 < cap) cap2 <<= 1;
@@ -189,10 +180,8 @@ nvdb_status launch_rescore(nvdb_hip_ctx* c, hipStream_t s, const float* q32, uin
     }
     const void* fn = c->dtype == NVDB_DTYPE_F32 ? reinterpret_cast<const void*>(rescore_lds_kernel<DT_F32>)
                    : c->dtype == NVDB_DTYPE_F16 ? reinterpret_cast<const void*>(rescore_lds_kernel<DT_F16>) : reinterpret_cast<const void*>(rescore_lds_kernel<DT_I8>);
-    if (lds > 48 * 1024 && !c->lds_attr_set.count(fn)) {
-      HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(SELECT_MAX_CAP * sizeof(Cand))));
-      c->lds_attr_set.insert(fn);
-    }
+    if (lds > 48 * 1024)
+      if (nvdb_status ls = raise_lds_limit(c, fn, SELECT_MAX_CAP * sizeof(Cand))) return ls;
     if (c->dtype == NVDB_DTYPE_F32) rescore_lds_kernel<DT_F32><<<nq, 256, lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot, cpp, fs);
     else if (c->dtype == NVDB_DTYPE_F16) rescore_lds_kernel<DT_F16><<<nq, 256, lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot, cpp, fs);
     else rescore_lds_kernel<DT_I8><<<nq, 256, lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot, cpp, fs);
@@ -244,10 +233,7 @@ nvdb_status launch_scores_exact_mfma(nvdb_hip_ctx* c, hipStream_t s, const float
       uint32_t P = std::max<uint32_t>(1, (2u * static_cast<uint32_t>(c->num_cu)) / gy);                                  \
       P = std::max<uint32_t>(1, std::min(P, std::max<uint32_t>(1, tiles / 8)));                                                    \
       const void* fn = reinterpret_cast<const void*>(exact_mfma_lds_kernel<DT, D, true>);                                          \
-      if (!c->lds_attr_set.count(fn)) {                                                                                            \
-        HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, exact_lds_bytes<DT, D>()));                  \
-        c->lds_attr_set.insert(fn);                                                                                                \
-      }                                                                                                                            \
+      if (nvdb_status ls = raise_lds_limit(c, fn, exact_lds_bytes<DT, D>())) return ls;                                            \
       exact_mfma_lds_kernel<DT, D, true><<<dim3(P, gy), 256, exact_lds_bytes<DT, D>(), s>>>(c->rows, c->scales, 0u, n, q32, gy * 64, 0u, nullptr, \
                                                                                             nullptr, nullptr, 0u, nullptr, out, ld);   \
       HIPCHK(c, hipGetLastError());                                                                                                \
@@ -261,10 +247,7 @@ nvdb_status launch_scores_exact_mfma(nvdb_hip_ctx* c, hipStream_t s, const float
       uint32_t P = std::max<uint32_t>(1, (2u * static_cast<uint32_t>(c->num_cu)) / gy);                                  \
       P = std::max<uint32_t>(1, std::min(P, std::max<uint32_t>(1, tiles / 8)));                                                    \
       const void* fn = reinterpret_cast<const void*>(exact_mfma_img_kernel<DT, D, true>);                                          \
-      if (!c->lds_attr_set.count(fn)) {                                                                                            \
-        HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, exact_img_bytes<DT, D>()));                  \
-        c->lds_attr_set.insert(fn);                                                                                                \
-      }                                                                                                                            \
+      if (nvdb_status ls = raise_lds_limit(c, fn, exact_img_bytes<DT, D>())) return ls;                                            \
       exact_mfma_img_kernel<DT, D, true><<<dim3(P, gy), 256, exact_img_bytes<DT, D>(), s>>>(c->rows, c->scales, 0u, n, q32, gy * 64, 0u, nullptr, \
                                                                                             nullptr, nullptr, 0u, nullptr, out, ld);   \
       HIPCHK(c, hipGetLastError());                                                                                                \
@@ -335,10 +318,7 @@ nvdb_status search_largek(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, ui
   RadixState* rst = static_cast<RadixState*>(c->lk_state.p);
   if (K2 <= 8192) {
     const void* fn = reinterpret_cast<const void*>(bitonic_lds_kernel);
-    if (!c->lds_attr_set.count(fn)) {
-      HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
-      c->lds_attr_set.insert(fn);
-    }
+    if (nvdb_status ls = raise_lds_limit(c, fn, 8192 * 8)) return ls;
   }
   for (uint32_t q0 = 0; q0 < nq; q0 += QB) {
     const uint32_t b = std::min(QB, nq - q0);

@@ -60,20 +60,12 @@ size_t parts_lds(uint32_t dim, uint32_t row_bytes, uint32_t qw, bool staged) {
   return PART_WAVES * qw * qstride * 4 + (staged ? static_cast<size_t>(PART_TILE_ROWS) * part_pitch(row_bytes) : 0);
 }
 
-nvdb_status raise_lds(nvdb_hip_ctx* c, const void* fn, size_t lds) {
-  if (lds > 64 * 1024 && !c->lds_attr_set.count(fn)) {
-    HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(PART_LDS_LIMIT)));
-    c->lds_attr_set.insert(fn);
-  }
-  return NVDB_OK;
-}
-
 template <int DT, int QW, bool AL, bool ST>
 nvdb_status launch_one(nvdb_hip_ctx* c, hipStream_t s, const PartItem* items, uint32_t nitems, const uint32_t* qidx, const uint32_t* dst,
                        const float* q32, uint32_t k, Cand* cand) {
   const size_t lds = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), QW, ST);
-  nvdb_status st = raise_lds(c, reinterpret_cast<const void*>(scan_parts_kernel<DT, QW, AL, ST>), lds);
-  if (st) return st;
+  if (lds > 64 * 1024)
+    if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(scan_parts_kernel<DT, QW, AL, ST>), PART_LDS_LIMIT)) return st;
   scan_parts_kernel<DT, QW, AL, ST><<<nitems, PART_THREADS, lds, s>>>(c->rows, c->scales, c->dim, items, qidx, dst, q32, k, cand);
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;

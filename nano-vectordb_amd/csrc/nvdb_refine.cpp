@@ -15,14 +15,6 @@ static nvdb_status refine_args(nvdb_hip_ctx* c, const void* q, const void* cand,
   return NVDB_OK;
 }
 
-static nvdb_status raise_lds_limit(nvdb_hip_ctx* c, const void* fn, size_t lds) {
-  if (!c->lds_attr_set.count(fn)) {
-    HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    c->lds_attr_set.insert(fn);
-  }
-  return NVDB_OK;
-}
-
 // dbg != nullptr: the stamped twin of the kernel chosen below (same arithmetic, same results; wave 0 of the first dbg_q
 // workgroups writes its phase cycles to dbg[3q ..]).
 static nvdb_status launch_refine(nvdb_hip_ctx* c, hipStream_t s, const float* dq, const uint32_t* dc, uint32_t Q, uint32_t R,

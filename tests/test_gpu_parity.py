@@ -188,6 +188,38 @@ def test_filter_path_mfma16_variant_matches_default(ctx_dev, oracle):
     _check_against_oracle(oracle, base, po.DT_F16, None, queries, res[1][0], res[1][1], k, "mfma16")
 
 
+@pytest.mark.parametrize("tag,d,nq", [("f16", 768, 300), ("f16", 384, 300), ("f16", 1024, 200), ("f16", 1152, 200), ("f16", 2048, 100),
+                                      ("i8", 768, 300), ("i8", 1024, 200)])
+def test_filter_launch_options_leave_the_results_unchanged(ctx, oracle, tag, d, nq):
+    """Two query tiles per row stream (QT == 2: 256 / 128 / 64 queries per workgroup), so the sibling rendezvous applies on a
+    256-CU grid.  Options sibling_sync (the SYNC = false instantiation of every build) and, for fp16, waves8 (8-wave build /
+    4-wave sync build; d = 1152 has no 8-wave build) choose between launches that must log the same survivors: ids and score
+    bits are identical across the grid and match the CPU path."""
+    n, k = 40000, 10
+    dt, odt = (nvdb_amd.DT_F16, po.DT_F16) if tag == "f16" else (nvdb_amd.DT_I8, po.DT_I8)
+    ctx.generate_corpus(SEED + 120, n, d, dt)
+    base, scales = nvdb_amd.synth_corpus(SEED + 120, 0, n, d, dt)
+    queries = nvdb_amd.synth_rows_f32(SEED + 121, 0, nq, d)
+    grid = [(sync, w8) for sync in (1, 0) for w8 in ((1, 0) if tag == "f16" else (1,))]
+    ctx.set_option("path", 2)
+    res = {}
+    try:
+        for sync, w8 in grid:
+            ctx.set_option("sibling_sync", sync)
+            ctx.set_option("waves8", w8)
+            res[sync, w8] = ctx.search_batch(queries, k)
+            st = ctx.stats()
+            assert st["path"] == 2 and st["bound_violations"] == 0 and st["overflow_queries"] == 0, (sync, w8, st)
+    finally:
+        ctx.set_option("sibling_sync", 1)
+        ctx.set_option("waves8", 1)
+        ctx.set_option("path", 0)
+    ids, sc = res[grid[0]]
+    for key in grid[1:]:
+        assert np.array_equal(res[key][0], ids) and np.array_equal(res[key][1].view(np.uint32), sc.view(np.uint32)), key
+    _check_against_oracle(oracle, base, odt, scales, queries[:8], ids[:8], sc[:8], k, f"launch-options/{tag}/d{d}")
+
+
 @pytest.mark.parametrize("nq,k,d", [(64, 10, 768), (300, 10, 768), (40, 64, 256)])
 def test_filter_path_int8_matches_oracle(ctx, oracle, nq, k, d):
     """int8(+scale) corpus on the integer matrix cores (two-plane int8 query), exact rescore in the
