@@ -47,6 +47,39 @@ uint32_t nvdb_permuted_tile(uint32_t g, uint32_t n_tiles);
  * Developer option "debug_rows" (nvdb_hip_set_option, this build only): the launches cover rows [0, debug_rows) instead of the corpus. */
 nvdb_status nvdb_hip_debug_clock_i8(nvdb_hip_ctx* ctx, int variant, uint32_t nq, float seconds, float* out4);
 
+/* What one flat search of nq queries for the k best would do on a corpus of the given shape -- the plan the search entry
+ * points compute before their first launch (csrc/nvdb_plan.h), for a context described by plain numbers.  Needs NO device.
+ * The options are applied through nvdb_hip_set_option itself, so ranges and developer-only keys behave as in a real context. */
+typedef struct nvdb_hip_plan_shape {
+  uint64_t n;
+  uint32_t dim, fdim, dtype;                  /* fdim: the dim the filter kernels run at (== dim without a padded shadow) */
+  uint32_t owned, has_shadow16, has_shadow8, q8shadow, i8_scales_signed;
+  uint32_t num_cu, cap_hint;
+} nvdb_hip_plan_shape;
+
+typedef struct nvdb_hip_plan_option { const char* key; int64_t value; } nvdb_hip_plan_option;
+
+#define NVDB_PLAN_MAX_CHUNKS 64
+typedef struct nvdb_hip_plan {
+  uint32_t route;                             /* 1 exact, 2 filter, 3 any-k: nvdb_hip_scan_stats.path of the search */
+  uint32_t prep, prep_inits, k_wide;          /* prep: the filter flow's prep launch runs (also ahead of an any-k search the bootstrap rules sent there) */
+  uint32_t k_eff, cap, QPB, QT, nq_pad, prog_words;
+  uint32_t head;                              /* exact route: rows of the prescan (0: one scan) */
+  uint32_t padded, perm_on;
+  uint32_t boot;                              /* filter route: 0 MFMA bootstrap, 1 exact chunk [0, r0), 2 any-k machinery seeding the lists from [0, r0) */
+  uint32_t tile_rows, n_al, growth, boot_tiles, boot_rows, r0, tail_exact;
+  uint32_t helper_tile_rows;                  /* what the launchers' shared helper says a tile of this shape holds */
+  uint32_t n_chunks;                          /* filter route: the filter launches, [chunk_lo[i], chunk_hi[i]) */
+  uint32_t chunk_lo[NVDB_PLAN_MAX_CHUNKS], chunk_hi[NVDB_PLAN_MAX_CHUNKS];
+  uint32_t stat_chunks;                       /* nvdb_hip_scan_stats.chunks / .rows_scanned the search will report (any-k: for a batch */
+  uint64_t stat_rows_scanned;                 /* whose score matrix fits the HBM budget in one piece -- only the device knows) */
+} nvdb_hip_plan;
+
+/* err (may be NULL): err_len bytes for the message of a status != NVDB_OK -- a rejected option, an unsupported shape
+ * (the search's own message), more than NVDB_PLAN_MAX_CHUNKS chunks. */
+nvdb_status nvdb_hip_debug_plan(const nvdb_hip_plan_shape* shape, const nvdb_hip_plan_option* opts, uint32_t n_opts, uint32_t nq, uint32_t k,
+                                int force_path, uint32_t cap_override, nvdb_hip_plan* out, char* err, size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif

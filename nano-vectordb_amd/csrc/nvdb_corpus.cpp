@@ -398,12 +398,8 @@ nvdb_status nvdb_hip_get_stats(nvdb_hip_ctx* c, nvdb_hip_scan_stats* stats) {
   if (c->stats_lazy) {                             // the small-call path skips this read-back; do it now
     c->stats_lazy = false;
     unsigned long long tot = 0;
-    if (c->last_nq) {
-      HIPCHK(c, hipSetDevice(c->device));
-      std::vector<uint32_t> cn(c->last_nq);
-      HIPCHK(c, hipMemcpy(cn.data(), c->cnt.p, c->last_nq * 4, hipMemcpyDeviceToHost));
-      for (uint32_t v : cn) tot += std::min(v, c->last_cap);
-    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (nvdb_status st = sum_candidates(c, &tot)) return st;
     c->stats.candidates = tot;
   }
   *stats = c->stats;

@@ -2,7 +2,9 @@
 // translation unit uses, and the declarations of what one unit calls in another.  Not installed, not part of the boundary.
 //
 //   nvdb_corpus.cpp        create / destroy, corpus upload / adopt / generate (+ shadow copies, row-norm pass), options, statistics
-//   nvdb_search.cpp        orchestration of one flat search (search_core), the search entry points and their self-checks
+//   nvdb_plan.h            what one flat search will do (plan_search): route, list capacity, query tiling, bootstrap, chunk boundaries -- decided
+//                          before anything is enqueued, from corpus facts, options and the launchers' shape facts below; no HIP call
+//   nvdb_search.cpp        one flat search: plan -> workspace -> launches (search_core); the search entry points, their self-checks and retry ladder
 //   nvdb_launch_f16.cpp    launch helpers of the fp16 MFMA filter kernels (kernels_filter.h), query prep for them
 //   nvdb_launch_i8.cpp     ... of the int8 kernels (kernels_filter.h, kernels_filter_i8s.h)
 //   nvdb_launch_exact.cpp  ... of the exact fp32-order kernels, select / rescore / merge, the any-k path (kernels_exact*.h, kernels_largek.h)
@@ -97,7 +99,7 @@ struct nvdb_hip_ctx {
   void* pinned = nullptr;                           // pinned host staging of small calls: status words, results, queries
   void* pinned_dev = nullptr;                       // ... as the device addresses it (hipHostGetDevicePointer)
   size_t pinned_bytes = 0;
-  bool perm_on = false;                             // this search streams tiles in permuted order (set by search_core)
+  bool perm_on = false;                             // this search streams tiles in permuted order (search_core, from its plan)
   int64_t opt_tile_permute = 1;
   uint32_t cap_hint = 0;                            // this corpus has needed the longest candidate lists before: start with them
   bool stats_lazy = false;                          // stats.candidates not read back yet (nvdb_hip_get_stats does it)
@@ -241,6 +243,33 @@ inline uint32_t filter_nb(const nvdb_hip_ctx* c, uint32_t nq) {
   return nq <= 128 ? 1u : 2u;
 }
 
+// ---- shape facts of the filter builds: written here once, used by the launchers (nvdb_launch_f16.cpp, nvdb_launch_i8.cpp)
+// AND by plan_search (nvdb_plan.h), which sizes the query tiles and aligns the chunk boundaries with them ----
+// a corpus this library allocated (a shadow copy always is) is zero-padded to whole tiles
+inline bool corpus_padded(const nvdb_hip_ctx* c) { return c->owned || c->shadow16 != nullptr || c->shadow8 != nullptr; }
+// fp16, dims <= 768: batches > 128 (NB == 2) run the 16x16x32 build (developer library: unless option mfma16 = 0) ...
+inline bool f16_m16_build(const nvdb_hip_ctx* c, uint32_t nb) { return nb == 2 && c->opt_mfma16; }
+// ... whose tiles are MB 16-row blocks: 64-row tiles up to d = 384, 32-row tiles beyond
+constexpr uint32_t f16_m16_tile_rows(uint32_t dim) { return dim <= 384 ? 64u : 32u; }
+// the int8 two-stage kernel: 64-row tiles (two 32-row blocks) up to d = 768, 32-row tiles beyond
+constexpr uint32_t i8w_tile_rows(uint32_t dim) { return dim <= 768 ? I8W_TILE_ROWS : FILTER_ROWS; }
+// rows per tile of the build that streams this batch, as far as chunk boundaries care (the 16-row-tile fp16 builds of
+// dims > 768 take any multiple of 32)
+inline uint32_t filter_tile_rows(const nvdb_hip_ctx* c, uint32_t nq) {
+  if (filter_is_i8(c)) return i8_two_stage(c) ? i8w_tile_rows(c->fdim) : FILTER_ROWS;
+  return (c->fdim <= 768 && f16_m16_build(c, filter_nb(c, nq))) ? f16_m16_tile_rows(c->fdim) : FILTER_ROWS;
+}
+// queries per workgroup: fp16 64 on the K-split build (dims > 1536), 128 on the 16-row-tile build (768 < dim <= 1536), else and
+// for every int8 build 128 per 32-query block of a wave
+constexpr uint32_t f16_filter_qpb(uint32_t dim, uint32_t nb) { return dim > 1536 ? 64u : dim > 768 ? 128u : 128u * nb; }
+constexpr uint32_t f16_m16_qpb(uint32_t nqb, uint32_t wpb) { return 16u * nqb * wpb; }   // filter_f16_m16_kernel<.., NQB, WPB>: WPB waves x NQB 16-query blocks
+inline uint32_t filter_qpb(const nvdb_hip_ctx* c, uint32_t nq) { return filter_is_i8(c) ? 128u * filter_nb(c, nq) : f16_filter_qpb(c->fdim, filter_nb(c, nq)); }
+// int8 two-stage, dims <= 768: batches > 128 run a software-pipelined build (developer library: unless option i8_pipe = 0), which
+// logs the first stage's survivors and finishes them after the stream unless the second stage has to stay in the tile loop
+inline bool i8_pipelined(const nvdb_hip_ctx* c, uint32_t nb) { return nb == 2 && c->opt_i8_pipe; }
+inline bool i8_stage2_in_loop(const nvdb_hip_ctx* c) { return c->opt_i8_defer != 0 || c->i8_scales_signed; }
+inline bool i8_logs_survivors(const nvdb_hip_ctx* c, uint32_t nb) { return i8_pipelined(c, nb) && !i8_stage2_in_loop(c); }
+
 inline hipEvent_t get_event(nvdb_hip_ctx* c, size_t idx) {
   while (c->ev_pool.size() <= idx) { hipEvent_t e; (void)hipEventCreate(&e); c->ev_pool.push_back(e); }
   return c->ev_pool[idx];
@@ -269,6 +298,8 @@ void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace
 // nvdb_search.cpp
 nvdb_status next_prog_region(nvdb_hip_ctx* c, hipStream_t s, uint32_t nwg, uint32_t** out);
 ScatterArgs scatter_args(nvdb_hip_ctx* c, uint32_t cap, uint32_t trows = 0);
+float filter_events_ms(const nvdb_hip_ctx* c);                                 // sum over the last search's timed filter launches (ev_filter)
+nvdb_status sum_candidates(nvdb_hip_ctx* c, unsigned long long* total);         // list lengths the last thresholding select left, each capped at last_cap
 
 // ---- launching a filter kernel (nvdb_launch_f16.cpp, nvdb_launch_i8.cpp, nvdb_debug.cpp) ----------------------------
 // the dynamic-LDS limit of a kernel, raised once per kernel and device
@@ -328,6 +359,7 @@ nvdb_status launch_filter_kernel(nvdb_hip_ctx* c, hipStream_t s, void (*kern)(KA
 template <typename... KA, typename... Rest>
 nvdb_status launch_filter_f16_kernel(nvdb_hip_ctx* c, const FilterCall& f, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, DevBuf* log,
                                      uint32_t trows, Rest... rest) {
+  if (trows && (f.row_hi - f.row_lo) % trows) return fail(c, NVDB_ERR_INTERNAL, "fp16 filter kernel: row range is not a multiple of its tile");
   return launch_filter_kernel(c, f.s, kern, nwg, g, filter_rows_f16(c), f.row_lo, f.row_hi, static_cast<const _Float16*>(c->q16.p), f.nq, f.QT, f.thr,
                               static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p), log, scatter_args(c, f.cap, trows), rest...);
 }

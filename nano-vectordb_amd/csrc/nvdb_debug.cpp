@@ -1,7 +1,7 @@
 // nvdb_debug.cpp -- developer entry points (include/nvdb_hip_dev.h): stamped / ablation builds of the filter kernels, the device's
-// tile partition function.  Compiled into libnvdb_hip_dev.so only; the product library does not contain this file's code.
+// tile partition function, the plan of a search for a shape given as plain numbers (no device).  Compiled into libnvdb_hip_dev.so only; the product library does not contain this file's code.
 #ifdef NVDB_HIP_DEV
-#include "nvdb_ctx.h"
+#include "nvdb_plan.h"
 #include "kernels_filter_i8s.h"
 
 namespace {
@@ -262,6 +262,44 @@ nvdb_status nvdb_hip_debug_tile_ranges(nvdb_hip_ctx* c, uint32_t n_tiles, uint32
   HIPCHK(c, hipMemcpy(out_hi, hi, static_cast<size_t>(n_streams) * 4, hipMemcpyDeviceToHost));
   if (weights_out8) HIPCHK(c, hipMemcpy(weights_out8, w, 32, hipMemcpyDeviceToHost));
   HIPCHK(c, hipFree(buf.p));
+  return NVDB_OK;
+}
+
+// plan_search on a detached context: nothing here touches a device
+nvdb_status nvdb_hip_debug_plan(const nvdb_hip_plan_shape* shape, const nvdb_hip_plan_option* opts, uint32_t n_opts, uint32_t nq, uint32_t k,
+                                int force_path, uint32_t cap_override, nvdb_hip_plan* out, char* err, size_t err_len) {
+  if (!shape || !out || (n_opts && !opts) || !nq || !k || !shape->n) return NVDB_ERR_INVALID;
+  static _Float16 shadow16;                        // (the plan only asks whether a shadow exists)
+  static signed char shadow8;
+  nvdb_hip_ctx c;
+  c.n = shape->n; c.dim = shape->dim; c.fdim = shape->fdim; c.dtype = shape->dtype;
+  c.owned = shape->owned != 0; c.q8shadow = shape->q8shadow != 0; c.i8_scales_signed = shape->i8_scales_signed != 0;
+  if (shape->has_shadow16) c.shadow16 = &shadow16;
+  if (shape->has_shadow8) c.shadow8 = &shadow8;
+  c.num_cu = static_cast<int>(shape->num_cu); c.cap_hint = shape->cap_hint;
+  auto failed = [&](nvdb_status st, const char* msg) { if (err && err_len) std::snprintf(err, err_len, "%s", msg); return st; };
+  for (uint32_t i = 0; i < n_opts; ++i)
+    if (nvdb_status st = nvdb_hip_set_option(&c, opts[i].key, opts[i].value)) return failed(st, c.err.c_str());
+  SearchPlan p;
+  if (nvdb_status st = plan_search(c, nq, k, force_path, cap_override, p)) return failed(st, p.error);
+  *out = nvdb_hip_plan{};
+  out->route = p.route; out->prep = p.prep; out->prep_inits = p.prep_inits; out->k_wide = p.k_wide;
+  out->k_eff = p.k_eff; out->cap = p.cap; out->QPB = p.QPB; out->QT = p.QT; out->nq_pad = p.nq_pad; out->prog_words = p.prog_words;
+  out->head = p.head;
+  out->stat_chunks = p.route == ROUTE_EXACT && p.head ? 2 : 1;
+  out->stat_rows_scanned = c.n;
+  if (p.route != ROUTE_FILTER) return NVDB_OK;
+  out->padded = p.padded; out->perm_on = p.perm_on; out->boot = p.boot;
+  out->tile_rows = p.tile_rows; out->n_al = p.n_al; out->growth = p.growth; out->boot_tiles = p.boot_tiles; out->boot_rows = p.boot_rows;
+  out->r0 = p.r0; out->tail_exact = p.tail_exact;
+  out->helper_tile_rows = filter_tile_rows(&c, nq);
+  out->stat_rows_scanned = p.tail_exact ? (c.n - p.n_al) * p.QT : 0;
+  for (uint32_t r = p.r0; r < p.n_al; r = chunk_end(p, r)) {
+    if (out->n_chunks == NVDB_PLAN_MAX_CHUNKS) return failed(NVDB_ERR_INTERNAL, "plan: more than NVDB_PLAN_MAX_CHUNKS chunks");
+    out->chunk_lo[out->n_chunks] = r; out->chunk_hi[out->n_chunks++] = chunk_end(p, r);
+    out->stat_rows_scanned += static_cast<uint64_t>(chunk_end(p, r) - r) * p.QT;
+  }
+  out->stat_chunks = out->n_chunks;
   return NVDB_OK;
 }
 }  // extern "C"

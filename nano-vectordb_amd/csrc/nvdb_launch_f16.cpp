@@ -19,11 +19,13 @@ nvdb_status launch_prep_q16(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, 
 // queries per wave -- with siblings to keep in step its SYNC build, on 8 waves of 32 queries unless option waves8 = 0
 template <int DIM, int NB>
 nvdb_status launch_filter_dim(nvdb_hip_ctx* c, const FilterCall& f) {
-  constexpr int MBK = DIM <= 384 ? 4 : 2;                 // 16-row blocks per tile of the m16 build: 64-row tiles up to d=384
+  constexpr uint32_t TROWS = f16_m16_tile_rows(DIM);     // tile of the m16 build
+  constexpr int MBK = TROWS / 16;                         // ... in 16-row blocks
+  static_assert(f16_m16_qpb(2, 8) == f16_filter_qpb(DIM, 2) && f16_m16_qpb(4, 4) == f16_filter_qpb(DIM, 2), "m16 builds: queries per workgroup");
   // both builds of a dim are launched with the larger of their two carve-ups (they differ up to d=384)
   constexpr size_t lds = std::max(filter_f16_lds_bytes<DIM>(), filter_f16_m16_lds_bytes<DIM, MBK>());
 #ifdef NVDB_HIP_DEV
-  const bool m16 = (NB == 2) && c->opt_mfma16;           // developer build: option mfma16 = 0 selects the 32x32x16 build for batches > 128 (A/B only)
+  const bool m16 = f16_m16_build(c, NB);                 // developer build: option mfma16 = 0 selects the 32x32x16 build for batches > 128 (A/B only)
   constexpr bool HAS_WIDE32 = true;
 #else
   const bool m16 = (NB == 2);
@@ -39,15 +41,16 @@ nvdb_status launch_filter_dim(nvdb_hip_ctx* c, const FilterCall& f) {
   if ((st = sibling_sync_args(c, f.s, f.QT, nwg, sy))) return st;
   if constexpr (DIM <= 768)
     if (sy.prog && c->opt_waves8)
-      return launch_filter_f16_kernel(c, f, filter_f16_m16_kernel<DIM, 4, true, false, 0, MBK, 2, 8>, nwg, FilterGeom{512, lds, 8, true}, &c->hitlog, 16 * MBK,
+      return launch_filter_f16_kernel(c, f, filter_f16_m16_kernel<DIM, 4, true, false, 0, MBK, 2, 8>, nwg, FilterGeom{512, lds, 8, true}, &c->hitlog, TROWS,
                                       sy.prog, sy.mask, sy.lead);
   return launch_filter_f16_kernel(c, f, sy.prog ? filter_f16_m16_kernel<DIM, 6, true, false, 0, MBK> : filter_f16_m16_kernel<DIM, 6, false, false, 0, MBK>, nwg,
-                                  FilterGeom{256, lds, 4, true}, &c->hitlog, 16 * MBK, sy.prog, sy.mask, sy.lead);
+                                  FilterGeom{256, lds, 4, true}, &c->hitlog, TROWS, sy.prog, sy.mask, sy.lead);
 }
 
 // dims 2048 / 2560 / 3072: K-split build, 16-row tiles in two half-K stages, 16 queries per wave, 64 per workgroup
 template <int DIM>
 nvdb_status launch_filter_k2_dim(nvdb_hip_ctx* c, const FilterCall& f) {
+  static_assert(f16_filter_qpb(DIM, 1) == 4 * 16, "K-split build: 4 waves x 16 queries");
   const uint32_t nwg = filter_grid(c, f.QT);
   nvdb_status st;
   SyncArgs sy;
@@ -62,6 +65,7 @@ nvdb_status launch_filter_k2_dim(nvdb_hip_ctx* c, const FilterCall& f) {
 template <int DIM>
 nvdb_status launch_filter_k_dim(nvdb_hip_ctx* c, const FilterCall& f) {
   constexpr size_t lds = filter_f16_m16_lds_bytes<DIM, 1>();
+  static_assert(f16_m16_qpb(1, 8) == f16_filter_qpb(DIM, 1) && f16_m16_qpb(2, 4) == f16_filter_qpb(DIM, 1), "16-row-tile builds: queries per workgroup");
   const uint32_t nwg = filter_grid(c, f.QT);
   nvdb_status st;
   SyncArgs sy;

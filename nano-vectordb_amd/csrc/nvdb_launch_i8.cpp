@@ -42,18 +42,19 @@ template <int DIM, int WPB> auto i8s_build(bool sync) { return sync ? filter_i8s
 // and the developer library every build at every batch (options i8_pipe, i8_waves8, i8_mfma16, i8_small8).
 template <int DIM, int NB>
 nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t nq_pad) {
-  if ((f.row_hi - f.row_lo) % I8W_TILE_ROWS) return fail(c, NVDB_ERR_INTERNAL, "int8 two-stage kernel: row range is not a multiple of its 64-row tile");
+  constexpr uint32_t TROWS = i8w_tile_rows(DIM);
+  static_assert(TROWS == I8W_TILE_ROWS, "the builds of dims <= 768 stream two 32-row blocks per tile");
+  if ((f.row_hi - f.row_lo) % TROWS) return fail(c, NVDB_ERR_INTERNAL, "int8 two-stage kernel: row range is not a multiple of its 64-row tile");
+  const bool pipe = i8_pipelined(c, NB);                 // (developer build: i8_pipe = 0 runs filter_i8w_kernel at 64 queries per wave, i8_waves8 = 1 the 8-wave pipelined build)
+  const bool defer = i8_stage2_in_loop(c), logs = i8_logs_survivors(c, NB);
 #ifdef NVDB_HIP_DEV
-  const bool pipe = (NB == 2) && c->opt_i8_pipe;         // developer build: i8_pipe = 0 runs filter_i8w_kernel at 64 queries per wave, i8_waves8 = 1 the 8-wave pipelined build
   const bool w8 = pipe && c->opt_i8_waves8 && DIM != 384;
   constexpr bool HAS_I8W = true, HAS_I8P32 = true;
 #else
-  const bool pipe = (NB == 2);
   constexpr bool w8 = false;
   constexpr bool HAS_I8W = (NB == 1);                    // the product runs filter_i8w_kernel for batches <= 128 only
   constexpr bool HAS_I8P32 = (DIM < 384);                // ... and the 32x32x32 logged build only where the 16x16x64 build does not exist
 #endif
-  const bool defer = c->opt_i8_defer != 0 || c->i8_scales_signed;
   const uint32_t nwg = filter_grid(c, f.QT);
   nvdb_status st;
   SyncArgs sy;
@@ -61,7 +62,7 @@ nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t
   const bool sync = sy.prog != nullptr;
   // (every build's survivor log is sized for 8 waves per workgroup)
   auto launch = [&](auto kern, uint32_t waves, size_t lds) {
-    return launch_filter_i8w_kernel(c, f, kern, nwg, FilterGeom{64 * waves, lds, 8, true}, static_cast<size_t>(nq_pad) * DIM, I8W_TILE_ROWS, sy);
+    return launch_filter_i8w_kernel(c, f, kern, nwg, FilterGeom{64 * waves, lds, 8, true}, static_cast<size_t>(nq_pad) * DIM, TROWS, sy);
   };
   // batches <= 128 at d = 512 / 768: the 16x16x64 logged build on 8 waves of 32 queries (waves without queries only load): its first-stage
   // test rides in the MFMA shadow, so four busy waves stay inside the tile time the HBM stream allows (+6.5 % at batch 128,
@@ -73,7 +74,7 @@ nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t
   if constexpr (NB == 1 && DIM == 384)               // d = 384 has no 8-wave schedule: 64 < batch <= 128 on the 4-wave build, two waves without queries (+4 % at 128; equal at 64)
     if (c->opt_i8_small8 && !defer && f.QT == 1 && f.nq > 64)
       return launch(filter_i8s_kernel<DIM, false, false, 6, 0, 4>, 4, filter_i8s_lds_bytes<DIM, 4>());
-  if (pipe && !defer && c->opt_i8_mfma16) {
+  if (logs && c->opt_i8_mfma16) {
 #ifdef NVDB_HIP_DEV
     if constexpr (DIM == 768 || DIM == 512)            // the 16x16x64 build on 8 waves (run at d = 768 only; measured equal to 4 waves)
       if (w8 && DIM == 768) return launch(i8s_build<DIM, 8>(sync), 8, filter_i8s_lds_bytes<DIM, 8>());
@@ -97,13 +98,15 @@ nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t
 // the reference takes any dim (src/simd_dot.cpp:160-213)
 template <int DIM>
 nvdb_status launch_filter_i8w_big_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t nq_pad) {
-  if ((f.row_hi - f.row_lo) % FILTER_ROWS) return fail(c, NVDB_ERR_INTERNAL, "int8 kernel: row range is not a multiple of its 32-row tile");
+  constexpr uint32_t TROWS = i8w_tile_rows(DIM);
+  static_assert(TROWS == FILTER_ROWS, "the builds of dims > 768 stream one 32-row block per tile");
+  if ((f.row_hi - f.row_lo) % TROWS) return fail(c, NVDB_ERR_INTERNAL, "int8 kernel: row range is not a multiple of its 32-row tile");
   const uint32_t nwg = filter_grid(c, f.QT);
   nvdb_status st;
   SyncArgs sy;
   if ((st = sibling_sync_args(c, f.s, f.QT, nwg, sy))) return st;
   return launch_filter_i8w_kernel(c, f, i8w_build<DIM, 1, 1>(sy.prog != nullptr), nwg, FilterGeom{256, filter_i8w_lds_bytes<DIM, 1>(), 4, true},
-                                  static_cast<size_t>(nq_pad) * DIM, FILTER_ROWS, sy);
+                                  static_cast<size_t>(nq_pad) * DIM, TROWS, sy);
 }
 
 // the boot build is the 128-queries-per-workgroup two-plane kernel; QT counts ITS query tiles (the caller multiplies by nb)
@@ -122,7 +125,7 @@ nvdb_status launch_boot_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t n0, uint32_t
 
 nvdb_status launch_filter_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint32_t row_hi, uint32_t nq, uint32_t QT, uint32_t cap) {
   const uint32_t nb = filter_nb(c, nq);
-  const uint32_t nq_pad = QT * 128u * nb;
+  const uint32_t nq_pad = QT * filter_qpb(c, nq);
   const FilterCall f{s, row_lo, row_hi, nq, QT, cap, static_cast<const float*>(c->thr.p)};
   nvdb_status st;
   if (dispatch_dim(I8DimsBig{}, c->fdim, st, [&](auto D) { return launch_filter_i8w_big_dim<decltype(D)::value>(c, f, nq_pad); })) return st;

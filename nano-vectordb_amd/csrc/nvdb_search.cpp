@@ -4,7 +4,7 @@
 //                     -> rescore in the reference's fp32 order + final select
 //   path 3 (any k):   score matrix of a query sub-batch -> radix select -> sort
 // No kernel is defined or launched from this file: the launch helpers live in nvdb_launch_*.cpp.
-#include "nvdb_ctx.h"
+#include "nvdb_plan.h"
 
 namespace nvdbhip {
 
@@ -46,11 +46,9 @@ ScatterArgs scatter_args(nvdb_hip_ctx* c, uint32_t cap, uint32_t trows) {
                 static_cast<uint32_t*>(c->misc.p) + 1, cap, static_cast<uint32_t>(c->n), 1u, 0u, 0u,
                 c->opt_xcd_balance ? static_cast<float*>(c->xcdw.p) : nullptr, static_cast<uint32_t>(c->opt_i8_lo_bits)};
   if (trows && c->perm_on) {
-    const bool padded = c->owned || c->shadow16 != nullptr || c->shadow8 != nullptr;
     const uint32_t n = static_cast<uint32_t>(c->n);
-    const uint32_t T = padded ? (n + trows - 1) / trows : n / trows;
-    perm_params(T, a.perm_mul, a.perm_mask);
-    a.perm_T = T;
+    a.perm_T = corpus_padded(c) ? (n + trows - 1) / trows : n / trows;
+    perm_params(a.perm_T, a.perm_mul, a.perm_mask);
   }
   return a;
 }
@@ -64,7 +62,7 @@ nvdb_status launch_filter(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint3
   return filter_is_i8(c) ? launch_filter_i8(c, s, row_lo, row_hi, nq, QT, cap) : launch_filter_f16(c, s, row_lo, row_hi, nq, QT, cap);
 }
 
-// Enqueue one whole search of nq (<= 2048) queries resident at dev_q.  No host synchronisation.
+// Enqueue one whole search of nq (<= 2048) queries resident at dev_q: plan (nvdb_plan.h), workspace, launches.  No host synchronisation.
 // host_q != nullptr (host API, small calls): the queries are still in pinned host memory at host_q and `dev_q` is the device
 // buffer they belong in -- the filter path's prep launch reads them over PCIe and fills dev_q itself, every other path gets a
 // copy enqueued here.  status_out != nullptr: pinned host memory for the 8 status words; c->status_by_kernel tells the caller
@@ -73,165 +71,60 @@ nvdb_status search_core(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint
                         float* dev_out_scores, int force_path, bool time_filter, uint32_t cap_override = 0, bool sticky = true,
                         const float* host_q = nullptr, uint32_t* status_out = nullptr) {
   c->status_by_kernel = false;
+  SearchPlan p;
+  nvdb_status st = plan_search(*c, nq, k, force_path, cap_override, p);
+  if (st) return fail(c, st, p.error);
   const int final_mode = sticky ? 1 : 3;          // select_kernel: 3 = final select without folding into the sticky self-check words
-  const uint32_t k_eff = static_cast<uint32_t>(std::min<uint64_t>(k, c->n));
-  const uint32_t n = static_cast<uint32_t>(c->n);
-  int path = force_path ? force_path : static_cast<int>(c->opt_path);
-  if (path == 0) path = (filter_supported(c) && nq >= c->opt_min_filter_batch && c->n >= 4ull * c->opt_chunk0) ? 2 : 1;
-  if (path == 2 && !filter_supported(c)) return fail(c, NVDB_ERR_UNSUPPORTED, "MFMA filter path needs an fp16/fp32 corpus with dim <= 3072 or an int8 corpus with dim <= 1536");
-
-  uint32_t cap = cap_override ? cap_override : c->opt_cap > 0 ? static_cast<uint32_t>(c->opt_cap) : std::max<uint32_t>(c->cap_hint, nq <= 64 ? SELECT_MAX_CAP : 2048u);
-  cap = std::min(cap, SELECT_MAX_CAP);
-  if (cap < 4 * k_eff) cap = std::min<uint32_t>(SELECT_MAX_CAP, 4 * k_eff);
-  // 64 < k <= 1024 on the filter path (its kernels do not depend on k; the lists do): the longest lists, a bootstrap over
-  // 8k tile maxima and chunks small enough that k * (growth - 1) new survivors + the k kept ones + the error band fit.
-  // Anything else beyond the wavefront lists' 64 entries takes the any-k path.
-  const bool k_wide = k_eff > WAVE_KMAX;
-  // dims whose kernels have no MFMA bootstrap build (768 < dim): an EXACT bootstrap over the first 8k tiles' rows on the any-k
-  // machinery (score matrix of the sample -> radix select -> the k best seed the lists), then the filter streams the rest
-  const bool wide_exact_boot = k_wide && path == 2 && force_path != 1 && k_eff <= FILTER_KMAX && c->fdim > 768 &&
-                               c->n >= 4ull * FILTER_ROWS * 8 * k_eff;
-  const bool wide_on_filter = wide_exact_boot || (k_wide && path == 2 && force_path != 1 && k_eff <= FILTER_KMAX && c->opt_mfma_boot &&
-                              c->fdim <= 768 && c->n >= 2ull * FILTER_ROWS * 8 * k_eff);
-  if (wide_on_filter) cap = SELECT_MAX_CAP;
-  // queries per filter workgroup: 256 / 128, or 64 on the K-split build (dims > 1536)
-  const uint32_t QPB = (!filter_is_i8(c) && c->fdim > 1536) ? 64u : 128u * filter_nb(c, nq);
-  const uint32_t QT = (nq + QPB - 1) / QPB;
-  const uint32_t nq_pad = QT * QPB;
-
-  nvdb_status st;
-  if ((st = ensure(c, c->thr, nq_pad * 4))) return st;
-  if ((st = ensure(c, c->cnt, nq_pad * 4))) return st;
-  if ((st = ensure(c, c->overflow, nq_pad * 4))) return st;
-  if ((st = ensure(c, c->cand, static_cast<size_t>(nq) * cap * sizeof(Cand)))) return st;
-  if ((st = ensure(c, c->misc, 64))) return st;
-  // one region of sibling-rendezvous counters per filter launch of this search, all reset by the init kernel
-  const uint32_t prog_words = PROG_SLOTS * static_cast<uint32_t>(c->num_cu) * 8u;
-  if ((st = ensure(c, c->prog, static_cast<size_t>(prog_words) * 4))) return st;
-  c->prog_slot = 0;
-  if ((st = ensure(c, c->tickets, FUSE_TICKETS * 4))) return st;
-  // The filter path's prep launch does the per-search resets itself (and, for the host API's small calls, reads the queries
-  // straight from pinned host memory); the exact and any-k paths have no prep launch: init_search_kernel, queries copied here.
-  const bool filter_flow = path == 2 && !(k_wide && !wide_on_filter);
-  const bool prep_inits = c->opt_fuse && filter_flow;
-  if (host_q && !prep_inits) { HIPCHK(c, hipMemcpyAsync(const_cast<float*>(dev_q), host_q, static_cast<size_t>(nq) * c->dim * 4, hipMemcpyDefault, s)); host_q = nullptr; }   // (host_q is the pinned block as the device addresses it)
-  // (one query tile per stream has no siblings to keep in step: nothing to reset)
-  if (!prep_inits) {
-    if ((st = launch_init_search(c, s, nq_pad, QT > 1 ? prog_words : 0u))) return st;
-  }
-  const PrepInit pinit = prep_inits ? PrepInit{static_cast<uint32_t*>(c->cnt.p), static_cast<float*>(c->thr.p), static_cast<uint32_t*>(c->misc.p),
-                                               static_cast<uint32_t*>(c->prog.p), QT > 1 ? prog_words : 0u, static_cast<uint32_t*>(c->tickets.p), host_q, const_cast<float*>(dev_q)}
-                                    : PrepInit{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, nullptr};
-
+  const uint32_t n = static_cast<uint32_t>(c->n), k_eff = p.k_eff, cap = p.cap, QT = p.QT;
+  const size_t per_q = static_cast<size_t>(p.nq_pad) * 4;
+  const struct { DevBuf& buf; size_t bytes; bool filter_flow; } workspace[] = {
+      {c->thr, per_q, false}, {c->cnt, per_q, false}, {c->overflow, per_q, false}, {c->cand, static_cast<size_t>(nq) * cap * sizeof(Cand), false},
+      {c->misc, 64, false}, {c->prog, static_cast<size_t>(p.prog_words) * 4, false}, {c->tickets, FUSE_TICKETS * 4, false},
+      {c->q16, static_cast<size_t>(p.nq_pad) * c->fdim * 2, true}, {c->qscale, per_q, true}, {c->qinv, per_q, true},
+      {c->ebound, per_q, true}, {c->slack, per_q, true}, {c->qdelta, per_q, true}};
+  for (const auto& w : workspace)
+    if ((p.prep || !w.filter_flow) && (st = ensure(c, w.buf, w.bytes))) return st;
+  // the state of "the last search", all of it from the plan
   c->stats = nvdb_hip_scan_stats{};
-  c->stats.path = static_cast<uint32_t>(path);
-  c->last_nq = nq; c->last_cap = cap; c->last_filter = (path == 2);
+  c->stats.path = p.route;
+  c->last_nq = nq; c->last_cap = cap; c->last_filter = p.route == ROUTE_FILTER;
   c->ev_filter.clear();
+  c->prog_slot = 0;
+  if (p.route == ROUTE_FILTER) c->perm_on = p.perm_on;
 
-  if (k_wide && !wide_on_filter) {
-    // beyond the wavefront-resident lists (k <= 64) and not on the filter path: the any-k path (scores -> radix select -> sort)
-    c->stats.path = 3; c->last_filter = false;
-    return search_largek(c, s, dev_q, nq, k, dev_out_ids, dev_out_scores);
-  }
-  if (path == 1) {
-    // Two launches on big corpora (round 4): every workgroup of the scan starts with empty top-k lists, and until a list has warmed up
-    // nearly every tile takes the serial insertion path (~0.65 ms per round at 64 queries: profiles/r04_exact_wgs_sweep.txt).  So the
-    // first 1/64 of the rows is scanned on its own, a select turns it into the exact k-th best score per query (slack 0: the k best
-    // stay in the list), and the scan of the other 63/64 starts with that bar: a row reaches a list only if it beats it.  Same lists,
-    // same final select, same results.  (Only where the MFMA scan runs: more than 8 queries; the VALU kernel's lists warm up per wave.)
-    const uint32_t head = (c->opt_exact_prescan && nq > 8 && n >= (1u << 20)) ? std::max<uint32_t>(1u << 15, (n >> 6) & ~255u) : 0u;
-    if (head) {
-      if ((st = launch_scan_exact(c, s, 0, head, dev_q, nq, k_eff, nullptr, cap, 0))) return st;
-      if ((st = launch_select(c, s, nq, cap, k_eff, nullptr, 0, nullptr, nullptr, 0))) return st;
-      if ((st = launch_scan_exact(c, s, head, n, dev_q, nq, k_eff, static_cast<const float*>(c->thr.p), cap, k_eff))) return st;
-      c->stats.chunks = 2;
-    } else {
-      if ((st = launch_scan_exact(c, s, 0, n, dev_q, nq, k_eff, nullptr, cap, 0))) return st;
-      c->stats.chunks = 1;
-    }
+  // per-search resets and queries: the prep launch does both itself (option fuse), else init_search_kernel and a copy
+  // (one query tile per stream has no siblings to keep in step: no rendezvous counters to reset)
+  if (host_q && !p.prep_inits) { HIPCHK(c, hipMemcpyAsync(const_cast<float*>(dev_q), host_q, static_cast<size_t>(nq) * c->dim * 4, hipMemcpyDefault, s)); host_q = nullptr; }   // (host_q is the pinned block as the device addresses it)
+  if (!p.prep_inits && (st = launch_init_search(c, s, p.nq_pad, QT > 1 ? p.prog_words : 0u))) return st;
+  const PrepInit pinit = p.prep_inits ? PrepInit{static_cast<uint32_t*>(c->cnt.p), static_cast<float*>(c->thr.p), static_cast<uint32_t*>(c->misc.p),
+                                                 static_cast<uint32_t*>(c->prog.p), QT > 1 ? p.prog_words : 0u, static_cast<uint32_t*>(c->tickets.p), host_q, const_cast<float*>(dev_q)}
+                                      : PrepInit{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, nullptr};
+  if (p.prep && (st = filter_is_i8(c) ? launch_prep_q8(c, s, dev_q, nq, p.nq_pad, pinit) : launch_prep_q16(c, s, dev_q, nq, p.nq_pad, pinit))) return st;
+  const float* thr = static_cast<const float*>(c->thr.p);
+  const float* slack = static_cast<const float*>(c->slack.p);
+
+  if (p.route == ROUTE_ANYK) return search_largek(c, s, dev_q, nq, k, dev_out_ids, dev_out_scores);
+  if (p.route == ROUTE_EXACT) {
+    // prescan (plan_search): rows [0, head) alone, their exact k-th best score is the bar the rest of the scan starts with
+    if (p.head && (st = launch_scan_exact(c, s, 0, p.head, dev_q, nq, k_eff, nullptr, cap, 0))) return st;
+    if (p.head && (st = launch_select(c, s, nq, cap, k_eff, nullptr, 0, nullptr, nullptr, 0))) return st;
+    if ((st = launch_scan_exact(c, s, p.head, n, dev_q, nq, k_eff, p.head ? thr : nullptr, cap, p.head ? k_eff : 0))) return st;
+    c->stats.chunks = p.head ? 2 : 1;
     c->stats.rows_scanned = c->n;
     return launch_select(c, s, nq, cap, k_eff, nullptr, final_mode, dev_out_ids, dev_out_scores, k);
   }
 
-  // ---- path 2: MFMA filter ----------------------------------------------------------------------
-  if ((st = ensure(c, c->q16, static_cast<size_t>(nq_pad) * c->fdim * 2))) return st;
-  if ((st = ensure(c, c->qscale, nq_pad * 4))) return st;
-  if ((st = ensure(c, c->qinv, nq_pad * 4))) return st;
-  if ((st = ensure(c, c->ebound, nq_pad * 4))) return st;
-  if ((st = ensure(c, c->slack, nq_pad * 4))) return st;
-  if ((st = ensure(c, c->qdelta, nq_pad * 4))) return st;
-  if ((st = filter_is_i8(c) ? launch_prep_q8(c, s, dev_q, nq, nq_pad, pinit) : launch_prep_q16(c, s, dev_q, nq, nq_pad, pinit))) return st;
-  const float* slack = static_cast<const float*>(c->slack.p);
-  // Whole tiles: a corpus this library allocated is zero-padded to a multiple of 32 rows (the padded rows are
-  // dropped when the wave files its survivors); for an adopted corpus the ragged tail goes to the exact kernel.
-  const bool padded = c->owned || c->shadow16 != nullptr || c->shadow8 != nullptr;          // a shadow copy is always ours, hence padded
-  // chunk boundaries are whole tiles of the streaming kernel: 64 rows for the int8 two-stage kernel and for the m16
-  // fp16 build at d <= 384, 32 otherwise
-  const bool f16_wide_tiles = !filter_is_i8(c) && c->fdim <= 384 && filter_nb(c, nq) == 2 && c->opt_mfma16;
-  const uint32_t tile_rows = ((i8_two_stage(c) && c->fdim <= 768) || f16_wide_tiles) ? I8W_TILE_ROWS : FILTER_ROWS;
-  const uint32_t n_al = padded ? (n + tile_rows - 1) / tile_rows * tile_rows : n / tile_rows * tile_rows;
-  uint32_t r = 0;
-  uint64_t size;
-  // chunk i covers (growth-1) x the rows seen before it.  fp16: 8 (flat between 4 and 8).  int8 batches > 128: 3 --
-  // tighter thresholds earlier mean fewer tiles for which the two-stage kernel needs the lo plane, and a tile costs
-  // what its slowest wave costs (profiles/r01d_i8_growth_sweep.txt)
-  // (with the first-stage survivors finished after the stream a flagged value costs little: 6 and a 1024-tile bootstrap on big
-  // corpora, profiles/r02_i8_boot_growth_sweep.txt; the in-loop second stage wants 3)
-  const bool i8_big = i8_two_stage(c) && nq > 128 && c->fdim <= 768;
-  const bool i8_log = i8_big && c->opt_i8_pipe && !c->opt_i8_defer && !c->i8_scales_signed && !c->opt_i8_waves8 && c->n >= 64ull * FILTER_ROWS * 1024;
-  uint64_t growth = c->opt_growth > 0 ? static_cast<uint64_t>(c->opt_growth) : (i8_log ? 6u : i8_big ? 3u : 8u);
-  if (k_wide) growth = std::max<uint64_t>(2, std::min<uint64_t>(growth, cap / (3ull * k_eff)));     // k * (growth - 1) + k + band <= cap
-  // T tile maxima with T >= 8k: their k-th largest is then close to the k-th best of the 32*T rows (with T == k it
-  // would be the smallest tile maximum, a uselessly weak threshold)
-  uint32_t boot_tiles = std::max<uint32_t>(64u, 8u * k_eff);
-  if (c->opt_boot_tiles > 0) boot_tiles = std::max<uint32_t>(boot_tiles, std::min<uint32_t>(static_cast<uint32_t>(c->opt_boot_tiles), cap));
-  else if (i8_log && !k_wide) boot_tiles = std::max<uint32_t>(boot_tiles, std::min<uint32_t>(1024u, cap));
-  else if (!k_wide) {
-    // A bootstrap of up to 256 tiles that saves a whole chunk (a filter launch + its select, ~12 us) pays for itself; a larger
-    // bootstrap that saves none does not (profiles/r04_boot_tiles_sweep.txt: 500K rows 3 -> 2 chunks -9 us, 2.9M rows 4 -> 3 chunks
-    // -14..-28 us; 1M / 10M rows, where 256 tiles save nothing: +0.5..2 %).  So: the smallest bootstrap <= 256 tiles with which the
-    // chunks (each `growth` x the rows before it) reach the corpus one launch earlier.
-    uint64_t reach = static_cast<uint64_t>(FILTER_ROWS) * boot_tiles, per = 1;
-    uint32_t J = 0;
-    while (reach < n) { reach *= growth; per *= growth; ++J; }
-    if (J >= 2) {
-      per /= growth;                                                             // growth^(J-1)
-      uint64_t need = (static_cast<uint64_t>(n) + per * FILTER_ROWS - 1) / (per * FILTER_ROWS);
-      need = (need + 3) & ~3ull;                                                 // chunk boundaries stay multiples of the 64-row tiles whatever the growth
-      if (need > boot_tiles && need <= 256 && need <= cap) boot_tiles = static_cast<uint32_t>(need);
-    }
-  }
-  const uint32_t boot_rows = FILTER_ROWS * boot_tiles;
-  const bool mfma_boot = c->opt_mfma_boot && n >= boot_rows && boot_rows / FILTER_ROWS >= k_eff &&
-                         boot_rows / FILTER_ROWS <= cap &&
-                         c->fdim <= 768;    // no bootstrap build of the 16-row-tile fp16 kernel / the 32-query int8 kernel: exact bootstrap chunk
-  if (k_wide && !mfma_boot && !wide_exact_boot) {
-    // 64 < k on the filter path needs the MFMA bootstrap (the exact bootstrap chunk's wavefront lists hold 64 entries);
-    // e.g. option boot_tiles larger than the corpus: the any-k path takes the search instead
-    c->stats.path = 3; c->last_filter = false;
-    return search_largek(c, s, dev_q, nq, k, dev_out_ids, dev_out_scores);
-  }
-  // permuted tile order needs the bootstrap whose entries are discarded (the exact bootstrap chunk keeps rows [0, r))
-  c->perm_on = c->opt_tile_permute && mfma_boot;
-  if (mfma_boot) {
-    // thresholds from the k-th largest of the 64 tile maxima of rows [0,2048); those rows are then scanned
-    // again by the normal build, so the bootstrap entries are discarded (select mode 2)
-    if ((st = launch_boot(c, s, boot_rows, nq, QT, cap, filter_nb(c, nq)))) return st;
-    if ((st = launch_select(c, s, nq, cap, k_eff, slack, 2, nullptr, nullptr, boot_rows / FILTER_ROWS))) return st;   // mode 2: out_k = list length
-    size = static_cast<uint64_t>(boot_rows) * growth;
-  } else {
-    // bootstrap chunk [0,r) on the exact kernel; r is a multiple of the 32-row MFMA tile
-    r = std::min<uint32_t>(n_al, (static_cast<uint32_t>(k_wide ? FILTER_ROWS * 8u * k_eff : c->opt_chunk0) + tile_rows - 1) / tile_rows * tile_rows);
-    if (r > n) r = n / tile_rows * tile_rows;
-    if (k_wide) { if ((st = search_largek(c, s, dev_q, nq, k_eff, nullptr, nullptr, r, static_cast<Cand*>(c->cand.p), static_cast<uint32_t*>(c->cnt.p), cap))) return st; }
-    else
-    if ((st = launch_scan_exact(c, s, 0, r, dev_q, nq, k_eff, nullptr, cap, 0))) return st;
-    if ((st = launch_select(c, s, nq, cap, k_eff, slack, 0, nullptr, nullptr, 0))) return st;
-    size = static_cast<uint64_t>(r) * (growth - 1);
-  }
+  // ---- the filter route: bootstrap + select, { chunk + select }*, tail, rescore + final select ----
+  // MFMA bootstrap: thresholds from the k-th largest of the tile maxima of rows [0, boot_rows); those rows are scanned again by
+  // the normal build, so the select discards the bootstrap's entries (mode 2: out_k = list length)
+  if (p.boot == BOOT_MFMA) st = launch_boot(c, s, p.boot_rows, nq, QT, cap, filter_nb(c, nq));
+  else if (p.boot == BOOT_ANYK_SEEDED) st = search_largek(c, s, dev_q, nq, k_eff, nullptr, nullptr, p.r0, static_cast<Cand*>(c->cand.p), static_cast<uint32_t*>(c->cnt.p), cap);
+  else st = launch_scan_exact(c, s, 0, p.r0, dev_q, nq, k_eff, nullptr, cap, 0);
+  if (st) return st;
+  if ((st = launch_select(c, s, nq, cap, k_eff, slack, p.boot == BOOT_MFMA ? 2 : 0, nullptr, nullptr, p.boot == BOOT_MFMA ? p.boot_tiles : 0))) return st;
   size_t ev = 0;
-  while (r < n_al) {
-    const uint32_t hi = static_cast<uint32_t>(std::min<uint64_t>(n_al, static_cast<uint64_t>(r) + size));
+  for (uint32_t r = p.r0; r < p.n_al;) {
+    const uint32_t hi = chunk_end(p, r);
     nvdb_hip_ctx::KLaunch kl{nullptr, nullptr, 0.0, 0.0};
     const bool acct = c->opt_time_kernels && c->klaunch.size() < 8192;
     if (acct) {
@@ -257,24 +150,78 @@ nvdb_status search_core(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint
     c->stats.chunks++;
     c->stats.rows_scanned += static_cast<uint64_t>(hi - r) * QT;
     r = hi;
-    size = static_cast<uint64_t>(r) * (growth - 1);   // rows seen so far x (growth-1)
   }
-  if (n_al < n) {   // ragged tail of an adopted corpus: exact scores, pruned by the current thresholds
-    // (fewer than one tile of rows per workgroup: the wavefront lists' 64 entries keep every row that clears the threshold)
-    if ((st = launch_scan_exact(c, s, n_al, n, dev_q, nq, std::min(k_eff, WAVE_KMAX), static_cast<const float*>(c->thr.p), cap, 0))) return st;
-    c->stats.rows_scanned += static_cast<uint64_t>(n - n_al) * QT;
-  }
+  // ragged tail of an adopted corpus: exact scores, pruned by the current thresholds
+  // (fewer than one tile of rows per workgroup: the wavefront lists' 64 entries keep every row that clears the threshold)
+  if (p.tail_exact && (st = launch_scan_exact(c, s, p.n_al, n, dev_q, nq, std::min(k_eff, WAVE_KMAX), thr, cap, 0))) return st;
+  if (p.tail_exact) c->stats.rows_scanned += static_cast<uint64_t>(n - p.n_al) * QT;
   // the final select rides in the rescore launch (one workgroup per query in both); its last workgroup folds the self-check words
   FinalSelect fs{};
   if (c->opt_fuse)
     fs = FinalSelect{final_mode, k_eff, k, c->row_base, reinterpret_cast<unsigned long long*>(dev_out_ids), dev_out_scores, static_cast<float*>(c->thr.p),
                      static_cast<uint32_t*>(c->overflow.p), static_cast<uint32_t*>(c->misc.p) + 6,
-                     prep_inits ? static_cast<uint32_t*>(c->tickets.p) + (FUSE_TICKETS - 1) : nullptr, prep_inits ? status_out : nullptr};
+                     p.prep_inits ? static_cast<uint32_t*>(c->tickets.p) + (FUSE_TICKETS - 1) : nullptr, p.prep_inits ? status_out : nullptr};
   if (fs.mode == 1 && fs.ticket == nullptr) fs.mode = 0;          // (the sticky fold needs the ticket: separate select launch)
   bool fused = false;
   if ((st = launch_rescore(c, s, dev_q, nq, cap, fs, &fused))) return st;
   if (fused) { c->status_by_kernel = fs.status_out != nullptr; return NVDB_OK; }
   return launch_select(c, s, nq, cap, k_eff, nullptr, final_mode, dev_out_ids, dev_out_scores, k);
+}
+
+float filter_events_ms(const nvdb_hip_ctx* c) {
+  float total = 0.f;
+  for (auto& pr : c->ev_filter) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->ev_pool[pr.first], c->ev_pool[pr.second]) == hipSuccess) total += ms; }
+  return total;
+}
+
+// candidates that reached the rescore = the list lengths left by the last thresholding select (the final select
+// does not touch them); summed here rather than by 1024 same-address atomics in the rescore kernel
+nvdb_status sum_candidates(nvdb_hip_ctx* c, unsigned long long* total) {
+  *total = 0;
+  if (!c->last_nq) return NVDB_OK;
+  std::vector<uint32_t> cn(c->last_nq);
+  HIPCHK(c, hipMemcpy(cn.data(), c->cnt.p, c->last_nq * 4, hipMemcpyDeviceToHost));
+  for (uint32_t v : cn) *total += std::min(v, c->last_cap);
+  return NVDB_OK;
+}
+
+// One sub-batch (<= 1024 queries) of the host API: search, and when the self-check tripped (rare) redo it -- rung 1 on the filter path
+// with the longest candidate lists the select kernel can sort (near-duplicate-heavy corpora: thousands of rows inside the filter's
+// error band of the k-th score; re-scoring them is cheap, only the list was too short), rung 2, if that is still not enough or the
+// bound itself was violated, on the always-correct exact path.  (The queries are in the device buffer by then: the retries read
+// them there.)  verdict(rung) waits for the attempt and says NVDB_ERR_INTERNAL when its self-check tripped; at rung 0 it leaves
+// the exact counts in c->stats (search_check_impl).  *part: the statistics of the FIRST attempt, the ones that are reported.
+template <typename Verdict>
+static nvdb_status search_sub_batch(nvdb_hip_ctx* c, hipStream_t s, const float* dq, uint32_t nq, uint32_t k, uint64_t* oi, float* os, bool time_filter,
+                                    const float* host_q, uint32_t* st_out, Verdict&& verdict, nvdb_hip_scan_stats* part, bool* tripped = nullptr) {
+  nvdb_status st;
+  if ((st = search_core(c, s, dq, nq, k, oi, os, 0, time_filter, 0, false, host_q, st_out))) return st;
+  nvdb_status chk = verdict(0);
+  *part = c->stats;
+  if (tripped) *tripped = chk == NVDB_ERR_INTERNAL;
+  if (chk != NVDB_ERR_INTERNAL) return chk;
+  if (part->path == 2 && !part->bound_violations && c->last_cap < SELECT_MAX_CAP) {
+    if ((st = search_core(c, s, dq, nq, k, oi, os, 2, false, SELECT_MAX_CAP, false, nullptr, st_out))) return st;
+    if ((chk = verdict(1)) == NVDB_OK) c->cap_hint = SELECT_MAX_CAP;
+    else if (chk != NVDB_ERR_INTERNAL) return chk;
+  }
+  if (chk != NVDB_OK) {
+    if ((st = search_core(c, s, dq, nq, k, oi, os, 1, false, 0, false, nullptr, st_out))) return st;
+    if ((chk = verdict(2)) != NVDB_OK && chk != NVDB_ERR_INTERNAL) return chk;
+  }
+  c->stats = *part;
+  return NVDB_OK;
+}
+
+// (shmem_bytes: the dynamic LDS of the 32x32 filter builds, filter_f16_lds_bytes / filter_i8_lds_bytes at the corpus' dim -- what
+// the ABI's callers have always been told)
+static void fill_timing(const nvdb_hip_ctx* c, nvdb_hip_timing* t, const hipEvent_t (&e)[4], uint32_t k, uint32_t path) {
+  (void)hipEventElapsedTime(&t->h2d_ms, e[0], e[1]);
+  (void)hipEventElapsedTime(&t->kernel_ms, e[1], e[2]);
+  (void)hipEventElapsedTime(&t->d2h_ms, e[2], e[3]);
+  t->total_ms = t->h2d_ms + t->kernel_ms + t->d2h_ms;
+  t->threads = 256; t->nwarps = 4; t->K = k;
+  t->shmem_bytes = path != 2 ? 0 : filter_is_i8(c) ? static_cast<size_t>(FILTER_STAGES_I8) * (FILTER_ROWS * c->fdim + 4096) : static_cast<size_t>(FILTER_STAGES) * FILTER_ROWS * c->fdim * 2;
 }
 
 }  // namespace nvdbhip
@@ -329,18 +276,10 @@ static nvdb_status search_check_impl(nvdb_hip_ctx* c, nvdb_hip_scan_stats* stats
   if (misc[1]) nov = c->last_nq;                 // a wave's survivor log overflowed: which queries lost entries is unknown
   c->stats.overflow_queries = nov;
   c->stats.bound_violations = misc[0];
-  // candidates that reached the rescore = the list lengths left by the last thresholding select (the final select
-  // does not touch them); summed here rather than by 1024 same-address atomics in the rescore kernel
   unsigned long long tot = 0;
-  if (c->last_filter && c->last_nq) {
-    std::vector<uint32_t> cn(c->last_nq);
-    HIPCHK(c, hipMemcpy(cn.data(), c->cnt.p, c->last_nq * 4, hipMemcpyDeviceToHost));
-    for (uint32_t v : cn) tot += std::min(v, c->last_cap);
-  }
+  if (c->last_filter) { if (nvdb_status st = sum_candidates(c, &tot)) return st; }
   c->stats.candidates = tot;
-  float fms = 0.f;
-  for (auto& pr : c->ev_filter) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->ev_pool[pr.first], c->ev_pool[pr.second]) == hipSuccess) fms += ms; }
-  c->stats.filter_kernel_ms = fms;
+  c->stats.filter_kernel_ms = filter_events_ms(c);
   if (stats) *stats = c->stats;
   if (misc[0]) return fail(c, NVDB_ERR_INTERNAL, "filter error bound violated (bound_violations > 0)");
   if (nov) return fail(c, NVDB_ERR_INTERNAL, "candidate list overflow: re-run these queries with option path=1");
@@ -371,8 +310,9 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
     if ((st = ensure(c, c->out_ids, static_cast<size_t>(nq) * k * 8))) return st;
     if ((st = ensure(c, c->out_scores, static_cast<size_t>(nq) * k * 4))) return st;
   }
-  hipEvent_t e0 = get_event(c, 60), e1 = get_event(c, 61), e2 = get_event(c, 62), e3 = get_event(c, 63);
+  const hipEvent_t e[4] = {get_event(c, 60), get_event(c, 61), get_event(c, 62), get_event(c, 63)};
   c->stats_lazy = false;
+  const bool time_filter = timing != nullptr && c->opt_time_launches;
   const size_t pad_bytes = 8 * static_cast<size_t>(c->dim) * 4;
   // The 8 query rows after the batch must read as zeros (the exact kernel loads query groups of 8).  The buffer is zero beyond
   // q32_dirty (zeroed when allocated, only ever written through [0, qbytes) of some call): a memset is enqueued only when an
@@ -382,6 +322,7 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
     c->q32_dirty = std::max(c->q32_dirty, qbytes);
     return NVDB_OK;
   };
+  nvdb_hip_scan_stats total{};
   if (nq <= 1024) {
     // One sub-batch: everything the host needs comes back in ONE synchronisation through pinned staging -- the
     // self-check words (32 B), ids and scores -- instead of five small pageable copies of ~20 us each (a third of
@@ -407,7 +348,7 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
     uint32_t* pin_status = reinterpret_cast<uint32_t*>(pin);
     const size_t off_ids = 64, off_sc = off_ids + (stage_out ? ob_ids : 0), off_q = off_sc + (stage_out ? ob_sc : 0);
     char* pin_ids = pin + off_ids; char* pin_sc = pin + off_sc; char* pin_q = pin + off_q;
-    if (timing) HIPCHK(c, hipEventRecord(e0, s));
+    if (timing) HIPCHK(c, hipEventRecord(e[0], s));
     if ((st = zero_pad())) return st;
     const float* host_q = nullptr;                                                 // non-null: search_core brings the queries down itself
     if (q_stage) {
@@ -415,14 +356,14 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
       if (zc_in) host_q = reinterpret_cast<const float*>(pin_d + off_q);
       else HIPCHK(c, hipMemcpyAsync(c->q32.p, pin_q, qbytes, hipMemcpyHostToDevice, s));
     } else HIPCHK(c, hipMemcpyAsync(c->q32.p, queries, qbytes, hipMemcpyHostToDevice, s));
-    if (timing) HIPCHK(c, hipEventRecord(e1, s));
+    if (timing) HIPCHK(c, hipEventRecord(e[1], s));
     const float* dq = static_cast<const float*>(c->q32.p);
     uint64_t* oi = zc_out ? reinterpret_cast<uint64_t*>(pin_d + off_ids) : reinterpret_cast<uint64_t*>(static_cast<char*>(c->hostblock.p) + 64);
     float* os = zc_out ? reinterpret_cast<float*>(pin_d + off_sc) : reinterpret_cast<float*>(static_cast<char*>(c->hostblock.p) + 64 + ob_ids);
     uint32_t* st_out = zc_out ? reinterpret_cast<uint32_t*>(pin_d) : nullptr;
-    if ((st = search_core(c, s, dq, nq, k, oi, os, 0, timing != nullptr && c->opt_time_launches, 0, false, host_q, st_out))) return st;
-    if (timing) HIPCHK(c, hipEventRecord(e2, s));
-    auto fetch = [&]() -> nvdb_status {
+    // the verdict comes down with the results: the pinned status words
+    auto verdict = [&](int rung) -> nvdb_status {
+      if (rung == 0 && timing) HIPCHK(c, hipEventRecord(e[2], s));
       if (zc_out) {
         // ids and scores were written into the pinned block by the final kernel; the status words too when that kernel was the
         // fused rescore + select (else: 32 bytes copied here)
@@ -435,109 +376,53 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
         HIPCHK(c, hipMemcpyAsync(out_ids, oi, ob_ids, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(out_scores, os, ob_sc, hipMemcpyDeviceToHost, s));
       }
-      if (timing) HIPCHK(c, hipEventRecord(e3, s));
+      if (timing) HIPCHK(c, hipEventRecord(e[3], s));
       HIPCHK(c, hipStreamSynchronize(s));
-      return NVDB_OK;
+      if (!(pin_status[0] | pin_status[1] | pin_status[6])) return NVDB_OK;
+      // tripped; the first attempt's exact counts for the statistics
+      return (rung == 0 && search_check_impl(c, nullptr, true) == NVDB_ERR_HIP) ? NVDB_ERR_HIP : NVDB_ERR_INTERNAL;
     };
-    if ((st = fetch())) return st;
-    nvdb_hip_scan_stats part = c->stats;
-    if (pin_status[0] | pin_status[1] | pin_status[6]) {
-      // self-check tripped (rare): exact counts for the statistics, then redo the batch -- first on the filter path with
-      // the longest candidate lists the select kernel can sort (near-duplicate-heavy corpora: thousands of rows inside
-      // the filter's error band of the k-th score; re-scoring them is cheap, only the list was too short), and if that
-      // is still not enough, or the bound itself was violated, on the always-correct exact path
-      // (the queries are in the device buffer by now: the retries read them there)
-      nvdb_status chk = search_check_impl(c, &part, true);
-      if (chk == NVDB_ERR_HIP) return chk;
-      bool done = false;
-      if (part.path == 2 && !pin_status[0] && c->last_cap < SELECT_MAX_CAP) {
-        if ((st = search_core(c, s, dq, nq, k, oi, os, 2, false, SELECT_MAX_CAP, false, nullptr, st_out))) return st;
-        if ((st = fetch())) return st;
-        done = !(pin_status[0] | pin_status[1] | pin_status[6]);
-        if (done) c->cap_hint = SELECT_MAX_CAP;
-      }
-      if (!done) {
-        if ((st = search_core(c, s, dq, nq, k, oi, os, 1, false, 0, false, nullptr, st_out))) return st;
-        if ((st = fetch())) return st;
-      }
-      c->stats = part;
-    } else {
-      part.i8_stage1_tiles = pin_status[4]; part.i8_stage2_blocks = pin_status[5];
-      float fms = 0.f;
-      for (auto& pr : c->ev_filter) { float ms = 0.f; if (hipEventElapsedTime(&ms, c->ev_pool[pr.first], c->ev_pool[pr.second]) == hipSuccess) fms += ms; }
-      part.filter_kernel_ms = fms;
-      c->stats = part;
+    bool tripped = false;
+    if ((st = search_sub_batch(c, s, dq, nq, k, oi, os, time_filter, host_q, st_out, verdict, &total, &tripped))) return st;
+    if (!tripped) {
+      total.i8_stage1_tiles = pin_status[4]; total.i8_stage2_blocks = pin_status[5];
+      total.filter_kernel_ms = filter_events_ms(c);
+      c->stats = total;
       c->stats_lazy = c->last_filter;                 // candidates: read back on demand
     }
     if (stage_out) {
       std::memcpy(out_ids, pin_ids, ob_ids);
       std::memcpy(out_scores, pin_sc, ob_sc);
     }
-    if (timing) {
-      (void)hipEventElapsedTime(&timing->h2d_ms, e0, e1);
-      (void)hipEventElapsedTime(&timing->kernel_ms, e1, e2);
-      (void)hipEventElapsedTime(&timing->d2h_ms, e2, e3);
-      timing->total_ms = timing->h2d_ms + timing->kernel_ms + timing->d2h_ms;
-      timing->threads = 256; timing->nwarps = 4; timing->K = k;
-      timing->shmem_bytes = part.path != 2 ? 0 : filter_is_i8(c) ? static_cast<size_t>(FILTER_STAGES_I8) * (FILTER_ROWS * c->fdim + 4096) : static_cast<size_t>(FILTER_STAGES) * FILTER_ROWS * c->fdim * 2;
+  } else {
+    if ((st = zero_pad())) return st;
+    HIPCHK(c, hipEventRecord(e[0], s));
+    HIPCHK(c, hipMemcpyAsync(c->q32.p, queries, qbytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(e[1], s));
+    auto verdict = [&](int rung) -> nvdb_status {     // (nothing reads the verdict of the exact path)
+      HIPCHK(c, hipStreamSynchronize(s));
+      return rung < 2 ? search_check_impl(c, nullptr, true) : NVDB_OK;
+    };
+    for (uint32_t q0 = 0; q0 < nq; q0 += 1024) {
+      const float* dq = static_cast<const float*>(c->q32.p) + static_cast<size_t>(q0) * c->dim;
+      uint64_t* oi = static_cast<uint64_t*>(c->out_ids.p) + static_cast<size_t>(q0) * k;
+      float* os = static_cast<float*>(c->out_scores.p) + static_cast<size_t>(q0) * k;
+      nvdb_hip_scan_stats part{};
+      if ((st = search_sub_batch(c, s, dq, std::min<uint32_t>(1024, nq - q0), k, oi, os, time_filter, nullptr, nullptr, verdict, &part))) return st;
+      total.path = std::max(total.path, part.path);
+      total.chunks += part.chunks; total.rows_scanned += part.rows_scanned; total.candidates += part.candidates;
+      total.overflow_queries += part.overflow_queries; total.bound_violations += part.bound_violations;
+      total.i8_stage1_tiles += part.i8_stage1_tiles; total.i8_stage2_blocks += part.i8_stage2_blocks;
+      total.filter_kernel_ms += part.filter_kernel_ms;
     }
-    if (part.bound_violations) return fail(c, NVDB_ERR_INTERNAL, "filter error bound violated; results were recomputed on the exact path");
-    return NVDB_OK;
-  }
-  if ((st = zero_pad())) return st;
-  HIPCHK(c, hipEventRecord(e0, s));
-  HIPCHK(c, hipMemcpyAsync(c->q32.p, queries, qbytes, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipEventRecord(e1, s));
-  nvdb_hip_scan_stats total{};
-  float filter_ms = 0.f;
-  for (uint32_t q0 = 0; q0 < nq; q0 += 1024) {
-    const uint32_t b = std::min<uint32_t>(1024, nq - q0);
-    const float* dq = static_cast<const float*>(c->q32.p) + static_cast<size_t>(q0) * c->dim;
-    uint64_t* oi = static_cast<uint64_t*>(c->out_ids.p) + static_cast<size_t>(q0) * k;
-    float* os = static_cast<float*>(c->out_scores.p) + static_cast<size_t>(q0) * k;
-    if ((st = search_core(c, s, dq, b, k, oi, os, 0, timing != nullptr && c->opt_time_launches, 0, false))) return st;
+    HIPCHK(c, hipEventRecord(e[2], s));
+    HIPCHK(c, hipMemcpyAsync(out_ids, c->out_ids.p, static_cast<size_t>(nq) * k * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(out_scores, c->out_scores.p, static_cast<size_t>(nq) * k * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(e[3], s));
     HIPCHK(c, hipStreamSynchronize(s));
-    nvdb_hip_scan_stats part{};
-    nvdb_status chk = search_check_impl(c, &part, true);
-    if (chk == NVDB_ERR_HIP) return chk;
-    if (chk == NVDB_ERR_INTERNAL) {
-      // self-check tripped: longest lists first, then the always-correct exact path (see the small-call path above)
-      bool done = false;
-      if (part.path == 2 && !part.bound_violations && c->last_cap < SELECT_MAX_CAP) {
-        if ((st = search_core(c, s, dq, b, k, oi, os, 2, false, SELECT_MAX_CAP, false))) return st;
-        HIPCHK(c, hipStreamSynchronize(s));
-        nvdb_hip_scan_stats again{};
-        const nvdb_status chk2 = search_check_impl(c, &again, true);
-        if (chk2 == NVDB_ERR_HIP) return chk2;
-        done = (chk2 == NVDB_OK);
-        if (done) c->cap_hint = SELECT_MAX_CAP;
-      }
-      if (!done) {
-        if ((st = search_core(c, s, dq, b, k, oi, os, 1, false, 0, false))) return st;
-        HIPCHK(c, hipStreamSynchronize(s));
-      }
-    }
-    total.path = std::max(total.path, part.path);
-    total.chunks += part.chunks; total.rows_scanned += part.rows_scanned; total.candidates += part.candidates;
-    total.overflow_queries += part.overflow_queries; total.bound_violations += part.bound_violations;
-    total.i8_stage1_tiles += part.i8_stage1_tiles; total.i8_stage2_blocks += part.i8_stage2_blocks;
-    filter_ms += part.filter_kernel_ms;
+    c->stats = total;
   }
-  HIPCHK(c, hipEventRecord(e2, s));
-  HIPCHK(c, hipMemcpyAsync(out_ids, c->out_ids.p, static_cast<size_t>(nq) * k * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(out_scores, c->out_scores.p, static_cast<size_t>(nq) * k * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipEventRecord(e3, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  total.filter_kernel_ms = filter_ms;
-  c->stats = total;
-  if (timing) {
-    (void)hipEventElapsedTime(&timing->h2d_ms, e0, e1);
-    (void)hipEventElapsedTime(&timing->kernel_ms, e1, e2);
-    (void)hipEventElapsedTime(&timing->d2h_ms, e2, e3);
-    timing->total_ms = timing->h2d_ms + timing->kernel_ms + timing->d2h_ms;
-    timing->threads = 256; timing->nwarps = 4; timing->K = k;
-    timing->shmem_bytes = total.path != 2 ? 0 : filter_is_i8(c) ? static_cast<size_t>(FILTER_STAGES_I8) * (FILTER_ROWS * c->fdim + 4096) : static_cast<size_t>(FILTER_STAGES) * FILTER_ROWS * c->fdim * 2;
-  }
+  if (timing) fill_timing(c, timing, e, k, total.path);
   if (total.bound_violations) return fail(c, NVDB_ERR_INTERNAL, "filter error bound violated; results were recomputed on the exact path");
   return NVDB_OK;
 }

@@ -34,7 +34,8 @@ EXPORTS = [
     "nvdb_hip_set_partitions", "nvdb_hip_set_centroids", "nvdb_hip_search_partitions", "nvdb_hip_search_ivf",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
-DEV_EXPORTS = ["nvdb_hip_debug_filter_variant", "nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges"]
+DEV_EXPORTS = ["nvdb_hip_debug_filter_variant", "nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
+               "nvdb_hip_debug_plan"]
 
 
 class NvdbError(RuntimeError):
@@ -60,6 +61,27 @@ class ScanStats(C.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class PlanShape(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("dim", C.c_uint32), ("fdim", C.c_uint32), ("dtype", C.c_uint32), ("owned", C.c_uint32),
+                ("has_shadow16", C.c_uint32), ("has_shadow8", C.c_uint32), ("q8shadow", C.c_uint32), ("i8_scales_signed", C.c_uint32),
+                ("num_cu", C.c_uint32), ("cap_hint", C.c_uint32)]
+
+
+class PlanOption(C.Structure):
+    _fields_ = [("key", C.c_char_p), ("value", C.c_int64)]
+
+
+PLAN_MAX_CHUNKS = 64
+
+
+class Plan(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("route", "prep", "prep_inits", "k_wide", "k_eff", "cap", "QPB", "QT", "nq_pad", "prog_words", "head",
+                                          "padded", "perm_on", "boot", "tile_rows", "n_al", "growth", "boot_tiles", "boot_rows", "r0",
+                                          "tail_exact", "helper_tile_rows", "n_chunks")] + \
+               [("chunk_lo", C.c_uint32 * PLAN_MAX_CHUNKS), ("chunk_hi", C.c_uint32 * PLAN_MAX_CHUNKS), ("stat_chunks", C.c_uint32),
+                ("stat_rows_scanned", C.c_uint64)]
 
 
 class GroupStats(C.Structure):
@@ -159,6 +181,7 @@ def _bind(L, dev):
         L.nvdb_permuted_tile.argtypes = [u32, u32]
         L.nvdb_hip_debug_tile_ranges.argtypes = [vp, u32, u32, f32p, C.POINTER(u32), C.POINTER(u32), f32p]
         L.nvdb_permuted_tile.restype = u32
+        L.nvdb_hip_debug_plan.argtypes = [C.POINTER(PlanShape), C.POINTER(PlanOption), u32, u32, u32, C.c_int, u32, C.POINTER(Plan), C.c_char_p, C.c_size_t]
     return L
 
 
@@ -218,6 +241,21 @@ def synth_corpus(seed, row0, nrows, dim, dtype):
     if dtype == DT_F16:
         return f32_to_f16(f), None
     return quantize_i8(f)
+
+
+def debug_plan(shape, nq, k, options=None, force_path=0, cap_override=0):
+    """What a flat search of nq queries for the k best would do on a corpus of `shape` (the PlanShape fields as a dict; fdim
+    defaults to dim): nvdb_hip_debug_plan of the developer library, as a dict with the chunk lists cut to n_chunks."""
+    sh = PlanShape(**{"fdim": shape["dim"], **shape})
+    items = list((options or {}).items())
+    opts = (PlanOption * max(len(items), 1))(*[PlanOption(key.encode(), int(v)) for key, v in items])
+    out, err = Plan(), C.create_string_buffer(256)
+    st = load_dev_library().nvdb_hip_debug_plan(C.byref(sh), opts, len(items), nq, k, force_path, cap_override, C.byref(out), err, len(err))
+    if st:
+        raise NvdbError(st, err.value.decode())
+    p = {f: getattr(out, f) for f, _ in Plan._fields_}
+    p["chunk_lo"], p["chunk_hi"] = list(out.chunk_lo[:out.n_chunks]), list(out.chunk_hi[:out.n_chunks])
+    return p
 
 
 def merge_topk_host(ids, scores):

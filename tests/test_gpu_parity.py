@@ -1535,6 +1535,85 @@ def test_exact_mfma_pruned_by_thresholds_and_small_row_ranges(oracle):
     _check_against_oracle(oracle, base, po.DT_F16, None, queries[:6], ids[:6], sc[:6], k, "exact-mfma k=64")
 
 
+# key (as in tests/golden/search_plan_stats.json), dtype, d, n, adopted, nq, k, options
+PLAN_SHAPES = [
+    ("f16_d256_n40037_adopted_nq256_k10", nvdb_amd.DT_F16, 256, 40037, True, 256, 10, {}),
+    ("f16_d768_n40000_nq1_k10", nvdb_amd.DT_F16, 768, 40000, False, 1, 10, {}),
+    ("f16_d768_n40000_nq129_k10", nvdb_amd.DT_F16, 768, 40000, False, 129, 10, {}),
+    ("i8_d768_n65536_nq256_k10", nvdb_amd.DT_I8, 768, 65536, False, 256, 10, {}),
+    ("f16_d2048_n8192_nq65_k10", nvdb_amd.DT_F16, 2048, 8192, False, 65, 10, {}),
+    ("f16_d896_n102400_nq32_k100", nvdb_amd.DT_F16, 896, 102400, False, 32, 100, {}),
+    ("f16_d128_n1048576_nq64_k10_path1", nvdb_amd.DT_F16, 128, 1 << 20, False, 64, 10, {"path": 1}),
+    ("f16_d256_n4096_nq4_k2000", nvdb_amd.DT_F16, 256, 4096, False, 4, 2000, {}),
+]
+
+
+@pytest.mark.parametrize("i", range(len(PLAN_SHAPES)), ids=[s[0] for s in PLAN_SHAPES])
+def test_plan_agrees_with_what_ran(oracle, i):
+    """The plan (nvdb_hip_debug_plan, no device) and a live search of the same shape report the same path / chunks / rows_scanned,
+    and both equal tests/golden/search_plan_stats.json: what these searches reported BEFORE the planning code became a function
+    (recorded per CU count; a machine with another count skips, an MI355X has 256 and skips nothing)."""
+    import json, os, torch
+    key, dt, d, n, adopted, nq, k, opts = PLAN_SHAPES[i]
+    cu = torch.cuda.get_device_properties(0).multi_processor_count
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "search_plan_stats.json")))
+    want = golden.get(f"{key}@cu{cu}")
+    if want is None:
+        assert cu != 256, f"{key}: no golden row for an MI355X"
+        pytest.skip(f"no golden row for {cu} CUs")
+    c = nvdb_amd.HipContext(0)
+    base, scales = nvdb_amd.synth_corpus(SEED + 300 + i, 0, n, d, dt)
+    if adopted:
+        t_rows = torch.from_numpy(base.view(np.int16)).to(torch.device("cuda", 0))
+        torch.cuda.synchronize()
+        c.adopt_corpus(t_rows.data_ptr(), n, d, dt)
+    else:
+        c.generate_corpus(SEED + 300 + i, n, d, dt)
+    for o, v in opts.items():
+        c.set_option(o, v)
+    q = nvdb_amd.synth_rows_f32(SEED + 400 + i, 0, nq, d)
+    ids, sc = c.search_batch(q, k)
+    st = c.stats()
+    c.close()
+    p = nvdb_amd.debug_plan(dict(n=n, dim=d, dtype=dt, owned=0 if adopted else 1, num_cu=cu), nq, k, opts)
+    got = {f: st[f] for f in ("path", "chunks", "rows_scanned")}
+    planned = {"path": p["route"], "chunks": p["stat_chunks"], "rows_scanned": p["stat_rows_scanned"]}
+    print(key, "ran", got, "planned", planned, "golden", want)
+    assert got == want and planned == want, (key, got, planned, want)
+    assert st["bound_violations"] == 0 and st["overflow_queries"] == 0, st
+    m = min(nq, 16)                                            # the oracle on a subset keeps the big rows short
+    oid, osc = oracle.flat_topk(base, po.DT_F16 if dt == nvdb_amd.DT_F16 else po.DT_I8, q[:m], k, scales)
+    assert np.array_equal(ids[:m], oid) and np.array_equal(sc[:m].view(np.uint32), osc.view(np.uint32)), key
+
+
+def test_retry_ladder_beyond_1024_queries_reports_the_first_attempt(oracle):
+    """Host API, two sub-batches (1100 queries), lists of 64 entries on a corpus of near-duplicates: both sub-batches overflow and are
+    redone with the longest lists (8192 entries hold the whole corpus, so that attempt is clean).  Results equal the oracle's; the
+    statistics are those of the first attempts: the filter path, its chunks, the overflowing queries."""
+    n, d, nq, k, C = 8192, 128, 1100, 10, 8
+    rs = np.random.RandomState(17)
+    cent = rs.randn(C, d).astype(np.float32); cent /= np.linalg.norm(cent, axis=1, keepdims=True)
+    x = cent[rs.randint(0, C, size=n)] + np.float32(0.05) * rs.randn(n, d).astype(np.float32) / np.float32(np.sqrt(d))
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    base = oracle.f32_to_f16(x.astype(np.float32))
+    q = cent[rs.randint(0, C, size=nq)] + np.float32(0.05) * rs.randn(nq, d).astype(np.float32) / np.float32(np.sqrt(d))
+    q = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
+    c = nvdb_amd.HipContext(0)
+    c.upload_corpus(base, po.DT_F16)
+    c.set_option("cand_cap", 64)
+    ids, sc = c.search_batch(q, k)
+    st = c.stats()
+    c.close()
+    one = nvdb_amd.debug_plan(dict(n=n, dim=d, dtype=nvdb_amd.DT_F16, owned=1, num_cu=256), 1024, k, {"cand_cap": 64})
+    two = nvdb_amd.debug_plan(dict(n=n, dim=d, dtype=nvdb_amd.DT_F16, owned=1, num_cu=256), nq - 1024, k, {"cand_cap": 64})
+    print("ladder", st)
+    assert st["path"] == 2 and st["bound_violations"] == 0 and st["overflow_queries"] > 0, st
+    assert st["chunks"] == one["stat_chunks"] + two["stat_chunks"], (st, one, two)            # not the retries' chunks on top
+    assert st["rows_scanned"] == one["stat_rows_scanned"] + two["stat_rows_scanned"], (st, one, two)
+    oid, osc = oracle.flat_topk(base, po.DT_F16, q, k)
+    assert np.array_equal(ids, oid) and np.array_equal(sc.view(np.uint32), osc.view(np.uint32))
+
+
 def test_product_library_rejects_developer_variants(ctx):
     for key, val in (("mfma16", 0), ("i8_wide", 0), ("i8_pipe", 0), ("i8_waves8", 1), ("i8_mfma16", 0), ("i8_small8", 0)):
         with pytest.raises(nvdb_amd.NvdbError) as e:
