@@ -252,6 +252,72 @@ nvdb_status nvdb_hip_search_ivf(nvdb_hip_ctx* ctx, const float* queries, uint32_
                                 uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                 uint32_t* out_probe, nvdb_hip_timing* timing);
 
+/* ---------------------------------------------------------------------------------------------
+ * IVF-Flat build: from a resident corpus to an index the probe search above can serve -- centroids trained on the GPU
+ * (the reference trains them with FAISS, apps/nvdb_ivf_build.cpp:59-64), every row assigned to its best centroid, the rows
+ * copied into list order, results answered in the ORIGINAL ids.
+ * "A row as an f32 query" below means: an f32 row as it is, an f16 row widened exactly, an int8 row float(x) * scale
+ * rounded once.
+ * ------------------------------------------------------------------------------------------- */
+
+/* out_assign[i] (host, nrows entries) = the centroid with the largest dot product with resident row row0 + i taken as an f32
+ * query, in the reference's fp32 order (the flat search over the centroids: the bits of nvdb_hip_search_batch on an f32 corpus);
+ * ties go to the lowest centroid number.  centroids: [nparts][dim] f32, host memory.
+ * NVDB_ERR_INVALID: null context / centroids, null out_assign with nrows > 0, nparts == 0 or 0xFFFFFFFF, row0 + nrows > n;
+ * NVDB_ERR_NO_CORPUS: nothing resident.  nrows == 0 -> NVDB_OK, nothing written.
+ * Non-finite rows or centroids: no fault, no hang, every output < nparts, the value otherwise unspecified. */
+nvdb_status nvdb_hip_assign_rows(nvdb_hip_ctx* ctx, const float* centroids, uint32_t nparts,
+                                 uint64_t row0, uint64_t nrows, uint32_t* out_assign);
+
+/* Spherical k-means (the companion of search_ivf's dot-product probe): a centroid is the mean of its members scaled to unit
+ * length.  out_centroids: [nparts][dim] f32, host memory.  Same arguments + same corpus -> the same bytes (no atomics).
+ *   training set: every resident row when max_train_rows == 0 or >= n, else the m = max_train_rows rows floor(i * n / m), i < m.
+ *                 nparts > training rows -> NVDB_ERR_INVALID.
+ *   start:        init ([nparts][dim] f32, host) as given; NULL: nparts DISTINCT training rows, each as an f32 query scaled to
+ *                 unit length in fp64 (one rounding to f32).  Draw rule for centroid j, attempt t = 0, 1, ...: with mix32 and
+ *                 synth_row_key the synthetic generator's mixers,
+ *                   key = synth_row_key(seed, (uint64) t << 32 | j),
+ *                   training row = (((uint64) mix32(key ^ 0x9E3779B9) << 32) | mix32(key + 0x85EBCA6B)) mod m;
+ *                 a row some centroid < j already took is drawn again; after 64 attempts the next free training row
+ *                 (wrapping at m) is taken.  iters == 0 returns the start.
+ *   iteration:    assign the training rows (nvdb_hip_assign_rows' rule); per centroid, sum the members per column in fp64 in
+ *                 ascending row order (lists longer than 512 rows: per 512-row chunk, the chunks added in order); the norm in
+ *                 fp64; centroid = sum / norm rounded once to f32.  A centroid without members, or with a zero or non-finite
+ *                 sum, keeps its value. */
+nvdb_status nvdb_hip_train_centroids(nvdb_hip_ctx* ctx, uint32_t nparts, uint32_t iters, uint64_t seed,
+                                     uint64_t max_train_rows, const float* init, float* out_centroids);
+
+/* The inverted lists of an assignment (host, no GPU needed): a stable counting sort.  out_offsets[p] (nparts + 1 entries) =
+ * first position of list p, out_perm[j] (n entries) = the original row at position j; positions are ordered by partition, then
+ * by original row.  NVDB_ERR_INVALID with nothing written: a null pointer, n > 0xFFFFFF00, an entry >= nparts.
+ * n == 0 -> every offset 0. */
+nvdb_status nvdb_ivf_layout_host(const uint32_t* assign, uint64_t n, uint32_t nparts,
+                                 uint64_t* out_offsets /* nparts+1 */, uint32_t* out_perm /* n */);
+
+/* The index: the rows of `src` copied into list order (nvdb_hip_assign_rows -> nvdb_ivf_layout_host -> a permuting copy,
+ * int8 scales included) into a context of its own on the same device, with the partition table and the centroids set.
+ * src is not touched and may be destroyed afterwards to give its HBM back; DURING the build the device holds the source
+ * AND the copy (plus shadows of both where the dtype / dim has them).  Options that act when a corpus becomes resident
+ * ("f32_shadow", "q8_shadow") are taken over from src.  The index's context has global_row_base 0; src's base is kept and
+ * added when ids are mapped back.  NVDB_ERR_NO_CORPUS: src holds no corpus.
+ * NVDB_IVF_DEBUG (environment): build / train report their assignment / update / gather hipEvent times on stderr. */
+typedef struct nvdb_hip_ivf nvdb_hip_ivf;
+nvdb_status nvdb_hip_ivf_build(nvdb_hip_ctx* src, const float* centroids, uint32_t nparts, nvdb_hip_ivf** out);
+void nvdb_hip_ivf_destroy(nvdb_hip_ivf* ivf);
+const char* nvdb_hip_ivf_last_error(const nvdb_hip_ivf* ivf);     /* NULL: last build error */
+/* the index's own context (options, statistics, download_rows: the rows in list order); owned by the index */
+nvdb_hip_ctx* nvdb_hip_ivf_ctx(nvdb_hip_ivf* ivf);
+/* offsets_out (nparts + 1) / perm_out (n) may be NULL; perm[position] = row of src (without its global_row_base) */
+nvdb_status nvdb_hip_ivf_info(const nvdb_hip_ivf* ivf, uint64_t* n, uint32_t* nparts,
+                              uint64_t* offsets_out, uint32_t* perm_out);
+/* nvdb_hip_search_ivf on the index's context, then every id that is not padding becomes src's global_row_base + perm[id].
+ * Scores and their bits are the probe search's.  ORDER: score descending; equal scores by (partition number, original id) --
+ * the order of the positions in the lists; the result is not re-sorted by original id.  out_probe, out_counts, timing and the
+ * k > 64, nprobe == 0, k == 0 rules are nvdb_hip_search_ivf's. */
+nvdb_status nvdb_hip_ivf_search(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+                                uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                uint32_t* out_probe, nvdb_hip_timing* timing);
+
 /* Tunables (defaults are what bench.py measures; the table with meanings is in INTEGRATION.md section 4b):
  * "path" (0 auto, 1 exact, 2 mfma-filter), "chunk0_rows", "chunk_growth", "cand_cap", "min_filter_batch", "mfma_boot", "waves8",
  * "sibling_sync", "sync_every", "sync_lead", "tile_permute", "f32_shadow" (set before the upload), "exact_mfma" (exact scores on the fp32

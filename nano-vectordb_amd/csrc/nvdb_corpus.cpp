@@ -175,6 +175,44 @@ nvdb_status check_corpus_args(nvdb_hip_ctx* c, uint64_t n, uint32_t dim, uint32_
 
 }  // namespace
 
+namespace nvdbhip {
+
+// Buffers of the shape every owned corpus has: the rows zero-padded by PAD_ROWS rows (+ slack for vector loads), for int8 the
+// scales padded by PAD_ROWS zeros.  The caller fills rows [0, n) and hands both to corpus_take_ownership.
+nvdb_status corpus_alloc_padded(nvdb_hip_ctx* c, uint64_t n, uint32_t dim, uint32_t dtype, void** rows, float** scales) {
+  *rows = nullptr; *scales = nullptr;
+  const size_t bytes = static_cast<size_t>(n) * dim * bpe_of(dtype);
+  const size_t pad = static_cast<size_t>(PAD_ROWS) * dim * bpe_of(dtype) + 4096;
+  HIPCHK(c, hipMalloc(rows, bytes + pad));
+  hipError_t e = hipMemset(static_cast<char*>(*rows) + bytes, 0, pad);
+  if (e == hipSuccess && dtype == NVDB_DTYPE_I8) {
+    e = hipMalloc(reinterpret_cast<void**>(scales), (n + PAD_ROWS) * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(*scales + n, 0, PAD_ROWS * sizeof(float));
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(*rows); *rows = nullptr;
+    if (*scales) { (void)hipFree(*scales); *scales = nullptr; }
+    return fail(c, NVDB_ERR_HIP, std::string("corpus allocation: ") + hipGetErrorString(e));
+  }
+  return NVDB_OK;
+}
+
+// The third way a corpus becomes resident, next to upload and adopt: device buffers from corpus_alloc_padded, filled by the caller,
+// become the context's OWNED corpus (freed with it; from this call on, also when it fails); shadows and row norms as for an upload.
+nvdb_status corpus_take_ownership(nvdb_hip_ctx* c, void* dev_rows, float* dev_scales, uint64_t n, uint32_t dim, uint32_t dtype,
+                                  uint64_t global_row_base) {
+  free_corpus(c);
+  c->rows = dev_rows; c->scales = dev_scales; c->owned = true;
+  nvdb_status st = check_corpus_args(c, n, dim, dtype);
+  if (!st && (!dev_rows || (dtype == NVDB_DTYPE_I8 && !dev_scales))) st = fail(c, NVDB_ERR_INVALID, "take_ownership: null buffer");
+  if (st) { free_corpus(c); return st; }
+  HIPCHK(c, hipSetDevice(c->device));
+  c->n = n; c->dim = dim; c->dtype = dtype; c->row_base = global_row_base;
+  return compute_max_norm(c);
+}
+
+}  // namespace nvdbhip
+
 extern "C" {
 
 int nvdb_hip_abi_version(void) { return NVDB_HIP_ABI_VERSION; }
@@ -251,21 +289,15 @@ nvdb_status nvdb_hip_upload_corpus(nvdb_hip_ctx* c, const void* rows, const floa
   HIPCHK(c, hipSetDevice(c->device));
   free_corpus(c);
   const size_t bytes = static_cast<size_t>(n) * dim * bpe_of(dtype);
-  const size_t pad = static_cast<size_t>(PAD_ROWS) * dim * bpe_of(dtype) + 4096;   // zero rows up to a whole tile (+ slack for vector loads)
   const bool dbg = std::getenv("NVDB_UPLOAD_DEBUG") != nullptr;      // stderr: where an upload's time goes
   const auto t0 = std::chrono::steady_clock::now();
   auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-  HIPCHK(c, hipMalloc(&c->rows, bytes + pad));
-  HIPCHK(c, hipMemset(static_cast<char*>(c->rows) + bytes, 0, pad));
+  if ((st = corpus_alloc_padded(c, n, dim, dtype, &c->rows, &c->scales))) return st;   // zero rows up to a whole tile (+ slack for vector loads)
   c->owned = true;
   const double t_alloc = since();
   if ((st = upload_rows(c, c->rows, rows, bytes))) return st;
   const double t_rows = since();
-  if (dtype == NVDB_DTYPE_I8) {
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->scales), (n + PAD_ROWS) * sizeof(float)));
-    HIPCHK(c, hipMemset(c->scales + n, 0, PAD_ROWS * sizeof(float)));
-    HIPCHK(c, hipMemcpy(c->scales, scales, n * sizeof(float), hipMemcpyHostToDevice));
-  }
+  if (dtype == NVDB_DTYPE_I8) HIPCHK(c, hipMemcpy(c->scales, scales, n * sizeof(float), hipMemcpyHostToDevice));
   c->n = n; c->dim = dim; c->dtype = dtype; c->row_base = global_row_base;
   st = compute_max_norm(c);
   if (dbg) std::fprintf(stderr, "[nvdb upload] %.2f GB: device allocation %.1f ms, rows %.1f ms (%.1f GB/s), scales + row-norm pass (+ shadow copy) %.1f ms\n",
@@ -292,15 +324,8 @@ nvdb_status nvdb_hip_generate_corpus(nvdb_hip_ctx* c, uint64_t seed, uint64_t n,
   if (st) return st;
   HIPCHK(c, hipSetDevice(c->device));
   free_corpus(c);
-  const size_t bytes = static_cast<size_t>(n) * dim * bpe_of(dtype);
-  const size_t pad = static_cast<size_t>(PAD_ROWS) * dim * bpe_of(dtype) + 4096;
-  HIPCHK(c, hipMalloc(&c->rows, bytes + pad));
-  HIPCHK(c, hipMemset(static_cast<char*>(c->rows) + bytes, 0, pad));
+  if ((st = corpus_alloc_padded(c, n, dim, dtype, &c->rows, &c->scales))) return st;
   c->owned = true;
-  if (dtype == NVDB_DTYPE_I8) {
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->scales), (n + PAD_ROWS) * sizeof(float)));
-    HIPCHK(c, hipMemset(c->scales + n, 0, PAD_ROWS * sizeof(float)));
-  }
   c->n = n; c->dim = dim; c->dtype = dtype; c->row_base = global_row_base;
   // launch in slabs so that a single launch stays well inside the grid-size limit
   const uint64_t slab = 1ull << 24;

@@ -10,6 +10,7 @@
 //   nvdb_launch_exact.cpp  ... of the exact fp32-order kernels, select / rescore / merge, the any-k path (kernels_exact*.h, kernels_largek.h)
 //   nvdb_refine.cpp        exact-L2 refine (kernels_refine.h)
 //   nvdb_partitions.cpp    partitioned probe search: partition table, coarse quantiser, work list, launches (kernels_partitions.h)
+//   nvdb_ivf.cpp           IVF-Flat build: row assignment, spherical k-means, list layout, the reordered index (kernels_ivf.h, ivf_layout.h)
 //   nvdb_debug.cpp         developer entry points (libnvdb_hip_dev.so only)
 //   nvdb_group.cpp         device group, layered on the public ABI (does not include this header)
 // There is NO CPU fallback anywhere in these files: without a working HIP device every entry point that computes returns
@@ -292,6 +293,9 @@ nvdb_status launch_filter_f16(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, u
 nvdb_status launch_filter_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint32_t row_hi, uint32_t nq, uint32_t QT, uint32_t cap);
 nvdb_status launch_boot_f16(nvdb_hip_ctx* c, hipStream_t s, uint32_t n0, uint32_t nq, uint32_t QT, uint32_t cap, uint32_t nb);
 nvdb_status launch_boot_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t n0, uint32_t nq, uint32_t QT, uint32_t cap);
+// nvdb_corpus.cpp
+nvdb_status corpus_alloc_padded(nvdb_hip_ctx* c, uint64_t n, uint32_t dim, uint32_t dtype, void** rows, float** scales);
+nvdb_status corpus_take_ownership(nvdb_hip_ctx* c, void* dev_rows, float* dev_scales, uint64_t n, uint32_t dim, uint32_t dtype, uint64_t global_row_base);
 // nvdb_partitions.cpp
 void parts_drop(nvdb_hip_ctx* c);        // the corpus changes: forget the partition table and the centroids (the workspace stays)
 void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace

@@ -32,6 +32,8 @@ EXPORTS = [
     "nvdb_hip_group_exchange", "nvdb_hip_group_upload_corpus", "nvdb_hip_group_generate_corpus", "nvdb_hip_group_set_option",
     "nvdb_hip_group_search_batch",
     "nvdb_hip_set_partitions", "nvdb_hip_set_centroids", "nvdb_hip_search_partitions", "nvdb_hip_search_ivf",
+    "nvdb_hip_assign_rows", "nvdb_hip_train_centroids", "nvdb_ivf_layout_host",
+    "nvdb_hip_ivf_build", "nvdb_hip_ivf_destroy", "nvdb_hip_ivf_last_error", "nvdb_hip_ivf_ctx", "nvdb_hip_ivf_info", "nvdb_hip_ivf_search",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_filter_variant", "nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -172,6 +174,18 @@ def _bind(L, dev):
     L.nvdb_hip_set_centroids.argtypes = [vp, vp]
     L.nvdb_hip_search_partitions.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_search_ivf.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_assign_rows.argtypes = [vp, vp, u32, u64, u64, vp]
+    L.nvdb_hip_train_centroids.argtypes = [vp, u32, u32, u64, u64, vp, vp]
+    L.nvdb_ivf_layout_host.argtypes = [vp, u64, u32, vp, vp]
+    L.nvdb_hip_ivf_build.argtypes = [vp, vp, u32, C.POINTER(vp)]
+    L.nvdb_hip_ivf_destroy.argtypes = [vp]
+    L.nvdb_hip_ivf_destroy.restype = None
+    L.nvdb_hip_ivf_last_error.argtypes = [vp]
+    L.nvdb_hip_ivf_last_error.restype = C.c_char_p
+    L.nvdb_hip_ivf_ctx.argtypes = [vp]
+    L.nvdb_hip_ivf_ctx.restype = vp
+    L.nvdb_hip_ivf_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u32), vp, vp]
+    L.nvdb_hip_ivf_search.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, C.POINTER(Timing)]
     for name in EXPORTS:
         getattr(L, name)
     if dev:
@@ -270,6 +284,18 @@ def merge_topk_host(ids, scores):
     if st:
         raise NvdbError(st, "merge_topk_host")
     return oi, os_
+
+
+def ivf_layout_host(assign, nparts):
+    """assign: [n] partition numbers -> (offsets [nparts + 1] u64, perm [n] u32): the lists ordered by partition, then by row."""
+    assign = np.ascontiguousarray(assign, dtype=np.uint32).ravel()
+    offsets = np.zeros(nparts + 1, dtype=np.uint64)
+    perm = np.zeros(max(assign.size, 1), dtype=np.uint32)
+    st = load_library().nvdb_ivf_layout_host(assign.ctypes.data if assign.size else perm.ctypes.data, assign.size, nparts,
+                                             offsets.ctypes.data, perm.ctypes.data)
+    if st:
+        raise NvdbError(st, "ivf_layout_host: an entry >= nparts, or more than 0xFFFFFF00 rows")
+    return offsets, perm[:assign.size]
 
 
 # ------------------------------------------------------------------------------- device context
@@ -412,6 +438,27 @@ class HipContext:
                                                counts.ctypes.data, probe.ctypes.data if want_probe else None, None))
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
+    # -- IVF-Flat build
+    def assign_rows(self, centroids, row0=0, nrows=None):
+        """Best centroid ([nparts, dim] f32) of the resident rows [row0, row0 + nrows) -> [nrows] u32."""
+        centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+        if nrows is None:
+            nrows = self.corpus_info()["n"] - row0
+        out = np.zeros(max(nrows, 0), dtype=np.uint32)
+        self._chk(self.lib.nvdb_hip_assign_rows(self.h, centroids.ctypes.data, centroids.shape[0], row0, nrows,
+                                                out.ctypes.data if out.size else None))
+        return out
+
+    def train_centroids(self, nparts, iters, seed, max_train_rows=0, init=None):
+        """Spherical k-means over the resident corpus -> [nparts, dim] f32 unit centroids."""
+        dim = self.corpus_info()["dim"]
+        if init is not None:
+            init = np.ascontiguousarray(init, dtype=np.float32).reshape(nparts, dim)
+        out = np.zeros((nparts, dim), dtype=np.float32)
+        self._chk(self.lib.nvdb_hip_train_centroids(self.h, nparts, iters, seed, max_train_rows,
+                                                    init.ctypes.data if init is not None else None, out.ctypes.data))
+        return out
+
     # -- refine
     def refine_l2_topk(self, queries, cand_ids, K, want_dist=True, want_timing=False):
         queries = np.ascontiguousarray(queries, dtype=np.float32)
@@ -427,6 +474,74 @@ class HipContext:
 
     def refine_l2_topk_dev(self, dev_q, dev_cand, Q, R, K, dev_out_ids, dev_out_dist, stream=None):
         self._chk(self.lib.nvdb_hip_refine_l2_topk_dev(self.h, dev_q, dev_cand, Q, R, K, dev_out_ids, dev_out_dist, stream))
+
+
+class _BorrowedContext(HipContext):
+    """A context somebody else owns (an IvfIndex's): every method of HipContext, close() only forgets the handle."""
+
+    def __init__(self, lib, handle, device):
+        self.lib, self.h, self.device = lib, handle, device
+
+    def close(self):
+        self.h = None
+
+
+class IvfIndex:
+    """IVF-Flat index over the corpus resident in `src_ctx` (nvdb_hip_ivf): the rows copied into list order under `centroids`
+    ([nparts, dim] f32, e.g. from HipContext.train_centroids), searched by probe, answered in src_ctx's ids.  src_ctx is not
+    touched and may be closed afterwards."""
+
+    def __init__(self, src_ctx, centroids):
+        self.lib = src_ctx.lib
+        centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+        if centroids.ndim != 2:
+            raise ValueError("centroids must be [nparts, dim]")
+        h = C.c_void_p()
+        st = self.lib.nvdb_hip_ivf_build(src_ctx.h, centroids.ctypes.data, centroids.shape[0], C.byref(h))
+        if st:
+            raise NvdbError(st, self.lib.nvdb_hip_ivf_last_error(None).decode())
+        self.h = h
+        self.ctx = _BorrowedContext(self.lib, C.c_void_p(self.lib.nvdb_hip_ivf_ctx(h)), src_ctx.device)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.close()
+            self.lib.nvdb_hip_ivf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, st):
+        if st:
+            raise NvdbError(st, self.lib.nvdb_hip_ivf_last_error(self.h).decode())
+
+    def info(self):
+        """dict(n, nparts, offsets [nparts + 1] u64, perm [n] u32: perm[position] = row of the source corpus)."""
+        n, nparts = C.c_uint64(), C.c_uint32()
+        self._chk(self.lib.nvdb_hip_ivf_info(self.h, C.byref(n), C.byref(nparts), None, None))
+        offsets = np.zeros(nparts.value + 1, dtype=np.uint64)
+        perm = np.zeros(max(n.value, 1), dtype=np.uint32)
+        self._chk(self.lib.nvdb_hip_ivf_info(self.h, None, None, offsets.ctypes.data, perm.ctypes.data))
+        return dict(n=n.value, nparts=nparts.value, offsets=offsets, perm=perm[:n.value])
+
+    def search(self, queries, k, nprobe, want_probe=False):
+        """(ids [nq, k] in the source corpus' ids, scores [nq, k], counts [nq][, probe [nq, nprobe]]); equal scores are ordered
+        by (partition, original id)."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        nq = queries.shape[0]
+        ids = np.full((nq, k), np.iinfo(np.uint64).max, dtype=np.uint64)
+        scores = np.full((nq, k), -np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        probe = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
+        self._chk(self.lib.nvdb_hip_ivf_search(self.h, queries.ctypes.data, nq, k, nprobe, ids.ctypes.data, scores.ctypes.data,
+                                               counts.ctypes.data, probe.ctypes.data if want_probe else None, None))
+        return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
 
 class DeviceGroup:
