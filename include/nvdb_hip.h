@@ -156,6 +156,12 @@ nvdb_status nvdb_hip_search_check(nvdb_hip_ctx* ctx, nvdb_hip_scan_stats* stats)
 /* Statistics of the last nvdb_hip_search_batch() (summed over its sub-batches). */
 nvdb_status nvdb_hip_get_stats(nvdb_hip_ctx* ctx, nvdb_hip_scan_stats* stats);
 
+/* The int8 filter shadow of an fp16 / fp32 corpus (option "q8_shadow"), read-only: out4[0] = 1 if one is resident, out4[1] = its bytes
+ * of HBM, out4[2] = 1 if it has overflowed on this corpus and searches now start on the fp16 filter (cleared by the next corpus load),
+ * out4[3] = what the filter launches of the last search streamed: 0 nothing (exact / any-k route), 1 the fp16 rows, 2 the int8
+ * shadow, 3 an int8 corpus.  After a host-API call that retried, out4[3] describes the last attempt. */
+nvdb_status nvdb_hip_shadow_info(const nvdb_hip_ctx* ctx, uint64_t* out4);
+
 /* Merge per-shard top-k lists (e.g. after an RCCL all-gather): in[s][nq][k] -> out[nq][k] with
  * the same (score desc, id asc) order.  Device buffers, enqueued on hip_stream.  Any k the flat path accepts (the reference
  * bounds k by N only, src/flat_index.cpp:24): up to nshards*k = 4096 the lists of one query are ranked in LDS; longer ones are
@@ -298,7 +304,7 @@ nvdb_status nvdb_ivf_layout_host(const uint32_t* assign, uint64_t n, uint32_t np
  * int8 scales included) into a context of its own on the same device, with the partition table and the centroids set.
  * src is not touched and may be destroyed afterwards to give its HBM back; DURING the build the device holds the source
  * AND the copy (plus shadows of both where the dtype / dim has them).  Options that act when a corpus becomes resident
- * ("f32_shadow", "q8_shadow") are taken over from src.  The index's context has global_row_base 0; src's base is kept and
+ * ("f32_shadow", "q8_shadow" = 1; the automatic shadow serves the flat scan only) are taken over from src.  The index's context has global_row_base 0; src's base is kept and
  * added when ids are mapped back.  NVDB_ERR_NO_CORPUS: src holds no corpus.
  * NVDB_IVF_DEBUG (environment): build / train report their assignment / update / gather hipEvent times on stderr. */
 typedef struct nvdb_hip_ivf nvdb_hip_ivf;
@@ -320,7 +326,8 @@ nvdb_status nvdb_hip_ivf_search(nvdb_hip_ivf* ivf, const float* queries, uint32_
 
 /* Tunables (defaults are what bench.py measures; the table with meanings is in INTEGRATION.md section 4b):
  * "path" (0 auto, 1 exact, 2 mfma-filter), "chunk0_rows", "chunk_growth", "cand_cap", "min_filter_batch", "mfma_boot", "waves8",
- * "sibling_sync", "sync_every", "sync_lead", "tile_permute", "f32_shadow" (set before the upload), "exact_mfma" (exact scores on the fp32
+ * "sibling_sync", "sync_every", "sync_lead", "tile_permute", "f32_shadow", "q8_shadow" (-1 automatic, 0 never, 1 always),
+ * "q8_auto_min_rows", "q8_auto_max_mb" (all set before the upload), "exact_mfma" (exact scores on the fp32
  * matrix cores), "exact_lds", "i8_defer", "i8_lo_bits", "boot_tiles", "xcd_balance", "rescore8", "refine_v2", "refine_pinned" (reference CUDA_PINNED:
  * pinned host staging in nvdb_hip_refine_l2_topk), "largek_budget_mb" (HBM for the any-k path's score matrix), "time_kernels" (1: start /
  * stop events attached to every launch of the dominant kernel, read by nvdb_hip_collect_kernel_times), "time_launches" (the same for one host-API

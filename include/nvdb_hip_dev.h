@@ -55,6 +55,9 @@ typedef struct nvdb_hip_plan_shape {
   uint32_t dim, fdim, dtype;                  /* fdim: the dim the filter kernels run at (== dim without a padded shadow) */
   uint32_t owned, has_shadow16, has_shadow8, q8shadow, i8_scales_signed;
   uint32_t num_cu, cap_hint;
+  uint32_t shadow_demoted;                    /* the int8 filter shadow has overflowed on this corpus before (the retry ladder's flag) */
+  uint32_t load_rule;                         /* 1: whether the corpus has an int8 filter shadow is decided as at load time, from the options */
+  uint64_t free_hbm;                          /* ... "q8_shadow", "q8_auto_min_rows", "q8_auto_max_mb" and this many bytes of free HBM */
 } nvdb_hip_plan_shape;
 
 typedef struct nvdb_hip_plan_option { const char* key; int64_t value; } nvdb_hip_plan_option;
@@ -73,6 +76,7 @@ typedef struct nvdb_hip_plan {
   uint32_t chunk_lo[NVDB_PLAN_MAX_CHUNKS], chunk_hi[NVDB_PLAN_MAX_CHUNKS];
   uint32_t stat_chunks;                       /* nvdb_hip_scan_stats.chunks / .rows_scanned the search will report (any-k: for a batch */
   uint64_t stat_rows_scanned;                 /* whose score matrix fits the HBM budget in one piece -- only the device knows) */
+  uint32_t filter_shadow;                     /* filter route: 1 = the launches stream the int8 shadow of an fp16 / fp32 corpus, 0 = the corpus' own dtype's kernels */
 } nvdb_hip_plan;
 
 /* err (may be NULL): err_len bytes for the message of a status != NVDB_OK -- a rejected option, an unsupported shape

@@ -106,6 +106,7 @@ __global__ __launch_bounds__(256) void shadow_q8_kernel(const SrcT* __restrict__
       ss = __builtin_fmaf(d, d, ss);
     }
     for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    if (!(ss == ss)) bad = true;                       // a NaN element: fmaxf above dropped it, its residual did not
     if (lane == 0) dst_scales[r] = scale;
     wres = fmaxf(wres, sqrtf(ss) * 1.0001f);
   }

@@ -18,6 +18,7 @@ void free_corpus(nvdb_hip_ctx* c) {
   c->rows = nullptr; c->scales = nullptr; c->owned = false; c->n = 0; c->dim = 0; c->fdim = 0; c->dtype = 0; c->max_norm = 0.f;
   c->cap_hint = 0;
   c->q8shadow = false; c->resid_max = 0.f; c->filter_max_norm = 0.f;
+  c->shadow_demoted = false; c->last_filter_kind = 0;
   parts_drop(c);                                   // a partition table describes the rows it was set for
 }
 
@@ -43,15 +44,31 @@ nvdb_status compute_max_norm(nvdb_hip_ctx* c) {
   c->fdim = c->dim;
   c->filter_max_norm = c->max_norm;
   c->q8shadow = false; c->resid_max = 0.f;
-  // Option q8_shadow (off by default): an fp16 / fp32 corpus is FILTERED through an int8 copy of itself -- half (a quarter) of the bytes per
-  // row and integer MFMAs at twice the fp16 rate; the rows' quantisation residual joins the filter's error bound and every survivor is
-  // re-scored from the ORIGINAL rows, so ids and scores stay bit-exact.  Costs n x dim bytes of HBM.
-  if (c->opt_q8_shadow && c->dtype != NVDB_DTYPE_I8 && i8_filter_dim(c->dim)) {
+  // Option q8_shadow: an fp16 / fp32 corpus is FILTERED through an int8 copy of itself -- half (a quarter) of the bytes per row and
+  // integer MFMAs at twice the fp16 rate; the rows' quantisation residual joins the filter's error bound and every survivor is
+  // re-scored from the ORIGINAL rows, so ids and scores stay bit-exact.  Costs n x (dim + 4) bytes of HBM.  1: always; automatic
+  // (the default): large fp16 corpora within an HBM budget (q8_shadow_wanted), and an allocation that fails there is no error --
+  // the context is then what it would have been without the option.  max_norm stays the fp16 filter's bound beside the shadow's.
+  size_t free_hbm = 0, total_hbm = 0;
+  const bool automatic = c->opt_q8_shadow < 0;
+  if (automatic && hipMemGetInfo(&free_hbm, &total_hbm) != hipSuccess) { (void)hipGetLastError(); free_hbm = 0; }
+  if (q8_shadow_wanted(c, free_hbm)) {
     const uint32_t sdim = c->dim;
     const size_t count = static_cast<size_t>(c->n) * sdim, pad = static_cast<size_t>(PAD_ROWS) * sdim + 4096;
     const size_t n_pad = (static_cast<size_t>(c->n) + PAD_ROWS - 1) / PAD_ROWS * PAD_ROWS + PAD_ROWS;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->shadow8), count + pad));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->shadow8_scales), n_pad * 4));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->shadow8), count + pad);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->shadow8_scales), n_pad * 4);
+    if (e != hipSuccess) {
+      if (c->shadow8) (void)hipFree(c->shadow8);
+      c->shadow8 = nullptr; c->shadow8_scales = nullptr;
+      (void)hipGetLastError();                                 // (clears the sticky error state)
+      if (!automatic) return fail(c, NVDB_ERR_HIP, std::string("q8_shadow allocation: ") + hipGetErrorString(e));
+    }
+  }
+  if (c->shadow8) {
+    const uint32_t sdim = c->dim;
+    const size_t count = static_cast<size_t>(c->n) * sdim, pad = static_cast<size_t>(PAD_ROWS) * sdim + 4096;
+    const size_t n_pad = (static_cast<size_t>(c->n) + PAD_ROWS - 1) / PAD_ROWS * PAD_ROWS + PAD_ROWS;
     HIPCHK(c, hipMemsetAsync(c->shadow8 + count, 0, pad, c->stream));
     HIPCHK(c, hipMemsetAsync(c->shadow8_scales, 0, n_pad * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(bits, 0, 8, c->stream));
@@ -374,7 +391,9 @@ nvdb_status nvdb_hip_set_option(nvdb_hip_ctx* c, const char* key, int64_t value)
   else if (k == "sync_lead") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "sync_lead must be >= 1"); c->opt_sync_lead = value; }
   else if (k == "sibling_sync") { c->opt_sibling_sync = value ? 1 : 0; }
   else if (k == "f32_shadow") { c->opt_f32_shadow = value ? 1 : 0; }
-  else if (k == "q8_shadow") { c->opt_q8_shadow = value ? 1 : 0; }
+  else if (k == "q8_shadow") { c->opt_q8_shadow = value < 0 ? -1 : value ? 1 : 0; }
+  else if (k == "q8_auto_min_rows") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "q8_auto_min_rows must be >= 1"); c->opt_q8_auto_min_rows = value; }
+  else if (k == "q8_auto_max_mb") { if (value < 0 || value > (int64_t(1) << 30)) return fail(c, NVDB_ERR_INVALID, "q8_auto_max_mb out of range"); c->opt_q8_auto_max_mb = value; }
 #ifdef NVDB_HIP_DEV
   else if (k == "mfma16") { c->opt_mfma16 = value ? 1 : 0; }
   else if (k == "i8_wide") { c->opt_i8_wide = value ? 1 : 0; }
@@ -415,6 +434,15 @@ nvdb_status nvdb_hip_set_option(nvdb_hip_ctx* c, const char* key, int64_t value)
   else if (k == "chunk_growth") { if (value != 0 && (value < 2 || value > 64)) return fail(c, NVDB_ERR_INVALID, "chunk_growth must be 0 (automatic) or in [2,64]"); c->opt_growth = value; }
   else if (k == "min_filter_batch") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "min_filter_batch must be >= 1"); c->opt_min_filter_batch = value; }
   else return fail(c, NVDB_ERR_INVALID, "unknown option: " + k);
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_shadow_info(const nvdb_hip_ctx* c, uint64_t* out4) {
+  if (!c || !out4) return NVDB_ERR_INVALID;
+  out4[0] = c->q8shadow ? 1u : 0u;
+  out4[1] = c->q8shadow ? q8_shadow_bytes(c->n, c->dim) : 0u;
+  out4[2] = c->shadow_demoted ? 1u : 0u;
+  out4[3] = c->last_filter_kind;
   return NVDB_OK;
 }
 

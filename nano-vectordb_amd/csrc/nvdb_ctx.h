@@ -83,10 +83,16 @@ struct nvdb_hip_ctx {
   float max_norm = 0.f;
   bool i8_scales_signed = false;                   // int8 corpus with a negative or NaN row scale: the in-loop second-stage build (no biased accumulators)
   signed char* shadow8 = nullptr;                  // int8 corpus with a dim the kernels are not instantiated for: rows zero-padded to fdim; or (q8shadow) the int8 FILTER shadow of an fp16 / fp32 corpus
-  bool q8shadow = false;                           // fp16 / fp32 corpus filtered through an int8 shadow (option q8_shadow): the int8 MFMA kernels stream shadow8, every survivor is re-scored from the original rows
-  float filter_max_norm = 0.f;                     // max row norm of what the int8 filter streams (== max_norm for an int8 corpus; the shadow's for q8shadow)
+  bool q8shadow = false;                           // fp16 / fp32 corpus with a resident int8 FILTER shadow (option q8_shadow): the int8 MFMA kernels can stream shadow8, every survivor is re-scored from the original rows
+  bool use_shadow = true;                          // ... and this search's filter launches stream it (plan_search's choice, which the shape helpers below read); false: the corpus' own fp16 filter
+  bool shadow_demoted = false;                     // the shadow's lists or wave logs overflowed on this corpus (host API's retry ladder): searches start on the fp16 filter, in the spirit of cap_hint; a reload clears it
+  uint32_t last_filter_kind = 0;                   // what the last search's filter launches streamed: 0 none (exact / any-k route), 1 fp16 rows, 2 the int8 shadow, 3 an int8 corpus
+  float filter_max_norm = 0.f;                     // max row norm of what the int8 filter streams (== max_norm for an int8 corpus; the shadow's for q8shadow -- max_norm stays the fp16 filter's)
   float resid_max = 0.f;                           // q8shadow: largest ||x - scale * x_q|| over the rows -- the corpus side of the filter's error bound
-  int64_t opt_q8_shadow = 0;                       // set before the corpus is loaded: build the int8 filter shadow for fp16 / fp32 corpora whose dim the int8 kernels take
+  int64_t opt_q8_shadow = -1;                      // set before the corpus is loaded: 1 = build the int8 filter shadow for fp16 / fp32 corpora whose dim the int8 kernels take, 0 = never (set later: also stop
+                                                   // streaming a resident one where the fp16 filter stands beside it), -1 = automatic (q8_shadow_wanted below)
+  int64_t opt_q8_auto_min_rows = 1 << 20;          // automatic shadow: corpora with at least this many rows (smaller ones are latency-bound: today's chain) ...
+  int64_t opt_q8_auto_max_mb = 16384;              // ... whose shadow takes at most this much HBM (and at most a quarter of what is free once the corpus is resident)
   float* shadow8_scales = nullptr;                 // ... and its scales in a buffer padded to whole tiles
   _Float16* shadow16 = nullptr;                    // fp16 copy streamed by the MFMA filter (fp32 corpus and/or padded dim)
   uint32_t fdim = 0;                               // dim the filter kernels run at (>= dim; == dim without padding)
@@ -225,7 +231,23 @@ inline const _Float16* filter_rows_f16(const nvdb_hip_ctx* c) {
 }
 
 // the int8 MFMA kernels do the filtering: an int8 corpus, or an fp16 / fp32 corpus with an int8 filter shadow
-inline bool filter_is_i8(const nvdb_hip_ctx* c) { return c->dtype == NVDB_DTYPE_I8 || c->q8shadow; }
+inline bool filter_is_i8(const nvdb_hip_ctx* c) { return c->dtype == NVDB_DTYPE_I8 || (c->q8shadow && c->use_shadow); }
+// a shadow context whose corpus the fp16 filter streams as it is (every int8 dim is an fp16 dim too): both filters are available
+inline bool f16_beside_shadow(const nvdb_hip_ctx* c) { return c->q8shadow && c->dtype == NVDB_DTYPE_F16 && f16_filter_dim(c->dim); }
+// which of the two a search starts on: the shadow, unless it was switched off after the load or has overflowed on this corpus
+inline bool shadow_preferred(const nvdb_hip_ctx* c) { return c->q8shadow && !(f16_beside_shadow(c) && (c->opt_q8_shadow == 0 || c->shadow_demoted)); }
+// HBM the int8 filter shadow of a corpus takes: a byte per element and a scale per row (padding aside)
+inline uint64_t q8_shadow_bytes(uint64_t n, uint32_t dim) { return n * (static_cast<uint64_t>(dim) + 4u); }
+// Does a corpus get the shadow when it becomes resident?  free_hbm: what hipMemGetInfo reports free with the corpus resident.
+// 1: wherever the int8 kernels take the dim.  Automatic: fp16 corpora only (the fp16 filter streams the corpus itself, so the
+// fallback costs no second copy), large enough to be throughput-bound, within the HBM budget.
+inline bool q8_shadow_wanted(const nvdb_hip_ctx* c, uint64_t free_hbm) {
+  if (c->opt_q8_shadow == 0 || c->dtype == NVDB_DTYPE_I8 || !i8_filter_dim(c->dim)) return false;
+  if (c->opt_q8_shadow > 0) return true;
+  const uint64_t bytes = q8_shadow_bytes(c->n, c->dim);
+  return c->dtype == NVDB_DTYPE_F16 && f16_filter_dim(c->dim) && c->n >= static_cast<uint64_t>(c->opt_q8_auto_min_rows) &&
+         bytes <= (static_cast<uint64_t>(c->opt_q8_auto_max_mb) << 20) && bytes <= free_hbm / 4;
+}
 inline bool filter_supported(const nvdb_hip_ctx* c) {
   if (c->q8shadow) return true;
   if (c->dtype == NVDB_DTYPE_F16) return f16_filter_dim(c->dim) || c->shadow16 != nullptr;
@@ -247,7 +269,8 @@ inline uint32_t filter_nb(const nvdb_hip_ctx* c, uint32_t nq) {
 // ---- shape facts of the filter builds: written here once, used by the launchers (nvdb_launch_f16.cpp, nvdb_launch_i8.cpp)
 // AND by plan_search (nvdb_plan.h), which sizes the query tiles and aligns the chunk boundaries with them ----
 // a corpus this library allocated (a shadow copy always is) is zero-padded to whole tiles
-inline bool corpus_padded(const nvdb_hip_ctx* c) { return c->owned || c->shadow16 != nullptr || c->shadow8 != nullptr; }
+// (as far as the filter that streams this search goes: the fp16 filter beside an int8 shadow reads the corpus itself)
+inline bool corpus_padded(const nvdb_hip_ctx* c) { return c->owned || c->shadow16 != nullptr || (c->shadow8 != nullptr && filter_is_i8(c)); }
 // fp16, dims <= 768: batches > 128 (NB == 2) run the 16x16x32 build (developer library: unless option mfma16 = 0) ...
 inline bool f16_m16_build(const nvdb_hip_ctx* c, uint32_t nb) { return nb == 2 && c->opt_mfma16; }
 // ... whose tiles are MB 16-row blocks: 64-row tiles up to d = 384, 32-row tiles beyond

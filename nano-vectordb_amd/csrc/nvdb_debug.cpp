@@ -277,12 +277,16 @@ nvdb_status nvdb_hip_debug_plan(const nvdb_hip_plan_shape* shape, const nvdb_hip
   if (shape->has_shadow16) c.shadow16 = &shadow16;
   if (shape->has_shadow8) c.shadow8 = &shadow8;
   c.num_cu = static_cast<int>(shape->num_cu); c.cap_hint = shape->cap_hint;
+  c.shadow_demoted = shape->shadow_demoted != 0;
   auto failed = [&](nvdb_status st, const char* msg) { if (err && err_len) std::snprintf(err, err_len, "%s", msg); return st; };
   for (uint32_t i = 0; i < n_opts; ++i)
     if (nvdb_status st = nvdb_hip_set_option(&c, opts[i].key, opts[i].value)) return failed(st, c.err.c_str());
+  // load_rule: the corpus got its int8 filter shadow by the rule a load applies (q8_shadow_wanted, the options above, free_hbm bytes free)
+  if (shape->load_rule && q8_shadow_wanted(&c, shape->free_hbm)) { c.shadow8 = &shadow8; c.q8shadow = true; }
   SearchPlan p;
   if (nvdb_status st = plan_search(c, nq, k, force_path, cap_override, p)) return failed(st, p.error);
   *out = nvdb_hip_plan{};
+  out->filter_shadow = p.route == ROUTE_FILTER && p.shadow;
   out->route = p.route; out->prep = p.prep; out->prep_inits = p.prep_inits; out->k_wide = p.k_wide;
   out->k_eff = p.k_eff; out->cap = p.cap; out->QPB = p.QPB; out->QT = p.QT; out->nq_pad = p.nq_pad; out->prog_words = p.prog_words;
   out->head = p.head;

@@ -224,7 +224,9 @@ nvdb_status search_sub_batch(nvdb_hip_group* g, const float* queries, uint32_t n
   return NVDB_OK;
 }
 
-// the round-2 flow, kept for what the device exchange does not take (a tripped self-check): every shard through the host API (which retries and falls back by itself), lists merged on the host
+// the round-2 flow, kept for what the device exchange does not take (a tripped self-check): every shard through the host API (which retries and falls back by itself), lists merged on the host.
+// The host API's ladder is also what demotes a shard's overflowing int8 filter shadow to the fp16 filter: the flag lives in the shard's
+// context, so the group's later device-side searches on that shard start on the fp16 filter and stop tripping.
 nvdb_status search_host_merge(nvdb_hip_group* g, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores) {
   const size_t G = g->ctx.size();
   const size_t per = static_cast<size_t>(nq) * k;

@@ -1,7 +1,8 @@
 // nvdb_plan.h -- everything one flat search decides before its first launch (DESIGN.md "pipeline"): route, list capacity,
-// query tiling, bootstrap, chunk boundaries.  plan_search is pure integer arithmetic over corpus facts and options: no HIP
-// call, no context field written, so tests/test_search_plan_cpu.py pins it without a device (nvdb_hip_debug_plan).  The
-// shape facts it shares with the launchers (tile rows, queries per workgroup, which int8 build logs) live in nvdb_ctx.h.
+// which filter streams, query tiling, bootstrap, chunk boundaries.  plan_search is pure integer arithmetic over corpus facts
+// and options: no HIP call, so tests/test_search_plan_cpu.py pins it without a device (nvdb_hip_debug_plan).  It writes ONE
+// context field, use_shadow (which of a shadow context's two filters streams this search): the shape facts it shares with
+// the launchers (tile rows, queries per workgroup, which int8 build logs; nvdb_ctx.h) are read off the context and follow it.
 #pragma once
 #include "nvdb_ctx.h"
 
@@ -28,6 +29,7 @@ struct SearchPlan {
   uint32_t r0 = 0;                      // rows the exact / seeded bootstrap covers; the chunks tile [r0, n_al)
   uint64_t size0 = 0;                   // rows of the first chunk; every later one covers (growth - 1) x the rows before it
   bool tail_exact = false;              // ragged tail [n_al, n) of an adopted corpus on the exact kernel
+  bool shadow = false;                  // the filter launches stream the int8 shadow of an fp16 / fp32 corpus (else: the kernels of the corpus' own dtype)
 };
 
 // end of the chunk that starts at row r
@@ -36,9 +38,13 @@ inline uint32_t chunk_end(const SearchPlan& p, uint32_t r) {
   return static_cast<uint32_t>(std::min<uint64_t>(p.n_al, r + size));
 }
 
-inline nvdb_status plan_search(const nvdb_hip_ctx& ctx, uint32_t nq, uint32_t k, int force_path, uint32_t cap_override, SearchPlan& p) {
+inline nvdb_status plan_search(nvdb_hip_ctx& ctx, uint32_t nq, uint32_t k, int force_path, uint32_t cap_override, SearchPlan& p) {
+  // a shadow context: the int8 shadow streams unless it was switched off or has overflowed on this corpus (shadow_preferred);
+  // everything below -- tiles, queries per workgroup, growth, bootstrap -- is then that filter's
+  ctx.use_shadow = shadow_preferred(&ctx);
   const nvdb_hip_ctx* c = &ctx;
   p = SearchPlan{};
+  p.shadow = c->use_shadow;
   const uint32_t n = static_cast<uint32_t>(c->n);
   const uint32_t k_eff = p.k_eff = static_cast<uint32_t>(std::min<uint64_t>(k, c->n));
   int path = force_path ? force_path : static_cast<int>(c->opt_path);

@@ -91,6 +91,7 @@ nvdb_status search_core(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint
   c->ev_filter.clear();
   c->prog_slot = 0;
   if (p.route == ROUTE_FILTER) c->perm_on = p.perm_on;
+  c->last_filter_kind = p.route != ROUTE_FILTER ? 0u : p.shadow ? 2u : c->dtype == NVDB_DTYPE_I8 ? 3u : 1u;
 
   // per-search resets and queries: the prep launch does both itself (option fuse), else init_search_kernel and a copy
   // (one query tile per stream has no siblings to keep in step: no rendezvous counters to reset)
@@ -185,12 +186,25 @@ nvdb_status sum_candidates(nvdb_hip_ctx* c, unsigned long long* total) {
   return NVDB_OK;
 }
 
-// One sub-batch (<= 1024 queries) of the host API: search, and when the self-check tripped (rare) redo it -- rung 1 on the filter path
-// with the longest candidate lists the select kernel can sort (near-duplicate-heavy corpora: thousands of rows inside the filter's
-// error band of the k-th score; re-scoring them is cheap, only the list was too short), rung 2, if that is still not enough or the
-// bound itself was violated, on the always-correct exact path.  (The queries are in the device buffer by then: the retries read
-// them there.)  verdict(rung) waits for the attempt and says NVDB_ERR_INTERNAL when its self-check tripped; at rung 0 it leaves
-// the exact counts in c->stats (search_check_impl).  *part: the statistics of the FIRST attempt, the ones that are reported.
+// a query with a NaN / infinite element is flagged like a list overflow by the prep launch, with a negative error bound
+static nvdb_status any_non_finite_query(nvdb_hip_ctx* c, uint32_t nq, bool* any) {
+  std::vector<float> eb(nq);
+  HIPCHK(c, hipMemcpy(eb.data(), c->ebound.p, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToHost));
+  *any = std::any_of(eb.begin(), eb.end(), [](float v) { return v < 0.f; });
+  return NVDB_OK;
+}
+
+// One sub-batch (<= 1024 queries) of the host API: search, and when the self-check tripped (rare) redo it.  The ladder after a filter
+// attempt whose lists or wave logs overflowed:
+//   rung 1a  (the attempt streamed the int8 shadow and the fp16 filter stands beside it) the fp16 filter at the same list capacity --
+//            the shadow's band is the widest (||q|| x the largest quantisation residual of ANY row), so a corpus that quantises badly
+//            overflows there alone; the context is marked shadow_demoted and later searches start on the fp16 filter
+//   rung 1b  the filter with the longest candidate lists the select kernel can sort (near-duplicate-heavy corpora: thousands of rows
+//            inside the filter's error band of the k-th score; re-scoring them is cheap, only the list was too short)
+//   rung 2   if that is still not enough, the bound itself was violated, or a query is not finite: the always-correct exact path.
+// (The queries are in the device buffer by then: the retries read them there.)  verdict(rung) waits for the attempt and says
+// NVDB_ERR_INTERNAL when its self-check tripped; at rung 0 it leaves the exact counts in c->stats (search_check_impl).
+// *part: the statistics of the FIRST attempt, the ones that are reported.
 template <typename Verdict>
 static nvdb_status search_sub_batch(nvdb_hip_ctx* c, hipStream_t s, const float* dq, uint32_t nq, uint32_t k, uint64_t* oi, float* os, bool time_filter,
                                     const float* host_q, uint32_t* st_out, Verdict&& verdict, nvdb_hip_scan_stats* part, bool* tripped = nullptr) {
@@ -200,7 +214,19 @@ static nvdb_status search_sub_batch(nvdb_hip_ctx* c, hipStream_t s, const float*
   *part = c->stats;
   if (tripped) *tripped = chk == NVDB_ERR_INTERNAL;
   if (chk != NVDB_ERR_INTERNAL) return chk;
-  if (part->path == 2 && !part->bound_violations && c->last_cap < SELECT_MAX_CAP) {
+  const uint32_t cap0 = c->last_cap;
+  bool retry_filter = part->path == 2 && !part->bound_violations;
+  if (retry_filter && c->last_filter_kind == 2 && f16_beside_shadow(c)) {
+    bool non_finite = false;
+    if ((st = any_non_finite_query(c, nq, &non_finite))) return st;
+    if (non_finite) retry_filter = false;
+    else {
+      c->shadow_demoted = true;                            // (plan_search now picks the fp16 filter, here and in later searches)
+      if ((st = search_core(c, s, dq, nq, k, oi, os, 2, false, cap0, false, nullptr, st_out))) return st;
+      if ((chk = verdict(1)) != NVDB_OK && chk != NVDB_ERR_INTERNAL) return chk;
+    }
+  }
+  if (chk != NVDB_OK && retry_filter && cap0 < SELECT_MAX_CAP) {
     if ((st = search_core(c, s, dq, nq, k, oi, os, 2, false, SELECT_MAX_CAP, false, nullptr, st_out))) return st;
     if ((chk = verdict(1)) == NVDB_OK) c->cap_hint = SELECT_MAX_CAP;
     else if (chk != NVDB_ERR_INTERNAL) return chk;

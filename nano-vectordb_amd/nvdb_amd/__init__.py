@@ -25,7 +25,7 @@ EXPORTS = [
     "nvdb_hip_abi_version", "nvdb_hip_device_count", "nvdb_hip_create", "nvdb_hip_destroy", "nvdb_hip_last_error",
     "nvdb_hip_upload_corpus", "nvdb_hip_adopt_corpus", "nvdb_hip_generate_corpus", "nvdb_hip_corpus_info",
     "nvdb_hip_download_rows", "nvdb_hip_search_batch", "nvdb_hip_search_batch_dev", "nvdb_hip_search_check",
-    "nvdb_hip_get_stats", "nvdb_hip_collect_kernel_times", "nvdb_hip_merge_topk_dev", "nvdb_hip_merge_topk_strided_dev", "nvdb_merge_topk_host", "nvdb_hip_set_option",
+    "nvdb_hip_get_stats", "nvdb_hip_shadow_info", "nvdb_hip_collect_kernel_times", "nvdb_hip_merge_topk_dev", "nvdb_hip_merge_topk_strided_dev", "nvdb_merge_topk_host", "nvdb_hip_set_option",
     "nvdb_hip_refine_l2_topk", "nvdb_hip_refine_l2_topk_dev", "nvdb_synth_rows_f32", "nvdb_f32_to_f16",
     "nvdb_quantize_i8_rows",
     "nvdb_hip_group_create", "nvdb_hip_group_destroy", "nvdb_hip_group_last_error", "nvdb_hip_group_size", "nvdb_hip_group_ctx",
@@ -68,7 +68,8 @@ class ScanStats(C.Structure):
 class PlanShape(C.Structure):
     _fields_ = [("n", C.c_uint64), ("dim", C.c_uint32), ("fdim", C.c_uint32), ("dtype", C.c_uint32), ("owned", C.c_uint32),
                 ("has_shadow16", C.c_uint32), ("has_shadow8", C.c_uint32), ("q8shadow", C.c_uint32), ("i8_scales_signed", C.c_uint32),
-                ("num_cu", C.c_uint32), ("cap_hint", C.c_uint32)]
+                ("num_cu", C.c_uint32), ("cap_hint", C.c_uint32), ("shadow_demoted", C.c_uint32), ("load_rule", C.c_uint32),
+                ("free_hbm", C.c_uint64)]
 
 
 class PlanOption(C.Structure):
@@ -83,7 +84,7 @@ class Plan(C.Structure):
                                           "padded", "perm_on", "boot", "tile_rows", "n_al", "growth", "boot_tiles", "boot_rows", "r0",
                                           "tail_exact", "helper_tile_rows", "n_chunks")] + \
                [("chunk_lo", C.c_uint32 * PLAN_MAX_CHUNKS), ("chunk_hi", C.c_uint32 * PLAN_MAX_CHUNKS), ("stat_chunks", C.c_uint32),
-                ("stat_rows_scanned", C.c_uint64)]
+                ("stat_rows_scanned", C.c_uint64), ("filter_shadow", C.c_uint32)]
 
 
 class GroupStats(C.Structure):
@@ -141,6 +142,7 @@ def _bind(L, dev):
     L.nvdb_hip_search_batch_dev.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.nvdb_hip_search_check.argtypes = [vp, C.POINTER(ScanStats)]
     L.nvdb_hip_get_stats.argtypes = [vp, C.POINTER(ScanStats)]
+    L.nvdb_hip_shadow_info.argtypes = [vp, C.POINTER(u64)]
     L.nvdb_hip_collect_kernel_times.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double)]
     L.nvdb_hip_merge_topk_dev.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp]
@@ -386,6 +388,13 @@ class HipContext:
         s = ScanStats()
         self._chk(self.lib.nvdb_hip_get_stats(self.h, C.byref(s)))
         return s.as_dict()
+
+    def shadow_info(self):
+        """The int8 filter shadow of an fp16 / fp32 corpus: resident, its bytes, demoted (searches start on the fp16 filter),
+        last_filter (what the last search's filter launches streamed: None, "f16", "shadow" or "i8")."""
+        out = (C.c_uint64 * 4)()
+        self._chk(self.lib.nvdb_hip_shadow_info(self.h, out))
+        return dict(resident=bool(out[0]), bytes=int(out[1]), demoted=bool(out[2]), last_filter=(None, "f16", "shadow", "i8")[out[3]])
 
     def collect_kernel_times(self):
         n, ms, fl, by = C.c_uint32(), C.c_double(), C.c_double(), C.c_double()
