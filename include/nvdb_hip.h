@@ -68,7 +68,8 @@ typedef struct nvdb_hip_timing {
 
 /* What the last flat search did (for tests, bench.py and the roofline arithmetic). */
 typedef struct nvdb_hip_scan_stats {
-  uint32_t path;               /* 1 = exact fp32 scan, 2 = MFMA filter + exact rescore (k <= 1024), 3 = any-k (k > 64 off the filter path), 4 = partitioned probe search */
+  uint32_t path;               /* 1 = exact fp32 scan, 2 = MFMA filter + exact rescore (k <= 1024), 3 = any-k (k > 64 off the filter path), 4 = partitioned probe search,
+                                  5 = range search, filter route, 6 = range search, exact route */
   uint32_t chunks;             /* corpus chunks (kernel launches of the dominant kernel)          */
   uint64_t rows_scanned;       /* rows x query-tiles streamed by the dominant kernel              */
   uint64_t candidates;         /* (query,row) pairs that reached the exact rescore                */
@@ -153,8 +154,37 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* ctx, const float* queries, uint3
 nvdb_status nvdb_hip_search_batch_dev(nvdb_hip_ctx* ctx, const float* dev_queries, uint32_t nq, uint32_t k,
                                       uint64_t* dev_out_ids, float* dev_out_scores, void* hip_stream);
 nvdb_status nvdb_hip_search_check(nvdb_hip_ctx* ctx, nvdb_hip_scan_stats* stats);
-/* Statistics of the last nvdb_hip_search_batch() (summed over its sub-batches). */
+/* Statistics of the last nvdb_hip_search_batch() / nvdb_hip_range_search() (summed over its sub-batches). */
 nvdb_status nvdb_hip_get_stats(nvdb_hip_ctx* ctx, nvdb_hip_scan_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * range search: every row whose score reaches a per-query radius.  The reference has no range entry point; the shape is the one
+ * users know from FAISS: Index::range_search fills a RangeSearchResult whose lims[nq + 1] delimit each query's slice of the
+ * labels / distances arrays (faiss/impl/AuxIndexStructures.h).  Here the slices are exact: the scores are the reference-order dot
+ * products nvdb_hip_search_batch returns, bit for bit, whichever route (MFMA filter + exact rescore, or exact scores) found them.
+ * ------------------------------------------------------------------------------------------- */
+
+/* queries [nq][dim] f32, radius [nq], out_lims [nq + 1]: host memory; synchronous.
+ * Row i belongs to query q iff score(q, i) >= radius[q] as a C float comparison: a NaN score never belongs, a NaN radius gives an
+ * empty slice, radius = -inf every row whose score is not NaN, +0.0 and -0.0 compare equal.  Inside a slice: score descending, id
+ * ascending.  out_lims[q] .. out_lims[q + 1] is query q's slice, out_lims[0] = 0, out_lims[nq] the total; the lims are complete and
+ * exact whenever the call returns NVDB_OK or NVDB_ERR_UNSUPPORTED.
+ * The packed results (uint64 global ids = global_row_base + local row, float scores) stay in grow-only device buffers of the context
+ * until the next range search or corpus load; nvdb_hip_range_results copies them out.
+ * Budget: option "range_max_mb" (default 4096).  Packed results (12 bytes per entry) beyond it -> NVDB_ERR_UNSUPPORTED, the message names
+ * the total and the option, the lims are written (tighten the radii or raise the option), nothing is held.
+ * nq == 0 -> NVDB_OK, out_lims[0] = 0.  Null pointer -> NVDB_ERR_INVALID.  No corpus -> NVDB_ERR_NO_CORPUS.  Any nq (sub-batches of
+ * 1024 queries inside).  Option "path": 0 automatic, 1 exact route, 2 filter route, as for the flat search; the result does not depend on it.
+ * A violated filter bound (never observed) -> the results are recomputed on the exact route and the call returns NVDB_ERR_INTERNAL.
+ * nvdb_hip_get_stats afterwards: path 5 / 6, chunks (filter launches + score-matrix passes), rows_scanned, candidates (list entries
+ * that reached the rescore), overflow_queries (queries redone on the exact route), bound_violations.
+ * timing (optional): h2d / kernel / total; the results' copy is nvdb_hip_range_results'. */
+nvdb_status nvdb_hip_range_search(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq,
+                                  const float* radius /* [nq] */, uint64_t* out_lims /* [nq+1] */,
+                                  nvdb_hip_timing* timing /* may be NULL */);
+/* out_ids / out_scores: out_lims[nq] entries of the last range search (host memory).  NVDB_ERR_INVALID: a null pointer, no range
+ * search yet, the last one exceeded its budget, or the corpus has changed since. */
+nvdb_status nvdb_hip_range_results(nvdb_hip_ctx* ctx, uint64_t* out_ids, float* out_scores);
 
 /* The int8 filter shadow of an fp16 / fp32 corpus (option "q8_shadow"), read-only: out4[0] = 1 if one is resident, out4[1] = its bytes
  * of HBM, out4[2] = 1 if it has overflowed on this corpus and searches now start on the fp16 filter (cleared by the next corpus load),
@@ -329,7 +359,7 @@ nvdb_status nvdb_hip_ivf_search(nvdb_hip_ivf* ivf, const float* queries, uint32_
  * "sibling_sync", "sync_every", "sync_lead", "tile_permute", "f32_shadow", "q8_shadow" (-1 automatic, 0 never, 1 always),
  * "q8_auto_min_rows", "q8_auto_max_mb" (all set before the upload), "exact_mfma" (exact scores on the fp32
  * matrix cores), "exact_lds", "i8_defer", "i8_lo_bits", "boot_tiles", "xcd_balance", "rescore8", "refine_v2", "refine_pinned" (reference CUDA_PINNED:
- * pinned host staging in nvdb_hip_refine_l2_topk), "largek_budget_mb" (HBM for the any-k path's score matrix), "time_kernels" (1: start /
+ * pinned host staging in nvdb_hip_refine_l2_topk), "largek_budget_mb" (HBM for the any-k path's score matrix), "range_max_mb" (packed results a range search may hold), "time_kernels" (1: start /
  * stop events attached to every launch of the dominant kernel, read by nvdb_hip_collect_kernel_times), "time_launches" (the same for one host-API
  * call with a timing struct -> stats.filter_kernel_ms).  "mfma16", "i8_wide", "i8_pipe", "i8_waves8", "i8_mfma16", "i8_small8" select kernel
  * variants that exist in libnvdb_hip_dev.so only: the product accepts their default values (1, 1, 1, 0, 1) and returns

@@ -19,6 +19,7 @@ void free_corpus(nvdb_hip_ctx* c) {
   c->cap_hint = 0;
   c->q8shadow = false; c->resid_max = 0.f; c->filter_max_norm = 0.f;
   c->shadow_demoted = false; c->last_filter_kind = 0;
+  c->range_valid = false; c->range_total = 0;      // the held range results describe the rows they were found in
   parts_drop(c);                                   // a partition table describes the rows it was set for
 }
 
@@ -284,7 +285,8 @@ void nvdb_hip_destroy(nvdb_hip_ctx* c) {
   parts_destroy(c);
   if (c->hostblock.p) c->misc.p = nullptr;         // (misc lives inside the host API's result block)
   for (DevBuf* b : {&c->q32, &c->q16, &c->qscale, &c->qinv, &c->ebound, &c->slack, &c->thr, &c->cnt, &c->overflow, &c->cand,
-                    &c->out_ids, &c->out_scores, &c->misc, &c->hostblock, &c->hitlog, &c->prog, &c->qdelta, &c->rq, &c->rcand, &c->rout_ids, &c->rout_dist, &c->rdbg, &c->lk_scores, &c->lk_sel, &c->lk_hist, &c->lk_state, &c->xcdw, &c->tickets})
+                    &c->out_ids, &c->out_scores, &c->misc, &c->hostblock, &c->hitlog, &c->prog, &c->qdelta, &c->rq, &c->rcand, &c->rout_ids, &c->rout_dist, &c->rdbg, &c->lk_scores, &c->lk_sel, &c->lk_hist, &c->lk_state, &c->xcdw, &c->tickets,
+                    &c->rg_radius, &c->rg_kept, &c->rg_off, &c->rg_idx, &c->rg_q, &c->rg_desc, &c->rg_taken, &c->rg_slab, &c->rg_ids, &c->rg_scores})
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   for (auto& k : c->klaunch) { (void)hipEventDestroy(k.e0); (void)hipEventDestroy(k.e1); }
@@ -431,6 +433,7 @@ nvdb_status nvdb_hip_set_option(nvdb_hip_ctx* c, const char* key, int64_t value)
   else if (k == "refine_pinned") { c->opt_refine_pinned = value ? 1 : 0; }
   else if (k == "refine_dbg_q") { if (value < 0) return fail(c, NVDB_ERR_INVALID, "refine_dbg_q must be >= 0"); c->opt_refine_dbg_q = value; }
   else if (k == "largek_budget_mb") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "largek_budget_mb must be >= 1"); c->opt_largek_budget_mb = value; }
+  else if (k == "range_max_mb") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "range_max_mb must be >= 1"); c->opt_range_max_mb = value; }
   else if (k == "chunk_growth") { if (value != 0 && (value < 2 || value > 64)) return fail(c, NVDB_ERR_INVALID, "chunk_growth must be 0 (automatic) or in [2,64]"); c->opt_growth = value; }
   else if (k == "min_filter_batch") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "min_filter_batch must be >= 1"); c->opt_min_filter_batch = value; }
   else return fail(c, NVDB_ERR_INVALID, "unknown option: " + k);

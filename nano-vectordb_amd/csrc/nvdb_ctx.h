@@ -5,6 +5,7 @@
 //   nvdb_plan.h            what one flat search will do (plan_search): route, list capacity, query tiling, bootstrap, chunk boundaries -- decided
 //                          before anything is enqueued, from corpus facts, options and the launchers' shape facts below; no HIP call
 //   nvdb_search.cpp        one flat search: plan -> workspace -> launches (search_core); the search entry points, their self-checks and retry ladder
+//   nvdb_range.cpp         range search (every row whose score reaches a per-query radius): plan, filter route, exact route, packing (kernels_range.h)
 //   nvdb_launch_f16.cpp    launch helpers of the fp16 MFMA filter kernels (kernels_filter.h), query prep for them
 //   nvdb_launch_i8.cpp     ... of the int8 kernels (kernels_filter.h, kernels_filter_i8s.h)
 //   nvdb_launch_exact.cpp  ... of the exact fp32-order kernels, select / rescore / merge, the any-k path (kernels_exact*.h, kernels_largek.h)
@@ -145,6 +146,12 @@ struct nvdb_hip_ctx {
   void* rpinned = nullptr;                         // ... [queries | candidates | out ids | out dist]
   size_t rpinned_bytes = 0;
   int64_t opt_largek_budget_mb = 8192;             // HBM the any-k path may use for its score matrix
+  // range search (nvdb_range.cpp): the last call's packed results stay here for nvdb_hip_range_results
+  DevBuf rg_radius, rg_kept, rg_off, rg_idx, rg_q, rg_desc, rg_taken, rg_slab;   // radii, list / score counts, pack offsets, flagged queries (numbers, compact batch), exact-route passes
+  DevBuf rg_ids, rg_scores;                        // packed global ids / scores of the last range search (grow-only)
+  uint64_t range_total = 0;                        // ... their entries
+  bool range_valid = false;                        // ... and whether nvdb_hip_range_results may hand them out (false: none yet, over budget, corpus changed)
+  int64_t opt_range_max_mb = 4096;                 // packed results (12 bytes per entry) a range search may hold
 
   // options
   int64_t opt_path = 0, opt_chunk0 = 512, opt_cap = 0, opt_min_filter_batch = 1, opt_growth = 0;   // opt_growth 0 = automatic
@@ -309,6 +316,11 @@ nvdb_status launch_select(nvdb_hip_ctx* c, hipStream_t s, uint32_t nq, uint32_t 
 nvdb_status launch_rescore(nvdb_hip_ctx* c, hipStream_t s, const float* q32, uint32_t nq, uint32_t cap, FinalSelect fs = FinalSelect{}, bool* fused = nullptr);
 nvdb_status search_largek(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint32_t nq, uint32_t k, uint64_t* dev_out_ids, float* dev_out_scores,
                           uint32_t n_rows = 0, Cand* seed_cand = nullptr, uint32_t* seed_cnt = nullptr, uint32_t seed_cap = 0);
+// what the any-k path and the range search's exact route share: queries per score-matrix sub-batch (QB) and per workgroup (QG) within
+// largek_budget_mb, the [queries][ld] score matrix of the first n rows, the descending sort of `lists` key lists of K2 (power of two) entries
+nvdb_status score_matrix_batch(nvdb_hip_ctx* c, uint32_t nq, size_t per_query_bytes, size_t held_bytes, uint32_t& QB, uint32_t& QG);
+nvdb_status launch_score_matrix(nvdb_hip_ctx* c, hipStream_t s, const float* q32, uint32_t nq, float* scores, uint64_t ld, uint32_t n, uint32_t QG, bool mfma_ok);
+nvdb_status launch_sort_keys(nvdb_hip_ctx* c, hipStream_t s, unsigned long long* keys, uint32_t K2, uint32_t lists);
 // nvdb_launch_f16.cpp / nvdb_launch_i8.cpp
 nvdb_status launch_prep_q16(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint32_t nq, uint32_t nq_pad, const PrepInit& pinit);
 nvdb_status launch_prep_q8(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint32_t nq, uint32_t nq_pad, const PrepInit& pinit);
@@ -323,6 +335,8 @@ nvdb_status corpus_take_ownership(nvdb_hip_ctx* c, void* dev_rows, float* dev_sc
 void parts_drop(nvdb_hip_ctx* c);        // the corpus changes: forget the partition table and the centroids (the workspace stays)
 void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace
 // nvdb_search.cpp
+nvdb_status ensure_q32(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes);          // the host API's query buffer: qbytes + 8 rows; a new buffer starts all zero
+nvdb_status zero_q32_pad(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes);        // ... and the 8 rows behind this call's queries read as zeros
 nvdb_status next_prog_region(nvdb_hip_ctx* c, hipStream_t s, uint32_t nwg, uint32_t** out);
 ScatterArgs scatter_args(nvdb_hip_ctx* c, uint32_t cap, uint32_t trows = 0);
 float filter_events_ms(const nvdb_hip_ctx* c);                                 // sum over the last search's timed filter launches (ev_filter)

@@ -285,6 +285,45 @@ nvdb_status launch_scores_exact_mfma(nvdb_hip_ctx* c, hipStream_t s, const float
   return NVDB_OK;
 }
 
+// queries per sub-batch: what the score matrix + whatever else a query needs (per_query_bytes) may take of HBM; held_bytes: already ours, counts as available
+nvdb_status score_matrix_batch(nvdb_hip_ctx* c, uint32_t nq, size_t per_query_bytes, size_t held_bytes, uint32_t& QB, uint32_t& QG) {
+  const size_t qstride_bytes = static_cast<size_t>((c->dim + 3u) & ~3u) * 4;
+  if (qstride_bytes > 60 * 1024) return fail(c, NVDB_ERR_UNSUPPORTED, "dim too large for the exact kernel's LDS query staging (max ~14800)");
+  QG = nq >= 8 ? 8 : (nq >= 4 ? 4 : (nq >= 2 ? 2 : 1));
+  while (QG > 1 && QG * qstride_bytes > 60 * 1024) QG >>= 1;
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+  const size_t budget = std::min<size_t>(static_cast<size_t>(c->opt_largek_budget_mb) << 20, (free_b + held_bytes) / 2);
+  QB = static_cast<uint32_t>(std::min<size_t>(nq, std::max<size_t>(1, budget / per_query_bytes)));
+  if (QB >= QG) QB = QB / QG * QG;
+  if (per_query_bytes > free_b + held_bytes) return fail(c, NVDB_ERR_HIP, "any-k path: not enough free HBM for one query's score row");
+  return NVDB_OK;
+}
+
+// scores[q][row] for the first n rows: the fp32 matrix cores where the shape allows (mfma_ok: the whole corpus is scored), else the VALU kernel
+nvdb_status launch_score_matrix(nvdb_hip_ctx* c, hipStream_t s, const float* q32, uint32_t nq, float* scores, uint64_t ld, uint32_t n, uint32_t QG, bool mfma_ok) {
+  if (mfma_ok && c->opt_exact_mfma && nq > 8 && exact_mfma_dim(c->dim) && n >= 64u * EXACT_MFMA_ROWS) return launch_scores_exact_mfma(c, s, q32, nq, scores, ld);
+  switch (QG) {
+    case 8: return launch_scores_exact_qg<8>(c, s, q32, nq, scores, ld, n);
+    case 4: return launch_scores_exact_qg<4>(c, s, q32, nq, scores, ld, n);
+    case 2: return launch_scores_exact_qg<2>(c, s, q32, nq, scores, ld, n);
+    default: return launch_scores_exact_qg<1>(c, s, q32, nq, scores, ld, n);
+  }
+}
+
+// `lists` adjacent key lists of K2 entries each, sorted descending: in LDS up to 8192 entries, else step by step in global memory
+nvdb_status launch_sort_keys(nvdb_hip_ctx* c, hipStream_t s, unsigned long long* keys, uint32_t K2, uint32_t lists) {
+  if (K2 <= 8192) {
+    if (nvdb_status ls = raise_lds_limit(c, reinterpret_cast<const void*>(bitonic_lds_kernel), 8192 * 8)) return ls;
+    bitonic_lds_kernel<<<lists, 256, static_cast<size_t>(K2) * 8, s>>>(keys, K2);
+  } else
+    for (uint32_t size = 2; size <= K2; size <<= 1)
+      for (uint32_t stride = size >> 1; stride > 0; stride >>= 1)
+        bitonic_global_step_kernel<<<dim3((K2 / 2 + 255) / 256, lists), 256, 0, s>>>(keys, K2, size, stride);
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
 // seed_cand != nullptr: only the rows [0, n_rows) and the result goes into the filter path's candidate lists (exact bootstrap of a
 // wide-k search on dims without an MFMA bootstrap build) instead of the output arrays
 nvdb_status search_largek(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint32_t nq, uint32_t k, uint64_t* dev_out_ids, float* dev_out_scores,
@@ -294,20 +333,9 @@ nvdb_status search_largek(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, ui
   const uint64_t ld = (static_cast<uint64_t>(n) + 63u) & ~63ull;
   uint32_t K2 = 2;
   while (K2 < k_eff) K2 <<= 1;
-  const size_t qstride_bytes = static_cast<size_t>((c->dim + 3u) & ~3u) * 4;
-  if (qstride_bytes > 60 * 1024) return fail(c, NVDB_ERR_UNSUPPORTED, "dim too large for the exact kernel's LDS query staging (max ~14800)");
-  uint32_t QG = nq >= 8 ? 8 : (nq >= 4 ? 4 : (nq >= 2 ? 2 : 1));
-  while (QG > 1 && QG * qstride_bytes > 60 * 1024) QG >>= 1;
-  // queries per sub-batch: what the score matrix + key lists may take of HBM
-  const size_t per_query = ld * 4 + static_cast<size_t>(K2) * 8;
-  size_t free_b = 0, total_b = 0;
-  HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-  const size_t have = c->lk_scores.bytes + c->lk_sel.bytes;                     // already ours: counts as available
-  const size_t budget = std::min<size_t>(static_cast<size_t>(c->opt_largek_budget_mb) << 20, (free_b + have) / 2);
-  uint32_t QB = static_cast<uint32_t>(std::min<size_t>(nq, std::max<size_t>(1, budget / per_query)));
-  if (QB >= QG) QB = QB / QG * QG;
-  if (per_query > free_b + have) return fail(c, NVDB_ERR_HIP, "any-k path: not enough free HBM for one query's score row");
+  uint32_t QB = 0, QG = 0;
   nvdb_status st;
+  if ((st = score_matrix_batch(c, nq, ld * 4 + static_cast<size_t>(K2) * 8, c->lk_scores.bytes + c->lk_sel.bytes, QB, QG))) return st;
   if ((st = ensure(c, c->lk_scores, static_cast<size_t>(QB) * ld * 4))) return st;
   if ((st = ensure(c, c->lk_sel, static_cast<size_t>(QB) * K2 * 8))) return st;
   if ((st = ensure(c, c->lk_hist, static_cast<size_t>(QB) * 256 * 4))) return st;
@@ -316,33 +344,18 @@ nvdb_status search_largek(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, ui
   unsigned long long* sel = static_cast<unsigned long long*>(c->lk_sel.p);
   uint32_t* hist = static_cast<uint32_t*>(c->lk_hist.p);
   RadixState* rst = static_cast<RadixState*>(c->lk_state.p);
-  if (K2 <= 8192) {
-    const void* fn = reinterpret_cast<const void*>(bitonic_lds_kernel);
-    if (nvdb_status ls = raise_lds_limit(c, fn, 8192 * 8)) return ls;
-  }
   for (uint32_t q0 = 0; q0 < nq; q0 += QB) {
     const uint32_t b = std::min(QB, nq - q0);
     const float* q = dev_q + static_cast<size_t>(q0) * c->dim;
     radix_init_kernel<<<b, 256, 0, s>>>(rst, hist, b, k_eff);
-    if (!seed_cand && c->opt_exact_mfma && b > 8 && exact_mfma_dim(c->dim) && n >= 64u * EXACT_MFMA_ROWS) st = launch_scores_exact_mfma(c, s, q, b, scores, ld);
-    else switch (QG) {
-      case 8: st = launch_scores_exact_qg<8>(c, s, q, b, scores, ld, n); break;
-      case 4: st = launch_scores_exact_qg<4>(c, s, q, b, scores, ld, n); break;
-      case 2: st = launch_scores_exact_qg<2>(c, s, q, b, scores, ld, n); break;
-      default: st = launch_scores_exact_qg<1>(c, s, q, b, scores, ld, n); break;
-    }
-    if (st) return st;
+    if ((st = launch_score_matrix(c, s, q, b, scores, ld, n, QG, !seed_cand))) return st;
     const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>((n + 255u) / 256u, (8u * static_cast<uint32_t>(c->num_cu) + b - 1) / b));
     for (int pass = 0; pass < 8; ++pass) {
       radix_hist_kernel<<<dim3(G, b), 256, 0, s>>>(scores, ld, n, pass, rst, hist);
       radix_pick_kernel<<<b, 256, 0, s>>>(rst, hist);
     }
     collect_kernel<<<dim3(G, b), 256, 0, s>>>(scores, ld, n, rst, sel, K2, k_eff);
-    if (K2 <= 8192) bitonic_lds_kernel<<<b, 256, static_cast<size_t>(K2) * 8, s>>>(sel, K2);
-    else
-      for (uint32_t size = 2; size <= K2; size <<= 1)
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1)
-          bitonic_global_step_kernel<<<dim3((K2 / 2 + 255) / 256, b), 256, 0, s>>>(sel, K2, size, stride);
+    if ((st = launch_sort_keys(c, s, sel, K2, b))) return st;
     if (seed_cand) seed_lists_kernel<<<dim3((k_eff + 255) / 256, b), 256, 0, s>>>(sel, K2, scores, ld, k_eff, seed_cand + static_cast<size_t>(q0) * seed_cap, seed_cap, seed_cnt + q0);
     else emit_kernel<<<dim3((k + 255) / 256, b), 256, 0, s>>>(sel, K2, scores, ld, k_eff, k, c->row_base,
                                                              reinterpret_cast<unsigned long long*>(dev_out_ids) + static_cast<size_t>(q0) * k,

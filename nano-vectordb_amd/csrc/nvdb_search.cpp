@@ -27,6 +27,22 @@ nvdb_status ensure_hostblock(nvdb_hip_ctx* c, size_t out_bytes) {
   return NVDB_OK;
 }
 
+// The host API's query buffer.  The 8 query rows after a batch must read as zeros (the exact kernel loads query groups of 8).  The
+// buffer is zero beyond q32_dirty (zeroed when allocated, only ever written through [0, qbytes) of some call): a memset is enqueued
+// only when an earlier, larger batch left queries where this call's padding lies.
+nvdb_status ensure_q32(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes) {
+  const size_t before = c->q32.p ? c->q32.bytes : 0;
+  if (nvdb_status st = ensure(c, c->q32, qbytes + 8 * static_cast<size_t>(c->dim) * 4)) return st;
+  if (c->q32.bytes != before) { HIPCHK(c, hipMemsetAsync(c->q32.p, 0, c->q32.bytes, s)); c->q32_dirty = 0; }   // a new buffer starts all zero
+  return NVDB_OK;
+}
+nvdb_status zero_q32_pad(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes) {
+  const size_t pad_bytes = 8 * static_cast<size_t>(c->dim) * 4;
+  if (c->q32_dirty > qbytes) HIPCHK(c, hipMemsetAsync(static_cast<char*>(c->q32.p) + qbytes, 0, std::min(pad_bytes, c->q32_dirty - qbytes), s));
+  c->q32_dirty = std::max(c->q32_dirty, qbytes);
+  return NVDB_OK;
+}
+
 // rendezvous counters for the next filter launch: a region the init kernel already cleared, or (past PROG_SLOTS
 // launches in one search) a region cleared here
 nvdb_status next_prog_region(nvdb_hip_ctx* c, hipStream_t s, uint32_t nwg, uint32_t** out) {
@@ -326,11 +342,7 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t qbytes = static_cast<size_t>(nq) * c->dim * 4;
-  {
-    const size_t before = c->q32.p ? c->q32.bytes : 0;
-    if ((st = ensure(c, c->q32, qbytes + 8 * static_cast<size_t>(c->dim) * 4))) return st;
-    if (c->q32.bytes != before) { HIPCHK(c, hipMemsetAsync(c->q32.p, 0, c->q32.bytes, s)); c->q32_dirty = 0; }   // a new buffer starts all zero (zero_pad below)
-  }
+  if ((st = ensure_q32(c, s, qbytes))) return st;
   if (nq <= 1024) { if ((st = ensure_hostblock(c, static_cast<size_t>(nq) * k * 12))) return st; }
   else {
     if ((st = ensure(c, c->out_ids, static_cast<size_t>(nq) * k * 8))) return st;
@@ -339,15 +351,7 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
   const hipEvent_t e[4] = {get_event(c, 60), get_event(c, 61), get_event(c, 62), get_event(c, 63)};
   c->stats_lazy = false;
   const bool time_filter = timing != nullptr && c->opt_time_launches;
-  const size_t pad_bytes = 8 * static_cast<size_t>(c->dim) * 4;
-  // The 8 query rows after the batch must read as zeros (the exact kernel loads query groups of 8).  The buffer is zero beyond
-  // q32_dirty (zeroed when allocated, only ever written through [0, qbytes) of some call): a memset is enqueued only when an
-  // earlier, larger batch left queries where this call's padding lies.
-  auto zero_pad = [&]() -> nvdb_status {
-    if (c->q32_dirty > qbytes) HIPCHK(c, hipMemsetAsync(static_cast<char*>(c->q32.p) + qbytes, 0, std::min(pad_bytes, c->q32_dirty - qbytes), s));
-    c->q32_dirty = std::max(c->q32_dirty, qbytes);
-    return NVDB_OK;
-  };
+  auto zero_pad = [&]() -> nvdb_status { return zero_q32_pad(c, s, qbytes); };
   nvdb_hip_scan_stats total{};
   if (nq <= 1024) {
     // One sub-batch: everything the host needs comes back in ONE synchronisation through pinned staging -- the

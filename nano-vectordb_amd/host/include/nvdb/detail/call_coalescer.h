@@ -41,6 +41,20 @@ class CallCoalescer {
     return me.keff;
   }
 
+  // A call that is not a top-k search (a range search: its result has no fixed shape to coalesce) takes the context for itself
+  // through the same lock: it waits for the running batch, runs while the searches queue, and wakes them.
+  template <typename F>
+  void exclusive(F&& f) {
+    std::unique_lock<std::mutex> lk(mu_);
+    wake_.wait(lk, [&] { return !busy_; });
+    busy_ = true;
+    lk.unlock();
+    try { f(); } catch (...) { lk.lock(); busy_ = false; wake_.notify_all(); throw; }
+    lk.lock();
+    busy_ = false;
+    wake_.notify_all();
+  }
+
  private:
   struct Request {
     const float* q; uint32_t nq, k; uint64_t* ids; float* sc;

@@ -34,6 +34,12 @@ class FlatIndexHIP {
   std::vector<SearchResult> search_topk_dot(const float* q, uint32_t k) const;
   // nq queries [nq][dim]; result [nq][min(k,N)] row-major, best first
   std::vector<SearchResult> search_topk_dot_batch(const float* queries, uint32_t nq, uint32_t k) const;
+  // Every row whose dot product with q is >= radius (C float comparison; NaN never passes), score descending, id ascending: the
+  // exact scores of search_topk_dot.  The reference has no range entry point (FAISS users know it as Index::range_search).
+  // Serialised with the searches on the context; not coalesced (results have no common shape).
+  std::vector<SearchResult> range_search_dot(const float* q, float radius) const;
+  // nq queries [nq][dim], radius [nq]; *lims (nq + 1 entries) delimits each query's slice of the returned vector
+  std::vector<SearchResult> range_search_dot_batch(const float* queries, uint32_t nq, const float* radius, std::vector<uint64_t>* lims) const;
   double last_kernel_ms() const { return last_kernel_ms_; }       // of the calling thread's last search only when callers do not overlap
   nvdb_hip_ctx* context() const { return ctx_; }
 

@@ -49,6 +49,28 @@ std::vector<SearchResult> FlatIndexHIP::search_topk_dot_batch(const float* queri
 
 std::vector<SearchResult> FlatIndexHIP::search_topk_dot(const float* q, uint32_t k) const { return search_topk_dot_batch(q, 1, k); }
 
+std::vector<SearchResult> FlatIndexHIP::range_search_dot_batch(const float* queries, uint32_t nq, const float* radius, std::vector<uint64_t>* lims) const {
+  if (!queries || !radius) throw std::runtime_error(queries ? "Null radius" : "Null query");
+  std::vector<uint64_t> lm(static_cast<size_t>(nq) + 1, 0);
+  std::vector<uint64_t> ids;
+  std::vector<float> sc;
+  std::string err;
+  calls_->exclusive([&] {
+    // (the error text lives in the context: read before the next batch may start)
+    if (nvdb_hip_range_search(ctx_, queries, nq, radius, lm.data(), nullptr) != NVDB_OK) { err = nvdb_hip_last_error(ctx_); return; }
+    ids.resize(std::max<size_t>(lm[nq], 1));
+    sc.resize(ids.size());
+    if (nvdb_hip_range_results(ctx_, ids.data(), sc.data()) != NVDB_OK) err = nvdb_hip_last_error(ctx_);
+  });
+  if (!err.empty()) throw std::runtime_error(err);
+  std::vector<SearchResult> out(lm[nq]);
+  for (size_t i = 0; i < out.size(); ++i) out[i] = SearchResult{ids[i], sc[i]};
+  if (lims) *lims = std::move(lm);
+  return out;
+}
+
+std::vector<SearchResult> FlatIndexHIP::range_search_dot(const float* q, float radius) const { return range_search_dot_batch(q, 1, &radius, nullptr); }
+
 // ---- row-sharded over several GPUs: the C ABI's device group ---------------------------------------------------
 FlatIndexHIPSharded::FlatIndexHIPSharded(const VectorDataset* base, const std::vector<int>& devices) {
   if (!base || base->count() == 0) throw std::runtime_error("Empty base");

@@ -96,6 +96,44 @@ int nvdb_host_hip_concurrent_search(void* h, const float* queries, uint32_t nq, 
   } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
+// FlatIndexHIP::range_search_dot_batch (device 0) over the dataset: out_lims [nq + 1]; up to max_out results into out_ids / out_scores
+// (all of them when max_out >= out_lims[nq]).  From `threads` > 1 host threads at once the call runs once per thread (serialised by
+// the index) and every thread's answer must equal the first's.
+int nvdb_host_hip_range_search(void* h, const float* queries, uint32_t nq, const float* radius, int threads, uint64_t* out_lims, uint64_t max_out,
+                               uint64_t* out_ids, float* out_scores) {
+  try {
+    nvdb::FlatIndexHIP idx(static_cast<nvdb::VectorDataset*>(h));
+    const int T = threads > 1 ? threads : 1;
+    std::vector<std::vector<nvdb::SearchResult>> res(static_cast<size_t>(T));
+    std::vector<std::vector<uint64_t>> lims(static_cast<size_t>(T));
+    std::vector<std::string> errs(static_cast<size_t>(T));
+    std::vector<std::thread> th;
+    for (int t = 0; t < T; ++t)
+      th.emplace_back([&, t] {
+        try { res[static_cast<size_t>(t)] = idx.range_search_dot_batch(queries, nq, radius, &lims[static_cast<size_t>(t)]); }
+        catch (const std::exception& e) { errs[static_cast<size_t>(t)] = e.what(); }
+      });
+    for (auto& x : th) x.join();
+    for (const auto& e : errs) if (!e.empty()) { g_err = e; return -1; }
+    for (int t = 1; t < T; ++t) {
+      bool same = lims[static_cast<size_t>(t)] == lims[0] && res[static_cast<size_t>(t)].size() == res[0].size();
+      for (size_t i = 0; same && i < res[0].size(); ++i)
+        same = res[static_cast<size_t>(t)][i].id == res[0][i].id && std::memcmp(&res[static_cast<size_t>(t)][i].score, &res[0][i].score, 4) == 0;
+      if (!same) { g_err = "range_search_dot_batch: concurrent callers got different answers"; return -1; }
+    }
+    for (uint32_t q = 0; q <= nq; ++q) out_lims[q] = lims[0][q];
+    for (uint64_t i = 0; i < res[0].size() && i < max_out; ++i) { out_ids[i] = res[0][i].id; out_scores[i] = res[0][i].score; }
+    // the single-query form against the batched slice of query 0
+    if (nq > 0) {
+      const std::vector<nvdb::SearchResult> one = idx.range_search_dot(queries, radius[0]);
+      bool same = one.size() == lims[0][1];
+      for (size_t i = 0; same && i < one.size(); ++i) same = one[i].id == res[0][i].id && std::memcmp(&one[i].score, &res[0][i].score, 4) == 0;
+      if (!same) { g_err = "range_search_dot: differs from the batched answer"; return -1; }
+    }
+    return 0;
+  } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
 // Throughput of overlapping single-query callers (the coalescing of FlatIndexHIP::search_topk_dot): out_ms[0] = one thread running
 // `reps` single-query searches, out_ms[1] = `threads` threads running `reps` each at the same time (thread t cycles through the
 // queries t, t + threads, ...).  Every result is compared with out-of-band batched answers by the caller through out_ids / out_scores

@@ -25,7 +25,7 @@ EXPORTS = [
     "nvdb_hip_abi_version", "nvdb_hip_device_count", "nvdb_hip_create", "nvdb_hip_destroy", "nvdb_hip_last_error",
     "nvdb_hip_upload_corpus", "nvdb_hip_adopt_corpus", "nvdb_hip_generate_corpus", "nvdb_hip_corpus_info",
     "nvdb_hip_download_rows", "nvdb_hip_search_batch", "nvdb_hip_search_batch_dev", "nvdb_hip_search_check",
-    "nvdb_hip_get_stats", "nvdb_hip_shadow_info", "nvdb_hip_collect_kernel_times", "nvdb_hip_merge_topk_dev", "nvdb_hip_merge_topk_strided_dev", "nvdb_merge_topk_host", "nvdb_hip_set_option",
+    "nvdb_hip_get_stats", "nvdb_hip_range_search", "nvdb_hip_range_results", "nvdb_hip_shadow_info", "nvdb_hip_collect_kernel_times", "nvdb_hip_merge_topk_dev", "nvdb_hip_merge_topk_strided_dev", "nvdb_merge_topk_host", "nvdb_hip_set_option",
     "nvdb_hip_refine_l2_topk", "nvdb_hip_refine_l2_topk_dev", "nvdb_synth_rows_f32", "nvdb_f32_to_f16",
     "nvdb_quantize_i8_rows",
     "nvdb_hip_group_create", "nvdb_hip_group_destroy", "nvdb_hip_group_last_error", "nvdb_hip_group_size", "nvdb_hip_group_ctx",
@@ -142,6 +142,8 @@ def _bind(L, dev):
     L.nvdb_hip_search_batch_dev.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.nvdb_hip_search_check.argtypes = [vp, C.POINTER(ScanStats)]
     L.nvdb_hip_get_stats.argtypes = [vp, C.POINTER(ScanStats)]
+    L.nvdb_hip_range_search.argtypes = [vp, vp, u32, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_range_results.argtypes = [vp, vp, vp]
     L.nvdb_hip_shadow_info.argtypes = [vp, C.POINTER(u64)]
     L.nvdb_hip_collect_kernel_times.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double)]
@@ -388,6 +390,30 @@ class HipContext:
         s = ScanStats()
         self._chk(self.lib.nvdb_hip_get_stats(self.h, C.byref(s)))
         return s.as_dict()
+
+    # -- range search
+    def range_search(self, queries, radius, want_timing=False):
+        """Every row whose score reaches the query's radius (a scalar, or one per query) -> (lims [nq + 1] u64, ids u64, scores f32):
+        query q's rows are ids[lims[q]:lims[q + 1]], score descending, id ascending.  Over the result budget (option range_max_mb)
+        the NvdbError carries the complete lims as `.lims`."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        nq = queries.shape[0]
+        radius = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)))
+        lims = np.zeros(nq + 1, dtype=np.uint64)
+        t = Timing()
+        st = self.lib.nvdb_hip_range_search(self.h, queries.ctypes.data, nq, radius.ctypes.data, lims.ctypes.data,
+                                            C.byref(t) if want_timing else None)
+        if st:
+            err = NvdbError(st, self.lib.nvdb_hip_last_error(self.h).decode())
+            err.lims = lims
+            raise err
+        total = int(lims[nq])
+        ids = np.empty(max(total, 1), dtype=np.uint64)
+        scores = np.empty(max(total, 1), dtype=np.float32)
+        self._chk(self.lib.nvdb_hip_range_results(self.h, ids.ctypes.data, scores.ctypes.data))
+        return (lims, ids[:total], scores[:total], t) if want_timing else (lims, ids[:total], scores[:total])
 
     def shadow_info(self):
         """The int8 filter shadow of an fp16 / fp32 corpus: resident, its bytes, demoted (searches start on the fp16 filter),
