@@ -254,7 +254,7 @@ nvdb_status nvdb_hip_group_search_batch(nvdb_hip_group* group, const float* quer
 /* ---------------------------------------------------------------------------------------------
  * partitioned probe search: exact top-k over a per-query CHOICE of contiguous row partitions -- the inverted-list probe of
  * the reference's IVF evaluation (apps/nvdb_ivf_eval.cpp, done there through FAISS) over a list-ordered corpus, and the
- * tenant / namespace filter of a multi-tenant corpus.  Queries that probe the same partition share one read of it.
+ * tenant / namespace filter of a multi-tenant corpus whose tenants' rows are contiguous (row masks, below, lift that).  Queries that probe the same partition share one read of it.
  * ------------------------------------------------------------------------------------------- */
 
 /* partition p = local rows [offsets[p], offsets[p+1]); offsets[0] == 0, non-decreasing, offsets[nparts] == n (nparts >= 1).
@@ -287,6 +287,61 @@ nvdb_status nvdb_hip_search_partitions(nvdb_hip_ctx* ctx, const float* queries, 
 nvdb_status nvdb_hip_search_ivf(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                                 uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                 uint32_t* out_probe, nvdb_hip_timing* timing);
+
+/* ---------------------------------------------------------------------------------------------
+ * row masks: top-k restricted to live rows on the probe-search path -- deleted rows (tombstones) that must stop being returned
+ * without a new upload, and tenant / metadata predicates whose rows are NOT contiguous.  FAISS users know this as
+ * SearchParameters::sel with an IDSelectorBitmap.  A context holds nmasks bit planes over its resident corpus; plane m is
+ * W = ceil(n / 32) uint32 words, LOCAL row r (global_row_base plays no part) is live in mask m iff bit r & 31 of word
+ * m * W + (r >> 5) is 1.  Bits at positions >= n of a plane's last word are ignored on input and read back as 0.
+ * NOT masked (out of scope so far): nvdb_hip_search_batch and its MFMA filter / exact / any-k routes, nvdb_hip_range_search, the
+ * device group, the _dev stream entry points, k > 64, the nvdb:: C++ host layer.  Those entry points, and the unmasked probe
+ * searches above, ignore resident masks entirely: results, statistics and launches are what they are without masks.
+ * ------------------------------------------------------------------------------------------- */
+
+/* bits: [nmasks][W] words, host memory; NULL = every row live in every mask.  Copies the planes into HBM and replaces any
+ * earlier set; nmasks == 0 drops them.  Any upload / adopt / generate of a corpus drops them; nvdb_hip_set_partitions and
+ * nvdb_hip_set_centroids do not (the rows have not moved).  NVDB_ERR_NO_CORPUS: nothing resident.  NVDB_ERR_UNSUPPORTED:
+ * n > 0xFFFFFF00 (the partition table's own limit).  NVDB_ERR_INVALID: nmasks == 0xFFFFFFFF (the number that means "no mask"). */
+nvdb_status nvdb_hip_set_row_masks(nvdb_hip_ctx* ctx, const uint32_t* bits /* [nmasks][W], may be NULL */, uint32_t nmasks);
+
+/* The tombstone path: sets (live != 0) or clears the bits of the listed LOCAL rows (host memory) in plane `mask`, on the device
+ * (one atomic per listed row); duplicates are legal.  rows[i] >= n or mask >= nmasks -> NVDB_ERR_INVALID before anything is
+ * launched, nothing changed.  nrows == 0 -> NVDB_OK.  Synchronous: the next search sees the update. */
+nvdb_status nvdb_hip_update_row_mask(nvdb_hip_ctx* ctx, uint32_t mask, const uint64_t* rows, uint64_t nrows, int live);
+
+/* Reads the planes back: *nmasks, *words_per_mask (W; 0 without masks) and, where bits_out is not NULL, the nmasks * W words.
+ * Every pointer is optional. */
+nvdb_status nvdb_hip_get_row_masks(nvdb_hip_ctx* ctx, uint32_t* nmasks, uint64_t* words_per_mask, uint32_t* bits_out /* may be NULL */);
+
+/* The masked searches: the arguments of the unmasked twin plus mask_of[nq] (host): the plane query q searches under;
+ * 0xFFFFFFFF = no mask, every row live; mask_of == NULL = plane 0 for every query.  Any other entry >= nmasks, or a call with no
+ * masks resident -> NVDB_ERR_INVALID before anything is launched, nothing written.
+ * Result per query: the exact top-k by dot product over the rows of the probed union that are LIVE in the query's mask, with the
+ * score bits and the (score desc, global id asc) order of nvdb_hip_search_partitions.  out_counts[q] (optional) = min(k, live rows
+ * in the union) -- counted on the device; slots beyond it hold id UINT64_MAX / -inf.  A query whose live set is empty gets count 0
+ * and all padding: not an error.  k > 64, k == 0, nq == 0, nprobe == 0, the probe-table rules, timing and nvdb_hip_get_stats
+ * (path 4) are the unmasked calls' (rows_scanned counts the rows of the work items, live or not).
+ * Cost: the scan reads at most three mask words per 64-row tile and query beside the rows, and skips the arithmetic of a tile in
+ * which none of a wavefront's queries has a live row (the rows are still fetched). */
+nvdb_status nvdb_hip_search_partitions_masked(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t k,
+                                              const uint32_t* probe, uint32_t nprobe, const uint32_t* mask_of /* [nq], may be NULL */,
+                                              uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                              nvdb_hip_timing* timing);
+/* The coarse step is nvdb_hip_search_ivf's: centroids are not masked, a partition without a live row can still be probed. */
+nvdb_status nvdb_hip_search_ivf_masked(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+                                       const uint32_t* mask_of /* [nq], may be NULL */,
+                                       uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                       uint32_t* out_probe, nvdb_hip_timing* timing);
+/* The masked flat search: the whole corpus as ONE implicit partition that every query probes, on the same scan.  Needs no
+ * partition table and leaves a table that is set untouched.  What this costs, plainly: the rows are read once per group of up to
+ * 32 queries (16 where the LDS holds no more beside a row tile, e.g. fp16 d = 768: a batch of 1024 then reads the corpus 64 times); it is the fp32-order VALU scan, not the matrix cores -- the right tool
+ * for small batches and the exact answer for large ones; the MFMA filter route of nvdb_hip_search_batch does not take masks yet.
+ * k > 64 -> NVDB_ERR_UNSUPPORTED (unlike nvdb_hip_search_batch, k is not clamped: out_counts says how many entries there are). */
+nvdb_status nvdb_hip_search_batch_masked(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t k,
+                                         const uint32_t* mask_of /* [nq], may be NULL */,
+                                         uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                         nvdb_hip_timing* timing);
 
 /* ---------------------------------------------------------------------------------------------
  * IVF-Flat build: from a resident corpus to an index the probe search above can serve -- centroids trained on the GPU
@@ -353,6 +408,18 @@ nvdb_status nvdb_hip_ivf_info(const nvdb_hip_ivf* ivf, uint64_t* n, uint32_t* np
 nvdb_status nvdb_hip_ivf_search(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                                 uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                 uint32_t* out_probe, nvdb_hip_timing* timing);
+
+/* Row masks of an index, in ORIGINAL rows (rows of src, without its global_row_base).  bits: [nmasks][ceil(n / 32)] as for
+ * nvdb_hip_set_row_masks; position j of the index is live iff bit perm[j] is set (NULL: every row live).  Errors as there. */
+nvdb_status nvdb_hip_ivf_set_row_masks(nvdb_hip_ivf* ivf, const uint32_t* bits, uint32_t nmasks);
+/* nvdb_hip_update_row_mask with original rows: mapped through the inverse permutation, which is built once, on first use. */
+nvdb_status nvdb_hip_ivf_update_row_mask(nvdb_hip_ivf* ivf, uint32_t mask, const uint64_t* rows, uint64_t nrows, int live);
+/* nvdb_hip_search_ivf_masked on the index's context, then the id mapping and the ORDER of nvdb_hip_ivf_search: equal scores by
+ * (partition number, original id). */
+nvdb_status nvdb_hip_ivf_search_masked(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+                                       const uint32_t* mask_of /* [nq], may be NULL */,
+                                       uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                       uint32_t* out_probe, nvdb_hip_timing* timing);
 
 /* Tunables (defaults are what bench.py measures; the table with meanings is in INTEGRATION.md section 4b):
  * "path" (0 auto, 1 exact, 2 mfma-filter), "chunk0_rows", "chunk_growth", "cand_cap", "min_filter_batch", "mfma_boot", "waves8",

@@ -12,8 +12,15 @@
 //                          for the LDS) the lanes read their rows from global memory directly.
 //                          Each (item, query) owns a slot of min(k, segment rows) Cand entries that the host placed: no atomics,
 //                          no counters, no overflow path.
+//                          MASKED: every query of the group searches under a row mask (a bit plane over the corpus, bit r = local
+//                          row r is live; PartMask): a lane tests its own row's bit per owned query and a dead row is never
+//                          offered.  A tile's mask words (at most three per query) are loaded one tile ahead by 4 lanes per
+//                          query, so the score chain hides them, and handed to the rows' lanes by a lane permute; a wave none of
+//                          whose lanes has a live row for any of its queries skips the tile's scores.
 //  * select_parts_kernel : one wave per query reduces the query's slots to the k best by (score desc, row asc), adds the global
-//                          row base and pads.
+//                          row base and pads; given a count pointer it stores how many entries the query has (masked searches:
+//                          the host cannot derive min(k, live rows) from the partition sizes).
+//  * update_row_mask_kernel : one thread per listed row sets or clears the row's bit in a plane (the tombstone path).
 //
 // Scores: exact_scores<> of kernels_exact.h, i.e. the bits of nvdb_hip_search_batch.  Non-finite scores: no fault, no hang,
 // order unspecified.
@@ -33,16 +40,35 @@ constexpr uint32_t PART_SEG_ROWS = 2048;       // a partition is cut into segmen
 // one workgroup's work; qoff indexes qidx[], doff indexes dst[] (both: one entry per query of the group)
 struct PartItem { uint32_t row_lo, row_hi, qoff, doff, nqg, pad; };
 
+// MASKED builds: mask_of[q] = the plane query q searches under (0xFFFFFFFF: none, every row live), planes = [nmasks][W] words,
+// local row r live in plane m iff bit r & 31 of word m * W + (r >> 5).  Unmasked builds ignore it.
+struct PartMask { const uint32_t* mask_of; const uint32_t* planes; uint32_t W; };
+
+// The mask words of the tile that starts at row T, for a wave's QW queries in ONE register: lane 4 * g + j (j < 3) holds word
+// (T >> 5) + j of query g's plane -- a tile of 64 rows starts anywhere, so it touches at most three words -- clamped to the
+// word of the segment's last row (the index stays inside the plane).  mid[g]: query g's plane, wave-uniform (0xFFFFFFFF: none,
+// the word reads as all ones).
+template <int QW>
+__device__ __forceinline__ uint32_t part_mask_words(const PartMask& mk, const uint32_t (&mid)[QW], uint32_t T, uint32_t row_hi, int lane) {
+  asm volatile("" : "+v"(lane));   // recomputed per tile: hoisted out of the tile loop, the lane's plane address cost the f32 QW = 4 build registers it does not have
+  uint32_t lmid = 0xFFFFFFFFu;
+#pragma unroll
+  for (int g = 0; g < QW; ++g)
+    if ((lane >> 2) == g && (lane & 3) < 3) lmid = mid[g];
+  const uint32_t wi = (T >> 5) + (static_cast<uint32_t>(lane) & 3u), wmax = (row_hi - 1u) >> 5;
+  return lmid == 0xFFFFFFFFu ? 0xFFFFFFFFu : mk.planes[static_cast<uint64_t>(lmid) * mk.W + (wi < wmax ? wi : wmax)];
+}
+
 // LDS row pitch of a staged tile: the smallest odd multiple of 16 bytes >= row_bytes.  A ds_read_b128 is served in groups of 16
 // lanes whose lane numbers cover every residue mod 16; with an odd pitch (in 16-byte slots) lane L's slot is L * pitch mod 16,
 // a bijection of the residues: the 16 lanes of a group touch 16 different 16-byte slots of the 256-byte bank window.
 __host__ __device__ inline uint32_t part_pitch(uint32_t row_bytes) { return ((row_bytes >> 4) | 1u) << 4; }
 
-template <int DT, int QW, bool ALIGNED, bool STAGED>
+template <int DT, int QW, bool ALIGNED, bool STAGED, bool MASKED>
 __global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
     const void* __restrict__ rows, const float* __restrict__ scales, uint32_t dim, const PartItem* __restrict__ items,
     const uint32_t* __restrict__ qidx, const uint32_t* __restrict__ dst, const float* __restrict__ q32, uint32_t k,
-    Cand* __restrict__ cand) {
+    Cand* __restrict__ cand, PartMask mk) {
   constexpr uint32_t BPE = (DT == DT_F32) ? 4 : (DT == DT_F16 ? 2 : 1);
   constexpr uint32_t QG = PART_WAVES * QW;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -91,11 +117,22 @@ __global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
       if (ch_ >= cpr) { ch_ -= cpr; ++r_; }                                                                                    \
     }                                                                                                                          \
   }
+  const bool wave_live = wave * QW < it.nqg;                               // this wave owns at least one query of the group
+  // MASKED: the mask numbers of this wave's queries, gathered by index like the queries (slots beyond the group repeat its first
+  // query's; scalar registers), and the first tile's mask words (part_mask_words)
+  [[maybe_unused]] uint32_t mid[QW], wcur = 0u;
+  if constexpr (MASKED) {
+#pragma unroll
+    for (int g = 0; g < QW; ++g) {
+      const uint32_t gi = wave * QW + g;
+      mid[g] = __builtin_amdgcn_readfirstlane(mk.mask_of[qidx[it.qoff + (gi < it.nqg ? gi : 0u)]]);
+    }
+    if (wave_live) wcur = part_mask_words<QW>(mk, mid, it.row_lo, it.row_hi, lane);
+  }
   if constexpr (STAGED) { NVDB_PART_FETCH(it.row_lo) NVDB_PART_STASH(it.row_lo) }
   __syncthreads();
 
   const float* qptr = q_lds + wave * QW * qstride;
-  const bool wave_live = wave * QW < it.nqg;                               // this wave owns at least one query of the group
   WaveTopK tk[QW];
 #pragma unroll
   for (int g = 0; g < QW; ++g) wtk_init(tk[g]);
@@ -107,15 +144,30 @@ __global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
       const uint32_t row = t_lo + lane;
       const bool valid = row < it.row_hi;
       const uint32_t rrow = valid ? row : (it.row_hi - 1);
-      const float scale = (DT == DT_I8) ? scales[rrow] : 1.f;
-      float sc[QW];
-      if constexpr (STAGED) exact_scores<DT, QW, ALIGNED>(tile + static_cast<uint32_t>(lane) * pitch, qptr, qstride, dim, scale, sc);
-      else exact_scores<DT, QW, ALIGNED>(row_ptr<DT>(rows, rrow, dim), qptr, qstride, dim, scale, sc);
+      [[maybe_unused]] uint32_t wnext = 0u;
+      uint32_t live = 0xFFFFFFFFu;                                         // bit g: this lane's row is offered to query g
+      if constexpr (MASKED) {
+        if (more) wnext = part_mask_words<QW>(mk, mid, t_lo + PART_TILE_ROWS, it.row_hi, lane);   // in flight while this tile is scored
+        live = 0u;
+        const int j = static_cast<int>((rrow >> 5) - (t_lo >> 5));         // which of the tile's words holds this lane's row: 0 .. 2
 #pragma unroll
-      for (int g = 0; g < QW; ++g) {
-        const bool pass = valid && wave * QW + g < it.nqg && wtk_accepts(tk[g], k, sc[g], row);
-        wtk_offer(tk[g], k, pass, sc[g], row, lane);
+        for (int g = 0; g < QW; ++g) {
+          const uint32_t w = static_cast<uint32_t>(__shfl(static_cast<int>(wcur), 4 * g + j));
+          if (valid && wave * QW + g < it.nqg) live |= ((w >> (rrow & 31u)) & 1u) << g;
+        }
       }
+      if (!MASKED || __any(live != 0u)) {                                  // (uniform over the wave) a tile without a live row: no scores
+        const float scale = (DT == DT_I8) ? scales[rrow] : 1.f;
+        float sc[QW];
+        if constexpr (STAGED) exact_scores<DT, QW, ALIGNED>(tile + static_cast<uint32_t>(lane) * pitch, qptr, qstride, dim, scale, sc);
+        else exact_scores<DT, QW, ALIGNED>(row_ptr<DT>(rows, rrow, dim), qptr, qstride, dim, scale, sc);
+#pragma unroll
+        for (int g = 0; g < QW; ++g) {
+          const bool pass = valid && wave * QW + g < it.nqg && ((live >> g) & 1u) && wtk_accepts(tk[g], k, sc[g], row);
+          wtk_offer(tk[g], k, pass, sc[g], row, lane);
+        }
+      }
+      if constexpr (MASKED) wcur = wnext;
     }
     if constexpr (STAGED) {
       if (more) {                                                          // (uniform over the workgroup)
@@ -143,7 +195,7 @@ __global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
 // grid = nq, block = 64: the query's slots are cand[cbeg[q] .. cbeg[q+1])
 static __global__ __launch_bounds__(64) void select_parts_kernel(
     const Cand* __restrict__ cand, const uint32_t* __restrict__ cbeg, uint32_t k, uint64_t row_base,
-    unsigned long long* __restrict__ out_ids, float* __restrict__ out_scores) {
+    unsigned long long* __restrict__ out_ids, float* __restrict__ out_scores, uint32_t* __restrict__ out_counts) {
   const uint32_t q = blockIdx.x;
   const int lane = threadIdx.x;
   const uint32_t lo = cbeg[q], hi = cbeg[q + 1];
@@ -161,6 +213,17 @@ static __global__ __launch_bounds__(64) void select_parts_kernel(
     out_ids[static_cast<uint64_t>(q) * k + lane] = have ? (row_base + tk.id) : ~0ull;
     out_scores[static_cast<uint64_t>(q) * k + lane] = have ? tk.s : NEG_INF;
   }
+  if (out_counts && lane == 0) out_counts[q] = tk.cnt;
+}
+
+// grid = ceil(nrows / 256), block = 256: rows[i] < n (the host checked); several listed rows may share a word, hence the atomics
+static __global__ __launch_bounds__(256) void update_row_mask_kernel(uint32_t* __restrict__ plane, const uint32_t* __restrict__ rows,
+                                                                     uint64_t nrows, bool live) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= nrows) return;
+  const uint32_t r = rows[i], bit = 1u << (r & 31u);
+  if (live) atomicOr(plane + (r >> 5), bit);
+  else atomicAnd(plane + (r >> 5), ~bit);
 }
 
 }  // namespace nvdbhip

@@ -10,7 +10,8 @@
 //   nvdb_launch_i8.cpp     ... of the int8 kernels (kernels_filter.h, kernels_filter_i8s.h)
 //   nvdb_launch_exact.cpp  ... of the exact fp32-order kernels, select / rescore / merge, the any-k path (kernels_exact*.h, kernels_largek.h)
 //   nvdb_refine.cpp        exact-L2 refine (kernels_refine.h)
-//   nvdb_partitions.cpp    partitioned probe search: partition table, coarse quantiser, work list, launches (kernels_partitions.h)
+//   nvdb_partitions.cpp    partitioned probe search: partition table, coarse quantiser, work list, launches; row masks and the masked searches
+//                          (kernels_partitions.h, row_mask.h)
 //   nvdb_ivf.cpp           IVF-Flat build: row assignment, spherical k-means, list layout, the reordered index (kernels_ivf.h, ivf_layout.h)
 //   nvdb_debug.cpp         developer entry points (libnvdb_hip_dev.so only)
 //   nvdb_group.cpp         device group, layered on the public ABI (does not include this header)
@@ -173,7 +174,9 @@ struct nvdb_hip_ctx {
   int64_t opt_refine_v2 = 2;                       // refine kernel: 0 lane per row, 1 column chunks through LDS, 2 whole rows through LDS (fp16 d = 256/384/512/768; else 1)
   int64_t opt_mfma16 = 1;                          // 1: use the 16x16x32 MFMA build for 256-query tiles
   std::set<const void*> lds_attr_set;              // kernels whose dynamic-LDS limit was raised on this device
-  nvdbhip::PartState* parts = nullptr;             // partitioned probe search (created by nvdb_hip_set_partitions)
+  nvdbhip::PartState* parts = nullptr;             // partitioned probe search (created by nvdb_hip_set_partitions, or by the first masked flat search)
+  DevBuf row_masks, mask_rows;                     // row masks (nvdb_hip_set_row_masks): [nmasks][ceil(n / 32)] words; staging of nvdb_hip_update_row_mask's row list
+  uint32_t nmasks = 0;                             // ... planes resident (0: none; any corpus load drops them, the buffer stays)
 };
 
 #define HIPCHK(ctx, call)                                                                        \

@@ -8,6 +8,7 @@
 // through the child's host API, which retries by itself -- the device group's pattern (nvdb_group.cpp).
 #include "nvdb_ctx.h"
 #include "ivf_layout.h"
+#include "row_mask.h"
 #include "kernels_ivf.h"
 
 namespace nvdbhip {
@@ -172,6 +173,7 @@ nvdb_status launch_gather_rows(nvdb_hip_ctx* c, hipStream_t s, const nvdb_hip_ct
 struct nvdb_hip_ivf {
   nvdb_hip_ctx* ctx = nullptr;                     // the list-ordered copy with its partition table and centroids; row_base 0
   std::vector<uint32_t> perm;                      // perm[position] = row of the source corpus
+  std::vector<uint32_t> inv;                       // inv[row of the source corpus] = position; built by the first nvdb_hip_ivf_update_row_mask
   std::vector<uint64_t> offsets;                   // nparts + 1
   uint64_t src_row_base = 0;
   std::string err;
@@ -397,6 +399,49 @@ nvdb_status nvdb_hip_ivf_search(nvdb_hip_ivf* ix, const float* queries, uint32_t
   if (nq == 0 || k == 0) return NVDB_OK;            // nothing was written
   // positions in the list-ordered copy -> ids of the source corpus; the order stays: equal scores by (list, original row)
   const uint32_t* perm = ix->perm.data();
+  for (size_t i = 0; i < static_cast<size_t>(nq) * k; ++i)
+    if (out_ids[i] != ~0ull) out_ids[i] = ix->src_row_base + perm[out_ids[i]];
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_ivf_set_row_masks(nvdb_hip_ivf* ix, const uint32_t* bits, uint32_t nmasks) {
+  if (!ix) return NVDB_ERR_INVALID;
+  nvdb_status st;
+  if (!bits || nmasks == 0 || nmasks == 0xFFFFFFFFu) st = nvdb_hip_set_row_masks(ix->ctx, nullptr, nmasks);   // nothing to permute
+  else {
+    // position j of the index is live iff bit perm[j] of the caller's plane is set
+    const uint64_t n = ix->perm.size(), W = rm_words(n);
+    std::vector<uint32_t> planes(static_cast<size_t>(nmasks) * W);
+    for (uint32_t m = 0; m < nmasks; ++m) rm_permute(bits + static_cast<size_t>(m) * W, ix->perm.data(), n, planes.data() + static_cast<size_t>(m) * W);
+    st = nvdb_hip_set_row_masks(ix->ctx, planes.data(), nmasks);
+  }
+  if (st) ix->err = nvdb_hip_last_error(ix->ctx);
+  return st;
+}
+
+nvdb_status nvdb_hip_ivf_update_row_mask(nvdb_hip_ivf* ix, uint32_t mask, const uint64_t* rows, uint64_t nrows, int live) {
+  if (!ix) return NVDB_ERR_INVALID;
+  const uint64_t n = ix->perm.size();
+  if (nrows && !rows) { ix->err = "ivf_update_row_mask: null row list"; return NVDB_ERR_INVALID; }
+  if (!rm_rows_valid(rows, nrows, n)) { ix->err = "ivf_update_row_mask: a listed row is >= the row count"; return NVDB_ERR_INVALID; }
+  if (ix->inv.empty() && nrows) {
+    ix->inv.resize(n);
+    if (!rm_inverse(ix->perm.data(), n, ix->inv.data())) { ix->inv.clear(); ix->err = "ivf_update_row_mask: the index's permutation is damaged"; return NVDB_ERR_INTERNAL; }
+  }
+  std::vector<uint64_t> pos(nrows);
+  for (uint64_t i = 0; i < nrows; ++i) pos[i] = ix->inv[rows[i]];
+  const nvdb_status st = nvdb_hip_update_row_mask(ix->ctx, mask, pos.data(), nrows, live);
+  if (st) ix->err = nvdb_hip_last_error(ix->ctx);
+  return st;
+}
+
+nvdb_status nvdb_hip_ivf_search_masked(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, const uint32_t* mask_of,
+                                       uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
+  if (!ix) return NVDB_ERR_INVALID;
+  const nvdb_status st = nvdb_hip_search_ivf_masked(ix->ctx, queries, nq, k, nprobe, mask_of, out_ids, out_scores, out_counts, out_probe, timing);
+  if (st) { ix->err = nvdb_hip_last_error(ix->ctx); return st; }
+  if (nq == 0 || k == 0) return NVDB_OK;            // nothing was written
+  const uint32_t* perm = ix->perm.data();           // (as nvdb_hip_ivf_search: the order stays, equal scores by (list, original row))
   for (size_t i = 0; i < static_cast<size_t>(nq) * k; ++i)
     if (out_ids[i] != ~0ull) out_ids[i] = ix->src_row_base + perm[out_ids[i]];
   return NVDB_OK;

@@ -1,6 +1,7 @@
 // nvdb_partitions.cpp -- partitioned probe search: the partition table and the optional coarse quantiser of a context, the
 // host-side work list, the launches of kernels_partitions.h, and the entry points nvdb_hip_set_partitions / set_centroids /
-// search_partitions / search_ivf (include/nvdb_hip.h).
+// search_partitions / search_ivf, the row masks (nvdb_hip_set_row_masks / update_row_mask / get_row_masks) and the masked
+// searches (include/nvdb_hip.h).
 //
 // Work list (built per call from the probe table, all on the host):
 //   1. every query's probes are de-duplicated; a counting sort by partition gives, per probed partition, the ascending list of
@@ -11,8 +12,12 @@
 //      (dst); the blocks are laid out by a prefix sum (cbeg), so the capacity is exact and nothing can overflow.
 // Items are sorted by group size into classes (<= 8, <= 16, <= 32 queries) that run the QW = 1, 2, 4 builds of the kernel (the
 // widest one the LDS has room for): a remainder group of three queries does not pay for sixteen.
+// A masked search is the same work list with every query's mask number appended to the pinned image; the MASKED builds of the
+// scan test a row's bit before they offer it, and the select kernel writes the counts the host can no longer derive.  The
+// masked flat search runs the corpus as one implicit partition that every query probes.
 #include "nvdb_ctx.h"
 #include "kernels_partitions.h"
+#include "row_mask.h"
 
 namespace nvdbhip {
 
@@ -21,7 +26,7 @@ struct PartState {
   nvdb_hip_ctx* coarse = nullptr;                  // child context that holds the centroids as an f32 corpus (same device)
   bool have_centroids = false;
   // grow-only workspace
-  DevBuf meta, cand, q, out_ids, out_scores;
+  DevBuf meta, cand, q, out_ids, out_scores, out_counts;
   void* pin = nullptr;                             // pinned staging of the work list
   size_t pin_bytes = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -44,7 +49,7 @@ void parts_destroy(nvdb_hip_ctx* c) {
   PartState* ps = c->parts;
   if (!ps) return;
   parts_drop(c);
-  for (DevBuf* b : {&ps->meta, &ps->cand, &ps->q, &ps->out_ids, &ps->out_scores}) if (b->p) (void)hipFree(b->p);
+  for (DevBuf* b : {&ps->meta, &ps->cand, &ps->q, &ps->out_ids, &ps->out_scores, &ps->out_counts}) if (b->p) (void)hipFree(b->p);
   if (ps->pin) (void)hipHostFree(ps->pin);
   for (hipEvent_t e : ps->ev) if (e) (void)hipEventDestroy(e);
   delete ps;
@@ -60,38 +65,46 @@ size_t parts_lds(uint32_t dim, uint32_t row_bytes, uint32_t qw, bool staged) {
   return PART_WAVES * qw * qstride * 4 + (staged ? static_cast<size_t>(PART_TILE_ROWS) * part_pitch(row_bytes) : 0);
 }
 
-template <int DT, int QW, bool AL, bool ST>
+// mk.mask_of != nullptr: the MASKED build
+template <int DT, int QW, bool AL, bool ST, bool MK>
 nvdb_status launch_one(nvdb_hip_ctx* c, hipStream_t s, const PartItem* items, uint32_t nitems, const uint32_t* qidx, const uint32_t* dst,
-                       const float* q32, uint32_t k, Cand* cand) {
+                       const float* q32, uint32_t k, Cand* cand, const PartMask& mk) {
   const size_t lds = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), QW, ST);
   if (lds > 64 * 1024)
-    if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(scan_parts_kernel<DT, QW, AL, ST>), PART_LDS_LIMIT)) return st;
-  scan_parts_kernel<DT, QW, AL, ST><<<nitems, PART_THREADS, lds, s>>>(c->rows, c->scales, c->dim, items, qidx, dst, q32, k, cand);
+    if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(scan_parts_kernel<DT, QW, AL, ST, MK>), PART_LDS_LIMIT)) return st;
+  scan_parts_kernel<DT, QW, AL, ST, MK><<<nitems, PART_THREADS, lds, s>>>(c->rows, c->scales, c->dim, items, qidx, dst, q32, k, cand, mk);
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
 }
 
+template <int DT, int QW, bool AL, bool ST>
+nvdb_status launch_mk(nvdb_hip_ctx* c, hipStream_t s, const PartItem* items, uint32_t nitems, const uint32_t* qidx, const uint32_t* dst,
+                      const float* q32, uint32_t k, Cand* cand, const PartMask& mk) {
+  if (mk.mask_of) return launch_one<DT, QW, AL, ST, true>(c, s, items, nitems, qidx, dst, q32, k, cand, mk);
+  return launch_one<DT, QW, AL, ST, false>(c, s, items, nitems, qidx, dst, q32, k, cand, mk);
+}
+
 template <int DT, int QW>
 nvdb_status launch_qw(nvdb_hip_ctx* c, hipStream_t s, bool staged, const PartItem* items, uint32_t nitems, const uint32_t* qidx,
-                      const uint32_t* dst, const float* q32, uint32_t k, Cand* cand) {
-  if (staged) return launch_one<DT, QW, true, true>(c, s, items, nitems, qidx, dst, q32, k, cand);
-  if (aligned_rows(c->dtype, c->dim)) return launch_one<DT, QW, true, false>(c, s, items, nitems, qidx, dst, q32, k, cand);
-  return launch_one<DT, QW, false, false>(c, s, items, nitems, qidx, dst, q32, k, cand);
+                      const uint32_t* dst, const float* q32, uint32_t k, Cand* cand, const PartMask& mk) {
+  if (staged) return launch_mk<DT, QW, true, true>(c, s, items, nitems, qidx, dst, q32, k, cand, mk);
+  if (aligned_rows(c->dtype, c->dim)) return launch_mk<DT, QW, true, false>(c, s, items, nitems, qidx, dst, q32, k, cand, mk);
+  return launch_mk<DT, QW, false, false>(c, s, items, nitems, qidx, dst, q32, k, cand, mk);
 }
 
 template <int DT>
 nvdb_status launch_dt(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const PartItem* items, uint32_t nitems, const uint32_t* qidx,
-                      const uint32_t* dst, const float* q32, uint32_t k, Cand* cand) {
-  if (qw == 4) return launch_qw<DT, 4>(c, s, staged, items, nitems, qidx, dst, q32, k, cand);
-  if (qw == 2) return launch_qw<DT, 2>(c, s, staged, items, nitems, qidx, dst, q32, k, cand);
-  return launch_qw<DT, 1>(c, s, staged, items, nitems, qidx, dst, q32, k, cand);
+                      const uint32_t* dst, const float* q32, uint32_t k, Cand* cand, const PartMask& mk) {
+  if (qw == 4) return launch_qw<DT, 4>(c, s, staged, items, nitems, qidx, dst, q32, k, cand, mk);
+  if (qw == 2) return launch_qw<DT, 2>(c, s, staged, items, nitems, qidx, dst, q32, k, cand, mk);
+  return launch_qw<DT, 1>(c, s, staged, items, nitems, qidx, dst, q32, k, cand, mk);
 }
 
 nvdb_status launch_scan_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const PartItem* items, uint32_t nitems,
-                              const uint32_t* qidx, const uint32_t* dst, const float* q32, uint32_t k, Cand* cand) {
-  if (c->dtype == NVDB_DTYPE_F32) return launch_dt<DT_F32>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand);
-  if (c->dtype == NVDB_DTYPE_F16) return launch_dt<DT_F16>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand);
-  return launch_dt<DT_I8>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand);
+                              const uint32_t* qidx, const uint32_t* dst, const float* q32, uint32_t k, Cand* cand, const PartMask& mk) {
+  if (c->dtype == NVDB_DTYPE_F32) return launch_dt<DT_F32>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand, mk);
+  if (c->dtype == NVDB_DTYPE_F16) return launch_dt<DT_F16>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand, mk);
+  return launch_dt<DT_I8>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand, mk);
 }
 
 nvdb_status parts_args(nvdb_hip_ctx* c, const char* who) {
@@ -101,12 +114,14 @@ nvdb_status parts_args(nvdb_hip_ctx* c, const char* who) {
   return NVDB_OK;
 }
 
-// the search proper; the caller has validated the context, the table, nq > 0 and 0 < k <= 64
-nvdb_status parts_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe, uint32_t nprobe,
-                         uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
+// how a masked search differs from its twin: mask_of as the caller gave it (nullptr: plane 0 for every query; validated by the caller)
+struct MaskSel { const uint32_t* mask_of; };
+
+// the search proper over the table off[0 .. nparts]; the caller has validated the context, nq > 0 and 0 < k <= 64.
+// msel != nullptr: the masked search (the caller has checked mask_of against the resident planes)
+nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe,
+                         uint32_t nprobe, const MaskSel* msel, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
   PartState* ps = c->parts;
-  const uint32_t nparts = static_cast<uint32_t>(ps->offsets.size() - 1);
-  const uint64_t* off = ps->offsets.data();
   const uint32_t row_bytes = c->dim * static_cast<uint32_t>(bpe_of(c->dtype));
 
   // kernel build: staged through LDS where the rows are whole 16-byte chunks and a tile fits beside the queries
@@ -168,7 +183,7 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uin
     for (uint32_t j = 0; j < ps->ucount[q]; ++j) { total += ps->psum[u[j]]; rows_union += off[u[j] + 1] - off[u[j]]; }
     if (total >= 0xFFFFFFFFull) return fail(c, NVDB_ERR_UNSUPPORTED, "search_partitions: more than 2^32 candidate slots in one call (split the batch)");
     ps->cbeg[q + 1] = static_cast<uint32_t>(total);
-    if (out_counts) out_counts[q] = static_cast<uint32_t>(std::min<uint64_t>(k, rows_union));
+    if (out_counts && !msel) out_counts[q] = static_cast<uint32_t>(std::min<uint64_t>(k, rows_union));   // (masked: the select kernel counts)
   }
   // 4. work items, by class of group size
   for (auto& v : ps->items) v.clear();
@@ -194,9 +209,9 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uin
   }
   const size_t nitems = ps->items[0].size() + ps->items[1].size() + ps->items[2].size();
 
-  // device workspace (grow-only) and the pinned image of the work list: [items | qidx | dst | cbeg]
-  const size_t w_items = nitems * (sizeof(PartItem) / 4), w_qidx = npairs, w_dst = ps->dst.size(), w_cbeg = nq + 1;
-  const size_t meta_bytes = (w_items + w_qidx + w_dst + w_cbeg) * 4;
+  // device workspace (grow-only) and the pinned image of the work list: [items | qidx | dst | cbeg | masked: mask_of]
+  const size_t w_items = nitems * (sizeof(PartItem) / 4), w_qidx = npairs, w_dst = ps->dst.size(), w_cbeg = nq + 1, w_mask = msel ? nq : 0;
+  const size_t meta_bytes = (w_items + w_qidx + w_dst + w_cbeg + w_mask) * 4;
   const size_t qbytes = static_cast<size_t>(nq) * c->dim * 4, ob_ids = static_cast<size_t>(nq) * k * 8, ob_sc = static_cast<size_t>(nq) * k * 4;
   nvdb_status st;
   HIPCHK(c, hipSetDevice(c->device));
@@ -205,6 +220,7 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uin
   if ((st = ensure(c, ps->q, qbytes))) return st;
   if ((st = ensure(c, ps->out_ids, ob_ids))) return st;
   if ((st = ensure(c, ps->out_scores, ob_sc))) return st;
+  if (msel && (st = ensure(c, ps->out_counts, static_cast<size_t>(nq) * 4))) return st;
   if (ps->pin_bytes < meta_bytes) {
     if (ps->pin) (void)hipHostFree(ps->pin);
     ps->pin = nullptr; ps->pin_bytes = 0;
@@ -224,6 +240,8 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uin
     if (w_dst) std::memcpy(w, ps->dst.data(), w_dst * 4);
     w += w_dst;
     std::memcpy(w, ps->cbeg.data(), w_cbeg * 4);
+    w += w_cbeg;
+    for (uint32_t q = 0; q < w_mask; ++q) w[q] = msel->mask_of ? msel->mask_of[q] : 0u;
   }
   hipStream_t s = c->stream;
   uint32_t* dmeta = static_cast<uint32_t*>(ps->meta.p);
@@ -231,6 +249,9 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uin
   const uint32_t* d_qidx = dmeta + w_items;
   const uint32_t* d_dst = d_qidx + w_qidx;
   const uint32_t* d_cbeg = d_dst + w_dst;
+  const PartMask mk = msel ? PartMask{d_cbeg + w_cbeg, static_cast<const uint32_t*>(c->row_masks.p), static_cast<uint32_t>(rm_words(c->n))}
+                           : PartMask{nullptr, nullptr, 0u};
+  uint32_t* d_counts = msel ? static_cast<uint32_t*>(ps->out_counts.p) : nullptr;
   if (timing) HIPCHK(c, hipEventRecord(ps->ev[0], s));
   HIPCHK(c, hipMemcpyAsync(ps->meta.p, pin, meta_bytes, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(ps->q.p, queries, qbytes, hipMemcpyHostToDevice, s));
@@ -242,17 +263,18 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uin
       const uint32_t n_cl = static_cast<uint32_t>(ps->items[cl].size());
       if (!n_cl) continue;
       const uint32_t qw = std::min<uint32_t>(qw_max, 1u << cl);
-      if ((st = launch_scan_parts(c, s, qw, staged, it, n_cl, d_qidx, d_dst, static_cast<const float*>(ps->q.p), k, static_cast<Cand*>(ps->cand.p)))) return st;
+      if ((st = launch_scan_parts(c, s, qw, staged, it, n_cl, d_qidx, d_dst, static_cast<const float*>(ps->q.p), k, static_cast<Cand*>(ps->cand.p), mk))) return st;
       it += n_cl;
       ++launches;
     }
   }
   select_parts_kernel<<<nq, 64, 0, s>>>(static_cast<const Cand*>(ps->cand.p), d_cbeg, k, c->row_base,
-                                         static_cast<unsigned long long*>(ps->out_ids.p), static_cast<float*>(ps->out_scores.p));
+                                         static_cast<unsigned long long*>(ps->out_ids.p), static_cast<float*>(ps->out_scores.p), d_counts);
   HIPCHK(c, hipGetLastError());
   if (timing) HIPCHK(c, hipEventRecord(ps->ev[2], s));
   HIPCHK(c, hipMemcpyAsync(out_ids, ps->out_ids.p, ob_ids, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipMemcpyAsync(out_scores, ps->out_scores.p, ob_sc, hipMemcpyDeviceToHost, s));
+  if (d_counts && out_counts) HIPCHK(c, hipMemcpyAsync(out_counts, d_counts, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToHost, s));
   if (timing) HIPCHK(c, hipEventRecord(ps->ev[3], s));
   HIPCHK(c, hipStreamSynchronize(s));
 
@@ -279,6 +301,60 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uin
 void pad_outputs(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
   for (size_t i = 0; i < static_cast<size_t>(nq) * k; ++i) { out_ids[i] = ~0ull; out_scores[i] = NEG_INF; }
   if (out_counts) for (uint32_t q = 0; q < nq; ++q) out_counts[q] = 0;
+}
+
+// a masked call's mask_of against the resident planes (before anything is launched)
+nvdb_status mask_args(nvdb_hip_ctx* c, const uint32_t* mask_of, uint32_t nq, const char* who) {
+  if (c->nmasks == 0) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no row masks (nvdb_hip_set_row_masks)");
+  if (!rm_mask_of_valid(mask_of, nq, c->nmasks)) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": mask_of entry names a mask >= nmasks");
+  return NVDB_OK;
+}
+
+// nvdb_hip_search_partitions and its masked twin (msel != nullptr)
+nvdb_status search_partitions_any(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe, uint32_t nprobe,
+                                  const MaskSel* msel, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
+  nvdb_status st = parts_args(c, who);
+  if (st) return st;
+  if (timing) std::memset(timing, 0, sizeof(*timing));
+  if (nq == 0 || k == 0) return NVDB_OK;
+  if (k > WAVE_KMAX) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": k <= 64 (wavefront-resident lists)");
+  if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
+  if (msel && (st = mask_args(c, msel->mask_of, nq, who))) return st;
+  if (nprobe == 0) { pad_outputs(nq, k, out_ids, out_scores, out_counts); return NVDB_OK; }
+  if (!probe) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": null probe table");
+  PartState* ps = c->parts;
+  return parts_search(c, ps->offsets.data(), static_cast<uint32_t>(ps->offsets.size() - 1), queries, nq, k, probe, nprobe, msel, out_ids, out_scores,
+                      out_counts, timing);
+}
+
+// nvdb_hip_search_ivf and its masked twin: the coarse step knows no masks
+nvdb_status search_ivf_any(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, const MaskSel* msel,
+                           uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
+  nvdb_status st = parts_args(c, who);
+  if (st) return st;
+  PartState* ps = c->parts;
+  if (!ps->have_centroids) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no centroids (nvdb_hip_set_centroids)");
+  if (timing) std::memset(timing, 0, sizeof(*timing));
+  if (nq == 0 || k == 0) return NVDB_OK;
+  if (k > WAVE_KMAX) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": k <= 64 (wavefront-resident lists)");
+  if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
+  if (msel && (st = mask_args(c, msel->mask_of, nq, who))) return st;
+  if (nprobe == 0) { pad_outputs(nq, k, out_ids, out_scores, out_counts); return NVDB_OK; }
+  const uint32_t nparts = static_cast<uint32_t>(ps->offsets.size() - 1);
+  const uint32_t np = std::min(nprobe, nparts);                            // the clamp; out_probe keeps the caller's row length
+  // coarse step: the flat search over the centroids (its order: score desc, partition number asc)
+  ps->coarse_ids.resize(static_cast<size_t>(nq) * np);
+  ps->coarse_scores.resize(static_cast<size_t>(nq) * np);
+  nvdb_hip_timing ct;
+  if ((st = nvdb_hip_search_batch(ps->coarse, queries, nq, np, ps->coarse_ids.data(), ps->coarse_scores.data(), nullptr, timing ? &ct : nullptr)))
+    return fail(c, st, std::string(who) + " (coarse step): " + nvdb_hip_last_error(ps->coarse));
+  ps->probe_tmp.resize(static_cast<size_t>(nq) * np);
+  for (size_t i = 0; i < ps->probe_tmp.size(); ++i) ps->probe_tmp[i] = static_cast<uint32_t>(ps->coarse_ids[i]);
+  if (out_probe)
+    for (uint32_t q = 0; q < nq; ++q)
+      for (uint32_t j = 0; j < nprobe; ++j) out_probe[static_cast<size_t>(q) * nprobe + j] = j < np ? ps->probe_tmp[static_cast<size_t>(q) * np + j] : 0xFFFFFFFFu;
+  if (timing) { timing->h2d_ms = ct.h2d_ms; timing->kernel_ms = ct.kernel_ms; timing->d2h_ms = ct.d2h_ms; }
+  return parts_search(c, ps->offsets.data(), nparts, queries, nq, k, ps->probe_tmp.data(), np, msel, out_ids, out_scores, out_counts, timing);
 }
 
 }  // namespace
@@ -320,43 +396,99 @@ nvdb_status nvdb_hip_set_centroids(nvdb_hip_ctx* c, const float* centroids) {
 nvdb_status nvdb_hip_search_partitions(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe,
                                        uint32_t nprobe, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                        nvdb_hip_timing* timing) {
-  nvdb_status st = parts_args(c, "search_partitions");
-  if (st) return st;
-  if (timing) std::memset(timing, 0, sizeof(*timing));
-  if (nq == 0 || k == 0) return NVDB_OK;
-  if (k > WAVE_KMAX) return fail(c, NVDB_ERR_UNSUPPORTED, "search_partitions: k <= 64 (wavefront-resident lists)");
-  if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
-  if (nprobe == 0) { pad_outputs(nq, k, out_ids, out_scores, out_counts); return NVDB_OK; }
-  if (!probe) return fail(c, NVDB_ERR_INVALID, "search_partitions: null probe table");
-  return parts_search(c, queries, nq, k, probe, nprobe, out_ids, out_scores, out_counts, timing);
+  return search_partitions_any(c, "search_partitions", queries, nq, k, probe, nprobe, nullptr, out_ids, out_scores, out_counts, timing);
 }
 
 nvdb_status nvdb_hip_search_ivf(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
                                 float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
-  nvdb_status st = parts_args(c, "search_ivf");
-  if (st) return st;
-  PartState* ps = c->parts;
-  if (!ps->have_centroids) return fail(c, NVDB_ERR_INVALID, "search_ivf: no centroids (nvdb_hip_set_centroids)");
+  return search_ivf_any(c, "search_ivf", queries, nq, k, nprobe, nullptr, out_ids, out_scores, out_counts, out_probe, timing);
+}
+
+// ---- row masks ------------------------------------------------------------------------------------------------------
+
+nvdb_status nvdb_hip_set_row_masks(nvdb_hip_ctx* c, const uint32_t* bits, uint32_t nmasks) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
+  if (c->n > ROW_MASK_MAX_ROWS) return fail(c, NVDB_ERR_UNSUPPORTED, "set_row_masks: corpus shard too large");
+  if (nmasks == 0xFFFFFFFFu) return fail(c, NVDB_ERR_INVALID, "set_row_masks: 0xFFFFFFFF masks (the number that means no mask)");
+  if (nmasks == 0) { c->nmasks = 0; return NVDB_OK; }
+  const uint64_t W = rm_words(c->n);
+  const size_t words = static_cast<size_t>(nmasks) * W;
+  std::vector<uint32_t> planes;                    // the caller's planes with their tail bits cleared (no planes given: all ones)
+  if (bits) planes.assign(bits, bits + words);
+  else planes.assign(words, 0xFFFFFFFFu);
+  for (uint32_t m = 0; m < nmasks; ++m) rm_clear_tail(planes.data() + static_cast<size_t>(m) * W, c->n);
+  HIPCHK(c, hipSetDevice(c->device));
+  c->nmasks = 0;                                   // (a failure below leaves no masks, not half of the new ones)
+  if (nvdb_status st = ensure(c, c->row_masks, words * 4)) return st;
+  HIPCHK(c, hipMemcpyAsync(c->row_masks.p, planes.data(), words * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->nmasks = nmasks;
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_update_row_mask(nvdb_hip_ctx* c, uint32_t mask, const uint64_t* rows, uint64_t nrows, int live) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
+  if (mask >= c->nmasks) return fail(c, NVDB_ERR_INVALID, "update_row_mask: mask >= nmasks (nvdb_hip_set_row_masks)");
+  if (nrows == 0) return NVDB_OK;
+  if (!rows) return fail(c, NVDB_ERR_INVALID, "update_row_mask: null row list");
+  if (!rm_rows_valid(rows, nrows, c->n)) return fail(c, NVDB_ERR_INVALID, "update_row_mask: a listed row is >= the row count");
+  if (nrows > (1ull << 31)) return fail(c, NVDB_ERR_UNSUPPORTED, "update_row_mask: row list too long (split it)");
+  std::vector<uint32_t> r32(rows, rows + nrows);   // (n <= 0xFFFFFF00: a local row fits 32 bits)
+  HIPCHK(c, hipSetDevice(c->device));
+  if (nvdb_status st = ensure(c, c->mask_rows, nrows * 4)) return st;
+  HIPCHK(c, hipMemcpyAsync(c->mask_rows.p, r32.data(), nrows * 4, hipMemcpyHostToDevice, c->stream));
+  uint32_t* plane = static_cast<uint32_t*>(c->row_masks.p) + static_cast<size_t>(mask) * rm_words(c->n);
+  update_row_mask_kernel<<<static_cast<unsigned>((nrows + 255) / 256), 256, 0, c->stream>>>(plane, static_cast<const uint32_t*>(c->mask_rows.p), nrows, live != 0);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_get_row_masks(nvdb_hip_ctx* c, uint32_t* nmasks, uint64_t* words_per_mask, uint32_t* bits_out) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (nmasks) *nmasks = c->nmasks;
+  if (words_per_mask) *words_per_mask = c->nmasks ? rm_words(c->n) : 0;
+  if (bits_out && c->nmasks) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(bits_out, c->row_masks.p, static_cast<size_t>(c->nmasks) * rm_words(c->n) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return NVDB_OK;
+}
+
+// ---- masked searches ------------------------------------------------------------------------------------------------
+
+nvdb_status nvdb_hip_search_partitions_masked(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe,
+                                              uint32_t nprobe, const uint32_t* mask_of, uint64_t* out_ids, float* out_scores,
+                                              uint32_t* out_counts, nvdb_hip_timing* timing) {
+  const MaskSel msel{mask_of};
+  return search_partitions_any(c, "search_partitions_masked", queries, nq, k, probe, nprobe, &msel, out_ids, out_scores, out_counts, timing);
+}
+
+nvdb_status nvdb_hip_search_ivf_masked(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, const uint32_t* mask_of,
+                                       uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe,
+                                       nvdb_hip_timing* timing) {
+  const MaskSel msel{mask_of};
+  return search_ivf_any(c, "search_ivf_masked", queries, nq, k, nprobe, &msel, out_ids, out_scores, out_counts, out_probe, timing);
+}
+
+nvdb_status nvdb_hip_search_batch_masked(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t k, const uint32_t* mask_of,
+                                         uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
   if (timing) std::memset(timing, 0, sizeof(*timing));
   if (nq == 0 || k == 0) return NVDB_OK;
-  if (k > WAVE_KMAX) return fail(c, NVDB_ERR_UNSUPPORTED, "search_ivf: k <= 64 (wavefront-resident lists)");
+  if (k > WAVE_KMAX) return fail(c, NVDB_ERR_UNSUPPORTED, "search_batch_masked: k <= 64 (wavefront-resident lists)");
   if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
-  if (nprobe == 0) { pad_outputs(nq, k, out_ids, out_scores, out_counts); return NVDB_OK; }
-  const uint32_t nparts = static_cast<uint32_t>(ps->offsets.size() - 1);
-  const uint32_t np = std::min(nprobe, nparts);                            // the clamp; out_probe keeps the caller's row length
-  // coarse step: the flat search over the centroids (its order: score desc, partition number asc)
-  ps->coarse_ids.resize(static_cast<size_t>(nq) * np);
-  ps->coarse_scores.resize(static_cast<size_t>(nq) * np);
-  nvdb_hip_timing ct;
-  if ((st = nvdb_hip_search_batch(ps->coarse, queries, nq, np, ps->coarse_ids.data(), ps->coarse_scores.data(), nullptr, timing ? &ct : nullptr)))
-    return fail(c, st, std::string("search_ivf (coarse step): ") + nvdb_hip_last_error(ps->coarse));
-  ps->probe_tmp.resize(static_cast<size_t>(nq) * np);
-  for (size_t i = 0; i < ps->probe_tmp.size(); ++i) ps->probe_tmp[i] = static_cast<uint32_t>(ps->coarse_ids[i]);
-  if (out_probe)
-    for (uint32_t q = 0; q < nq; ++q)
-      for (uint32_t j = 0; j < nprobe; ++j) out_probe[static_cast<size_t>(q) * nprobe + j] = j < np ? ps->probe_tmp[static_cast<size_t>(q) * np + j] : 0xFFFFFFFFu;
-  if (timing) { timing->h2d_ms = ct.h2d_ms; timing->kernel_ms = ct.kernel_ms; timing->d2h_ms = ct.d2h_ms; }
-  return parts_search(c, queries, nq, k, ps->probe_tmp.data(), np, out_ids, out_scores, out_counts, timing);
+  if (nvdb_status st = mask_args(c, mask_of, nq, "search_batch_masked")) return st;
+  if (!c->parts) c->parts = new PartState();       // the workspace only: no table is set, a table that is set stays as it is
+  // the corpus as one implicit partition that every query probes
+  const uint64_t off[2] = {0, c->n};
+  c->parts->probe_tmp.assign(nq, 0u);
+  const MaskSel msel{mask_of};
+  return parts_search(c, off, 1, queries, nq, k, c->parts->probe_tmp.data(), 1, &msel, out_ids, out_scores, out_counts, timing);
 }
 
 }  // extern "C"

@@ -34,6 +34,9 @@ EXPORTS = [
     "nvdb_hip_set_partitions", "nvdb_hip_set_centroids", "nvdb_hip_search_partitions", "nvdb_hip_search_ivf",
     "nvdb_hip_assign_rows", "nvdb_hip_train_centroids", "nvdb_ivf_layout_host",
     "nvdb_hip_ivf_build", "nvdb_hip_ivf_destroy", "nvdb_hip_ivf_last_error", "nvdb_hip_ivf_ctx", "nvdb_hip_ivf_info", "nvdb_hip_ivf_search",
+    "nvdb_hip_set_row_masks", "nvdb_hip_update_row_mask", "nvdb_hip_get_row_masks", "nvdb_hip_search_partitions_masked",
+    "nvdb_hip_search_ivf_masked", "nvdb_hip_search_batch_masked",
+    "nvdb_hip_ivf_set_row_masks", "nvdb_hip_ivf_update_row_mask", "nvdb_hip_ivf_search_masked",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_filter_variant", "nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -190,6 +193,15 @@ def _bind(L, dev):
     L.nvdb_hip_ivf_ctx.restype = vp
     L.nvdb_hip_ivf_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u32), vp, vp]
     L.nvdb_hip_ivf_search.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_set_row_masks.argtypes = [vp, vp, u32]
+    L.nvdb_hip_update_row_mask.argtypes = [vp, u32, vp, u64, C.c_int]
+    L.nvdb_hip_get_row_masks.argtypes = [vp, C.POINTER(u32), C.POINTER(u64), vp]
+    L.nvdb_hip_search_partitions_masked.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_search_ivf_masked.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_search_batch_masked.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_ivf_set_row_masks.argtypes = [vp, vp, u32]
+    L.nvdb_hip_ivf_update_row_mask.argtypes = [vp, u32, vp, u64, C.c_int]
+    L.nvdb_hip_ivf_search_masked.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, C.POINTER(Timing)]
     for name in EXPORTS:
         getattr(L, name)
     if dev:
@@ -300,6 +312,34 @@ def ivf_layout_host(assign, nparts):
     if st:
         raise NvdbError(st, "ivf_layout_host: an entry >= nparts, or more than 0xFFFFFF00 rows")
     return offsets, perm[:assign.size]
+
+
+def pack_row_masks(masks, n):
+    """Row masks as the library takes them: [nmasks, ceil(n / 32)] uint32, row r = bit r & 31 of word r >> 5.  `masks`: bool
+    [nmasks, n] (or [n]: one mask), or uint32 already packed."""
+    masks = np.asarray(masks)
+    words = (n + 31) // 32
+    if masks.dtype == np.uint32:
+        return np.ascontiguousarray(masks).reshape(-1, words)
+    if masks.dtype != np.bool_:
+        raise TypeError("row masks are bool [nmasks, n] or packed uint32 [nmasks, ceil(n / 32)]")
+    masks = masks.reshape(-1, n)
+    packed = np.zeros((masks.shape[0], words * 4), dtype=np.uint8)
+    packed[:, :(n + 7) // 8] = np.packbits(masks, axis=1, bitorder="little")
+    return np.ascontiguousarray(packed).view("<u4")
+
+
+def unpack_row_masks(packed, n):
+    """The inverse: packed uint32 [nmasks, ceil(n / 32)] -> bool [nmasks, n]."""
+    packed = np.ascontiguousarray(packed, dtype="<u4")
+    return np.unpackbits(packed.view(np.uint8), axis=1, bitorder="little")[:, :n].astype(bool)
+
+
+def _mask_of_arg(mask_of, nq):
+    """mask_of for a masked search: None (every query plane 0) or one plane number per query (0xFFFFFFFF: no mask)."""
+    if mask_of is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(mask_of, dtype=np.uint32), (nq,)))
 
 
 # ------------------------------------------------------------------------------- device context
@@ -473,6 +513,63 @@ class HipContext:
                                                counts.ctypes.data, probe.ctypes.data if want_probe else None, None))
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
+    # -- row masks (top-k restricted to live rows on the probe-search path; search_batch and range_search are NOT masked)
+    def set_row_masks(self, masks):
+        """masks: bool [nmasks, n] / packed uint32 [nmasks, ceil(n / 32)] (pack_row_masks); an int: that many all-live masks;
+        None or 0: drop them."""
+        if masks is None or (isinstance(masks, (int, np.integer)) and not isinstance(masks, (bool, np.bool_))):
+            self._chk(self.lib.nvdb_hip_set_row_masks(self.h, None, int(masks or 0)))
+            return
+        packed = pack_row_masks(masks, self.corpus_info()["n"])
+        self._chk(self.lib.nvdb_hip_set_row_masks(self.h, packed.ctypes.data, packed.shape[0]))
+
+    def update_row_mask(self, mask, rows, live):
+        """Set (live) or clear the listed local rows' bits of one mask on the device: the tombstone path."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64).ravel()
+        self._chk(self.lib.nvdb_hip_update_row_mask(self.h, mask, rows.ctypes.data if rows.size else None, rows.size, 1 if live else 0))
+
+    def get_row_masks(self):
+        """The resident planes as packed uint32 [nmasks, ceil(n / 32)] (unpack_row_masks gives bools)."""
+        nm, w = C.c_uint32(), C.c_uint64()
+        self._chk(self.lib.nvdb_hip_get_row_masks(self.h, C.byref(nm), C.byref(w), None))
+        out = np.zeros((nm.value, w.value), dtype=np.uint32)
+        if out.size:
+            self._chk(self.lib.nvdb_hip_get_row_masks(self.h, None, None, out.ctypes.data))
+        return out
+
+    def search_partitions_masked(self, queries, k, probe, mask_of=None, want_timing=False):
+        """search_partitions over the rows live in each query's mask: mask_of[q] = plane number (0xFFFFFFFF: none; None: plane 0
+        for every query) -> (ids, scores, counts); counts[q] = min(k, live rows in the probed union)."""
+        queries, nq, ids, scores, counts = self._probe_outputs(queries, k)
+        probe = np.ascontiguousarray(probe, dtype=np.uint32).reshape(nq, -1)
+        mo = _mask_of_arg(mask_of, nq)
+        t = Timing()
+        self._chk(self.lib.nvdb_hip_search_partitions_masked(self.h, queries.ctypes.data, nq, k, probe.ctypes.data, probe.shape[1],
+                                                             mo.ctypes.data if mo is not None else None, ids.ctypes.data,
+                                                             scores.ctypes.data, counts.ctypes.data, C.byref(t) if want_timing else None))
+        return (ids, scores, counts, t) if want_timing else (ids, scores, counts)
+
+    def search_ivf_masked(self, queries, k, nprobe, mask_of=None, want_probe=False):
+        """search_ivf (unmasked coarse step) with the partition scan restricted to live rows."""
+        queries, nq, ids, scores, counts = self._probe_outputs(queries, k)
+        probe = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
+        mo = _mask_of_arg(mask_of, nq)
+        self._chk(self.lib.nvdb_hip_search_ivf_masked(self.h, queries.ctypes.data, nq, k, nprobe, mo.ctypes.data if mo is not None else None,
+                                                      ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
+                                                      probe.ctypes.data if want_probe else None, None))
+        return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
+
+    def search_masked(self, queries, k, mask_of=None, want_timing=False):
+        """The masked flat search (nvdb_hip_search_batch_masked): exact top-k over ALL live rows, k <= 64, on the partition scan --
+        the rows are read once per group of up to 32 queries; the MFMA filter route of search_batch takes no masks."""
+        queries, nq, ids, scores, counts = self._probe_outputs(queries, k)
+        mo = _mask_of_arg(mask_of, nq)
+        t = Timing()
+        self._chk(self.lib.nvdb_hip_search_batch_masked(self.h, queries.ctypes.data, nq, k, mo.ctypes.data if mo is not None else None,
+                                                        ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
+                                                        C.byref(t) if want_timing else None))
+        return (ids, scores, counts, t) if want_timing else (ids, scores, counts)
+
     # -- IVF-Flat build
     def assign_rows(self, centroids, row0=0, nrows=None):
         """Best centroid ([nparts, dim] f32) of the resident rows [row0, row0 + nrows) -> [nrows] u32."""
@@ -576,6 +673,35 @@ class IvfIndex:
         probe = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
         self._chk(self.lib.nvdb_hip_ivf_search(self.h, queries.ctypes.data, nq, k, nprobe, ids.ctypes.data, scores.ctypes.data,
                                                counts.ctypes.data, probe.ctypes.data if want_probe else None, None))
+        return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
+
+    # -- row masks in the source corpus' rows (without its row base)
+    def set_row_masks(self, masks):
+        """As HipContext.set_row_masks, indexed by ORIGINAL row."""
+        if masks is None or (isinstance(masks, (int, np.integer)) and not isinstance(masks, (bool, np.bool_))):
+            self._chk(self.lib.nvdb_hip_ivf_set_row_masks(self.h, None, int(masks or 0)))
+            return
+        packed = pack_row_masks(masks, self.info()["n"])
+        self._chk(self.lib.nvdb_hip_ivf_set_row_masks(self.h, packed.ctypes.data, packed.shape[0]))
+
+    def update_row_mask(self, mask, rows, live):
+        rows = np.ascontiguousarray(rows, dtype=np.uint64).ravel()
+        self._chk(self.lib.nvdb_hip_ivf_update_row_mask(self.h, mask, rows.ctypes.data if rows.size else None, rows.size, 1 if live else 0))
+
+    def search_masked(self, queries, k, nprobe, mask_of=None, want_probe=False):
+        """search() over the rows live in each query's mask (mask_of as HipContext.search_partitions_masked)."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        nq = queries.shape[0]
+        ids = np.full((nq, k), np.iinfo(np.uint64).max, dtype=np.uint64)
+        scores = np.full((nq, k), -np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        probe = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
+        mo = _mask_of_arg(mask_of, nq)
+        self._chk(self.lib.nvdb_hip_ivf_search_masked(self.h, queries.ctypes.data, nq, k, nprobe, mo.ctypes.data if mo is not None else None,
+                                                      ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
+                                                      probe.ctypes.data if want_probe else None, None))
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
 
