@@ -69,7 +69,7 @@ typedef struct nvdb_hip_timing {
 /* What the last flat search did (for tests, bench.py and the roofline arithmetic). */
 typedef struct nvdb_hip_scan_stats {
   uint32_t path;               /* 1 = exact fp32 scan, 2 = MFMA filter + exact rescore (k <= 1024), 3 = any-k (k > 64 off the filter path), 4 = partitioned probe search,
-                                  5 = range search, filter route, 6 = range search, exact route */
+                                  5 = range search, filter route, 6 = range search, exact route, 7 = range search, partition scan */
   uint32_t chunks;             /* corpus chunks (kernel launches of the dominant kernel)          */
   uint64_t rows_scanned;       /* rows x query-tiles streamed by the dominant kernel              */
   uint64_t candidates;         /* (query,row) pairs that reached the exact rescore                */
@@ -294,8 +294,10 @@ nvdb_status nvdb_hip_search_ivf(nvdb_hip_ctx* ctx, const float* queries, uint32_
  * SearchParameters::sel with an IDSelectorBitmap.  A context holds nmasks bit planes over its resident corpus; plane m is
  * W = ceil(n / 32) uint32 words, LOCAL row r (global_row_base plays no part) is live in mask m iff bit r & 31 of word
  * m * W + (r >> 5) is 1.  Bits at positions >= n of a plane's last word are ignored on input and read back as 0.
- * NOT masked (out of scope so far): nvdb_hip_search_batch and its MFMA filter / exact / any-k routes, nvdb_hip_range_search, the
- * device group, the _dev stream entry points, k > 64, the nvdb:: C++ host layer.  Those entry points, and the unmasked probe
+ * Masked entry points: the top-k searches below (k <= 64) and the range searches of the next block (nvdb_hip_range_search_partitions /
+ * _ivf with masked != 0, nvdb_hip_range_search_masked, nvdb_hip_ivf_range_search).
+ * NOT masked (out of scope so far): nvdb_hip_search_batch and its MFMA filter / exact / any-k routes, nvdb_hip_range_search itself, the
+ * device group, the _dev stream entry points, top-k with k > 64, the nvdb:: C++ host layer.  Those entry points, and the unmasked probe
  * searches above, ignore resident masks entirely: results, statistics and launches are what they are without masks.
  * ------------------------------------------------------------------------------------------- */
 
@@ -342,6 +344,49 @@ nvdb_status nvdb_hip_search_batch_masked(nvdb_hip_ctx* ctx, const float* queries
                                          const uint32_t* mask_of /* [nq], may be NULL */,
                                          uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                          nvdb_hip_timing* timing);
+
+/* ---------------------------------------------------------------------------------------------
+ * range search on the probe path: nvdb_hip_range_search's question -- every row whose score reaches a per-query radius -- asked of
+ * a per-query choice of partitions, of an IVF index, and of the rows that are live in a query's mask.  FAISS users know the
+ * combination as IndexIVF::range_search with SearchParameters::sel.
+ * Row i belongs to query q iff it is in the union of q's probed partitions, it is live in q's plane (masked calls), and
+ * score(q, i) >= radius[q] as a C float comparison.  The score is the reference-order dot product -- the bits
+ * nvdb_hip_search_partitions returns.  A NaN score never belongs, a NaN radius gives an empty slice, radius = -inf takes every
+ * score that is not NaN, +0.0 and -0.0 compare equal.  Inside a slice: score descending, global id ascending.
+ * out_lims [nq + 1], the packed device arrays, option "range_max_mb" and NVDB_ERR_UNSUPPORTED with complete lims above it are
+ * nvdb_hip_range_search's; the result is fetched with nvdb_hip_range_results.  A range search of any kind replaces the held result.
+ * masked == 0: mask_of is ignored, resident masks play no part.  masked != 0: mask_of[nq] as for the masked searches above --
+ * 0xFFFFFFFF = no mask, NULL = plane 0 for every query; an entry >= nmasks or no planes resident -> NVDB_ERR_INVALID before
+ * anything is launched, nothing written.
+ * ------------------------------------------------------------------------------------------- */
+
+/* probe[nq][nprobe]: nvdb_hip_search_partitions' rules (0xFFFFFFFF = empty slot, duplicates count once, an entry >= nparts ->
+ * NVDB_ERR_INVALID before anything is launched).  nprobe == 0 -> all-zero lims.  nq == 0 -> NVDB_OK, out_lims[0] = 0.  Any nq:
+ * the batch is cut into query sub-batches inside whose candidate blocks (8 bytes per row of a query's probed union) stay within half
+ * of option "largek_budget_mb" -- the other half is the sort's key slabs; one query's block or slab is taken whatever the option
+ * says --; the caller does not see the cut.  No partition table -> NVDB_ERR_INVALID; no corpus -> NVDB_ERR_NO_CORPUS.
+ * nvdb_hip_get_stats afterwards: path = 7, chunks = scan launches, rows_scanned = rows of the work items, candidates = entries
+ * written (= results).  timing (optional): kernel / total (the work list's copies alternate with the launches and ride inside). */
+nvdb_status nvdb_hip_range_search_partitions(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq,
+                                             const float* radius /* [nq] */, const uint32_t* probe /* [nq][nprobe] */, uint32_t nprobe,
+                                             const uint32_t* mask_of /* [nq], may be NULL */, int masked,
+                                             uint64_t* out_lims /* [nq+1] */, nvdb_hip_timing* timing /* may be NULL */);
+/* The coarse step, the clamp of nprobe and out_probe (optional, [nq][nprobe]) are nvdb_hip_search_ivf's; centroids are not masked.
+ * Without centroids -> NVDB_ERR_INVALID. */
+nvdb_status nvdb_hip_range_search_ivf(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, const float* radius /* [nq] */,
+                                      uint32_t nprobe, const uint32_t* mask_of /* [nq], may be NULL */, int masked,
+                                      uint64_t* out_lims /* [nq+1] */, uint32_t* out_probe /* may be NULL */,
+                                      nvdb_hip_timing* timing /* may be NULL */);
+/* The masked flat range search: nvdb_hip_range_search over the rows live in each query's plane (always masked: mask_of as above).
+ * Where nvdb_hip_range_search takes the MFMA filter route so does this call -- the thresholds are fixed before the first row, so a
+ * dead row above one only occupies a list entry until the keep step drops it (a list that overflows because of them sends its
+ * query to the scan below like any overflow) -- and nvdb_hip_get_stats reports path 5.  Flagged queries, option path = 1 and
+ * dims / dtypes without a filter run on the partition range scan with the corpus as one implicit partition (path 7 when nothing
+ * was filtered); no partition table is needed, one that is set stays.  The result does not depend on the route.  A violated filter
+ * bound -> recomputed on that scan, NVDB_ERR_INTERNAL. */
+nvdb_status nvdb_hip_range_search_masked(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, const float* radius /* [nq] */,
+                                         const uint32_t* mask_of /* [nq], may be NULL */, uint64_t* out_lims /* [nq+1] */,
+                                         nvdb_hip_timing* timing /* may be NULL */);
 
 /* ---------------------------------------------------------------------------------------------
  * IVF-Flat build: from a resident corpus to an index the probe search above can serve -- centroids trained on the GPU
@@ -420,6 +465,17 @@ nvdb_status nvdb_hip_ivf_search_masked(nvdb_hip_ivf* ivf, const float* queries, 
                                        const uint32_t* mask_of /* [nq], may be NULL */,
                                        uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                        uint32_t* out_probe, nvdb_hip_timing* timing);
+
+/* nvdb_hip_range_search_ivf on the index's context; mask_of names planes set with nvdb_hip_ivf_set_row_masks (original rows).
+ * The lims are final; the slices are held by the index's context in list positions. */
+nvdb_status nvdb_hip_ivf_range_search(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, const float* radius /* [nq] */,
+                                      uint32_t nprobe, const uint32_t* mask_of /* [nq], may be NULL */, int masked,
+                                      uint64_t* out_lims /* [nq+1] */, uint32_t* out_probe /* may be NULL */,
+                                      nvdb_hip_timing* timing /* may be NULL */);
+/* nvdb_hip_range_results on the index's context, then every id becomes src's global_row_base + perm[id], as nvdb_hip_ivf_search
+ * maps them.  ORDER inside a slice: score descending; equal scores by (partition number, original id) -- the order of the
+ * positions in the lists. */
+nvdb_status nvdb_hip_ivf_range_results(nvdb_hip_ivf* ivf, uint64_t* out_ids, float* out_scores);
 
 /* Tunables (defaults are what bench.py measures; the table with meanings is in INTEGRATION.md section 4b):
  * "path" (0 auto, 1 exact, 2 mfma-filter), "chunk0_rows", "chunk_growth", "cand_cap", "min_filter_batch", "mfma_boot", "waves8",

@@ -287,7 +287,7 @@ void nvdb_hip_destroy(nvdb_hip_ctx* c) {
   if (c->hostblock.p) c->misc.p = nullptr;         // (misc lives inside the host API's result block)
   for (DevBuf* b : {&c->q32, &c->q16, &c->qscale, &c->qinv, &c->ebound, &c->slack, &c->thr, &c->cnt, &c->overflow, &c->cand,
                     &c->out_ids, &c->out_scores, &c->misc, &c->hostblock, &c->hitlog, &c->prog, &c->qdelta, &c->rq, &c->rcand, &c->rout_ids, &c->rout_dist, &c->rdbg, &c->lk_scores, &c->lk_sel, &c->lk_hist, &c->lk_state, &c->xcdw, &c->tickets,
-                    &c->rg_radius, &c->rg_kept, &c->rg_off, &c->rg_idx, &c->rg_q, &c->rg_desc, &c->rg_taken, &c->rg_slab, &c->rg_ids, &c->rg_scores, &c->row_masks, &c->mask_rows})
+                    &c->rg_radius, &c->rg_kept, &c->rg_off, &c->rg_idx, &c->rg_q, &c->rg_desc, &c->rg_taken, &c->rg_slab, &c->rg_pcnt, &c->rg_maskof, &c->rg_ids, &c->rg_scores, &c->row_masks, &c->mask_rows})
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   for (auto& k : c->klaunch) { (void)hipEventDestroy(k.e0); (void)hipEventDestroy(k.e1); }

@@ -6,6 +6,8 @@
 //                          before anything is enqueued, from corpus facts, options and the launchers' shape facts below; no HIP call
 //   nvdb_search.cpp        one flat search: plan -> workspace -> launches (search_core); the search entry points, their self-checks and retry ladder
 //   nvdb_range.cpp         range search (every row whose score reaches a per-query radius): plan, filter route, exact route, packing (kernels_range.h)
+//   nvdb_range_parts.cpp   range search on the probe path: the partition range scan, its per-query tail, the probe / IVF / masked entry points
+//                          (kernels_range_parts.h, range_plan.h; nvdb_range.h and nvdb_parts.h are what it shares with its two neighbours)
 //   nvdb_launch_f16.cpp    launch helpers of the fp16 MFMA filter kernels (kernels_filter.h), query prep for them
 //   nvdb_launch_i8.cpp     ... of the int8 kernels (kernels_filter.h, kernels_filter_i8s.h)
 //   nvdb_launch_exact.cpp  ... of the exact fp32-order kernels, select / rescore / merge, the any-k path (kernels_exact*.h, kernels_largek.h)
@@ -149,6 +151,7 @@ struct nvdb_hip_ctx {
   int64_t opt_largek_budget_mb = 8192;             // HBM the any-k path may use for its score matrix
   // range search (nvdb_range.cpp): the last call's packed results stay here for nvdb_hip_range_results
   DevBuf rg_radius, rg_kept, rg_off, rg_idx, rg_q, rg_desc, rg_taken, rg_slab;   // radii, list / score counts, pack offsets, flagged queries (numbers, compact batch), exact-route passes
+  DevBuf rg_pcnt, rg_maskof;                       // partition range scan: per-query entry counts; masked flat range search: mask_of on the device
   DevBuf rg_ids, rg_scores;                        // packed global ids / scores of the last range search (grow-only)
   uint64_t range_total = 0;                        // ... their entries
   bool range_valid = false;                        // ... and whether nvdb_hip_range_results may hand them out (false: none yet, over budget, corpus changed)

@@ -447,4 +447,24 @@ nvdb_status nvdb_hip_ivf_search_masked(nvdb_hip_ivf* ix, const float* queries, u
   return NVDB_OK;
 }
 
+nvdb_status nvdb_hip_ivf_range_search(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, const float* radius, uint32_t nprobe, const uint32_t* mask_of, int masked,
+                                      uint64_t* out_lims, uint32_t* out_probe, nvdb_hip_timing* timing) {
+  if (!ix) return NVDB_ERR_INVALID;
+  const nvdb_status st = nvdb_hip_range_search_ivf(ix->ctx, queries, nq, radius, nprobe, mask_of, masked, out_lims, out_probe, timing);
+  if (st) ix->err = nvdb_hip_last_error(ix->ctx);
+  return st;
+}
+
+nvdb_status nvdb_hip_ivf_range_results(nvdb_hip_ivf* ix, uint64_t* out_ids, float* out_scores) {
+  if (!ix) return NVDB_ERR_INVALID;
+  const nvdb_status st = nvdb_hip_range_results(ix->ctx, out_ids, out_scores);
+  if (st) { ix->err = nvdb_hip_last_error(ix->ctx); return st; }
+  // positions in the list-ordered copy -> ids of the source corpus; the order stays: equal scores by (list, original row)
+  const uint32_t* perm = ix->perm.data();
+  const uint64_t total = ix->ctx->range_total, n = ix->perm.size();
+  for (uint64_t i = 0; i < total; ++i)
+    if (out_ids[i] < n) out_ids[i] = ix->src_row_base + perm[out_ids[i]];
+  return NVDB_OK;
+}
+
 }  // extern "C"

@@ -12,30 +12,14 @@
 //      (dst); the blocks are laid out by a prefix sum (cbeg), so the capacity is exact and nothing can overflow.
 // Items are sorted by group size into classes (<= 8, <= 16, <= 32 queries) that run the QW = 1, 2, 4 builds of the kernel (the
 // widest one the LDS has room for): a remainder group of three queries does not pay for sixteen.
+// The list builder and its pinned image (parts_worklist / parts_stage, nvdb_parts.h) are shared with the partition range scan
+// (nvdb_range_parts.cpp), whose slots hold a segment's row count instead of min(k, rows).
 // A masked search is the same work list with every query's mask number appended to the pinned image; the MASKED builds of the
 // scan test a row's bit before they offer it, and the select kernel writes the counts the host can no longer derive.  The
 // masked flat search runs the corpus as one implicit partition that every query probes.
-#include "nvdb_ctx.h"
-#include "kernels_partitions.h"
-#include "row_mask.h"
+#include "nvdb_parts.h"
 
 namespace nvdbhip {
-
-struct PartState {
-  std::vector<uint64_t> offsets;                   // nparts + 1; empty: no table
-  nvdb_hip_ctx* coarse = nullptr;                  // child context that holds the centroids as an f32 corpus (same device)
-  bool have_centroids = false;
-  // grow-only workspace
-  DevBuf meta, cand, q, out_ids, out_scores, out_counts;
-  void* pin = nullptr;                             // pinned staging of the work list
-  size_t pin_bytes = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  // host scratch, reused across calls
-  std::vector<uint32_t> uniq, ucount, pcount, pstart, cursor, qidx, dst, cbeg, psum, probe_tmp;
-  std::vector<uint64_t> coarse_ids;
-  std::vector<float> coarse_scores;
-  std::vector<PartItem> items[3];
-};
 
 void parts_drop(nvdb_hip_ctx* c) {
   PartState* ps = c->parts;
@@ -57,13 +41,6 @@ void parts_destroy(nvdb_hip_ctx* c) {
 }
 
 namespace {
-
-constexpr size_t PART_LDS_LIMIT = 160 * 1024;
-
-size_t parts_lds(uint32_t dim, uint32_t row_bytes, uint32_t qw, bool staged) {
-  const size_t qstride = (dim + 3u) & ~3u;
-  return PART_WAVES * qw * qstride * 4 + (staged ? static_cast<size_t>(PART_TILE_ROWS) * part_pitch(row_bytes) : 0);
-}
 
 // mk.mask_of != nullptr: the MASKED build
 template <int DT, int QW, bool AL, bool ST, bool MK>
@@ -107,6 +84,8 @@ nvdb_status launch_scan_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool 
   return launch_dt<DT_I8>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand, mk);
 }
 
+}  // namespace
+
 nvdb_status parts_args(nvdb_hip_ctx* c, const char* who) {
   if (!c) return NVDB_ERR_INVALID;
   if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
@@ -114,46 +93,58 @@ nvdb_status parts_args(nvdb_hip_ctx* c, const char* who) {
   return NVDB_OK;
 }
 
-// how a masked search differs from its twin: mask_of as the caller gave it (nullptr: plane 0 for every query; validated by the caller)
-struct MaskSel { const uint32_t* mask_of; };
+PartState* parts_workspace(nvdb_hip_ctx* c) {
+  if (!c->parts) c->parts = new PartState();
+  return c->parts;
+}
 
-// the search proper over the table off[0 .. nparts]; the caller has validated the context, nq > 0 and 0 < k <= 64.
-// msel != nullptr: the masked search (the caller has checked mask_of against the resident planes)
-nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe,
-                         uint32_t nprobe, const MaskSel* msel, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
-  PartState* ps = c->parts;
+PartBuild parts_build(const nvdb_hip_ctx* c) {
   const uint32_t row_bytes = c->dim * static_cast<uint32_t>(bpe_of(c->dtype));
-
-  // kernel build: staged through LDS where the rows are whole 16-byte chunks and a tile fits beside the queries
   const bool can_stage = row_bytes % 16 == 0 && row_bytes <= PART_STAGE_MAX_ROW_BYTES && reinterpret_cast<uintptr_t>(c->rows) % 16 == 0;
-  uint32_t qw_max = 0;
-  bool staged = false;
-  for (int pass = 0; pass < 2 && !qw_max; ++pass) {
+  PartBuild b;
+  for (int pass = 0; pass < 2 && !b.qw_max; ++pass) {
     if (pass == 0 && !can_stage) continue;
     for (uint32_t qw : {4u, 2u, 1u})
-      if (parts_lds(c->dim, row_bytes, qw, pass == 0) <= PART_LDS_LIMIT) { qw_max = qw; staged = pass == 0; break; }
+      if (parts_lds(c->dim, row_bytes, qw, pass == 0) <= PART_LDS_LIMIT) { b.qw_max = qw; b.staged = pass == 0; break; }
   }
-  if (!qw_max) return fail(c, NVDB_ERR_UNSUPPORTED, "search_partitions: dim too large for the query staging");
-  const uint32_t qg_max = PART_WAVES * qw_max;
+  return b;
+}
 
-  // 1. de-duplicated probes, per-partition query counts
+nvdb_status parts_probes(nvdb_hip_ctx* c, const char* who, const uint64_t* off, uint32_t nparts, uint32_t nq, const uint32_t* probe, uint32_t nprobe,
+                         uint64_t* rows_union) {
+  PartState* ps = c->parts;
   ps->uniq.resize(static_cast<size_t>(nq) * nprobe);
   ps->ucount.assign(nq, 0);
-  ps->pcount.assign(nparts, 0);
   for (uint32_t q = 0; q < nq; ++q) {
     uint32_t* u = ps->uniq.data() + static_cast<size_t>(q) * nprobe;
     uint32_t m = 0;
     for (uint32_t j = 0; j < nprobe; ++j) {
       const uint32_t p = probe[static_cast<size_t>(q) * nprobe + j];
       if (p == 0xFFFFFFFFu) continue;
-      if (p >= nparts) return fail(c, NVDB_ERR_INVALID, "search_partitions: probe entry names a partition >= nparts");
+      if (p >= nparts) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": probe entry names a partition >= nparts");
       u[m++] = p;
     }
     std::sort(u, u + m);
     m = static_cast<uint32_t>(std::unique(u, u + m) - u);
     ps->ucount[q] = m;
-    for (uint32_t j = 0; j < m; ++j) ++ps->pcount[u[j]];
+    if (rows_union) {
+      uint64_t rows = 0;
+      for (uint32_t j = 0; j < m; ++j) rows += off[u[j] + 1] - off[u[j]];
+      rows_union[q] = rows;
+    }
   }
+  return NVDB_OK;
+}
+
+nvdb_status parts_worklist(nvdb_hip_ctx* c, const char* who, const uint64_t* off, uint32_t nparts, uint32_t q0, uint32_t nq, uint32_t nprobe,
+                           uint32_t qg_max, uint32_t slot_cap, PartList& wl) {
+  PartState* ps = c->parts;
+  // 1. the de-duplicated probes of queries q0 .. q0 + nq (parts_probes): per-partition query counts
+  const uint32_t* uniq = ps->uniq.data() + static_cast<size_t>(q0) * nprobe;
+  const uint32_t* ucount = ps->ucount.data() + q0;
+  ps->pcount.assign(nparts, 0);
+  for (uint32_t q = 0; q < nq; ++q)
+    for (uint32_t j = 0; j < ucount[q]; ++j) ++ps->pcount[uniq[static_cast<size_t>(q) * nprobe + j]];
   // 2. counting sort: the queries of every partition, ascending
   ps->pstart.assign(nparts + 1, 0);
   for (uint32_t p = 0; p < nparts; ++p) ps->pstart[p + 1] = ps->pstart[p] + ps->pcount[p];
@@ -161,8 +152,8 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, 
   ps->qidx.resize(npairs);
   ps->cursor.assign(ps->pstart.begin(), ps->pstart.end() - 1);
   for (uint32_t q = 0; q < nq; ++q) {
-    const uint32_t* u = ps->uniq.data() + static_cast<size_t>(q) * nprobe;
-    for (uint32_t j = 0; j < ps->ucount[q]; ++j) ps->qidx[ps->cursor[u[j]]++] = q;
+    const uint32_t* u = uniq + static_cast<size_t>(q) * nprobe;
+    for (uint32_t j = 0; j < ucount[q]; ++j) ps->qidx[ps->cursor[u[j]]++] = q;
   }
   // 3. candidate slots a probe of partition p costs a query; the queries' blocks
   auto nseg_of = [](uint64_t size) { return static_cast<uint32_t>((size + PART_SEG_ROWS - 1) / PART_SEG_ROWS); };
@@ -172,18 +163,16 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, 
     if (!ps->pcount[p] || !size) continue;
     const uint32_t nseg = nseg_of(size);
     uint64_t sum = 0;
-    for (uint32_t sg = 0; sg < nseg; ++sg) sum += std::min<uint64_t>(k, size * (sg + 1) / nseg - size * sg / nseg);
+    for (uint32_t sg = 0; sg < nseg; ++sg) sum += std::min<uint64_t>(slot_cap, size * (sg + 1) / nseg - size * sg / nseg);
     ps->psum[p] = static_cast<uint32_t>(sum);
   }
   ps->cbeg.assign(nq + 1, 0);
   uint64_t total = 0;
   for (uint32_t q = 0; q < nq; ++q) {
-    const uint32_t* u = ps->uniq.data() + static_cast<size_t>(q) * nprobe;
-    uint64_t rows_union = 0;
-    for (uint32_t j = 0; j < ps->ucount[q]; ++j) { total += ps->psum[u[j]]; rows_union += off[u[j] + 1] - off[u[j]]; }
-    if (total >= 0xFFFFFFFFull) return fail(c, NVDB_ERR_UNSUPPORTED, "search_partitions: more than 2^32 candidate slots in one call (split the batch)");
+    const uint32_t* u = uniq + static_cast<size_t>(q) * nprobe;
+    for (uint32_t j = 0; j < ucount[q]; ++j) total += ps->psum[u[j]];
+    if (total >= 0xFFFFFFFFull) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 candidate slots in one call (split the batch)");
     ps->cbeg[q + 1] = static_cast<uint32_t>(total);
-    if (out_counts && !msel) out_counts[q] = static_cast<uint32_t>(std::min<uint64_t>(k, rows_union));   // (masked: the select kernel counts)
   }
   // 4. work items, by class of group size
   for (auto& v : ps->items) v.clear();
@@ -201,26 +190,24 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, 
       for (uint32_t sg = 0; sg < nseg; ++sg) {
         const uint32_t lo = static_cast<uint32_t>(off[p] + size * sg / nseg), hi = static_cast<uint32_t>(off[p] + size * (sg + 1) / nseg);
         ps->items[cl].push_back(PartItem{lo, hi, ps->pstart[p] + g0, static_cast<uint32_t>(ps->dst.size()), nqg, 0u});
-        const uint32_t slot = std::min<uint32_t>(k, hi - lo);
+        const uint32_t slot = std::min<uint32_t>(slot_cap, hi - lo);
         for (uint32_t g = 0; g < nqg; ++g) { uint32_t& cur = ps->cursor[ps->qidx[ps->pstart[p] + g0 + g]]; ps->dst.push_back(cur); cur += slot; }
         rows_read += hi - lo;
       }
     }
   }
-  const size_t nitems = ps->items[0].size() + ps->items[1].size() + ps->items[2].size();
+  wl.npairs = npairs;
+  wl.total = total;
+  wl.rows_read = rows_read;
+  wl.nitems = ps->items[0].size() + ps->items[1].size() + ps->items[2].size();
+  return NVDB_OK;
+}
 
-  // device workspace (grow-only) and the pinned image of the work list: [items | qidx | dst | cbeg | masked: mask_of]
-  const size_t w_items = nitems * (sizeof(PartItem) / 4), w_qidx = npairs, w_dst = ps->dst.size(), w_cbeg = nq + 1, w_mask = msel ? nq : 0;
-  const size_t meta_bytes = (w_items + w_qidx + w_dst + w_cbeg + w_mask) * 4;
-  const size_t qbytes = static_cast<size_t>(nq) * c->dim * 4, ob_ids = static_cast<size_t>(nq) * k * 8, ob_sc = static_cast<size_t>(nq) * k * 4;
-  nvdb_status st;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((st = ensure(c, ps->meta, meta_bytes))) return st;
-  if ((st = ensure(c, ps->cand, std::max<size_t>(total, 1) * sizeof(Cand)))) return st;
-  if ((st = ensure(c, ps->q, qbytes))) return st;
-  if ((st = ensure(c, ps->out_ids, ob_ids))) return st;
-  if ((st = ensure(c, ps->out_scores, ob_sc))) return st;
-  if (msel && (st = ensure(c, ps->out_counts, static_cast<size_t>(nq) * 4))) return st;
+nvdb_status parts_stage(nvdb_hip_ctx* c, const PartList& wl, uint32_t nq, const MaskSel* msel, const uint32_t* extra, uint32_t extra_words, PartImage& im) {
+  PartState* ps = c->parts;
+  const size_t w_items = wl.nitems * (sizeof(PartItem) / 4), w_qidx = wl.npairs, w_dst = ps->dst.size(), w_cbeg = nq + 1, w_mask = msel ? nq : 0;
+  const size_t meta_bytes = (w_items + w_qidx + w_dst + w_cbeg + w_mask + extra_words) * 4;
+  if (nvdb_status st = ensure(c, ps->meta, meta_bytes)) return st;
   if (ps->pin_bytes < meta_bytes) {
     if (ps->pin) (void)hipHostFree(ps->pin);
     ps->pin = nullptr; ps->pin_bytes = 0;
@@ -228,32 +215,92 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, 
     ps->pin_bytes = meta_bytes + meta_bytes / 2;
   }
   for (hipEvent_t& e : ps->ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-  uint32_t* pin = static_cast<uint32_t*>(ps->pin);
-  {
-    uint32_t* w = pin;
-    for (int cl = 2; cl >= 0; --cl) {                                     // the widest groups first: the longest items start early
-      if (!ps->items[cl].empty()) std::memcpy(w, ps->items[cl].data(), ps->items[cl].size() * sizeof(PartItem));
-      w += ps->items[cl].size() * (sizeof(PartItem) / 4);
-    }
-    if (w_qidx) std::memcpy(w, ps->qidx.data(), w_qidx * 4);
-    w += w_qidx;
-    if (w_dst) std::memcpy(w, ps->dst.data(), w_dst * 4);
-    w += w_dst;
-    std::memcpy(w, ps->cbeg.data(), w_cbeg * 4);
-    w += w_cbeg;
-    for (uint32_t q = 0; q < w_mask; ++q) w[q] = msel->mask_of ? msel->mask_of[q] : 0u;
+  uint32_t* w = static_cast<uint32_t*>(ps->pin);
+  for (int cl = 2; cl >= 0; --cl) {                                     // the widest groups first: the longest items start early
+    if (!ps->items[cl].empty()) std::memcpy(w, ps->items[cl].data(), ps->items[cl].size() * sizeof(PartItem));
+    w += ps->items[cl].size() * (sizeof(PartItem) / 4);
   }
-  hipStream_t s = c->stream;
+  if (w_qidx) std::memcpy(w, ps->qidx.data(), w_qidx * 4);
+  w += w_qidx;
+  if (w_dst) std::memcpy(w, ps->dst.data(), w_dst * 4);
+  w += w_dst;
+  std::memcpy(w, ps->cbeg.data(), w_cbeg * 4);
+  w += w_cbeg;
+  for (uint32_t q = 0; q < w_mask; ++q) w[q] = msel->mask_of ? msel->mask_of[q] : 0u;
+  w += w_mask;
+  if (extra_words) std::memcpy(w, extra, static_cast<size_t>(extra_words) * 4);
   uint32_t* dmeta = static_cast<uint32_t*>(ps->meta.p);
-  const PartItem* d_items = reinterpret_cast<const PartItem*>(dmeta);
-  const uint32_t* d_qidx = dmeta + w_items;
-  const uint32_t* d_dst = d_qidx + w_qidx;
-  const uint32_t* d_cbeg = d_dst + w_dst;
-  const PartMask mk = msel ? PartMask{d_cbeg + w_cbeg, static_cast<const uint32_t*>(c->row_masks.p), static_cast<uint32_t>(rm_words(c->n))}
-                           : PartMask{nullptr, nullptr, 0u};
+  im.bytes = meta_bytes;
+  im.items = reinterpret_cast<const PartItem*>(dmeta);
+  im.qidx = dmeta + w_items;
+  im.dst = im.qidx + w_qidx;
+  im.cbeg = im.dst + w_dst;
+  im.extra = im.cbeg + w_cbeg + w_mask;
+  im.mk = msel ? PartMask{im.cbeg + w_cbeg, static_cast<const uint32_t*>(c->row_masks.p), static_cast<uint32_t>(rm_words(c->n))}
+               : PartMask{nullptr, nullptr, 0u};
+  return NVDB_OK;
+}
+
+nvdb_status parts_coarse(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, uint32_t nprobe, uint32_t* out_probe, nvdb_hip_timing* timing,
+                         uint32_t& np) {
+  PartState* ps = c->parts;
+  nvdb_status st;
+  const uint32_t nparts = static_cast<uint32_t>(ps->offsets.size() - 1);
+  np = std::min(nprobe, nparts);                                           // the clamp; out_probe keeps the caller's row length
+  // coarse step: the flat search over the centroids (its order: score desc, partition number asc)
+  ps->coarse_ids.resize(static_cast<size_t>(nq) * np);
+  ps->coarse_scores.resize(static_cast<size_t>(nq) * np);
+  nvdb_hip_timing ct;
+  if ((st = nvdb_hip_search_batch(ps->coarse, queries, nq, np, ps->coarse_ids.data(), ps->coarse_scores.data(), nullptr, timing ? &ct : nullptr)))
+    return fail(c, st, std::string(who) + " (coarse step): " + nvdb_hip_last_error(ps->coarse));
+  ps->probe_tmp.resize(static_cast<size_t>(nq) * np);
+  for (size_t i = 0; i < ps->probe_tmp.size(); ++i) ps->probe_tmp[i] = static_cast<uint32_t>(ps->coarse_ids[i]);
+  if (out_probe)
+    for (uint32_t q = 0; q < nq; ++q)
+      for (uint32_t j = 0; j < nprobe; ++j) out_probe[static_cast<size_t>(q) * nprobe + j] = j < np ? ps->probe_tmp[static_cast<size_t>(q) * np + j] : 0xFFFFFFFFu;
+  if (timing) { timing->h2d_ms = ct.h2d_ms; timing->kernel_ms = ct.kernel_ms; timing->d2h_ms = ct.d2h_ms; }
+  return NVDB_OK;
+}
+
+namespace {
+
+// the search proper over the table off[0 .. nparts]; the caller has validated the context, nq > 0 and 0 < k <= 64.
+// msel != nullptr: the masked search (the caller has checked mask_of against the resident planes)
+nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe,
+                         uint32_t nprobe, const MaskSel* msel, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
+  PartState* ps = c->parts;
+  const uint32_t row_bytes = c->dim * static_cast<uint32_t>(bpe_of(c->dtype));
+  const PartBuild pb = parts_build(c);
+  const uint32_t qw_max = pb.qw_max;
+  const bool staged = pb.staged;
+  if (!qw_max) return fail(c, NVDB_ERR_UNSUPPORTED, "search_partitions: dim too large for the query staging");
+  nvdb_status st;
+  const bool host_counts = out_counts && !msel;                          // (masked: the select kernel counts)
+  if (host_counts) ps->rows_union.resize(nq);
+  if ((st = parts_probes(c, "search_partitions", off, nparts, nq, probe, nprobe, host_counts ? ps->rows_union.data() : nullptr))) return st;
+  PartList wl;
+  if ((st = parts_worklist(c, "search_partitions", off, nparts, 0, nq, nprobe, PART_WAVES * qw_max, k, wl))) return st;
+  if (host_counts)
+    for (uint32_t q = 0; q < nq; ++q) out_counts[q] = static_cast<uint32_t>(std::min<uint64_t>(k, ps->rows_union[q]));
+  const uint64_t total = wl.total, rows_read = wl.rows_read;
+
+  // device workspace (grow-only) and the pinned image of the work list: [items | qidx | dst | cbeg | masked: mask_of]
+  const size_t qbytes = static_cast<size_t>(nq) * c->dim * 4, ob_ids = static_cast<size_t>(nq) * k * 8, ob_sc = static_cast<size_t>(nq) * k * 4;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((st = ensure(c, ps->cand, std::max<size_t>(total, 1) * sizeof(Cand)))) return st;
+  if ((st = ensure(c, ps->q, qbytes))) return st;
+  if ((st = ensure(c, ps->out_ids, ob_ids))) return st;
+  if ((st = ensure(c, ps->out_scores, ob_sc))) return st;
+  if (msel && (st = ensure(c, ps->out_counts, static_cast<size_t>(nq) * 4))) return st;
+  PartImage im;
+  if ((st = parts_stage(c, wl, nq, msel, nullptr, 0, im))) return st;
+  hipStream_t s = c->stream;
+  const PartItem* d_items = im.items;
+  const uint32_t *d_qidx = im.qidx, *d_dst = im.dst, *d_cbeg = im.cbeg;
+  const PartMask mk = im.mk;
   uint32_t* d_counts = msel ? static_cast<uint32_t*>(ps->out_counts.p) : nullptr;
   if (timing) HIPCHK(c, hipEventRecord(ps->ev[0], s));
-  HIPCHK(c, hipMemcpyAsync(ps->meta.p, pin, meta_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(ps->meta.p, ps->pin, im.bytes, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(ps->q.p, queries, qbytes, hipMemcpyHostToDevice, s));
   if (timing) HIPCHK(c, hipEventRecord(ps->ev[1], s));
   uint32_t launches = 0;
@@ -303,13 +350,6 @@ void pad_outputs(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, 
   if (out_counts) for (uint32_t q = 0; q < nq; ++q) out_counts[q] = 0;
 }
 
-// a masked call's mask_of against the resident planes (before anything is launched)
-nvdb_status mask_args(nvdb_hip_ctx* c, const uint32_t* mask_of, uint32_t nq, const char* who) {
-  if (c->nmasks == 0) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no row masks (nvdb_hip_set_row_masks)");
-  if (!rm_mask_of_valid(mask_of, nq, c->nmasks)) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": mask_of entry names a mask >= nmasks");
-  return NVDB_OK;
-}
-
 // nvdb_hip_search_partitions and its masked twin (msel != nullptr)
 nvdb_status search_partitions_any(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe, uint32_t nprobe,
                                   const MaskSel* msel, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
@@ -340,20 +380,9 @@ nvdb_status search_ivf_any(nvdb_hip_ctx* c, const char* who, const float* querie
   if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
   if (msel && (st = mask_args(c, msel->mask_of, nq, who))) return st;
   if (nprobe == 0) { pad_outputs(nq, k, out_ids, out_scores, out_counts); return NVDB_OK; }
+  uint32_t np = 0;
+  if ((st = parts_coarse(c, who, queries, nq, nprobe, out_probe, timing, np))) return st;
   const uint32_t nparts = static_cast<uint32_t>(ps->offsets.size() - 1);
-  const uint32_t np = std::min(nprobe, nparts);                            // the clamp; out_probe keeps the caller's row length
-  // coarse step: the flat search over the centroids (its order: score desc, partition number asc)
-  ps->coarse_ids.resize(static_cast<size_t>(nq) * np);
-  ps->coarse_scores.resize(static_cast<size_t>(nq) * np);
-  nvdb_hip_timing ct;
-  if ((st = nvdb_hip_search_batch(ps->coarse, queries, nq, np, ps->coarse_ids.data(), ps->coarse_scores.data(), nullptr, timing ? &ct : nullptr)))
-    return fail(c, st, std::string(who) + " (coarse step): " + nvdb_hip_last_error(ps->coarse));
-  ps->probe_tmp.resize(static_cast<size_t>(nq) * np);
-  for (size_t i = 0; i < ps->probe_tmp.size(); ++i) ps->probe_tmp[i] = static_cast<uint32_t>(ps->coarse_ids[i]);
-  if (out_probe)
-    for (uint32_t q = 0; q < nq; ++q)
-      for (uint32_t j = 0; j < nprobe; ++j) out_probe[static_cast<size_t>(q) * nprobe + j] = j < np ? ps->probe_tmp[static_cast<size_t>(q) * np + j] : 0xFFFFFFFFu;
-  if (timing) { timing->h2d_ms = ct.h2d_ms; timing->kernel_ms = ct.kernel_ms; timing->d2h_ms = ct.d2h_ms; }
   return parts_search(c, ps->offsets.data(), nparts, queries, nq, k, ps->probe_tmp.data(), np, msel, out_ids, out_scores, out_counts, timing);
 }
 
@@ -483,7 +512,7 @@ nvdb_status nvdb_hip_search_batch_masked(nvdb_hip_ctx* c, const float* queries, 
   if (k > WAVE_KMAX) return fail(c, NVDB_ERR_UNSUPPORTED, "search_batch_masked: k <= 64 (wavefront-resident lists)");
   if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
   if (nvdb_status st = mask_args(c, mask_of, nq, "search_batch_masked")) return st;
-  if (!c->parts) c->parts = new PartState();       // the workspace only: no table is set, a table that is set stays as it is
+  parts_workspace(c);                              // the workspace only: no table is set, a table that is set stays as it is
   // the corpus as one implicit partition that every query probes
   const uint64_t off[2] = {0, c->n};
   c->parts->probe_tmp.assign(nq, 0u);

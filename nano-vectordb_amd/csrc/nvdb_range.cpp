@@ -5,16 +5,17 @@
 //   exact route   score matrix of a query sub-batch (the any-k path's) -> count -> collect -> sort -> emit; serves every dtype / dim,
 //                 option path = 1, and the queries the filter route could not answer (flagged: non-finite query or radius, list overflow;
 //                 all of them after a wave-log overflow or a bound violation)
+// nvdb_hip_range_search_masked is the same call under a row-mask plane per query: on the filter route only the keep step differs
+// (range_keep_masked_kernel; thresholds are fixed, so a dead row costs a list entry and nothing else), and what the exact route would
+// answer goes to the partition range scan of nvdb_range_parts.cpp instead, the corpus as one implicit partition.
 // The exclusive scan of the per-query counts runs on the HOST over the downloaded counts: the call is synchronous and has to bring the
 // counts down for out_lims anyway, and the packed arrays are sized from them before anything is written.
-#include "nvdb_ctx.h"
-#include "kernels_range.h"
+#include "nvdb_range.h"
+#include "kernels_range_parts.h"
 
 namespace nvdbhip {
 
 namespace {
-
-constexpr uint32_t RANGE_STAT_FILTER = 5, RANGE_STAT_EXACT = 6;     // nvdb_hip_scan_stats::path
 
 struct RangePlan {
   const char* error = nullptr;
@@ -60,45 +61,6 @@ nvdb_status plan_range(nvdb_hip_ctx& ctx, uint32_t nq, RangePlan& p) {
   // permuted tile order spreads a clustered corpus' survivors over the waves' logs; only where the streaming kernel's tile is the
   // plan's tile (dims <= 768), as for the flat search
   p.perm_on = c->opt_tile_permute && c->fdim <= 768;
-  return NVDB_OK;
-}
-
-// grow a packed result array, keeping what it holds
-nvdb_status grow_keep(nvdb_hip_ctx* c, hipStream_t s, DevBuf& b, size_t bytes, size_t limit_bytes) {
-  if (b.p && b.bytes >= bytes) return NVDB_OK;
-  const size_t want = std::max<size_t>(std::max(bytes, std::min(bytes + bytes / 2, limit_bytes)), static_cast<size_t>(1) << 20);
-  void* np = nullptr;
-  HIPCHK(c, hipMalloc(&np, want));
-  if (b.p) {
-    HIPCHK(c, hipMemcpyAsync(np, b.p, b.bytes, hipMemcpyDeviceToDevice, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, hipFree(b.p));
-  }
-  b.p = np; b.bytes = want;
-  return NVDB_OK;
-}
-
-// the packed arrays of one call: how far they are filled, and whether the call still packs (false: over budget, counting only)
-struct RangeOut {
-  uint64_t budget_entries = 0;
-  bool pack = true;
-};
-
-// room for `end` entries; false: the budget is exceeded (from here on the call only counts), or *st
-bool reserve_packed(nvdb_hip_ctx* c, hipStream_t s, RangeOut& out, uint64_t end, nvdb_status* st) {
-  *st = NVDB_OK;
-  if (!out.pack) return false;
-  if (end > out.budget_entries) { out.pack = false; return false; }
-  if ((*st = grow_keep(c, s, c->rg_ids, static_cast<size_t>(end) * 8, static_cast<size_t>(out.budget_entries) * 8))) return false;
-  if ((*st = grow_keep(c, s, c->rg_scores, static_cast<size_t>(end) * 4, static_cast<size_t>(out.budget_entries) * 4))) return false;
-  return true;
-}
-
-template <typename T>
-nvdb_status upload(nvdb_hip_ctx* c, hipStream_t s, DevBuf& b, const std::vector<T>& v) {
-  if (nvdb_status st = ensure(c, b, v.size() * sizeof(T))) return st;
-  HIPCHK(c, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipStreamSynchronize(s));       // (the vector may go away; earlier kernels that read the buffer have finished)
   return NVDB_OK;
 }
 
@@ -191,7 +153,9 @@ struct FilterVerdict {
 };
 
 // ---- filter route of one sub-batch: everything up to the ordered slabs in c->cand and their counts in c->rg_kept
-nvdb_status range_filter_pass(nvdb_hip_ctx* c, hipStream_t s, const RangePlan& p, const float* dq, const float* dradius, uint32_t nq, FilterVerdict& v) {
+// dmask_of != nullptr: the masked search -- the keep step also requires the row's bit in the query's plane (everything before it is the unmasked pass)
+nvdb_status range_filter_pass(nvdb_hip_ctx* c, hipStream_t s, const RangePlan& p, const float* dq, const float* dradius, uint32_t nq, const uint32_t* dmask_of,
+                              FilterVerdict& v) {
   nvdb_status st;
   const uint32_t n = static_cast<uint32_t>(c->n), cap = p.cap, QT = p.QT;
   const size_t per_q = static_cast<size_t>(p.nq_pad) * 4;
@@ -228,9 +192,16 @@ nvdb_status range_filter_pass(nvdb_hip_ctx* c, hipStream_t s, const RangePlan& p
   if ((st = launch_rescore(c, s, dq, nq, cap))) return st;          // exact scores into the lists, |filter - exact| <= E_q checked
   uint32_t cap2 = 1;
   while (cap2 < cap) cap2 <<= 1;
-  if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(range_keep_kernel), SELECT_MAX_CAP * sizeof(Cand)))) return st;
-  range_keep_kernel<<<nq, 256, cap2 * sizeof(Cand), s>>>(static_cast<Cand*>(c->cand.p), static_cast<const uint32_t*>(c->cnt.p), cap, dradius,
-                                                         static_cast<const uint32_t*>(c->overflow.p), static_cast<uint32_t*>(c->rg_kept.p));
+  if (dmask_of) {
+    if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(range_keep_masked_kernel), SELECT_MAX_CAP * sizeof(Cand)))) return st;
+    range_keep_masked_kernel<<<nq, 256, cap2 * sizeof(Cand), s>>>(static_cast<Cand*>(c->cand.p), static_cast<const uint32_t*>(c->cnt.p), cap, dradius,
+                                                                  static_cast<const uint32_t*>(c->overflow.p), static_cast<uint32_t*>(c->rg_kept.p), dmask_of,
+                                                                  static_cast<const uint32_t*>(c->row_masks.p), static_cast<uint32_t>(rm_words(c->n)), n);
+  } else {
+    if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(range_keep_kernel), SELECT_MAX_CAP * sizeof(Cand)))) return st;
+    range_keep_kernel<<<nq, 256, cap2 * sizeof(Cand), s>>>(static_cast<Cand*>(c->cand.p), static_cast<const uint32_t*>(c->cnt.p), cap, dradius,
+                                                           static_cast<const uint32_t*>(c->overflow.p), static_cast<uint32_t*>(c->rg_kept.p));
+  }
   HIPCHK(c, hipGetLastError());
   v.kept.resize(nq); v.overflow.resize(nq); v.listcnt.resize(nq);
   HIPCHK(c, hipMemcpyAsync(v.misc, c->misc.p, 32, hipMemcpyDeviceToHost, s));
@@ -243,14 +214,14 @@ nvdb_status range_filter_pass(nvdb_hip_ctx* c, hipStream_t s, const RangePlan& p
 
 }  // namespace
 
-}  // namespace nvdbhip
-
-extern "C" {
-
-nvdb_status nvdb_hip_range_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, const float* radius, uint64_t* out_lims, nvdb_hip_timing* timing) {
+nvdb_status range_search_flat(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, const float* radius, const MaskSel* msel, uint64_t* out_lims,
+                              nvdb_hip_timing* timing) {
   if (!c) return NVDB_ERR_INVALID;
-  if (!out_lims || (nq > 0 && (!queries || !radius))) return fail(c, NVDB_ERR_INVALID, !out_lims ? "range_search: null out_lims" : queries ? "range_search: null radius" : "Null query");
+  if (!out_lims || (nq > 0 && (!queries || !radius)))
+    return fail(c, NVDB_ERR_INVALID, !out_lims ? std::string(who) + ": null out_lims" : queries ? std::string(who) + ": null radius" : "Null query");
   if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
+  if (msel && nq > 0)                                               // (before anything is written or launched)
+    if (nvdb_status ms = mask_args(c, msel->mask_of, nq, who)) return ms;
   if (timing) std::memset(timing, 0, sizeof(*timing));
   out_lims[0] = 0;
   c->range_valid = false;
@@ -272,10 +243,16 @@ nvdb_status nvdb_hip_range_search(nvdb_hip_ctx* c, const float* queries, uint32_
   if ((st = zero_q32_pad(c, s, qbytes))) return st;
   HIPCHK(c, hipMemcpyAsync(c->q32.p, queries, qbytes, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->rg_radius.p, radius, static_cast<size_t>(nq) * 4, hipMemcpyHostToDevice, s));
+  std::vector<uint32_t> mask_host;                                  // masked: every query's plane, NULL resolved to plane 0
+  if (msel) {
+    mask_host.assign(nq, 0u);
+    if (msel->mask_of) std::copy(msel->mask_of, msel->mask_of + nq, mask_host.begin());
+    if ((st = upload(c, s, c->rg_maskof, mask_host))) return st;
+  }
   HIPCHK(c, hipEventRecord(e[1], s));
 
   c->stats = nvdb_hip_scan_stats{};
-  c->stats.path = RANGE_STAT_EXACT;
+  c->stats.path = msel ? RANGE_STAT_PARTS : RANGE_STAT_EXACT;
   c->stats_lazy = false;
   c->last_nq = 0; c->last_cap = 0; c->last_filter = false;           // (nvdb_hip_search_check describes flat searches)
   c->last_filter_kind = 0;
@@ -286,7 +263,8 @@ nvdb_status nvdb_hip_range_search(nvdb_hip_ctx* c, const float* queries, uint32_
   uint32_t violations = 0;
   FilterVerdict v;
   std::vector<uint64_t> cnt, off;
-  std::vector<uint32_t> flagged;
+  std::vector<uint32_t> flagged, fl_m, fl_probe;
+  std::vector<float> fl_q, fl_r;
   for (uint32_t q0 = 0; q0 < nq; q0 += 1024) {
     const uint32_t b = std::min<uint32_t>(1024u, nq - q0);
     const float* dq = static_cast<const float*>(c->q32.p) + static_cast<size_t>(q0) * c->dim;
@@ -298,7 +276,7 @@ nvdb_status nvdb_hip_range_search(nvdb_hip_ctx* c, const float* queries, uint32_
     if ((st = plan_range(*c, b, ps))) return fail(c, st, ps.error);
     if (ps.filter) {
       any_filter = true;
-      if ((st = range_filter_pass(c, s, ps, dq, dr, b, v))) return st;
+      if ((st = range_filter_pass(c, s, ps, dq, dr, b, msel ? static_cast<const uint32_t*>(c->rg_maskof.p) + q0 : nullptr, v))) return st;
       for (uint32_t q = 0; q < b; ++q) c->stats.candidates += std::min(v.listcnt[q], ps.cap);
       c->stats.bound_violations += v.misc[0];
       violations += v.misc[0];
@@ -313,7 +291,7 @@ nvdb_status nvdb_hip_range_search(nvdb_hip_ctx* c, const float* queries, uint32_
         }
         c->stats.overflow_queries += static_cast<uint32_t>(flagged.size());
       }
-      if (!flagged.empty() && flagged.size() < b) {
+      if (!msel && !flagged.empty() && flagged.size() < b) {
         // the flagged queries as a compact batch (64 zero rows behind it: the exact kernels load whole query groups)
         const size_t qb = flagged.size() * static_cast<size_t>(c->dim) * 4, padb = 64 * static_cast<size_t>(c->dim) * 4;
         if ((st = ensure(c, c->rg_q, qb + padb + flagged.size() * 4 + 256))) return st;
@@ -328,7 +306,24 @@ nvdb_status nvdb_hip_range_search(nvdb_hip_ctx* c, const float* queries, uint32_
     } else {
       for (uint32_t q = 0; q < b; ++q) flagged.push_back(q);
     }
-    if (!flagged.empty() && (st = range_exact(c, s, dq, dr, static_cast<uint32_t>(flagged.size()), flagged, cnt, total, out))) return st;
+    if (!flagged.empty() && msel) {
+      // masked: the flagged queries on the partition range scan, the corpus as one implicit partition that each of them probes
+      const uint32_t nf = static_cast<uint32_t>(flagged.size());
+      fl_q.resize(static_cast<size_t>(nf) * c->dim);
+      fl_r.resize(nf);
+      fl_m.resize(nf);
+      for (uint32_t i = 0; i < nf; ++i) {
+        const size_t src = static_cast<size_t>(q0) + flagged[i];
+        std::memcpy(fl_q.data() + static_cast<size_t>(i) * c->dim, queries + src * c->dim, static_cast<size_t>(c->dim) * 4);
+        fl_r[i] = radius[src];
+        fl_m[i] = mask_host[src];
+      }
+      fl_probe.assign(nf, 0u);
+      const uint64_t whole[2] = {0, c->n};
+      const MaskSel fsel{fl_m.data()};
+      parts_workspace(c);
+      if ((st = range_parts_core(c, s, who, whole, 1, fl_q.data(), fl_r.data(), nf, fl_probe.data(), 1, &fsel, flagged.data(), cnt, total, out))) return st;
+    } else if (!flagged.empty() && (st = range_exact(c, s, dq, dr, static_cast<uint32_t>(flagged.size()), flagged, cnt, total, out))) return st;
     off.assign(b, 0);
     uint64_t run = total;
     uint32_t max_kept = 0;
@@ -359,12 +354,27 @@ nvdb_status nvdb_hip_range_search(nvdb_hip_ctx* c, const float* queries, uint32_
     timing->threads = 256; timing->nwarps = 4;
   }
   if (!out.pack)
-    return fail(c, NVDB_ERR_UNSUPPORTED, "range_search: " + std::to_string(total) + " results (" + std::to_string((total * 12 + (1u << 20) - 1) >> 20) +
+    return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": " + std::to_string(total) + " results (" + std::to_string((total * 12 + (1u << 20) - 1) >> 20) +
                                             " MB packed) exceed option range_max_mb = " + std::to_string(c->opt_range_max_mb) + "; out_lims is complete");
   c->range_total = total;
   c->range_valid = true;
-  if (violations) return fail(c, NVDB_ERR_INTERNAL, "filter error bound violated; results were recomputed on the exact route");
+  if (violations) return fail(c, NVDB_ERR_INTERNAL, msel ? "filter error bound violated; results were recomputed on the partition range scan"
+                                                         : "filter error bound violated; results were recomputed on the exact route");
   return NVDB_OK;
+}
+
+}  // namespace nvdbhip
+
+extern "C" {
+
+nvdb_status nvdb_hip_range_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, const float* radius, uint64_t* out_lims, nvdb_hip_timing* timing) {
+  return range_search_flat(c, "range_search", queries, nq, radius, nullptr, out_lims, timing);
+}
+
+nvdb_status nvdb_hip_range_search_masked(nvdb_hip_ctx* c, const float* queries, uint32_t nq, const float* radius, const uint32_t* mask_of, uint64_t* out_lims,
+                                         nvdb_hip_timing* timing) {
+  const MaskSel msel{mask_of};
+  return range_search_flat(c, "range_search_masked", queries, nq, radius, &msel, out_lims, timing);
 }
 
 nvdb_status nvdb_hip_range_results(nvdb_hip_ctx* c, uint64_t* out_ids, float* out_scores) {

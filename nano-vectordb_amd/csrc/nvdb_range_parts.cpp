@@ -1,0 +1,259 @@
+// nvdb_range_parts.cpp -- range search on the probe path (DESIGN.md section 4 "range search"): every row of a query's probed
+// partitions that is live in its mask and whose reference-order score reaches its radius.  Per sub-batch of queries:
+//   work list     parts_worklist (nvdb_partitions.cpp) with uncapped slots: an (item, query) slab holds as many entries as its segment has rows
+//   scan          range_parts_kernel appends Cand{score, row} to the slabs and pads them (kernels_range_parts.h)
+//   tail          count per query -> host: exclusive scan, slab classes (range_plan.h) -> collect keys (score, position) -> launch_sort_keys -> emit
+// The host cuts a batch into consecutive query sub-batches whose candidate blocks stay within half of largek_budget_mb (the other
+// half is the key slabs') and below 2^32 entries (rp_cut); packed results are appended in query order, so the caller never sees the cut.
+// Entry points: nvdb_hip_range_search_partitions / nvdb_hip_range_search_ivf; nvdb_hip_range_search_masked (nvdb_range.cpp) sends
+// what its filter route cannot answer here, the corpus as one implicit partition.
+#include "nvdb_range.h"
+#include "kernels_range_parts.h"
+#include "range_plan.h"
+
+namespace nvdbhip {
+
+namespace {
+
+struct ScanArgs {
+  const PartItem* items; uint32_t nitems; const uint32_t* qidx; const uint32_t* dst; const float* q32; const float* radius; Cand* cand; PartMask mk;
+};
+
+template <int DT, int QW, bool AL, bool ST, bool MK>
+nvdb_status launch_one(nvdb_hip_ctx* c, hipStream_t s, const ScanArgs& a) {
+  const size_t lds = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), QW, ST);
+  if (lds > 64 * 1024)
+    if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(range_parts_kernel<DT, QW, AL, ST, MK>), PART_LDS_LIMIT)) return st;
+  range_parts_kernel<DT, QW, AL, ST, MK><<<a.nitems, PART_THREADS, lds, s>>>(c->rows, c->scales, c->dim, a.items, a.qidx, a.dst, a.q32, a.radius, a.cand, a.mk);
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+template <int DT, int QW, bool AL, bool ST>
+nvdb_status launch_mk(nvdb_hip_ctx* c, hipStream_t s, const ScanArgs& a) {
+  return a.mk.mask_of ? launch_one<DT, QW, AL, ST, true>(c, s, a) : launch_one<DT, QW, AL, ST, false>(c, s, a);
+}
+
+template <int DT, int QW>
+nvdb_status launch_qw(nvdb_hip_ctx* c, hipStream_t s, bool staged, const ScanArgs& a) {
+  if (staged) return launch_mk<DT, QW, true, true>(c, s, a);
+  if (aligned_rows(c->dtype, c->dim)) return launch_mk<DT, QW, true, false>(c, s, a);
+  return launch_mk<DT, QW, false, false>(c, s, a);
+}
+
+template <int DT>
+nvdb_status launch_dt(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const ScanArgs& a) {
+  if (qw == 4) return launch_qw<DT, 4>(c, s, staged, a);
+  if (qw == 2) return launch_qw<DT, 2>(c, s, staged, a);
+  return launch_qw<DT, 1>(c, s, staged, a);
+}
+
+nvdb_status launch_range_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const ScanArgs& a) {
+  if (c->dtype == NVDB_DTYPE_F32) return launch_dt<DT_F32>(c, s, qw, staged, a);
+  if (c->dtype == NVDB_DTYPE_F16) return launch_dt<DT_F16>(c, s, qw, staged, a);
+  return launch_dt<DT_I8>(c, s, qw, staged, a);
+}
+
+constexpr uint32_t RUN_MAX_SLABS = 32768;          // a run's slabs are the y dimension of its collect / sort / emit grids
+
+}  // namespace
+
+nvdb_status range_parts_core(nvdb_hip_ctx* c, hipStream_t s, const char* who, const uint64_t* off, uint32_t nparts, const float* queries, const float* radius,
+                             uint32_t nr, const uint32_t* probe, uint32_t nprobe, const MaskSel* msel, const uint32_t* qmap, std::vector<uint64_t>& cnt,
+                             uint64_t base, RangeOut& out) {
+  PartState* ps = c->parts;
+  const PartBuild pb = parts_build(c);
+  if (!pb.qw_max) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": dim too large for the query staging");
+  nvdb_status st;
+
+  // every query's block: the rows of its probed union (and the probe table's check, before anything is launched)
+  std::vector<uint64_t> block(nr, 0);
+  if ((st = parts_probes(c, who, off, nparts, nr, probe, nprobe, block.data()))) return st;
+  // largek_budget_mb bounds what a launch set holds: half of it for the candidate blocks, half for the key slabs of a run (a single
+  // query's block, or a single slab, is taken whatever the budget says: neither can be cut)
+  const uint64_t budget_entries = (static_cast<uint64_t>(c->opt_largek_budget_mb) << 20) / (2 * sizeof(Cand));
+  const uint64_t slab_max = budget_entries;
+  auto qnum = [&](uint32_t i) { return qmap ? qmap[i] : i; };
+  uint32_t pos = 0;                                  // cnt[0 .. pos) are summed in `before`
+  uint64_t before = 0;
+  std::vector<uint32_t> hc;
+  std::vector<uint64_t> out_off;
+  std::vector<RpSlab> slabs;
+  std::vector<uint32_t> run_end;
+  std::vector<RangeDesc> run;
+  for (uint32_t q0 = 0; q0 < nr;) {
+    const uint32_t q1 = rp_cut(block.data(), nr, q0, budget_entries);
+    if (q1 == q0) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": one query's probed union holds 2^32 rows or more");
+    const uint32_t b = q1 - q0;
+    PartList wl;
+    if ((st = parts_worklist(c, who, off, nparts, q0, b, nprobe, PART_WAVES * pb.qw_max, 0xFFFFFFFFu, wl))) return st;
+    hc.assign(b, 0u);
+    PartImage im;
+    if (wl.total) {
+      const size_t qbytes = static_cast<size_t>(b) * c->dim * 4;
+      if ((st = ensure(c, ps->cand, static_cast<size_t>(wl.total) * sizeof(Cand)))) return st;
+      if ((st = ensure(c, ps->q, qbytes))) return st;
+      if ((st = ensure(c, c->rg_pcnt, static_cast<size_t>(b) * 4))) return st;
+      const MaskSel sub{msel && msel->mask_of ? msel->mask_of + q0 : nullptr};
+      if ((st = parts_stage(c, wl, b, msel ? &sub : nullptr, reinterpret_cast<const uint32_t*>(radius + q0), b, im))) return st;
+      HIPCHK(c, hipMemcpyAsync(ps->meta.p, ps->pin, im.bytes, hipMemcpyHostToDevice, s));
+      HIPCHK(c, hipMemcpyAsync(ps->q.p, queries + static_cast<size_t>(q0) * c->dim, qbytes, hipMemcpyHostToDevice, s));
+      const PartItem* it = im.items;
+      for (int cl = 2; cl >= 0; --cl) {
+        const uint32_t n_cl = static_cast<uint32_t>(ps->items[cl].size());
+        if (!n_cl) continue;
+        const ScanArgs a{it, n_cl, im.qidx, im.dst, static_cast<const float*>(ps->q.p), reinterpret_cast<const float*>(im.extra), static_cast<Cand*>(ps->cand.p), im.mk};
+        if ((st = launch_range_parts(c, s, std::min<uint32_t>(pb.qw_max, 1u << cl), pb.staged, a))) return st;
+        it += n_cl;
+        c->stats.chunks++;
+      }
+      rparts_count_kernel<<<b, 256, 0, s>>>(static_cast<const Cand*>(ps->cand.p), im.cbeg, static_cast<uint32_t*>(c->rg_pcnt.p));
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(hc.data(), c->rg_pcnt.p, static_cast<size_t>(b) * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(c, hipStreamSynchronize(s));            // (also: the pinned image and the host vectors are free for the next sub-batch)
+      c->stats.rows_scanned += wl.rows_read;
+    }
+    // the slices' places in the packed arrays: behind every earlier query of the caller's sub-batch
+    out_off.assign(b, 0);
+    for (uint32_t i = 0; i < b; ++i) {
+      const uint32_t qn = qnum(q0 + i);
+      cnt[qn] = hc[i];
+      c->stats.candidates += hc[i];
+      while (pos < qn) before += cnt[pos++];
+      out_off[i] = base + before;
+    }
+    while (pos <= qnum(q1 - 1)) before += cnt[pos++];
+    q0 = q1;
+    if (!wl.total) continue;
+    if (!reserve_packed(c, s, out, base + before, &st)) { if (st) return st; continue; }
+    if (!rp_slab_runs(hc.data(), b, slab_max, RUN_MAX_SLABS, slabs, run_end)) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 results for one query");
+    size_t r0 = 0;
+    for (const uint32_t r1 : run_end) {
+      run.clear();
+      uint32_t max_cnt = 0, max_len = 0;
+      for (size_t i = r0; i < r1; ++i) {
+        run.push_back(RangeDesc{slabs[i].slab_off, out_off[slabs[i].q], slabs[i].q, slabs[i].cnt, static_cast<uint32_t>(slabs[i].K2), 0u});
+        max_cnt = std::max(max_cnt, slabs[i].cnt);
+        max_len = std::max(max_len, ps->cbeg[slabs[i].q + 1] - ps->cbeg[slabs[i].q]);
+      }
+      const uint64_t keys = slabs[r1 - 1].slab_off + slabs[r1 - 1].K2;
+      const uint32_t nrun = static_cast<uint32_t>(run.size());
+      if ((st = ensure(c, c->rg_slab, static_cast<size_t>(keys) * 8))) return st;
+      if ((st = ensure(c, c->rg_taken, static_cast<size_t>(nrun) * 4))) return st;
+      if ((st = upload(c, s, c->rg_desc, run))) return st;
+      const RangeDesc* desc = static_cast<const RangeDesc*>(c->rg_desc.p);
+      unsigned long long* slab = static_cast<unsigned long long*>(c->rg_slab.p);
+      uint32_t* taken = static_cast<uint32_t*>(c->rg_taken.p);
+      HIPCHK(c, hipMemsetAsync(taken, 0, static_cast<size_t>(nrun) * 4, s));
+      const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>((max_len + 1023u) / 1024u, (8u * static_cast<uint32_t>(c->num_cu) + nrun - 1) / nrun));
+      rparts_collect_kernel<<<dim3(G, nrun), 256, 0, s>>>(static_cast<const Cand*>(ps->cand.p), im.cbeg, desc, taken, slab);
+      HIPCHK(c, hipGetLastError());
+      for (uint32_t a = 0; a < nrun;) {
+        uint32_t e = a;
+        while (e < nrun && run[e].K2 == run[a].K2) ++e;
+        if ((st = launch_sort_keys(c, s, slab + run[a].slab_off, run[a].K2, e - a))) return st;
+        a = e;
+      }
+      rparts_emit_kernel<<<dim3((max_cnt + 255u) / 256u, nrun), 256, 0, s>>>(slab, desc, static_cast<const Cand*>(ps->cand.p), im.cbeg, c->row_base,
+                                                                            static_cast<unsigned long long*>(c->rg_ids.p), static_cast<float*>(c->rg_scores.p));
+      HIPCHK(c, hipGetLastError());
+      r0 = r1;
+    }
+    HIPCHK(c, hipStreamSynchronize(s));              // the next sub-batch rewrites the blocks, the image and the descriptors
+  }
+  return NVDB_OK;
+}
+
+namespace {
+
+// the probe forms' driver: the arguments are validated, nq > 0 and nprobe > 0
+nvdb_status range_parts_search(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, const float* radius, const uint32_t* probe, uint32_t nprobe,
+                               const MaskSel* msel, uint64_t* out_lims, nvdb_hip_timing* timing) {
+  PartState* ps = c->parts;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const hipEvent_t e[2] = {get_event(c, 60), get_event(c, 62)};
+  HIPCHK(c, hipEventRecord(e[0], s));
+  c->stats = nvdb_hip_scan_stats{};
+  c->stats.path = RANGE_STAT_PARTS;
+  c->stats_lazy = false;
+  c->last_nq = 0; c->last_cap = 0; c->last_filter = false;           // (nvdb_hip_search_check describes flat searches)
+  c->last_filter_kind = 0;
+  RangeOut out;
+  out.budget_entries = (static_cast<uint64_t>(c->opt_range_max_mb) << 20) / 12;
+  std::vector<uint64_t> cnt(nq, 0);
+  if (nvdb_status st = range_parts_core(c, s, who, ps->offsets.data(), static_cast<uint32_t>(ps->offsets.size() - 1), queries, radius, nq, probe, nprobe, msel, nullptr,
+                                        cnt, 0, out))
+    return st;
+  const uint64_t total = rp_scan(cnt.data(), nq, 0, nullptr, out_lims + 1);
+  HIPCHK(c, hipEventRecord(e[1], s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (timing) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e[0], e[1]);
+    timing->kernel_ms += ms;                                         // (the work list's and the queries' copies ride inside: they alternate with the launches)
+    timing->total_ms = timing->h2d_ms + timing->kernel_ms + timing->d2h_ms;
+    timing->threads = PART_THREADS; timing->nwarps = PART_WAVES;
+    timing->shmem_bytes = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), parts_build(c).qw_max, parts_build(c).staged);
+  }
+  if (!out.pack)
+    return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": " + std::to_string(total) + " results (" + std::to_string((total * 12 + (1u << 20) - 1) >> 20) +
+                                            " MB packed) exceed option range_max_mb = " + std::to_string(c->opt_range_max_mb) + "; out_lims is complete");
+  c->range_total = total;
+  c->range_valid = true;
+  return NVDB_OK;
+}
+
+// what the two probe forms check alike; *done: the call is answered (an error, or a batch without queries / probes)
+nvdb_status range_parts_args(nvdb_hip_ctx* c, const char* who, bool ivf, const float* queries, uint32_t nq, const float* radius, uint32_t nprobe,
+                             const MaskSel* msel, uint64_t* out_lims, nvdb_hip_timing* timing, bool* done) {
+  *done = true;
+  if (!c) return NVDB_ERR_INVALID;
+  if (!out_lims || (nq > 0 && (!queries || !radius)))
+    return fail(c, NVDB_ERR_INVALID, !out_lims ? std::string(who) + ": null out_lims" : queries ? std::string(who) + ": null radius" : "Null query");
+  if (nvdb_status st = parts_args(c, who)) return st;
+  if (ivf && !c->parts->have_centroids) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no centroids (nvdb_hip_set_centroids)");
+  if (msel && nq > 0)
+    if (nvdb_status st = mask_args(c, msel->mask_of, nq, who)) return st;
+  if (timing) std::memset(timing, 0, sizeof(*timing));
+  out_lims[0] = 0;
+  c->range_valid = false;                                            // a new range search of any kind replaces the held result
+  c->range_total = 0;
+  if (nq == 0 || nprobe == 0) {
+    for (uint32_t q = 0; q < nq; ++q) out_lims[q + 1] = 0;
+    c->range_valid = true;
+    return NVDB_OK;
+  }
+  *done = false;
+  return NVDB_OK;
+}
+
+}  // namespace
+}  // namespace nvdbhip
+
+extern "C" {
+
+nvdb_status nvdb_hip_range_search_partitions(nvdb_hip_ctx* c, const float* queries, uint32_t nq, const float* radius, const uint32_t* probe, uint32_t nprobe,
+                                             const uint32_t* mask_of, int masked, uint64_t* out_lims, nvdb_hip_timing* timing) {
+  const char* who = "range_search_partitions";
+  const MaskSel msel{mask_of};
+  bool done;
+  nvdb_status st = range_parts_args(c, who, false, queries, nq, radius, nprobe, masked ? &msel : nullptr, out_lims, timing, &done);
+  if (st || done) return st;
+  if (!probe) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": null probe table");
+  return range_parts_search(c, who, queries, nq, radius, probe, nprobe, masked ? &msel : nullptr, out_lims, timing);
+}
+
+nvdb_status nvdb_hip_range_search_ivf(nvdb_hip_ctx* c, const float* queries, uint32_t nq, const float* radius, uint32_t nprobe, const uint32_t* mask_of, int masked,
+                                      uint64_t* out_lims, uint32_t* out_probe, nvdb_hip_timing* timing) {
+  const char* who = "range_search_ivf";
+  const MaskSel msel{mask_of};
+  bool done;
+  nvdb_status st = range_parts_args(c, who, true, queries, nq, radius, nprobe, masked ? &msel : nullptr, out_lims, timing, &done);
+  if (st || done) return st;
+  uint32_t np = 0;
+  if ((st = parts_coarse(c, who, queries, nq, nprobe, out_probe, timing, np))) return st;
+  return range_parts_search(c, who, queries, nq, radius, c->parts->probe_tmp.data(), np, masked ? &msel : nullptr, out_lims, timing);
+}
+
+}  // extern "C"

@@ -37,6 +37,8 @@ EXPORTS = [
     "nvdb_hip_set_row_masks", "nvdb_hip_update_row_mask", "nvdb_hip_get_row_masks", "nvdb_hip_search_partitions_masked",
     "nvdb_hip_search_ivf_masked", "nvdb_hip_search_batch_masked",
     "nvdb_hip_ivf_set_row_masks", "nvdb_hip_ivf_update_row_mask", "nvdb_hip_ivf_search_masked",
+    "nvdb_hip_range_search_partitions", "nvdb_hip_range_search_ivf", "nvdb_hip_range_search_masked",
+    "nvdb_hip_ivf_range_search", "nvdb_hip_ivf_range_results",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_filter_variant", "nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -202,6 +204,11 @@ def _bind(L, dev):
     L.nvdb_hip_ivf_set_row_masks.argtypes = [vp, vp, u32]
     L.nvdb_hip_ivf_update_row_mask.argtypes = [vp, u32, vp, u64, C.c_int]
     L.nvdb_hip_ivf_search_masked.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_range_search_partitions.argtypes = [vp, vp, u32, vp, vp, u32, vp, C.c_int, vp, C.POINTER(Timing)]
+    L.nvdb_hip_range_search_ivf.argtypes = [vp, vp, u32, vp, u32, vp, C.c_int, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_range_search_masked.argtypes = [vp, vp, u32, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_ivf_range_search.argtypes = [vp, vp, u32, vp, u32, vp, C.c_int, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_ivf_range_results.argtypes = [vp, vp, vp]
     for name in EXPORTS:
         getattr(L, name)
     if dev:
@@ -340,6 +347,29 @@ def _mask_of_arg(mask_of, nq):
     if mask_of is None:
         return None
     return np.ascontiguousarray(np.broadcast_to(np.asarray(mask_of, dtype=np.uint32), (nq,)))
+
+
+def _range_call(owner, last_error, results, call, queries, radius, mask_of, masked):
+    """The shape every range search shares: call(queries, nq, radius, mask_of pointer, masked flag, lims) -> status, then the packed
+    results through results(ids, scores).  masked None: masked iff mask_of is given (masked=True with mask_of None: plane 0)."""
+    queries = np.ascontiguousarray(queries, dtype=np.float32)
+    if queries.ndim == 1:
+        queries = queries[None, :]
+    nq = queries.shape[0]
+    radius = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)))
+    mo = _mask_of_arg(mask_of, nq)
+    masked = (mo is not None) if masked is None else bool(masked)
+    lims = np.zeros(nq + 1, dtype=np.uint64)
+    st = call(queries, nq, radius, mo.ctypes.data if mo is not None else None, 1 if masked else 0, lims)
+    if st:
+        err = NvdbError(st, last_error())
+        err.lims = lims
+        raise err
+    total = int(lims[nq])
+    ids = np.empty(max(total, 1), dtype=np.uint64)
+    scores = np.empty(max(total, 1), dtype=np.float32)
+    owner._chk(results(ids.ctypes.data, scores.ctypes.data))
+    return lims, ids[:total], scores[:total]
 
 
 # ------------------------------------------------------------------------------- device context
@@ -513,7 +543,7 @@ class HipContext:
                                                counts.ctypes.data, probe.ctypes.data if want_probe else None, None))
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
-    # -- row masks (top-k restricted to live rows on the probe-search path; search_batch and range_search are NOT masked)
+    # -- row masks (live rows only, for the *_masked searches and the range searches on the probe path; search_batch and range_search are NOT masked)
     def set_row_masks(self, masks):
         """masks: bool [nmasks, n] / packed uint32 [nmasks, ceil(n / 32)] (pack_row_masks); an int: that many all-live masks;
         None or 0: drop them."""
@@ -569,6 +599,37 @@ class HipContext:
                                                         ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
                                                         C.byref(t) if want_timing else None))
         return (ids, scores, counts, t) if want_timing else (ids, scores, counts)
+
+    # -- range search on the probe path (lims, ids, scores as range_search; over range_max_mb the NvdbError carries `.lims`)
+    def _range(self, call, queries, radius, mask_of, masked):
+        return _range_call(self, lambda: self.lib.nvdb_hip_last_error(self.h).decode(),
+                           lambda i, s: self.lib.nvdb_hip_range_results(self.h, i, s), call, queries, radius, mask_of, masked)
+
+    def range_search_partitions(self, queries, radius, probe, mask_of=None, masked=None):
+        """range_search over each query's probed partitions (probe as search_partitions), optionally restricted to the rows live in
+        its mask (mask_of as search_partitions_masked; masked=True with mask_of None: plane 0 for every query)."""
+        def call(q, nq, r, mo, masked_, lims):
+            pr = np.ascontiguousarray(probe, dtype=np.uint32).reshape(nq, -1)
+            return self.lib.nvdb_hip_range_search_partitions(self.h, q.ctypes.data, nq, r.ctypes.data, pr.ctypes.data, pr.shape[1], mo, masked_,
+                                                             lims.ctypes.data, None)
+        return self._range(call, queries, radius, mask_of, masked)
+
+    def range_search_ivf(self, queries, radius, nprobe, mask_of=None, masked=None, want_probe=False):
+        """range_search over the nprobe partitions with the best centroids (search_ivf's coarse step); (lims, ids, scores[, probe])."""
+        box = {}
+
+        def call(q, nq, r, mo, masked_, lims):
+            box["probe"] = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
+            return self.lib.nvdb_hip_range_search_ivf(self.h, q.ctypes.data, nq, r.ctypes.data, nprobe, mo, masked_, lims.ctypes.data,
+                                                      box["probe"].ctypes.data if want_probe else None, None)
+        out = self._range(call, queries, radius, mask_of, masked)
+        return out + (box["probe"],) if want_probe else out
+
+    def range_search_masked(self, queries, radius, mask_of=None):
+        """The masked flat range search: range_search over the rows live in each query's mask (mask_of None: plane 0)."""
+        def call(q, nq, r, mo, masked_, lims):
+            return self.lib.nvdb_hip_range_search_masked(self.h, q.ctypes.data, nq, r.ctypes.data, mo, lims.ctypes.data, None)
+        return self._range(call, queries, radius, mask_of, True)
 
     # -- IVF-Flat build
     def assign_rows(self, centroids, row0=0, nrows=None):
@@ -703,6 +764,19 @@ class IvfIndex:
                                                       ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
                                                       probe.ctypes.data if want_probe else None, None))
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
+
+    def range_search(self, queries, radius, nprobe, mask_of=None, masked=None, want_probe=False):
+        """Every row of the nprobe best lists whose score reaches the query's radius, optionally restricted to the rows live in its
+        mask (original-row planes) -> (lims, ids in the source corpus' ids, scores[, probe]); equal scores by (partition, original id)."""
+        box = {}
+
+        def call(q, nq, r, mo, masked_, lims):
+            box["probe"] = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
+            return self.lib.nvdb_hip_ivf_range_search(self.h, q.ctypes.data, nq, r.ctypes.data, nprobe, mo, masked_, lims.ctypes.data,
+                                                      box["probe"].ctypes.data if want_probe else None, None)
+        out = _range_call(self, lambda: self.lib.nvdb_hip_ivf_last_error(self.h).decode(),
+                          lambda i, s: self.lib.nvdb_hip_ivf_range_results(self.h, i, s), call, queries, radius, mask_of, masked)
+        return out + (box["probe"],) if want_probe else out
 
 
 class DeviceGroup:
