@@ -304,23 +304,107 @@ __device__ __forceinline__ void fold_sticky_words(uint32_t* any_overflow) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// One row against one query on EIGHT lanes: lane j8 of the group IS accumulator lane j8 of the reference kernels
+// (acc[j] += q[8i+j] * x[8i+j], i ascending -- simd_dot.cpp:31-36, 106-111; int8's two groups of 8 per iteration land in
+// the same accumulators in the same order, :164-190), then the (a0+a4)+(a1+a5) .. reduction across the eight lanes (fp32
+// addition is commutative, so every lane ends with the same bits) and the scalar tails.  The int8 row scale is the
+// caller's.  All eight lanes of a group must make the call together (the shuffles stay inside the group).  ONE routine for
+// rescore_lds_kernel and for the exact bar of the thresholding select: a bar is bit for bit a score the rescore produces.
+// ------------------------------------------------------------------------------------------------
+template <int DT>
+__device__ __forceinline__ float score8(const void* rp, const float* qptr, uint32_t dim, uint32_t j8) {
+  const uint32_t body = (DT == DT_I8) ? (dim & ~15u) : (dim & ~7u);
+  float acc = 0.f;
+#pragma unroll 8
+  for (uint32_t e = 0; e < body; e += 8) acc = __builtin_fmaf(qptr[e + j8], load1<DT>(rp, e + j8), acc);   // (uniform trip count)
+  float s = acc + __shfl_xor(acc, 4);
+  s = s + __shfl_xor(s, 1);
+  s = s + __shfl_xor(s, 2);
+  uint32_t t = body;
+  if (t < dim) {
+    if constexpr (DT == DT_F32) {
+      if (dim - t >= 4) {
+        for (int u = 0; u < 4; ++u) { const float p = qptr[t + u] * load1<DT>(rp, t + u); s = s + p; }
+        t += 4;
+      }
+    }
+    for (; t < dim; ++t) s = __builtin_fmaf(qptr[t], load1<DT>(rp, t), s);
+  }
+  return s;
+}
+
+// The thresholding select's exact bar (int8 shadow of an fp16 / fp32 corpus, option shadow_exact_thr): the rows the list's scores
+// only approximate, and what it takes to score them.  The rows' type is a template argument of the select (XDT: DT_F16, DT_F32;
+// 0: no exact bar, today's k-th list score - slack, the struct is not read).
+struct ExactBar {
+  const void* rows;                  // the corpus' own rows (fp16 or fp32), NOT what the filter streamed
+  const float* q32;                  // the queries, [nq][dim]
+  const float* ebound;               // per query: |list score - exact score| <= ebound; negative: non-finite query, no exact bar
+  uint32_t dim, n_rows;
+  uint32_t q_off;                    // bytes from the start of the select's dynamic LDS to the query staging area (past the list)
+};
+constexpr uint32_t EXACT_BAR_MAX = 2 * 64;   // entries re-scored per select: the best 2k of the list, k <= 64
+
+// B = the k-th largest EXACT score among the rows s_row[0, M) (M <= EXACT_BAR_MAX; rows >= n_rows are padding and never
+// scored); -inf when fewer than k of them are real.  k distinct rows already seen score >= B, so the final k-th best exact
+// score is >= B.  Every thread of the workgroup makes the call; the leading barrier also publishes s_row.
+template <int XDT>
+__device__ __forceinline__ float exact_kth(const ExactBar& xb, uint32_t q, float* qptr, const uint32_t* s_row, float* s_sc, float* s_B,
+                                           uint32_t M, uint32_t k, uint32_t tid, uint32_t nth) {
+  for (uint32_t j = tid; j < xb.dim; j += nth) qptr[j] = xb.q32[static_cast<uint64_t>(q) * xb.dim + j];
+  if (tid == 0) *s_B = NEG_INF;
+  __syncthreads();
+  const uint32_t j8 = tid & 7u, grp = tid >> 3, per = nth >> 3;
+  for (uint32_t base = 0; base < M; base += per) {
+    const uint32_t i = base + grp;
+    if (i >= M) continue;                                          // whole groups of 8 lanes leave together
+    const uint32_t row = s_row[i];
+    float s = NEG_INF;
+    if (row < xb.n_rows) s = score8<XDT>(row_ptr<XDT>(xb.rows, row, xb.dim), qptr, xb.dim, j8);
+    if (j8 == 0) s_sc[i] = (s == s) ? s : NEG_INF;                 // (a NaN score bounds nothing)
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < M; i += nth) {
+    const float si = s_sc[i];
+    uint32_t r = 0;
+    for (uint32_t j = 0; j < M; ++j) { const float sj = s_sc[j]; r += (sj > si || (sj == si && j < i)) ? 1u : 0u; }
+    if (r == k - 1) *s_B = si;
+  }
+  __syncthreads();
+  return *s_B;
+}
+
+// ------------------------------------------------------------------------------------------------
 // select: sort a query's candidate list (score desc, id asc) in LDS, then either
 //   mode 0: thr[q] = (k-th score) - slack[q]; keep every entry with score >= thr (all of the top-k
 //           plus whatever lies inside the filter's error band); write the list back compacted;
 //   mode 1: emit the final top-k (global ids, padded with UINT64_MAX / -inf).
 //   mode 2: like mode 0 but the list is emptied afterwards (thresholds from bootstrap tile maxima).
-// grid = nq, block = 64..256 (any multiple of 64), dynamic LDS = cap * 8 bytes.
+//   modes 0 and 2 with an ExactBar (the list's scores come from the int8 shadow): the best M = min(len, 2k) entries are re-scored
+//           from the original rows, B = the k-th largest of those exact scores, thr[q] = max(thr[q], B - ebound[q]) -- ONE error
+//           bound under an EXACT bar instead of two under a list score (every final top-k row has list score >= exact - ebound
+//           >= B - ebound).  Never lower than the bar above: the k best list entries are among the M, so B >= k-th list score -
+//           ebound.  Entries are still kept by their list scores.
+// grid = nq, block = 64..256 (any multiple of 64), dynamic LDS = cap * 8 bytes (+ one query of floats with an ExactBar).
 // ------------------------------------------------------------------------------------------------
 // The body works on ONE query with all `nth` threads of the calling workgroup and `e` = LDS for the list (cap rounded up to a
 // power of two entries): select_kernel calls it for blockIdx.x, and rescore_lds_kernel, which folds the final select into its
 // own tail, calls it too -- one implementation, one order.  Every thread of the workgroup must make the call.
+template <int XDT>
 __device__ __forceinline__ void select_body(
     const uint32_t q, const uint32_t tid, const uint32_t nth, Cand* e,
     Cand* __restrict__ cand, uint32_t* __restrict__ cnt, uint32_t cap, uint32_t k, const float* __restrict__ slack,
     float* __restrict__ thr, uint32_t* __restrict__ overflow, int mode, uint64_t row_base,
     unsigned long long* __restrict__ out_ids, float* __restrict__ out_scores, uint32_t out_k, uint32_t* __restrict__ any_overflow,
-    float* __restrict__ xcdw, bool fold_sticky) {
+    float* __restrict__ xcdw, bool fold_sticky, const ExactBar& xb_in) {
+  // The exact bar's pointers live in VECTOR registers from here on: as kernel arguments they would sit in SGPRs through the whole
+  // body, and the select with a bar then parks scalar registers in VGPR lanes (tests/test_codegen_resources.py allows no new ones).
+  ExactBar xb = xb_in;
+  if constexpr (XDT != 0) asm volatile("" : "+v"(xb.rows), "+v"(xb.q32), "+v"(xb.ebound), "+v"(xb.n_rows), "+v"(xb.q_off));
   __shared__ uint32_t s_keep;
+  __shared__ uint32_t s_xrow[XDT != 0 ? EXACT_BAR_MAX : 1];
+  __shared__ float s_xsc[XDT != 0 ? EXACT_BAR_MAX : 1], s_xB;
+  float* xq = reinterpret_cast<float*>(reinterpret_cast<char*>(e) + (XDT != 0 ? xb.q_off : 0u));
   // XCD balance (kernels_filter.h, ScatterArgs::xcdw): the filter launch before this kernel filed tile-loop time and tile
   // counts per XCD label; turn them into the relative speeds the next launch partitions its tiles by.  Half-way steps,
   // a +-10 % cage and renormalisation to mean 1 keep one odd launch from skewing the shares.
@@ -400,9 +484,19 @@ __device__ __forceinline__ void select_body(
       return;
     }
     const float sl = slack ? slack[q] : 0.f;
-    // thresholds only ever rise: the previous one stays a valid lower bound of (k-th best - slack) when this list is
+    float bar = s_kth - sl;
+    if constexpr (XDT != 0) {
+      const float xeb = m >= k ? xb.ebound[q] : -1.f;
+      if (xeb >= 0.f) {                             // (workgroup-uniform)
+        const uint32_t M = m < 2 * k ? m : 2 * k;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) if (rk[u] < M) s_xrow[rk[u]] = my[u].row;
+        bar = exact_kth<XDT>(xb, q, xq, s_xrow, s_xsc, &s_xB, M, k, tid, nth) - xeb;
+      }
+    }
+    // thresholds only ever rise: the previous one stays a valid lower bound of the bar when this list is
     // shorter than k (s_kth = -inf) or its k-th entry is lower (bootstrap rows that are not part of the first chunk)
-    const float t = fmaxf(s_kth - sl, thr[q]);
+    const float t = fmaxf(bar, thr[q]);
     uint32_t local = 0;
 #pragma unroll
     for (int u = 0; u < 2; ++u) if (rk[u] != 0xFFFFFFFFu) local += (sl > 0.f ? (my[u].score >= t) : (rk[u] < k)) ? 1u : 0u;
@@ -442,7 +536,16 @@ __device__ __forceinline__ void select_body(
   }
   const float kth = (m >= k) ? e[k - 1].score : NEG_INF;
   const float sl = slack ? slack[q] : 0.f;
-  const float t = fmaxf(kth - sl, thr[q]);        // thresholds only ever rise (see the short-list path above)
+  float bar = kth - sl;
+  if constexpr (XDT != 0) {
+    const float xeb = m >= k ? xb.ebound[q] : -1.f;
+    if (xeb >= 0.f) {
+      const uint32_t M = m < 2 * k ? m : 2 * k;   // the sorted list's first M entries; the query is staged past the list's LDS
+      for (uint32_t i = tid; i < M; i += nth) s_xrow[i] = e[i].row;
+      bar = exact_kth<XDT>(xb, q, xq, s_xrow, s_xsc, &s_xB, M, k, tid, nth) - xeb;
+    }
+  }
+  const float t = fmaxf(bar, thr[q]);             // thresholds only ever rise (see the short-list path above)
   if (tid == 0) s_keep = 0;
   __syncthreads();
   uint32_t local = 0;
@@ -455,15 +558,16 @@ __device__ __forceinline__ void select_body(
   if (tid == 0) { cnt[q] = (mode == 2) ? 0u : keep; thr[q] = t; }
 }
 
-static __global__ __launch_bounds__(256) void select_kernel(
+template <int XDT>
+__global__ __launch_bounds__(256) void select_kernel(
     Cand* __restrict__ cand, uint32_t* __restrict__ cnt, uint32_t cap, uint32_t k, const float* __restrict__ slack,
     float* __restrict__ thr, uint32_t* __restrict__ overflow, int mode, uint64_t row_base,
     unsigned long long* __restrict__ out_ids, float* __restrict__ out_scores, uint32_t out_k, uint32_t* __restrict__ any_overflow,
-    float* __restrict__ xcdw) {
+    float* __restrict__ xcdw, ExactBar xb) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   // (every earlier kernel of the search has completed when this one runs: block 0 may fold the self-check words)
-  select_body(blockIdx.x, threadIdx.x, blockDim.x, reinterpret_cast<Cand*>(smem_raw), cand, cnt, cap, k, slack, thr, overflow, mode, row_base,
-              out_ids, out_scores, out_k, any_overflow, xcdw, blockIdx.x == 0);
+  select_body<XDT>(blockIdx.x, threadIdx.x, blockDim.x, reinterpret_cast<Cand*>(smem_raw), cand, cnt, cap, k, slack, thr, overflow, mode, row_base,
+              out_ids, out_scores, out_k, any_overflow, xcdw, blockIdx.x == 0, xb);
 }
 
 // one launch that resets all per-search words: list lengths, overflow flags, thresholds (-inf), self-check words
@@ -601,7 +705,6 @@ __global__ __launch_bounds__(256) void rescore_lds_kernel(
   const float eb = ebound ? ebound[q] : 0.f;
   Cand* mine = cand + static_cast<uint64_t>(q) * cap;
   const uint32_t j8 = tid & 7u, grp = tid >> 3;
-  const uint32_t body = (DT == DT_I8) ? (dim & ~15u) : (dim & ~7u);
   for (uint32_t base = 0; base < m; base += cpp) {
     const uint32_t nrows = (m - base < cpp) ? m - base : cpp;
     __syncthreads();                                               // previous pass has finished with the slots
@@ -615,24 +718,7 @@ __global__ __launch_bounds__(256) void rescore_lds_kernel(
     __syncthreads();
     if (grp < nrows) {                                             // whole groups of 8 lanes: the shuffles below stay inside a group
       const Cand c = s_cand[grp];
-      const void* rp = slots + grp * slot_bytes;
-      float acc = 0.f;
-      uint32_t e = j8;
-#pragma unroll 8
-      for (; e < body; e += 8) acc = __builtin_fmaf(qptr[e], load1<DT>(rp, e), acc);
-      float s = acc + __shfl_xor(acc, 4);
-      s = s + __shfl_xor(s, 1);
-      s = s + __shfl_xor(s, 2);
-      uint32_t t = body;
-      if (t < dim) {
-        if constexpr (DT == DT_F32) {
-          if (dim - t >= 4) {
-            for (int u = 0; u < 4; ++u) { const float p = qptr[t + u] * load1<DT>(rp, t + u); s = s + p; }
-            t += 4;
-          }
-        }
-        for (; t < dim; ++t) s = __builtin_fmaf(qptr[t], load1<DT>(rp, t), s);
-      }
+      float s = score8<DT>(slots + grp * slot_bytes, qptr, dim, j8);
       if constexpr (DT == DT_I8) s = s * scales[c.row];
       if (j8 == 0) {
         if (ebound && eb >= 0.f && !(__builtin_fabsf(s - c.score) <= eb)) atomicAdd(violations, 1u);
@@ -642,8 +728,8 @@ __global__ __launch_bounds__(256) void rescore_lds_kernel(
   }
   if (fs.mode == 0) return;
   __syncthreads();                                                 // my list's new scores are written (workgroup scope); the LDS is free
-  select_body(q, tid, 256u, reinterpret_cast<Cand*>(smem_raw), cand, cnt, cap, fs.k, nullptr, fs.thr, fs.overflow, fs.mode, fs.row_base,
-              fs.out_ids, fs.out_scores, fs.out_k, fs.any_overflow, nullptr, false);
+  select_body<0>(q, tid, 256u, reinterpret_cast<Cand*>(smem_raw), cand, cnt, cap, fs.k, nullptr, fs.thr, fs.overflow, fs.mode, fs.row_base,
+              fs.out_ids, fs.out_scores, fs.out_k, fs.any_overflow, nullptr, false, ExactBar{});
   if (fs.ticket == nullptr) return;
   // what the last workgroup reads of the others are agent-scope atomics (violations, flags): performed once vmcnt is 0 -- no
   // release fence (an L2 write-back per workgroup costs more than the select launch this fusion saves)

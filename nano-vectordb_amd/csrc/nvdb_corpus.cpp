@@ -421,6 +421,7 @@ nvdb_status nvdb_hip_set_option(nvdb_hip_ctx* c, const char* key, int64_t value)
   else if (k == "waves8") { c->opt_waves8 = value ? 1 : 0; }
   else if (k == "fuse") { c->opt_fuse = value ? 1 : 0; }
   else if (k == "zero_copy") { c->opt_zero_copy = value ? 1 : 0; }
+  else if (k == "shadow_exact_thr") { c->opt_shadow_exact_thr = value ? 1 : 0; }
   else if (k == "exact_mfma") { c->opt_exact_mfma = value ? 1 : 0; }
   else if (k == "exact_img") { c->opt_exact_img = value ? 1 : 0; }
   else if (k == "exact_prescan") { c->opt_exact_prescan = value ? 1 : 0; }

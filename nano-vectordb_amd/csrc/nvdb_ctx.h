@@ -132,6 +132,7 @@ struct nvdb_hip_ctx {
   DevBuf hostblock;                                // host API, <= 1024 queries: [status words (= misc, aliased) | ids | scores] in one allocation, one D2H copy
   DevBuf tickets;                                  // FUSE_TICKETS words, zeroed by the search's prep launch: "last workgroup" ticket of the fused rescore + final select
   int64_t opt_fuse = 1;                            // 1: init folded into the prep launch, the final select into the rescore launch; 0: separate launches
+  int64_t opt_shadow_exact_thr = 1;                // searches that stream the int8 shadow, k <= 64: thresholds one error bound under an EXACT k-th best score (the selects re-score their best 2k entries); 0: two bounds under the k-th list score
   int64_t opt_zero_copy = 1;                       // host API, small calls: queries read from / results written to pinned host memory by the kernels themselves (no H2D / D2H copy enqueued)
   bool status_by_kernel = false;                   // last search_core: its final kernel wrote the status words to the caller's pinned block
   size_t q32_dirty = 0;                            // bytes of q32 (from its start) that may hold old queries: beyond them the buffer is zero
@@ -317,8 +318,10 @@ inline hipEvent_t get_event(nvdb_hip_ctx* c, size_t idx) {
 nvdb_status launch_init_search(nvdb_hip_ctx* c, hipStream_t s, uint32_t nq_pad, uint32_t prog_words);
 nvdb_status launch_scan_exact(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint32_t row_hi, const float* q32, uint32_t nq, uint32_t k,
                               const float* thr, uint32_t cap, uint32_t reserve);
+// q32 != nullptr (modes 0 and 2, a search that streams the int8 shadow): the bar is exact -- the select re-scores its best 2k entries
+// from the corpus' own rows (c->rows, c->dtype, c->dim) against these queries and sets thr = k-th exact score - c->ebound (kernels_exact.h)
 nvdb_status launch_select(nvdb_hip_ctx* c, hipStream_t s, uint32_t nq, uint32_t cap, uint32_t k, const float* slack, int mode, uint64_t* out_ids,
-                          float* out_scores, uint32_t out_k);
+                          float* out_scores, uint32_t out_k, const float* q32 = nullptr);
 nvdb_status launch_rescore(nvdb_hip_ctx* c, hipStream_t s, const float* q32, uint32_t nq, uint32_t cap, FinalSelect fs = FinalSelect{}, bool* fused = nullptr);
 nvdb_status search_largek(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint32_t nq, uint32_t k, uint64_t* dev_out_ids, float* dev_out_scores,
                           uint32_t n_rows = 0, Cand* seed_cand = nullptr, uint32_t* seed_cnt = nullptr, uint32_t seed_cap = 0);

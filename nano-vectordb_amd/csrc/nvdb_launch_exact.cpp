@@ -142,18 +142,25 @@ nvdb_status launch_scan_exact(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, u
 }
 
 nvdb_status launch_select(nvdb_hip_ctx* c, hipStream_t s, uint32_t nq, uint32_t cap, uint32_t k, const float* slack,
-                          int mode, uint64_t* out_ids, float* out_scores, uint32_t out_k) {
-  const void* fn = reinterpret_cast<const void*>(select_kernel);
-  if (nvdb_status ls = raise_lds_limit(c, fn, SELECT_MAX_CAP * sizeof(Cand))) return ls;
+                          int mode, uint64_t* out_ids, float* out_scores, uint32_t out_k, const float* q32) {
+  constexpr size_t XQ_MAX = 16 * 1024;              // the exact bar's query staging, past the list
   // the bitonic branch pads a list to the next power of two >= its length (<= cap): size the LDS for that
   uint32_t cap2 = 1;
   while (cap2 < cap) cap2 <<= 1;
   static_assert(SELECT_MAX_CAP * sizeof(Cand) <= 64 * 1024 && (SELECT_MAX_CAP & (SELECT_MAX_CAP - 1)) == 0, "select_kernel LDS");
-  select_kernel<<<nq, 256, cap2 * sizeof(Cand), s>>>(static_cast<Cand*>(c->cand.p), static_cast<uint32_t*>(c->cnt.p), cap, k, slack,
+  const size_t qbytes = static_cast<size_t>(c->dim) * 4;
+  const bool f16 = c->dtype == NVDB_DTYPE_F16;
+  if (q32 != nullptr && ((mode & 1) || k > WAVE_KMAX || qbytes > XQ_MAX || (!f16 && c->dtype != NVDB_DTYPE_F32)))
+    return fail(c, NVDB_ERR_INTERNAL, "select: exact bar asked for a list it does not serve");
+  // (XDT = 0 is the select every other search launches: its code does not know the exact bar)
+  auto kern = q32 == nullptr ? select_kernel<0> : f16 ? select_kernel<DT_F16> : select_kernel<DT_F32>;
+  if (nvdb_status ls = raise_lds_limit(c, reinterpret_cast<const void*>(kern), SELECT_MAX_CAP * sizeof(Cand) + (q32 ? XQ_MAX : 0))) return ls;
+  const ExactBar xb{c->rows, q32, static_cast<const float*>(c->ebound.p), c->dim, static_cast<uint32_t>(c->n), static_cast<uint32_t>(cap2 * sizeof(Cand))};
+  kern<<<nq, 256, cap2 * sizeof(Cand) + (q32 ? qbytes : 0), s>>>(static_cast<Cand*>(c->cand.p), static_cast<uint32_t*>(c->cnt.p), cap, k, slack,
                                                    static_cast<float*>(c->thr.p), static_cast<uint32_t*>(c->overflow.p), mode,
                                                    c->row_base, reinterpret_cast<unsigned long long*>(out_ids), out_scores, out_k,
                                                    static_cast<uint32_t*>(c->misc.p) + 6,
-                                                   c->opt_xcd_balance ? static_cast<float*>(c->xcdw.p) : nullptr);
+                                                   c->opt_xcd_balance ? static_cast<float*>(c->xcdw.p) : nullptr, xb);
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
 }

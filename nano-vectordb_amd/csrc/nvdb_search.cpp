@@ -138,7 +138,10 @@ nvdb_status search_core(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint
   else if (p.boot == BOOT_ANYK_SEEDED) st = search_largek(c, s, dev_q, nq, k_eff, nullptr, nullptr, p.r0, static_cast<Cand*>(c->cand.p), static_cast<uint32_t*>(c->cnt.p), cap);
   else st = launch_scan_exact(c, s, 0, p.r0, dev_q, nq, k_eff, nullptr, cap, 0);
   if (st) return st;
-  if ((st = launch_select(c, s, nq, cap, k_eff, slack, p.boot == BOOT_MFMA ? 2 : 0, nullptr, nullptr, p.boot == BOOT_MFMA ? p.boot_tiles : 0))) return st;
+  // The int8 shadow's band is its widest term (||q|| x the largest quantisation residual of any row) counted twice under a list
+  // score; the thresholding selects of such a search put ONE bound under an exact k-th best score instead (select_body, ExactBar)
+  const float* xthr_q = (p.shadow && k_eff <= WAVE_KMAX && c->opt_shadow_exact_thr) ? dev_q : nullptr;
+  if ((st = launch_select(c, s, nq, cap, k_eff, slack, p.boot == BOOT_MFMA ? 2 : 0, nullptr, nullptr, p.boot == BOOT_MFMA ? p.boot_tiles : 0, xthr_q))) return st;
   size_t ev = 0;
   for (uint32_t r = p.r0; r < p.n_al;) {
     const uint32_t hi = chunk_end(p, r);
@@ -163,7 +166,7 @@ nvdb_status search_core(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint
     if (time_filter && acct) { HIPCHK(c, hipEventRecord(get_event(c, ev + 1), s)); }
     if (time_filter) { c->ev_filter.emplace_back(ev, ev + 1); ev += 2; }
     if (acct) c->klaunch.push_back(kl);
-    if ((st = launch_select(c, s, nq, cap, k_eff, slack, 0, nullptr, nullptr, 0))) return st;
+    if ((st = launch_select(c, s, nq, cap, k_eff, slack, 0, nullptr, nullptr, 0, xthr_q))) return st;
     c->stats.chunks++;
     c->stats.rows_scanned += static_cast<uint64_t>(hi - r) * QT;
     r = hi;
