@@ -1,22 +1,25 @@
 // kernels_partitions.h -- gfx950 kernels of the partitioned probe search (nvdb_hip_search_partitions / nvdb_hip_search_ivf).
 //
-//  * scan_parts_kernel   : one workgroup per work item = (a segment of contiguous rows, a group of <= PART_WAVES*QW queries that all
-//                          probe the partition the segment belongs to).  The queries are gathered BY INDEX into LDS once; the
-//                          segment is walked in tiles of 64 rows; one lane = one row (the reference order of exact_scores<> is a
-//                          strict chain over the row); the waves score the SAME 64 rows, each against its own QW queries,
-//                          so a wave owns its queries' top-k lists outright and nothing is merged across waves.
+//  * part_walk           : the walk over one work item = (a segment of contiguous rows, a group of <= PART_WAVES*QW queries that
+//                          all probe the partition the segment belongs to), one workgroup per item.  The queries are gathered BY
+//                          INDEX into LDS once; the segment is walked in tiles of 64 rows; one lane = one row (the reference
+//                          order of exact_scores<> is a strict chain over the row); the waves score the SAME 64 rows, each
+//                          against its own QW queries, so a wave owns its queries' results outright and nothing is merged
+//                          across waves.  What happens to a scored row is a SINK's business (below).
 //                          STAGED: the tile's rows are contiguous bytes -- the workgroup fetches them with coalesced 16-byte
 //                          global loads (the next tile's loads are in flight, in registers, while this tile is scored), stores
 //                          them into LDS at a row pitch that is an ODD number of 16-byte slots, and every lane reads its row
 //                          back with conflict-free ds_read_b128.  Otherwise (rows that are no multiple of 16 bytes, or too long
 //                          for the LDS) the lanes read their rows from global memory directly.
-//                          Each (item, query) owns a slot of min(k, segment rows) Cand entries that the host placed: no atomics,
-//                          no counters, no overflow path.
 //                          MASKED: every query of the group searches under a row mask (a bit plane over the corpus, bit r = local
 //                          row r is live; PartMask): a lane tests its own row's bit per owned query and a dead row is never
 //                          offered.  A tile's mask words (at most three per query) are loaded one tile ahead by 4 lanes per
 //                          query, so the score chain hides them, and handed to the rows' lanes by a lane permute; a wave none of
 //                          whose lanes has a live row for any of its queries skips the tile's scores.
+//  * scan_parts_kernel   : part_walk with the top-k sink (PartTopKSink): a wave-wide list of the k best per owned query.  Each
+//                          (item, query) owns a slot of min(k, segment rows) Cand entries that the host placed: no atomics,
+//                          no counters, no overflow path.  (The range scan is the same walk with an append sink:
+//                          range_parts_kernel, kernels_range_parts.h.)
 //  * select_parts_kernel : one wave per query reduces the query's slots to the k best by (score desc, row asc), adds the global
 //                          row base and pads; given a count pointer it stores how many entries the query has (masked searches:
 //                          the host cannot derive min(k, live rows) from the partition sizes).
@@ -64,11 +67,19 @@ __device__ __forceinline__ uint32_t part_mask_words(const PartMask& mk, const ui
 // a bijection of the residues: the 16 lanes of a group touch 16 different 16-byte slots of the 256-byte bank window.
 __host__ __device__ inline uint32_t part_pitch(uint32_t row_bytes) { return ((row_bytes >> 4) | 1u) << 4; }
 
-template <int DT, int QW, bool ALIGNED, bool STAGED, bool MASKED>
-__global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
-    const void* __restrict__ rows, const float* __restrict__ scales, uint32_t dim, const PartItem* __restrict__ items,
-    const uint32_t* __restrict__ qidx, const uint32_t* __restrict__ dst, const float* __restrict__ q32, uint32_t k,
-    Cand* __restrict__ cand, PartMask mk) {
+// The walk over one work item, shared by the probe search's scan (scan_parts_kernel, below) and the range scan
+// (range_parts_kernel, kernels_range_parts.h): the query gather, the staging of the tiles, the mask words, the tile loop and the
+// scores.  What happens to a scored row is the SINK's business:
+//   Sink::PerQuery                    what a wave keeps per owned query: wave-uniform values or a wave-wide list (a wave owns its
+//                                     queries outright)
+//   sink.open(pq, qi, dslot)          once per owned query: qi = the query's number, dst[dslot] = its (item, query) slot (wave
+//                                     slots beyond the group repeat the group's first query; nothing is ever kept for them)
+//   sink.row(pq, pass, score, row, lane)  once per scored tile and owned query, by every lane: pass = the lane's row exists, the
+//                                     query is one of the group's and the row is live in its mask
+//   sink.close(pq, seg, dslot, lane)  after the last tile, for the group's queries only: seg = the segment's rows
+template <int DT, int QW, bool ALIGNED, bool STAGED, bool MASKED, class Sink>
+__device__ __forceinline__ void part_walk(const void* rows, const float* scales, uint32_t dim, const PartItem* items,
+                                          const uint32_t* qidx, const float* q32, const PartMask& mk, const Sink& sink) {
   constexpr uint32_t BPE = (DT == DT_F32) ? 4 : (DT == DT_F16 ? 2 : 1);
   constexpr uint32_t QG = PART_WAVES * QW;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -100,7 +111,7 @@ __global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
     const uint32_t nch_ = nrows_ * cpr;                                                                                        \
     const uint4* src_ = reinterpret_cast<const uint4*>(static_cast<const char*>(rows) + static_cast<uint64_t>(T) * row_bytes); \
     _Pragma("unroll") for (uint32_t i_ = 0; i_ < PART_MAX_CHUNKS; ++i_) {                                                      \
-      const uint32_t c_ = tid + PART_THREADS * i_;                                                                                     \
+      const uint32_t c_ = tid + PART_THREADS * i_;                                                                             \
       pre[i_] = (c_ < nch_) ? src_[c_] : uint4{0u, 0u, 0u, 0u};                                                                \
     }                                                                                                                          \
   }
@@ -111,32 +122,32 @@ __global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
     const uint32_t nch_ = nrows_ * cpr;                                                                                        \
     uint32_t r_ = tid / cpr, ch_ = tid % cpr;                                                                                  \
     _Pragma("unroll") for (uint32_t i_ = 0; i_ < PART_MAX_CHUNKS; ++i_) {                                                      \
-      const uint32_t c_ = tid + PART_THREADS * i_;                                                                                     \
+      const uint32_t c_ = tid + PART_THREADS * i_;                                                                             \
       if (c_ < nch_) *reinterpret_cast<uint4*>(tile + r_ * pitch + ch_ * 16u) = pre[i_];                                       \
       r_ += r_step; ch_ += ch_step;                                                                                            \
       if (ch_ >= cpr) { ch_ -= cpr; ++r_; }                                                                                    \
     }                                                                                                                          \
   }
   const bool wave_live = wave * QW < it.nqg;                               // this wave owns at least one query of the group
-  // MASKED: the mask numbers of this wave's queries, gathered by index like the queries (slots beyond the group repeat its first
-  // query's; scalar registers), and the first tile's mask words (part_mask_words)
+  // this wave's queries, gathered by index like the query vectors (slots beyond the group repeat its first query's): the sink's
+  // per-query state and, MASKED, the mask numbers (scalar registers) and the first tile's mask words (part_mask_words)
+  typename Sink::PerQuery sq[QW];
   [[maybe_unused]] uint32_t mid[QW], wcur = 0u;
-  if constexpr (MASKED) {
 #pragma unroll
-    for (int g = 0; g < QW; ++g) {
-      const uint32_t gi = wave * QW + g;
-      mid[g] = __builtin_amdgcn_readfirstlane(mk.mask_of[qidx[it.qoff + (gi < it.nqg ? gi : 0u)]]);
-    }
+  for (int g = 0; g < QW; ++g) {
+    const uint32_t gi = wave * QW + g, gc = gi < it.nqg ? gi : 0u;
+    const uint32_t qi = qidx[it.qoff + gc];
+    sink.open(sq[g], qi, it.doff + gc);
+    if constexpr (MASKED) mid[g] = __builtin_amdgcn_readfirstlane(mk.mask_of[qi]);
+  }
+  if constexpr (MASKED) {
     if (wave_live) wcur = part_mask_words<QW>(mk, mid, it.row_lo, it.row_hi, lane);
   }
   if constexpr (STAGED) { NVDB_PART_FETCH(it.row_lo) NVDB_PART_STASH(it.row_lo) }
   __syncthreads();
 
   const float* qptr = q_lds + wave * QW * qstride;
-  WaveTopK tk[QW];
-#pragma unroll
-  for (int g = 0; g < QW; ++g) wtk_init(tk[g]);
-
+  // per tile: issue the next tile's loads, score this tile, barrier, stash, barrier
   for (uint32_t t_lo = it.row_lo; t_lo < it.row_hi; t_lo += PART_TILE_ROWS) {
     const bool more = t_lo + PART_TILE_ROWS < it.row_hi;
     if constexpr (STAGED) { if (more) NVDB_PART_FETCH(t_lo + PART_TILE_ROWS) }
@@ -162,10 +173,7 @@ __global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
         if constexpr (STAGED) exact_scores<DT, QW, ALIGNED>(tile + static_cast<uint32_t>(lane) * pitch, qptr, qstride, dim, scale, sc);
         else exact_scores<DT, QW, ALIGNED>(row_ptr<DT>(rows, rrow, dim), qptr, qstride, dim, scale, sc);
 #pragma unroll
-        for (int g = 0; g < QW; ++g) {
-          const bool pass = valid && wave * QW + g < it.nqg && ((live >> g) & 1u) && wtk_accepts(tk[g], k, sc[g], row);
-          wtk_offer(tk[g], k, pass, sc[g], row, lane);
-        }
+        for (int g = 0; g < QW; ++g) sink.row(sq[g], valid && wave * QW + g < it.nqg && ((live >> g) & 1u), sc[g], row, lane);
       }
       if constexpr (MASKED) wcur = wnext;
     }
@@ -177,20 +185,40 @@ __global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
       }
     }
   }
-
-  const uint32_t seg = it.row_hi - it.row_lo, slot = seg < k ? seg : k;    // entries of this (item, query): every row was offered
+  const uint32_t seg = it.row_hi - it.row_lo;
 #pragma unroll
-  for (int g = 0; g < QW; ++g) {
-    const uint32_t gi = wave * QW + g;
-    if (gi < it.nqg && static_cast<uint32_t>(lane) < slot) {
-      const uint32_t d = dst[it.doff + gi];
-      cand[static_cast<uint64_t>(d) + lane] = (static_cast<uint32_t>(lane) < tk[g].cnt) ? Cand{tk[g].s, tk[g].id} : Cand{NEG_INF, 0xFFFFFFFFu};
-    }
-  }
+  for (int g = 0; g < QW; ++g)
+    if (wave * QW + g < it.nqg) sink.close(sq[g], seg, it.doff + wave * QW + g, lane);
 }
 
 #undef NVDB_PART_FETCH
 #undef NVDB_PART_STASH
+
+// The top-k sink: a wave-wide list of the k best per owned query; at the end min(k, segment rows) entries per (item, query) go
+// to the slot the host placed (every row was offered, so a list that is not full is padded).
+struct PartTopKSink {
+  using PerQuery = WaveTopK;
+  const uint32_t* __restrict__ dst;
+  Cand* __restrict__ cand;
+  uint32_t k;
+  __device__ __forceinline__ void open(WaveTopK& tk, uint32_t, uint32_t) const { wtk_init(tk); }
+  __device__ __forceinline__ void row(WaveTopK& tk, bool pass, float sc, uint32_t row, int lane) const {
+    wtk_offer(tk, k, pass && wtk_accepts(tk, k, sc, row), sc, row, lane);
+  }
+  __device__ __forceinline__ void close(const WaveTopK& tk, uint32_t seg, uint32_t dslot, int lane) const {
+    if (static_cast<uint32_t>(lane) < (seg < k ? seg : k))
+      cand[static_cast<uint64_t>(dst[dslot]) + lane] = (static_cast<uint32_t>(lane) < tk.cnt) ? Cand{tk.s, tk.id} : Cand{NEG_INF, 0xFFFFFFFFu};
+  }
+};
+
+template <int DT, int QW, bool ALIGNED, bool STAGED, bool MASKED>
+__global__ __launch_bounds__(PART_THREADS) void scan_parts_kernel(
+    const void* __restrict__ rows, const float* __restrict__ scales, uint32_t dim, const PartItem* __restrict__ items,
+    const uint32_t* __restrict__ qidx, const uint32_t* __restrict__ dst, const float* __restrict__ q32, uint32_t k,
+    Cand* __restrict__ cand, PartMask mk) {
+  const PartTopKSink sink{dst, cand, k};
+  part_walk<DT, QW, ALIGNED, STAGED, MASKED>(rows, scales, dim, items, qidx, q32, mk, sink);
+}
 
 // grid = nq, block = 64: the query's slots are cand[cbeg[q] .. cbeg[q+1])
 static __global__ __launch_bounds__(64) void select_parts_kernel(

@@ -6,7 +6,8 @@
 //                         queries without a usable threshold are flagged and given +inf
 //   (filter launches, rescore launch: the flat search's kernels)
 //   range_keep_kernel     one workgroup per query over its re-scored list: drop what misses the radius, order the rest
-//                         (score desc, id asc) in LDS, write it back as the query's slab with its count
+//                         (score desc, id asc) in LDS, write it back as the query's slab with its count (range_keep_body<MASKED>:
+//                         also behind range_keep_masked_kernel of kernels_range_parts.h)
 //   range_pack_kernel     slabs -> the packed id / score arrays at the offsets of the exclusive scan (done on the host
 //                         over the downloaded counts), ids made global
 // Exact route (any dtype / dim; the queries the filter route flagged): the any-k path's score matrix, then
@@ -19,18 +20,9 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_largek.h"
+#include "range_plan.h"               // RangeDesc
 
 namespace nvdbhip {
-
-// one query's share of a collect / sort / emit pass of the exact route (built on the host from the downloaded counts)
-struct RangeDesc {
-  unsigned long long slab_off;       // first key of the query's slab (entries; the slabs of one K2 class are adjacent)
-  unsigned long long out_off;        // first entry of the query in the packed arrays
-  uint32_t q;                        // row of the score matrix
-  uint32_t cnt;                      // scores >= radius
-  uint32_t K2;                       // slab length: cnt rounded up to a power of two (>= 2)
-  uint32_t pad;
-};
 
 // grid = ceil(nq_pad / 256), block = 256.  overflow[q] arrives from the prep launch (1: a non-finite query element).
 static __global__ __launch_bounds__(256) void range_thr_kernel(const float* __restrict__ radius, const float* __restrict__ ebound, float* __restrict__ thr,
@@ -51,11 +43,13 @@ static __global__ __launch_bounds__(256) void range_thr_kernel(const float* __re
   thr[q] = t;
 }
 
-// grid = nq, block = 256, dynamic LDS = (cap rounded up to a power of two) * 8 bytes.  The list holds exact scores (the
-// rescore launch ran).  Flagged queries (overflow[q]) keep nothing: the exact route answers them.
-static __global__ __launch_bounds__(256) void range_keep_kernel(Cand* __restrict__ cand, const uint32_t* __restrict__ cnt, uint32_t cap,
-                                                                const float* __restrict__ radius, const uint32_t* __restrict__ overflow,
-                                                                uint32_t* __restrict__ kept) {
+// The keep step of one query's re-scored list (one workgroup of 256): drop what misses the radius -- MASKED: and what is dead in
+// the query's plane (mask_of[q]; 0xFFFFFFFF: none; planes = [nmasks][W] words over the n local rows) --, order the rest in LDS,
+// write it back with its count.  Flagged queries (overflow[q]) keep nothing.
+template <bool MASKED>
+__device__ __forceinline__ void range_keep_body(Cand* __restrict__ cand, const uint32_t* __restrict__ cnt, uint32_t cap, const float* __restrict__ radius,
+                                                const uint32_t* __restrict__ overflow, uint32_t* __restrict__ kept,
+                                                const uint32_t* __restrict__ mask_of, const uint32_t* __restrict__ planes, uint32_t W, uint32_t n) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   Cand* e = reinterpret_cast<Cand*>(smem_raw);
   __shared__ uint32_t s_wave[4];
@@ -64,6 +58,12 @@ static __global__ __launch_bounds__(256) void range_keep_kernel(Cand* __restrict
   if (m > cap) m = cap;
   if (overflow[q] != 0u) m = 0;
   const float r = radius[q];
+  [[maybe_unused]] uint32_t mq = 0xFFFFFFFFu;
+  [[maybe_unused]] const uint32_t* plane = nullptr;
+  if constexpr (MASKED) {
+    mq = mask_of[q];
+    plane = planes + static_cast<uint64_t>(mq == 0xFFFFFFFFu ? 0u : mq) * W;
+  }
   Cand* mine = cand + static_cast<uint64_t>(q) * cap;
   // compaction into LDS: a ballot per wave, the waves' totals through LDS, no atomics
   uint32_t keep = 0;                                                 // uniform: entries in LDS so far
@@ -71,7 +71,9 @@ static __global__ __launch_bounds__(256) void range_keep_kernel(Cand* __restrict
     const uint32_t i = base + tid;
     Cand c = Cand{0.f, 0u};
     if (i < m) c = mine[i];
-    const bool pass = i < m && c.score >= r;
+    bool pass = i < m && c.score >= r;
+    if constexpr (MASKED)
+      if (pass && mq != 0xFFFFFFFFu) pass = c.row < n && ((plane[c.row >> 5] >> (c.row & 31u)) & 1u) != 0u;
     const unsigned long long bal = __ballot(pass);
     if (lane == 0) s_wave[wave] = static_cast<uint32_t>(__builtin_popcountll(bal));
     __syncthreads();
@@ -99,6 +101,14 @@ static __global__ __launch_bounds__(256) void range_keep_kernel(Cand* __restrict
       __syncthreads();
     }
   for (uint32_t i = tid; i < keep; i += 256) mine[i] = e[i];
+}
+
+// grid = nq, block = 256, dynamic LDS = (cap rounded up to a power of two) * 8 bytes.  The list holds exact scores (the
+// rescore launch ran).  The masked search's twin is range_keep_masked_kernel (kernels_range_parts.h).
+static __global__ __launch_bounds__(256) void range_keep_kernel(Cand* __restrict__ cand, const uint32_t* __restrict__ cnt, uint32_t cap,
+                                                                const float* __restrict__ radius, const uint32_t* __restrict__ overflow,
+                                                                uint32_t* __restrict__ kept) {
+  range_keep_body<false>(cand, cnt, cap, radius, overflow, kept, nullptr, nullptr, 0u, 0u);
 }
 
 // grid = (ceil(max count / 512), nq), block = 256: two entries per thread, 16-byte accesses (slabs and, for even offsets,

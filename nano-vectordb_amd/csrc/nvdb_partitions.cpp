@@ -12,8 +12,9 @@
 //      (dst); the blocks are laid out by a prefix sum (cbeg), so the capacity is exact and nothing can overflow.
 // Items are sorted by group size into classes (<= 8, <= 16, <= 32 queries) that run the QW = 1, 2, 4 builds of the kernel (the
 // widest one the LDS has room for): a remainder group of three queries does not pay for sixteen.
-// The list builder and its pinned image (parts_worklist / parts_stage, nvdb_parts.h) are shared with the partition range scan
-// (nvdb_range_parts.cpp), whose slots hold a segment's row count instead of min(k, rows).
+// The list builder, its pinned image and the dispatch to a kernel build (parts_worklist / parts_stage / parts_dispatch,
+// nvdb_parts.h) are shared with the partition range scan (nvdb_range_parts.cpp), whose slots hold a segment's row count instead
+// of min(k, rows).
 // A masked search is the same work list with every query's mask number appended to the pinned image; the MASKED builds of the
 // scan test a row's bit before they offer it, and the select kernel writes the counts the host can no longer derive.  The
 // masked flat search runs the corpus as one implicit partition that every query probes.
@@ -42,46 +43,10 @@ void parts_destroy(nvdb_hip_ctx* c) {
 
 namespace {
 
-// mk.mask_of != nullptr: the MASKED build
-template <int DT, int QW, bool AL, bool ST, bool MK>
-nvdb_status launch_one(nvdb_hip_ctx* c, hipStream_t s, const PartItem* items, uint32_t nitems, const uint32_t* qidx, const uint32_t* dst,
-                       const float* q32, uint32_t k, Cand* cand, const PartMask& mk) {
-  const size_t lds = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), QW, ST);
-  if (lds > 64 * 1024)
-    if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(scan_parts_kernel<DT, QW, AL, ST, MK>), PART_LDS_LIMIT)) return st;
-  scan_parts_kernel<DT, QW, AL, ST, MK><<<nitems, PART_THREADS, lds, s>>>(c->rows, c->scales, c->dim, items, qidx, dst, q32, k, cand, mk);
-  HIPCHK(c, hipGetLastError());
-  return NVDB_OK;
-}
-
-template <int DT, int QW, bool AL, bool ST>
-nvdb_status launch_mk(nvdb_hip_ctx* c, hipStream_t s, const PartItem* items, uint32_t nitems, const uint32_t* qidx, const uint32_t* dst,
-                      const float* q32, uint32_t k, Cand* cand, const PartMask& mk) {
-  if (mk.mask_of) return launch_one<DT, QW, AL, ST, true>(c, s, items, nitems, qidx, dst, q32, k, cand, mk);
-  return launch_one<DT, QW, AL, ST, false>(c, s, items, nitems, qidx, dst, q32, k, cand, mk);
-}
-
-template <int DT, int QW>
-nvdb_status launch_qw(nvdb_hip_ctx* c, hipStream_t s, bool staged, const PartItem* items, uint32_t nitems, const uint32_t* qidx,
-                      const uint32_t* dst, const float* q32, uint32_t k, Cand* cand, const PartMask& mk) {
-  if (staged) return launch_mk<DT, QW, true, true>(c, s, items, nitems, qidx, dst, q32, k, cand, mk);
-  if (aligned_rows(c->dtype, c->dim)) return launch_mk<DT, QW, true, false>(c, s, items, nitems, qidx, dst, q32, k, cand, mk);
-  return launch_mk<DT, QW, false, false>(c, s, items, nitems, qidx, dst, q32, k, cand, mk);
-}
-
-template <int DT>
-nvdb_status launch_dt(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const PartItem* items, uint32_t nitems, const uint32_t* qidx,
-                      const uint32_t* dst, const float* q32, uint32_t k, Cand* cand, const PartMask& mk) {
-  if (qw == 4) return launch_qw<DT, 4>(c, s, staged, items, nitems, qidx, dst, q32, k, cand, mk);
-  if (qw == 2) return launch_qw<DT, 2>(c, s, staged, items, nitems, qidx, dst, q32, k, cand, mk);
-  return launch_qw<DT, 1>(c, s, staged, items, nitems, qidx, dst, q32, k, cand, mk);
-}
-
-nvdb_status launch_scan_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const PartItem* items, uint32_t nitems,
-                              const uint32_t* qidx, const uint32_t* dst, const float* q32, uint32_t k, Cand* cand, const PartMask& mk) {
-  if (c->dtype == NVDB_DTYPE_F32) return launch_dt<DT_F32>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand, mk);
-  if (c->dtype == NVDB_DTYPE_F16) return launch_dt<DT_F16>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand, mk);
-  return launch_dt<DT_I8>(c, s, qw, staged, items, nitems, qidx, dst, q32, k, cand, mk);
+nvdb_status launch_scan_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, uint32_t k, const ScanArgs& a) {
+  return parts_dispatch(c, qw, staged, a.mk.mask_of != nullptr, [&](auto dt, auto w, auto al, auto st, auto mk) {
+    return parts_launch(c, s, scan_parts_kernel<dt(), w(), al(), st(), mk()>, w(), st(), a.nitems, a.items, a.qidx, a.dst, a.q32, k, a.cand, a.mk);
+  });
 }
 
 }  // namespace
@@ -310,7 +275,8 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, 
       const uint32_t n_cl = static_cast<uint32_t>(ps->items[cl].size());
       if (!n_cl) continue;
       const uint32_t qw = std::min<uint32_t>(qw_max, 1u << cl);
-      if ((st = launch_scan_parts(c, s, qw, staged, it, n_cl, d_qidx, d_dst, static_cast<const float*>(ps->q.p), k, static_cast<Cand*>(ps->cand.p), mk))) return st;
+      const ScanArgs a{it, n_cl, d_qidx, d_dst, static_cast<const float*>(ps->q.p), static_cast<Cand*>(ps->cand.p), mk};
+      if ((st = launch_scan_parts(c, s, qw, staged, k, a))) return st;
       it += n_cl;
       ++launches;
     }

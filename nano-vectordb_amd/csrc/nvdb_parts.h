@@ -1,6 +1,9 @@
 // nvdb_parts.h -- what the probe search (nvdb_partitions.cpp) and the partition range scan (nvdb_range_parts.cpp) share: the
-// state behind nvdb_hip_ctx::parts, the kernel build a corpus takes, the host-side work list and its pinned image.  Internal.
+// state behind nvdb_hip_ctx::parts, the kernel build a corpus takes and the dispatch to it (parts_dispatch), the host-side work list
+// and its pinned image.  Internal.
 #pragma once
+#include <type_traits>
+
 #include "nvdb_ctx.h"
 #include "kernels_partitions.h"
 #include "row_mask.h"
@@ -44,6 +47,46 @@ inline nvdb_status mask_args(nvdb_hip_ctx* c, const uint32_t* mask_of, uint32_t 
 // the queries; qw_max = the most queries per wave the LDS has room for (0: not even one -- the dim is too large)
 struct PartBuild { uint32_t qw_max = 0; bool staged = false; };
 PartBuild parts_build(const nvdb_hip_ctx* c);
+
+// what a launch of either scan passes besides the corpus: nitems work items, the work list's arrays, the queries, the candidate
+// buffer; mk.mask_of != nullptr: the MASKED build
+struct ScanArgs {
+  const PartItem* items; uint32_t nitems; const uint32_t* qidx; const uint32_t* dst; const float* q32; Cand* cand; PartMask mk;
+};
+
+// The one place a launch's build -- dtype x QW x {staged, direct aligned, direct unaligned} x masked -- becomes compile-time
+// constants: launch(DT, QW, ALIGNED, STAGED, MASKED) receives them as std::integral_constant values and instantiates its kernel.
+template <class F>
+nvdb_status parts_dispatch(const nvdb_hip_ctx* c, uint32_t qw, bool staged, bool masked, F&& launch) {
+  auto with_mask = [&](auto dt, auto w, auto al, auto st) {
+    return masked ? launch(dt, w, al, st, std::true_type{}) : launch(dt, w, al, st, std::false_type{});
+  };
+  auto with_rows = [&](auto dt, auto w) {
+    if (staged) return with_mask(dt, w, std::true_type{}, std::true_type{});
+    if (aligned_rows(c->dtype, c->dim)) return with_mask(dt, w, std::true_type{}, std::false_type{});
+    return with_mask(dt, w, std::false_type{}, std::false_type{});
+  };
+  auto with_qw = [&](auto dt) {
+    if (qw == 4) return with_rows(dt, std::integral_constant<int, 4>{});
+    if (qw == 2) return with_rows(dt, std::integral_constant<int, 2>{});
+    return with_rows(dt, std::integral_constant<int, 1>{});
+  };
+  if (c->dtype == NVDB_DTYPE_F32) return with_qw(std::integral_constant<int, DT_F32>{});
+  if (c->dtype == NVDB_DTYPE_F16) return with_qw(std::integral_constant<int, DT_F16>{});
+  return with_qw(std::integral_constant<int, DT_I8>{});
+}
+
+// ... and what every build's launch does alike: the LDS it takes (raised above 64 KB where needed), the grid, the error check.
+// args: the kernel's arguments behind (rows, scales, dim)
+template <class K, class... A>
+nvdb_status parts_launch(nvdb_hip_ctx* c, hipStream_t s, K kernel, uint32_t qw, bool staged, uint32_t nitems, A... args) {
+  const size_t lds = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), qw, staged);
+  if (lds > 64 * 1024)
+    if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(kernel), PART_LDS_LIMIT)) return st;
+  kernel<<<nitems, PART_THREADS, lds, s>>>(c->rows, c->scales, c->dim, args...);
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
 
 // The probe table of a call, checked and de-duplicated, into the PartState's host scratch (uniq / ucount): 0xFFFFFFFF slots dropped,
 // a partition named twice counted once, an entry >= nparts -> NVDB_ERR_INVALID.  rows_union (optional, nq entries): the rows of

@@ -2,7 +2,7 @@
 // per-query radius, as variable-length slices (lims) over packed device arrays.  Per sub-batch of <= 1024 queries:
 //   filter route  prep -> thresholds radius - E_q -> the MFMA filter over the whole corpus at those FIXED thresholds (no bootstrap, no
 //                 select, no chunk schedule) -> rescore -> keep / order (range_keep_kernel) -> pack
-//   exact route   score matrix of a query sub-batch (the any-k path's) -> count -> collect -> sort -> emit; serves every dtype / dim,
+//   exact route   score matrix of a query sub-batch (the any-k path's) -> count -> range_tail (nvdb_range.h): collect, sort, emit; serves every dtype / dim,
 //                 option path = 1, and the queries the filter route could not answer (flagged: non-finite query or radius, list overflow;
 //                 all of them after a wave-log overflow or a bound violation)
 // nvdb_hip_range_search_masked is the same call under a row-mask plane per query: on the filter route only the keep step differs
@@ -77,16 +77,15 @@ nvdb_status range_exact(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, cons
   if ((st = ensure(c, c->lk_scores, static_cast<size_t>(QB) * ld * 4))) return st;
   if ((st = ensure(c, c->rg_taken, static_cast<size_t>(QB) * 4))) return st;
   float* scores = static_cast<float*>(c->lk_scores.p);
-  uint32_t* taken = static_cast<uint32_t*>(c->rg_taken.p);
-  // keys a pass may hold in slabs: a quarter of the score matrix' budget, or one query's slab
+  // keys a run may hold in slabs: a quarter of the score matrix' budget, or one query's slab
   const uint64_t slab_max = (static_cast<uint64_t>(c->opt_largek_budget_mb) << 20) / 32;
   std::vector<uint32_t> hc;
-  std::vector<uint64_t> pre;
-  std::vector<RangeDesc> all, run;
+  std::vector<uint64_t> pre, out_off;
   for (uint32_t g0 = 0; g0 < ne; g0 += QB) {
     const uint32_t b = std::min(QB, ne - g0);
     const float* rad = dev_radius + g0;
     if ((st = launch_score_matrix(c, s, dev_q + static_cast<size_t>(g0) * c->dim, b, scores, ld, n, QG, true))) return st;
+    uint32_t* taken = static_cast<uint32_t*>(c->rg_taken.p);
     HIPCHK(c, hipMemsetAsync(taken, 0, static_cast<size_t>(b) * 4, s));
     const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>((n + 1023u) / 1024u, (8u * static_cast<uint32_t>(c->num_cu) + b - 1) / b));
     range_count_kernel<<<dim3(G, b), 256, 0, s>>>(scores, ld, n, rad, taken);
@@ -101,47 +100,19 @@ nvdb_status range_exact(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, cons
     pre.assign(static_cast<size_t>(last) + 2, 0);
     for (uint32_t j = 0; j <= last; ++j) pre[j + 1] = pre[j] + cnt[j];
     if (!reserve_packed(c, s, out, base + pre[last + 1], &st)) { if (st) return st; continue; }
-    all.clear();
-    for (uint32_t i = 0; i < b; ++i) {
-      if (!hc[i]) continue;
-      uint64_t K2 = 2;
-      while (K2 < hc[i]) K2 <<= 1;
-      all.push_back(RangeDesc{0ull, base + pre[qmap[g0 + i]], i, hc[i], static_cast<uint32_t>(K2), 0u});
-    }
-    // slabs of one length side by side: one sort launch per length
-    std::stable_sort(all.begin(), all.end(), [](const RangeDesc& a, const RangeDesc& b2) { return a.K2 < b2.K2; });
-    for (size_t i0 = 0; i0 < all.size();) {
-      run.clear();
-      uint64_t keys = 0;
-      uint32_t max_cnt = 0;
-      size_t i1 = i0;
-      while (i1 < all.size() && (run.empty() || keys + all[i1].K2 <= slab_max)) {
-        RangeDesc d = all[i1++];
-        d.slab_off = keys;
-        keys += d.K2;
-        max_cnt = std::max(max_cnt, d.cnt);
-        run.push_back(d);
-      }
-      i0 = i1;
-      const uint32_t nr = static_cast<uint32_t>(run.size());
-      if ((st = ensure(c, c->rg_slab, static_cast<size_t>(keys) * 8))) return st;
-      if ((st = upload(c, s, c->rg_desc, run))) return st;
-      const RangeDesc* desc = static_cast<const RangeDesc*>(c->rg_desc.p);
-      unsigned long long* slab = static_cast<unsigned long long*>(c->rg_slab.p);
-      HIPCHK(c, hipMemsetAsync(taken, 0, static_cast<size_t>(nr) * 4, s));
-      const uint32_t Gr = std::max<uint32_t>(1, std::min<uint32_t>((n + 1023u) / 1024u, (8u * static_cast<uint32_t>(c->num_cu) + nr - 1) / nr));
-      range_collect_kernel<<<dim3(Gr, nr), 256, 0, s>>>(scores, ld, n, rad, desc, taken, slab);
-      HIPCHK(c, hipGetLastError());
-      for (uint32_t a = 0; a < nr;) {
-        uint32_t e = a;
-        while (e < nr && run[e].K2 == run[a].K2) ++e;
-        if ((st = launch_sort_keys(c, s, slab + run[a].slab_off, run[a].K2, e - a))) return st;
-        a = e;
-      }
-      range_emit_kernel<<<dim3((max_cnt + 255u) / 256u, nr), 256, 0, s>>>(slab, desc, scores, ld, n, c->row_base, static_cast<unsigned long long*>(c->rg_ids.p),
-                                                                          static_cast<float*>(c->rg_scores.p));
-      HIPCHK(c, hipGetLastError());
-    }
+    out_off.resize(b);
+    for (uint32_t i = 0; i < b; ++i) out_off[i] = base + pre[qmap[g0 + i]];
+    st = range_tail(c, s, "range_search", hc.data(), b, out_off.data(), slab_max,
+        [&](const std::vector<RangeDesc>& run, const RangeDesc* desc, uint32_t* taken, unsigned long long* slab) {
+          const uint32_t nr = static_cast<uint32_t>(run.size());
+          const uint32_t Gr = std::max<uint32_t>(1, std::min<uint32_t>((n + 1023u) / 1024u, (8u * static_cast<uint32_t>(c->num_cu) + nr - 1) / nr));
+          range_collect_kernel<<<dim3(Gr, nr), 256, 0, s>>>(scores, ld, n, rad, desc, taken, slab);
+        },
+        [&](const std::vector<RangeDesc>& run, uint32_t max_cnt, const RangeDesc* desc, const unsigned long long* slab) {
+          range_emit_kernel<<<dim3((max_cnt + 255u) / 256u, static_cast<uint32_t>(run.size())), 256, 0, s>>>(
+              slab, desc, scores, ld, n, c->row_base, static_cast<unsigned long long*>(c->rg_ids.p), static_cast<float*>(c->rg_scores.p));
+        });
+    if (st) return st;
   }
   return NVDB_OK;
 }

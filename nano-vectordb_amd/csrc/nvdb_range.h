@@ -1,8 +1,10 @@
 // nvdb_range.h -- what the flat range search (nvdb_range.cpp) and the range search on the probe path (nvdb_range_parts.cpp) share:
-// the packed result arrays of a call and their budget, and the partition range scan as the flat masked search calls it.  Internal.
+// the packed result arrays of a call and their budget, the tail that turns downloaded counts into sorted, emitted slices
+// (range_tail), and the partition range scan as the flat masked search calls it.  Internal.
 #pragma once
 #include "nvdb_parts.h"
 #include "kernels_range.h"
+#include "range_plan.h"
 
 namespace nvdbhip {
 
@@ -44,6 +46,49 @@ inline nvdb_status upload(nvdb_hip_ctx* c, hipStream_t s, DevBuf& b, const std::
   if (nvdb_status st = ensure(c, b, v.size() * sizeof(T))) return st;
   HIPCHK(c, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
   HIPCHK(c, hipStreamSynchronize(s));       // (the vector may go away; earlier kernels that read the buffer have finished)
+  return NVDB_OK;
+}
+
+constexpr uint32_t RUN_MAX_SLABS = 32768;          // a run's slabs are the y dimension of its collect / sort / emit grids
+
+// The tail both range routes share, from "the counts of a sub-batch are on the host" to "emit launched": hc[i] = query i's
+// count (i < b), out_off[i] = its first entry in the packed arrays (room reserved by the caller).  The slabs and their runs are
+// range_plan.h's (at most slab_max keys and RUN_MAX_SLABS slabs per run); per run the descriptors are uploaded, taken[] is
+// zeroed, collect(run, desc, taken, slab) launches the caller's collect kernel (grid y = run.size()), every length class is
+// sorted, emit(run, max_cnt, desc, slab) launches the caller's emit kernel.  run: the descriptors on the host; desc: on the device.
+template <class Collect, class Emit>
+nvdb_status range_tail(nvdb_hip_ctx* c, hipStream_t s, const char* who, const uint32_t* hc, uint32_t b, const uint64_t* out_off, uint64_t slab_max,
+                       Collect&& collect, Emit&& emit) {
+  std::vector<RpSlab> slabs;
+  std::vector<uint32_t> run_end;
+  std::vector<RangeDesc> run;
+  nvdb_status st;
+  if (!rp_slab_runs(hc, b, slab_max, RUN_MAX_SLABS, slabs, run_end)) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 results for one query");
+  size_t r0 = 0;
+  for (const uint32_t r1 : run_end) {
+    const uint64_t keys = rp_run_descs(slabs, r0, r1, out_off, run);
+    const uint32_t nrun = static_cast<uint32_t>(run.size());
+    uint32_t max_cnt = 0;
+    for (const RangeDesc& d : run) max_cnt = std::max(max_cnt, d.cnt);
+    if ((st = ensure(c, c->rg_slab, static_cast<size_t>(keys) * 8))) return st;
+    if ((st = ensure(c, c->rg_taken, static_cast<size_t>(nrun) * 4))) return st;
+    if ((st = upload(c, s, c->rg_desc, run))) return st;
+    const RangeDesc* desc = static_cast<const RangeDesc*>(c->rg_desc.p);
+    unsigned long long* slab = static_cast<unsigned long long*>(c->rg_slab.p);
+    uint32_t* taken = static_cast<uint32_t*>(c->rg_taken.p);
+    HIPCHK(c, hipMemsetAsync(taken, 0, static_cast<size_t>(nrun) * 4, s));
+    collect(run, desc, taken, slab);
+    HIPCHK(c, hipGetLastError());
+    for (uint32_t a = 0; a < nrun;) {                 // slabs of one length side by side: one sort launch per length
+      uint32_t e = a;
+      while (e < nrun && run[e].K2 == run[a].K2) ++e;
+      if ((st = launch_sort_keys(c, s, slab + run[a].slab_off, run[a].K2, e - a))) return st;
+      a = e;
+    }
+    emit(run, max_cnt, desc, slab);
+    HIPCHK(c, hipGetLastError());
+    r0 = r1;
+  }
   return NVDB_OK;
 }
 

@@ -2,59 +2,23 @@
 // partitions that is live in its mask and whose reference-order score reaches its radius.  Per sub-batch of queries:
 //   work list     parts_worklist (nvdb_partitions.cpp) with uncapped slots: an (item, query) slab holds as many entries as its segment has rows
 //   scan          range_parts_kernel appends Cand{score, row} to the slabs and pads them (kernels_range_parts.h)
-//   tail          count per query -> host: exclusive scan, slab classes (range_plan.h) -> collect keys (score, position) -> launch_sort_keys -> emit
+//   tail          count per query -> host: exclusive scan -> range_tail (nvdb_range.h): slab runs, collect keys (score, position), sort, emit
 // The host cuts a batch into consecutive query sub-batches whose candidate blocks stay within half of largek_budget_mb (the other
 // half is the key slabs') and below 2^32 entries (rp_cut); packed results are appended in query order, so the caller never sees the cut.
 // Entry points: nvdb_hip_range_search_partitions / nvdb_hip_range_search_ivf; nvdb_hip_range_search_masked (nvdb_range.cpp) sends
 // what its filter route cannot answer here, the corpus as one implicit partition.
 #include "nvdb_range.h"
 #include "kernels_range_parts.h"
-#include "range_plan.h"
 
 namespace nvdbhip {
 
 namespace {
 
-struct ScanArgs {
-  const PartItem* items; uint32_t nitems; const uint32_t* qidx; const uint32_t* dst; const float* q32; const float* radius; Cand* cand; PartMask mk;
-};
-
-template <int DT, int QW, bool AL, bool ST, bool MK>
-nvdb_status launch_one(nvdb_hip_ctx* c, hipStream_t s, const ScanArgs& a) {
-  const size_t lds = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), QW, ST);
-  if (lds > 64 * 1024)
-    if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(range_parts_kernel<DT, QW, AL, ST, MK>), PART_LDS_LIMIT)) return st;
-  range_parts_kernel<DT, QW, AL, ST, MK><<<a.nitems, PART_THREADS, lds, s>>>(c->rows, c->scales, c->dim, a.items, a.qidx, a.dst, a.q32, a.radius, a.cand, a.mk);
-  HIPCHK(c, hipGetLastError());
-  return NVDB_OK;
+nvdb_status launch_range_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const float* radius, const ScanArgs& a) {
+  return parts_dispatch(c, qw, staged, a.mk.mask_of != nullptr, [&](auto dt, auto w, auto al, auto st, auto mk) {
+    return parts_launch(c, s, range_parts_kernel<dt(), w(), al(), st(), mk()>, w(), st(), a.nitems, a.items, a.qidx, a.dst, a.q32, radius, a.cand, a.mk);
+  });
 }
-
-template <int DT, int QW, bool AL, bool ST>
-nvdb_status launch_mk(nvdb_hip_ctx* c, hipStream_t s, const ScanArgs& a) {
-  return a.mk.mask_of ? launch_one<DT, QW, AL, ST, true>(c, s, a) : launch_one<DT, QW, AL, ST, false>(c, s, a);
-}
-
-template <int DT, int QW>
-nvdb_status launch_qw(nvdb_hip_ctx* c, hipStream_t s, bool staged, const ScanArgs& a) {
-  if (staged) return launch_mk<DT, QW, true, true>(c, s, a);
-  if (aligned_rows(c->dtype, c->dim)) return launch_mk<DT, QW, true, false>(c, s, a);
-  return launch_mk<DT, QW, false, false>(c, s, a);
-}
-
-template <int DT>
-nvdb_status launch_dt(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const ScanArgs& a) {
-  if (qw == 4) return launch_qw<DT, 4>(c, s, staged, a);
-  if (qw == 2) return launch_qw<DT, 2>(c, s, staged, a);
-  return launch_qw<DT, 1>(c, s, staged, a);
-}
-
-nvdb_status launch_range_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const ScanArgs& a) {
-  if (c->dtype == NVDB_DTYPE_F32) return launch_dt<DT_F32>(c, s, qw, staged, a);
-  if (c->dtype == NVDB_DTYPE_F16) return launch_dt<DT_F16>(c, s, qw, staged, a);
-  return launch_dt<DT_I8>(c, s, qw, staged, a);
-}
-
-constexpr uint32_t RUN_MAX_SLABS = 32768;          // a run's slabs are the y dimension of its collect / sort / emit grids
 
 }  // namespace
 
@@ -78,9 +42,6 @@ nvdb_status range_parts_core(nvdb_hip_ctx* c, hipStream_t s, const char* who, co
   uint64_t before = 0;
   std::vector<uint32_t> hc;
   std::vector<uint64_t> out_off;
-  std::vector<RpSlab> slabs;
-  std::vector<uint32_t> run_end;
-  std::vector<RangeDesc> run;
   for (uint32_t q0 = 0; q0 < nr;) {
     const uint32_t q1 = rp_cut(block.data(), nr, q0, budget_entries);
     if (q1 == q0) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": one query's probed union holds 2^32 rows or more");
@@ -102,8 +63,8 @@ nvdb_status range_parts_core(nvdb_hip_ctx* c, hipStream_t s, const char* who, co
       for (int cl = 2; cl >= 0; --cl) {
         const uint32_t n_cl = static_cast<uint32_t>(ps->items[cl].size());
         if (!n_cl) continue;
-        const ScanArgs a{it, n_cl, im.qidx, im.dst, static_cast<const float*>(ps->q.p), reinterpret_cast<const float*>(im.extra), static_cast<Cand*>(ps->cand.p), im.mk};
-        if ((st = launch_range_parts(c, s, std::min<uint32_t>(pb.qw_max, 1u << cl), pb.staged, a))) return st;
+        const ScanArgs a{it, n_cl, im.qidx, im.dst, static_cast<const float*>(ps->q.p), static_cast<Cand*>(ps->cand.p), im.mk};
+        if ((st = launch_range_parts(c, s, std::min<uint32_t>(pb.qw_max, 1u << cl), pb.staged, reinterpret_cast<const float*>(im.extra), a))) return st;
         it += n_cl;
         c->stats.chunks++;
       }
@@ -126,39 +87,20 @@ nvdb_status range_parts_core(nvdb_hip_ctx* c, hipStream_t s, const char* who, co
     q0 = q1;
     if (!wl.total) continue;
     if (!reserve_packed(c, s, out, base + before, &st)) { if (st) return st; continue; }
-    if (!rp_slab_runs(hc.data(), b, slab_max, RUN_MAX_SLABS, slabs, run_end)) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 results for one query");
-    size_t r0 = 0;
-    for (const uint32_t r1 : run_end) {
-      run.clear();
-      uint32_t max_cnt = 0, max_len = 0;
-      for (size_t i = r0; i < r1; ++i) {
-        run.push_back(RangeDesc{slabs[i].slab_off, out_off[slabs[i].q], slabs[i].q, slabs[i].cnt, static_cast<uint32_t>(slabs[i].K2), 0u});
-        max_cnt = std::max(max_cnt, slabs[i].cnt);
-        max_len = std::max(max_len, ps->cbeg[slabs[i].q + 1] - ps->cbeg[slabs[i].q]);
-      }
-      const uint64_t keys = slabs[r1 - 1].slab_off + slabs[r1 - 1].K2;
-      const uint32_t nrun = static_cast<uint32_t>(run.size());
-      if ((st = ensure(c, c->rg_slab, static_cast<size_t>(keys) * 8))) return st;
-      if ((st = ensure(c, c->rg_taken, static_cast<size_t>(nrun) * 4))) return st;
-      if ((st = upload(c, s, c->rg_desc, run))) return st;
-      const RangeDesc* desc = static_cast<const RangeDesc*>(c->rg_desc.p);
-      unsigned long long* slab = static_cast<unsigned long long*>(c->rg_slab.p);
-      uint32_t* taken = static_cast<uint32_t*>(c->rg_taken.p);
-      HIPCHK(c, hipMemsetAsync(taken, 0, static_cast<size_t>(nrun) * 4, s));
-      const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>((max_len + 1023u) / 1024u, (8u * static_cast<uint32_t>(c->num_cu) + nrun - 1) / nrun));
-      rparts_collect_kernel<<<dim3(G, nrun), 256, 0, s>>>(static_cast<const Cand*>(ps->cand.p), im.cbeg, desc, taken, slab);
-      HIPCHK(c, hipGetLastError());
-      for (uint32_t a = 0; a < nrun;) {
-        uint32_t e = a;
-        while (e < nrun && run[e].K2 == run[a].K2) ++e;
-        if ((st = launch_sort_keys(c, s, slab + run[a].slab_off, run[a].K2, e - a))) return st;
-        a = e;
-      }
-      rparts_emit_kernel<<<dim3((max_cnt + 255u) / 256u, nrun), 256, 0, s>>>(slab, desc, static_cast<const Cand*>(ps->cand.p), im.cbeg, c->row_base,
-                                                                            static_cast<unsigned long long*>(c->rg_ids.p), static_cast<float*>(c->rg_scores.p));
-      HIPCHK(c, hipGetLastError());
-      r0 = r1;
-    }
+    const Cand* cand = static_cast<const Cand*>(ps->cand.p);
+    st = range_tail(c, s, who, hc.data(), b, out_off.data(), slab_max,
+        [&](const std::vector<RangeDesc>& run, const RangeDesc* desc, uint32_t* taken, unsigned long long* slab) {
+          const uint32_t nrun = static_cast<uint32_t>(run.size());
+          uint32_t max_len = 0;                          // the longest block of the run
+          for (const RangeDesc& d : run) max_len = std::max(max_len, ps->cbeg[d.q + 1] - ps->cbeg[d.q]);
+          const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>((max_len + 1023u) / 1024u, (8u * static_cast<uint32_t>(c->num_cu) + nrun - 1) / nrun));
+          rparts_collect_kernel<<<dim3(G, nrun), 256, 0, s>>>(cand, im.cbeg, desc, taken, slab);
+        },
+        [&](const std::vector<RangeDesc>& run, uint32_t max_cnt, const RangeDesc* desc, const unsigned long long* slab) {
+          rparts_emit_kernel<<<dim3((max_cnt + 255u) / 256u, static_cast<uint32_t>(run.size())), 256, 0, s>>>(
+              slab, desc, cand, im.cbeg, c->row_base, static_cast<unsigned long long*>(c->rg_ids.p), static_cast<float*>(c->rg_scores.p));
+        });
+    if (st) return st;
     HIPCHK(c, hipStreamSynchronize(s));              // the next sub-batch rewrites the blocks, the image and the descriptors
   }
   return NVDB_OK;

@@ -1,7 +1,8 @@
-// range_plan.h -- the host-side arithmetic of the partition range scan (nvdb_range_parts.cpp): where a batch is cut into query
-// sub-batches under the candidate-block budget, and what the downloaded per-query counts become -- offsets / lims, the
-// power-of-two key slabs and the runs of slabs that are collected, sorted and emitted together.  Plain C++ with no HIP in it, so
-// that the sanitizer build of tests/range_plan_check.cpp compiles the very code the entry points run.
+// range_plan.h -- the host-side arithmetic of the range searches: where the partition range scan (nvdb_range_parts.cpp) cuts a
+// batch into query sub-batches under the candidate-block budget, and what the downloaded per-query counts become on both the
+// probe path and the flat search's exact route (range_tail, nvdb_range.h) -- offsets / lims, the power-of-two key slabs, the runs
+// of slabs that are collected, sorted and emitted together, and a run's descriptors.  Plain C++ with no HIP in it, so that the
+// sanitizer build of tests/range_plan_check.cpp compiles the very code the entry points run.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -82,6 +83,24 @@ inline bool rp_slab_runs(const uint32_t* cnt, uint32_t nq, uint64_t slab_max, ui
   }
   if (!slabs.empty()) run_end.push_back(static_cast<uint32_t>(slabs.size()));
   return true;
+}
+
+// one query's share of a run's collect / sort / emit launches, as the kernels read it
+struct RangeDesc {
+  unsigned long long slab_off;       // first key of the query's slab (entries; the slabs of one K2 class are adjacent)
+  unsigned long long out_off;        // first entry of the query in the packed arrays
+  uint32_t q;                        // the query's number inside the sub-batch (row of the score matrix / candidate block)
+  uint32_t cnt;                      // entries that reach the radius
+  uint32_t K2;                       // slab length: cnt rounded up to a power of two (>= 2)
+  uint32_t pad;
+};
+
+// The descriptors of the run slabs[r0 .. r1) of rp_slab_runs; out_off[q] = query q's first entry in the packed arrays.  Returns
+// the run's keys (its last slab's end).
+inline uint64_t rp_run_descs(const std::vector<RpSlab>& slabs, size_t r0, size_t r1, const uint64_t* out_off, std::vector<RangeDesc>& run) {
+  run.clear();
+  for (size_t i = r0; i < r1; ++i) run.push_back(RangeDesc{slabs[i].slab_off, out_off[slabs[i].q], slabs[i].q, slabs[i].cnt, static_cast<uint32_t>(slabs[i].K2), 0u});
+  return r1 > r0 ? slabs[r1 - 1].slab_off + slabs[r1 - 1].K2 : 0;
 }
 
 }  // namespace nvdbhip

@@ -164,6 +164,59 @@ def test_builds(cases, dtype, dim):
         assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
+# ------------------------------------------------------------------------------------------------ one walk, two sinks
+# 12 uneven partitions over 6000 rows: an empty one, a single row, around a wave, one longer than a segment (PART_SEG_ROWS = 2048:
+# two items, a ragged last tile), the rest
+WALK_N, WALK_K = 6000, 10
+WALK_SIZES = [0, 1, 63, 64, 65, 257, 2500, 300, 700, 900, 500]
+WALK_OFFSETS = np.concatenate([[0], np.cumsum(WALK_SIZES + [WALK_N - sum(WALK_SIZES)])]).astype(np.uint64)
+WALK_ONE, WALK_BIG = 1, 6
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("dtype,dim", [(F16, 768), (I8, 100), (F32, 384)])       # staged; direct unaligned; QW = 4
+def test_topk_and_range_walk_the_same_rows(dtype, dim, masked):
+    """The top-k scan and the range scan are one tile walk with two sinks: with radius[q] = query q's k-th returned score, every
+    top-k entry is in the range slice with the same score bits, and every range entry strictly above the radius is in the top-k.
+    A query with fewer than k live rows takes radius -inf and gets exactly its top-k entries.  All 70 queries probe the one-row
+    partition (groups of 32, 32 and 6), 68 of them the 2500-row one."""
+    nq, nprobe, k = NQ_MAX, 4, WALK_K
+    assert len(WALK_OFFSETS) == 13 and WALK_SIZES[WALK_BIG] > 2048
+    base, scales = nvdb_amd.synth_corpus(SEED, ROW_BASE, WALK_N, dim, dtype)
+    queries = nvdb_amd.synth_rows_f32(SEED + 1, 0, nq, dim)
+    rs = np.random.RandomState(31 * dtype + dim)
+    probe = rs.randint(0, len(WALK_SIZES) + 1, size=(nq, nprobe)).astype(np.uint32)
+    probe[:, 0] = WALK_ONE
+    probe[:, 1] = WALK_BIG
+    probe[:2] = [WALK_ONE, EMPTY, SENT, SENT]                           # one row in all: fewer than k
+    mask_of = cycle(nq) if masked else None                              # planes of make_planes: all, none, single rows, 50 %, "no mask"
+    ctx = nvdb_amd.HipContext(0)
+    try:
+        ctx.upload_corpus(base, dtype, scales, ROW_BASE)
+        ctx.set_partitions(WALK_OFFSETS)
+        if masked:
+            ctx.set_row_masks(make_planes(WALK_N))
+            ids, sc, cnt = ctx.search_partitions_masked(queries, k, probe, mask_of)
+        else:
+            ids, sc, cnt = ctx.search_partitions(queries, k, probe)
+        assert cnt[0] == 1 and cnt.max() == k and (cnt < k).any()
+        radius = np.where(cnt < k, -INF, sc[:, k - 1]).astype(np.float32)
+        lims, rids, rsc = ctx.range_search_partitions(queries, radius, probe, mask_of)
+    finally:
+        ctx.close()
+    for q in range(nq):
+        lo, hi, m = int(lims[q]), int(lims[q + 1]), int(cnt[q])
+        in_range = dict(zip(rids[lo:hi].tolist(), rsc[lo:hi].view(np.uint32).tolist()))
+        assert len(in_range) == hi - lo, (q, "a row twice")
+        top = dict(zip(ids[q, :m].tolist(), sc[q, :m].view(np.uint32).tolist()))
+        for i, bits in top.items():
+            assert in_range.get(i) == bits, (q, i, "top-k entry missing from the range slice, or other score bits")
+        above = rids[lo:hi][rsc[lo:hi] > radius[q]].tolist()
+        assert all(i in top for i in above), (q, "a range entry above the radius that the top-k does not hold")
+        if m < k:
+            assert in_range == top, (q, "fewer than k live rows")
+
+
 # ------------------------------------------------------------------------------------------------ grouping, sizes, budgets
 @pytest.mark.parametrize("dtype,dim", [(F16, 768), (I8, 100)])
 def test_grouping_and_sizes(cases, dtype, dim):
