@@ -482,7 +482,7 @@ nvdb_status nvdb_hip_ivf_range_results(nvdb_hip_ivf* ivf, uint64_t* out_ids, flo
  * "sibling_sync", "sync_every", "sync_lead", "tile_permute", "f32_shadow", "q8_shadow" (-1 automatic, 0 never, 1 always),
  * "q8_auto_min_rows", "q8_auto_max_mb" (all set before the upload), "shadow_exact_thr" (1: a search that streams the int8 shadow
  * takes its thresholds from exact scores of its best 2k candidates, one error bound under them; 0: two bounds under the k-th filter score), "exact_mfma" (exact scores on the fp32
- * matrix cores), "exact_lds", "i8_defer", "i8_lo_bits", "boot_tiles", "xcd_balance", "rescore8", "refine_v2", "refine_pinned" (reference CUDA_PINNED:
+ * matrix cores), "exact_lds", "i8_dense8" (int8 filter, d = 768, batches > 128: 1 = 8 waves of 32 queries per workgroup, 0 = 4 of 64; same results), "i8_defer", "i8_lo_bits", "boot_tiles", "xcd_balance", "rescore8", "refine_v2", "refine_pinned" (reference CUDA_PINNED:
  * pinned host staging in nvdb_hip_refine_l2_topk), "largek_budget_mb" (HBM for the any-k path's score matrix), "range_max_mb" (packed results a range search may hold), "time_kernels" (1: start /
  * stop events attached to every launch of the dominant kernel, read by nvdb_hip_collect_kernel_times), "time_launches" (the same for one host-API
  * call with a timing struct -> stats.filter_kernel_ms).  "mfma16", "i8_wide", "i8_pipe", "i8_waves8", "i8_mfma16", "i8_small8" select kernel

@@ -411,6 +411,7 @@ nvdb_status nvdb_hip_set_option(nvdb_hip_ctx* c, const char* key, int64_t value)
   else if (k == "i8_waves8") { if (value) return fail(c, NVDB_ERR_UNSUPPORTED, "i8_waves8 = 1 selects a developer-build kernel variant (libnvdb_hip_dev.so)"); }
 #endif
 
+  else if (k == "i8_dense8") { c->opt_i8_dense8 = value ? 1 : 0; }
   else if (k == "i8_defer") { c->opt_i8_defer = value ? 1 : 0; }
   else if (k == "xcd_balance") { c->opt_xcd_balance = value ? 1 : 0; }
   else if (k == "i8_lo_bits") { if (value < 2 || value > 7) return fail(c, NVDB_ERR_INVALID, "i8_lo_bits must be in [2,7]"); c->opt_i8_lo_bits = value; }

@@ -102,7 +102,10 @@ struct nvdb_hip_ctx {
   uint32_t fdim = 0;                               // dim the filter kernels run at (>= dim; == dim without padding)
   DevBuf qdelta;                                   // int8: per query, what the lo plane can add to a filter value
   int64_t opt_i8_wide = 1;
-  int64_t opt_i8_waves8 = 0;                       // ... on 8 waves of 32 queries (two per SIMD) instead of 4 of 64: 1 % slower (profiles/r02_i8_waves8_ab.txt), off
+  int64_t opt_i8_waves8 = 0;                       // developer library: EVERY int8 build of a batch > 128 on 8 waves of 32 queries (two per SIMD) instead of 4 of 64, with the ladder of the
+                                                   // unlogged builds; off.  The product's 8-wave build is option i8_dense8
+  int64_t opt_i8_dense8 = 1;                       // int8 filter, d = 768, batches > 128: the 16x16x64 logged build on 8 waves of 32 queries -- while one wave of a SIMD logs first-stage
+                                                   // survivors the other's MFMAs keep the pipe busy: +2.4-4.0 % on the int8 shadow, +1.2-2.4 % on an int8 corpus (profiles/r07_ab_dense8.txt); 0: 4 waves of 64
   int64_t opt_i8_defer = 0;                        // pipelined build: 1 = second stage inside the tile loop (deferred v_dot4 slots), 0 = log the first stage's survivors, finish them after the stream
   int64_t opt_i8_mfma16 = 1;                       // int8 batches > 128, d = 512 / 768: the pipelined build on v_mfma_i32_16x16x64_i8 (kernels_filter_i8s.h): +7.3 % (profiles/r03_i8_mfma16_ab.txt); 0 (developer build): the 32x32x32 build
   int64_t opt_i8_pipe = 1;                         // int8 batches > 128: software-pipelined build (stage-1 test in the shadow of the other row block's MFMAs)

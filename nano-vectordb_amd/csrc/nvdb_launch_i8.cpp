@@ -37,7 +37,8 @@ template <int DIM, int WPB> auto i8s_build(bool sync) { return sync ? filter_i8s
 // int8, dims up to 768, 64-row tiles: which build streams which batch.  The product library holds
 //   batches <= 128 (NB = 1)  filter_i8w_kernel at 32 queries per wave; d = 512 / 768 and more than 8 queries (d = 384: more than 64): the
 //                            16x16x64 logged build on 8 (d = 384: 4) waves, waves without queries only load
-//   batches > 128 (NB = 2)   d >= 384: the 16x16x64 logged build (filter_i8s_kernel); d = 256: the 32x32x32 logged build (filter_i8p_kernel)
+//   batches > 128 (NB = 2)   d >= 384: the 16x16x64 logged build (filter_i8s_kernel), at d = 768 on 8 waves of 32 queries (option i8_dense8;
+//                            d = 384 / 512 / 640 on 4 of 64); d = 256: the 32x32x32 logged build (filter_i8p_kernel)
 //   option i8_defer, signed / huge row scales: the pipelined build with the in-loop second stage (filter_i8p_kernel, DEFER)
 // and the developer library every build at every batch (options i8_pipe, i8_waves8, i8_mfma16, i8_small8).
 template <int DIM, int NB>
@@ -49,8 +50,9 @@ nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t
   const bool defer = i8_stage2_in_loop(c), logs = i8_logs_survivors(c, NB);
 #ifdef NVDB_HIP_DEV
   const bool w8 = pipe && c->opt_i8_waves8 && DIM != 384;
-  constexpr bool HAS_I8W = true, HAS_I8P32 = true;
+  constexpr bool HAS_I8W = true, HAS_I8P32 = true, DEV_I8S8_512 = true;
 #else
+  constexpr bool DEV_I8S8_512 = false;
   constexpr bool w8 = false;
   constexpr bool HAS_I8W = (NB == 1);                    // the product runs filter_i8w_kernel for batches <= 128 only
   constexpr bool HAS_I8P32 = (DIM < 384);                // ... and the 32x32x32 logged build only where the 16x16x64 build does not exist
@@ -75,10 +77,12 @@ nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t
     if (c->opt_i8_small8 && !defer && f.QT == 1 && f.nq > 64)
       return launch(filter_i8s_kernel<DIM, false, false, 6, 0, 4>, 4, filter_i8s_lds_bytes<DIM, 4>());
   if (logs && c->opt_i8_mfma16) {
-#ifdef NVDB_HIP_DEV
-    if constexpr (DIM == 768 || DIM == 512)            // the 16x16x64 build on 8 waves (run at d = 768 only; measured equal to 4 waves)
-      if (w8 && DIM == 768) return launch(i8s_build<DIM, 8>(sync), 8, filter_i8s_lds_bytes<DIM, 8>());
-#endif
+    // d = 768: on 8 waves of 32 queries, two per SIMD (option i8_dense8).  A flagged block runs rare_log, serial work during which a lone wave's
+    // MFMA pipe idles; with two waves per SIMD the partner's MFMAs fill it.  Per launch of the N = 10M ladder the 8-wave build wins 10 / 10 / 5 %
+    // where many blocks are flagged and is equal on the last, sparse chunk -- but a 4-wave launch that FOLLOWS 8-wave ones ran 5 % slower than
+    // after 4-wave ones, so a search does not mix them (profiles/r07_step0_waves_per_launch.txt, r07_ab_dense8.txt)
+    if constexpr (DIM == 768 || (DEV_I8S8_512 && DIM == 512))      // (the developer library also holds the d = 512 build; it runs at d = 768 only)
+      if ((w8 || c->opt_i8_dense8) && DIM == 768) return launch(i8s_build<DIM, 8>(sync), 8, filter_i8s_lds_bytes<DIM, 8>());
     if constexpr (DIM >= 384)
       if (!w8) return launch(i8s_build<DIM, 4>(sync), 4, filter_i8s_lds_bytes<DIM, 4>());
   }
