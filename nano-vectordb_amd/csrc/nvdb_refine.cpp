@@ -15,10 +15,15 @@ static nvdb_status refine_args(nvdb_hip_ctx* c, const void* q, const void* cand,
   return NVDB_OK;
 }
 
+// what launch_refine launched, for the timing struct: the report is filled from the launch itself, not from a second reading
+// of the options
+struct RefineLaunch { uint32_t threads = 0, nwarps = 0; size_t lds = 0; };
+
 // dbg != nullptr: the stamped twin of the kernel chosen below (same arithmetic, same results; wave 0 of the first dbg_q
 // workgroups writes its phase cycles to dbg[3q ..]).
 static nvdb_status launch_refine(nvdb_hip_ctx* c, hipStream_t s, const float* dq, const uint32_t* dc, uint32_t Q, uint32_t R,
-                                 uint32_t K, uint32_t* doi, float* dod, uint64_t* dbg = nullptr, uint32_t dbg_q = 0) {
+                                 uint32_t K, uint32_t* doi, float* dod, uint64_t* dbg = nullptr, uint32_t dbg_q = 0,
+                                 RefineLaunch* launched = nullptr) {
   const bool al = aligned_rows(c->dtype, c->dim);
   nvdb_status st;
   // v3 (whole rows per request, four lanes per row): fp16 rows of 512 / 1024 / 1536 bytes
@@ -26,6 +31,7 @@ static nvdb_status launch_refine(nvdb_hip_ctx* c, hipStream_t s, const float* dq
 #define NVDB_REFINE3(D)                                                                                                        \
     {                                                                                                                          \
       constexpr size_t lds = static_cast<size_t>(REFINE3_WAVES) * refine3_slot_bytes<D>();                                      \
+      if (launched) *launched = {64 * REFINE3_WAVES, REFINE3_WAVES, lds};                                                      \
       if (dbg) {                                                                                                               \
         if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(refine_dbg_rows_kernel<D>), lds))) return st;               \
         refine_dbg_rows_kernel<D><<<Q, 64 * REFINE3_WAVES, lds, s>>>(c->rows, c->n, dq, dc, R, K, doi, dod, dbg, dbg_q);        \
@@ -42,6 +48,7 @@ static nvdb_status launch_refine(nvdb_hip_ctx* c, hipStream_t s, const float* dq
   // v2 (coalesced gather through LDS): whole 16-byte steps only (f16: dim % 8 == 0, f32: dim % 4 == 0)
   if (al && c->opt_refine_v2 && static_cast<uint64_t>(c->dim) * bpe_of(c->dtype) >= 256) {
     constexpr size_t lds = 4 * 2 * 64 * 256;
+    if (launched) *launched = {256, 4, lds};
     const bool f16 = c->dtype == NVDB_DTYPE_F16;
     const void* fn = dbg ? (f16 ? reinterpret_cast<const void*>(refine_dbg_lds_kernel<DT_F16>) : reinterpret_cast<const void*>(refine_dbg_lds_kernel<DT_F32>))
                          : (f16 ? reinterpret_cast<const void*>(refine_l2_lds_kernel<DT_F16>) : reinterpret_cast<const void*>(refine_l2_lds_kernel<DT_F32>));
@@ -56,6 +63,7 @@ static nvdb_status launch_refine(nvdb_hip_ctx* c, hipStream_t s, const float* dq
     HIPCHK(c, hipGetLastError());
     return NVDB_OK;
   }
+  if (launched) *launched = {256, 4, sizeof(float) * 4 * 64 + sizeof(uint32_t) * 4 * 64 + sizeof(uint32_t) * 4};   // v1: the merge lists only
   if (dbg) {
     if (c->dtype == NVDB_DTYPE_F16) {
       if (al) refine_dbg_kernel<DT_F16, true><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
@@ -129,9 +137,10 @@ nvdb_status nvdb_hip_refine_l2_topk(nvdb_hip_ctx* c, const float* queries, const
   HIPCHK(c, hipMemcpyAsync(c->rq.p, h_q, qb, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->rcand.p, h_c, cb, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipEventRecord(e1, s));
+  RefineLaunch launched;
   if ((st = launch_refine(c, s, static_cast<const float*>(c->rq.p), static_cast<const uint32_t*>(c->rcand.p), Q, R, K,
                           static_cast<uint32_t*>(c->rout_ids.p), out_dist ? static_cast<float*>(c->rout_dist.p) : nullptr,
-                          dbg_q ? static_cast<uint64_t*>(c->rdbg.p) : nullptr, dbg_q)))
+                          dbg_q ? static_cast<uint64_t*>(c->rdbg.p) : nullptr, dbg_q, &launched)))
     return st;
   HIPCHK(c, hipEventRecord(e2, s));
   HIPCHK(c, hipMemcpyAsync(h_oi, c->rout_ids.p, ob, hipMemcpyDeviceToHost, s));
@@ -147,10 +156,8 @@ nvdb_status nvdb_hip_refine_l2_topk(nvdb_hip_ctx* c, const float* queries, const
     (void)hipEventElapsedTime(&timing->kernel_ms, e1, e2);
     (void)hipEventElapsedTime(&timing->d2h_ms, e2, e3);
     timing->total_ms = timing->h2d_ms + timing->kernel_ms + timing->d2h_ms;
-    const bool rows_kernel = c->opt_refine_v2 >= 2 && c->dtype == NVDB_DTYPE_F16 && refine3_dim(c->dim);
-    timing->threads = rows_kernel ? 64 * REFINE3_WAVES : 256; timing->nwarps = rows_kernel ? REFINE3_WAVES : 4; timing->K = K; timing->R = R;
-    timing->shmem_bytes = rows_kernel ? static_cast<size_t>(REFINE3_WAVES) * (c->dim == 768 ? refine3_slot_bytes<768>() : c->dim == 512 ? refine3_slot_bytes<512>() : c->dim == 384 ? refine3_slot_bytes<384>() : refine3_slot_bytes<256>())
-                                      : (c->opt_refine_v2 ? 4 * 2 * 64 * 256 : 4 * 64 * 8 + 16);
+    timing->threads = launched.threads; timing->nwarps = launched.nwarps; timing->K = K; timing->R = R;
+    timing->shmem_bytes = launched.lds;
   }
   if (dbg_q) {                                   // after the events: h2d / kernel / d2h keep their meaning (cuda_refine.cu:1116-1144)
     std::vector<uint64_t> h(static_cast<size_t>(dbg_q) * 3);
