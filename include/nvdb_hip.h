@@ -296,7 +296,8 @@ nvdb_status nvdb_hip_search_ivf(nvdb_hip_ctx* ctx, const float* queries, uint32_
  * m * W + (r >> 5) is 1.  Bits at positions >= n of a plane's last word are ignored on input and read back as 0.
  * Masked entry points: the top-k searches below (k <= 64) and the range searches of the next block (nvdb_hip_range_search_partitions /
  * _ivf with masked != 0, nvdb_hip_range_search_masked, nvdb_hip_ivf_range_search).
- * NOT masked (out of scope so far): nvdb_hip_search_batch and its MFMA filter / exact / any-k routes, nvdb_hip_range_search itself, the
+ * The masked flat top-k (nvdb_hip_search_batch_masked) rides the MFMA filter kernels where the corpus is large enough to pay for it.
+ * NOT masked (out of scope so far): nvdb_hip_search_batch itself and its exact / any-k routes, nvdb_hip_range_search itself, the
  * device group, the _dev stream entry points, top-k with k > 64, the nvdb:: C++ host layer.  Those entry points, and the unmasked probe
  * searches above, ignore resident masks entirely: results, statistics and launches are what they are without masks.
  * ------------------------------------------------------------------------------------------- */
@@ -335,10 +336,23 @@ nvdb_status nvdb_hip_search_ivf_masked(nvdb_hip_ctx* ctx, const float* queries, 
                                        const uint32_t* mask_of /* [nq], may be NULL */,
                                        uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                        uint32_t* out_probe, nvdb_hip_timing* timing);
-/* The masked flat search: the whole corpus as ONE implicit partition that every query probes, on the same scan.  Needs no
- * partition table and leaves a table that is set untouched.  What this costs, plainly: the rows are read once per group of up to
- * 32 queries (16 where the LDS holds no more beside a row tile, e.g. fp16 d = 768: a batch of 1024 then reads the corpus 64 times); it is the fp32-order VALU scan, not the matrix cores -- the right tool
- * for small batches and the exact answer for large ones; the MFMA filter route of nvdb_hip_search_batch does not take masks yet.
+/* The masked flat search: exact top-k over ALL rows that are live in the query's plane.  Needs no partition table and leaves a
+ * table that is set untouched.  Two routes, one result (ids, score bits, counts, order and padding do not depend on the route):
+ *  - the partition scan (nvdb_hip_get_stats: path 4): the whole corpus as ONE implicit partition that every query probes.  What this
+ *    costs, plainly: the rows are read once per group of up to 32 queries (16 where the LDS holds no more beside a row tile, e.g.
+ *    fp16 d = 768: a batch of 1024 then reads the corpus 64 times); it is the fp32-order VALU scan, not the matrix cores.
+ *  - the MFMA filter route (path 2), per sub-batch of up to 1024 queries: per distinct plane the shortest prefix of the corpus that
+ *    holds enough live rows, the scan above over that prefix alone, whose k-th best score -- an exact score of a live row -- becomes
+ *    the query's bar; then ONE stream of the corpus through the filter kernels at thresholds fixed one error bound under the bars
+ *    (nvdb_hip_range_search's pass), the exact rescore, the drop of dead rows, and the k best of what is left.  Queries whose list
+ *    overflowed, with a non-finite element, or behind an overflowed wave log are redone on the scan, they alone; a violated filter
+ *    bound -> the sub-batch is redone on the scan and the call returns NVDB_ERR_INTERNAL.  A plane with fewer than 4 k live rows
+ *    is answered by the scan inside the same call.  Statistics: chunks = launches, rows_scanned = rows of the scan's work items +
+ *    rows streamed per query tile, candidates = list entries, overflow_queries = queries redone; nvdb_hip_shadow_info out4[3]
+ *    names what the filter streamed.
+ *  Option "path": 0 = the filter route where the corpus has a filter (as nvdb_hip_range_search decides: dtype / dim, option
+ *  "min_filter_batch", n >= 4 * option "chunk0") AND n >= 262144 rows, else the scan; 1 = the scan; 2 = the filter route, or
+ *  NVDB_ERR_UNSUPPORTED where there is no filter for the dtype / dim.  Option "cand_cap" bounds the lists as it does for the range search.
  * k > 64 -> NVDB_ERR_UNSUPPORTED (unlike nvdb_hip_search_batch, k is not clamped: out_counts says how many entries there are). */
 nvdb_status nvdb_hip_search_batch_masked(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t k,
                                          const uint32_t* mask_of /* [nq], may be NULL */,

@@ -14,6 +14,8 @@
 //   nvdb_refine.cpp        exact-L2 refine (kernels_refine.h)
 //   nvdb_partitions.cpp    partitioned probe search: partition table, coarse quantiser, work list, launches; row masks and the masked searches
 //                          (kernels_partitions.h, row_mask.h)
+//   nvdb_masked_flat.cpp   the masked flat top-k on the MFMA filter route: prefix rank, bootstrap bar, the range search's filter pass, top-k of the kept
+//                          lists (kernels_masked_topk.h, masked_plan.h)
 //   nvdb_ivf.cpp           IVF-Flat build: row assignment, spherical k-means, list layout, the reordered index (kernels_ivf.h, ivf_layout.h)
 //   nvdb_debug.cpp         developer entry points (libnvdb_hip_dev.so only)
 //   nvdb_group.cpp         device group, layered on the public ABI (does not include this header)
@@ -184,6 +186,9 @@ struct nvdb_hip_ctx {
   nvdbhip::PartState* parts = nullptr;             // partitioned probe search (created by nvdb_hip_set_partitions, or by the first masked flat search)
   DevBuf row_masks, mask_rows;                     // row masks (nvdb_hip_set_row_masks): [nmasks][ceil(n / 32)] words; staging of nvdb_hip_update_row_mask's row list
   uint32_t nmasks = 0;                             // ... planes resident (0: none; any corpus load drops them, the buffer stays)
+  std::vector<uint64_t> mask_live;                 // ... and their live rows as the host knows them: counted when the planes are set, moved by the length of every
+                                                   // update's row list (an ESTIMATE -- a list may name a row twice or a row already in that state); read by the masked
+                                                   // flat search's automatic route only, never by a result
 };
 
 #define HIPCHK(ctx, call)                                                                        \

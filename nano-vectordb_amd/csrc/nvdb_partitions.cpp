@@ -17,7 +17,8 @@
 // of min(k, rows).
 // A masked search is the same work list with every query's mask number appended to the pinned image; the MASKED builds of the
 // scan test a row's bit before they offer it, and the select kernel writes the counts the host can no longer derive.  The
-// masked flat search runs the corpus as one implicit partition that every query probes.
+// masked flat search runs the corpus as one implicit partition that every query probes -- or, where its plan says so, rides the MFMA
+// filter kernels (nvdb_masked_flat.cpp), which calls back into this scan for its bootstrap and for flagged queries.
 #include "nvdb_parts.h"
 
 namespace nvdbhip {
@@ -41,15 +42,11 @@ void parts_destroy(nvdb_hip_ctx* c) {
   c->parts = nullptr;
 }
 
-namespace {
-
 nvdb_status launch_scan_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, uint32_t k, const ScanArgs& a) {
   return parts_dispatch(c, qw, staged, a.mk.mask_of != nullptr, [&](auto dt, auto w, auto al, auto st, auto mk) {
     return parts_launch(c, s, scan_parts_kernel<dt(), w(), al(), st(), mk()>, w(), st(), a.nitems, a.items, a.qidx, a.dst, a.q32, k, a.cand, a.mk);
   });
 }
-
-}  // namespace
 
 nvdb_status parts_args(nvdb_hip_ctx* c, const char* who) {
   if (!c) return NVDB_ERR_INVALID;
@@ -227,8 +224,6 @@ nvdb_status parts_coarse(nvdb_hip_ctx* c, const char* who, const float* queries,
   return NVDB_OK;
 }
 
-namespace {
-
 // the search proper over the table off[0 .. nparts]; the caller has validated the context, nq > 0 and 0 < k <= 64.
 // msel != nullptr: the masked search (the caller has checked mask_of against the resident planes)
 nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe,
@@ -310,6 +305,8 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, 
   }
   return NVDB_OK;
 }
+
+namespace {
 
 void pad_outputs(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
   for (size_t i = 0; i < static_cast<size_t>(nq) * k; ++i) { out_ids[i] = ~0ull; out_scores[i] = NEG_INF; }
@@ -413,6 +410,9 @@ nvdb_status nvdb_hip_set_row_masks(nvdb_hip_ctx* c, const uint32_t* bits, uint32
   if (bits) planes.assign(bits, bits + words);
   else planes.assign(words, 0xFFFFFFFFu);
   for (uint32_t m = 0; m < nmasks; ++m) rm_clear_tail(planes.data() + static_cast<size_t>(m) * W, c->n);
+  c->mask_live.assign(nmasks, 0);
+  for (uint32_t m = 0; m < nmasks; ++m)
+    for (uint64_t w = 0; w < W; ++w) c->mask_live[m] += static_cast<uint64_t>(__builtin_popcount(planes[static_cast<size_t>(m) * W + w]));
   HIPCHK(c, hipSetDevice(c->device));
   c->nmasks = 0;                                   // (a failure below leaves no masks, not half of the new ones)
   if (nvdb_status st = ensure(c, c->row_masks, words * 4)) return st;
@@ -438,6 +438,10 @@ nvdb_status nvdb_hip_update_row_mask(nvdb_hip_ctx* c, uint32_t mask, const uint6
   update_row_mask_kernel<<<static_cast<unsigned>((nrows + 255) / 256), 256, 0, c->stream>>>(plane, static_cast<const uint32_t*>(c->mask_rows.p), nrows, live != 0);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (mask < c->mask_live.size()) {
+    uint64_t& est = c->mask_live[mask];
+    est = live ? std::min<uint64_t>(c->n, est + nrows) : (est > nrows ? est - nrows : 0);
+  }
   return NVDB_OK;
 }
 
@@ -479,11 +483,7 @@ nvdb_status nvdb_hip_search_batch_masked(nvdb_hip_ctx* c, const float* queries, 
   if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
   if (nvdb_status st = mask_args(c, mask_of, nq, "search_batch_masked")) return st;
   parts_workspace(c);                              // the workspace only: no table is set, a table that is set stays as it is
-  // the corpus as one implicit partition that every query probes
-  const uint64_t off[2] = {0, c->n};
-  c->parts->probe_tmp.assign(nq, 0u);
-  const MaskSel msel{mask_of};
-  return parts_search(c, off, 1, queries, nq, k, c->parts->probe_tmp.data(), 1, &msel, out_ids, out_scores, out_counts, timing);
+  return masked_flat_search(c, queries, nq, k, mask_of, out_ids, out_scores, out_counts, timing);
 }
 
 }  // extern "C"

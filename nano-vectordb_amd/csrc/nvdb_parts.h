@@ -119,6 +119,18 @@ PartState* parts_workspace(nvdb_hip_ctx* c);
 nvdb_status parts_coarse(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, uint32_t nprobe, uint32_t* out_probe, nvdb_hip_timing* timing,
                          uint32_t& np);
 
+// one launch of scan_parts_kernel's build for this corpus (qw queries per wave) over the items of `a`
+nvdb_status launch_scan_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, uint32_t k, const ScanArgs& a);
+
+// The probe search proper over the table off[0 .. nparts]: the caller has validated the context, nq > 0 and 0 < k <= 64.
+// msel != nullptr: the masked search (the caller has checked mask_of against the resident planes).  Replaces c->stats (path 4).
+nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe,
+                         uint32_t nprobe, const MaskSel* msel, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing);
+
+// nvdb_hip_search_batch_masked behind its argument checks (nvdb_masked_flat.cpp): the MFMA filter route where the plan takes it
+nvdb_status masked_flat_search(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t k, const uint32_t* mask_of, uint64_t* out_ids, float* out_scores,
+                               uint32_t* out_counts, nvdb_hip_timing* timing);
+
 // the context holds a corpus and a partition table
 nvdb_status parts_args(nvdb_hip_ctx* c, const char* who);
 

@@ -15,16 +15,6 @@
 
 namespace nvdbhip {
 
-namespace {
-
-struct RangePlan {
-  const char* error = nullptr;
-  bool filter = false;                  // the filter route serves this call's sub-batches (else: the exact route alone)
-  bool prep_inits = false, perm_on = false, tail_exact = false;
-  uint32_t cap = 0, QPB = 0, QT = 0, nq_pad = 0, prog_words = 0, tile_rows = 0, n_al = 0;
-  uint32_t launch_rows = 0;             // rows per filter launch
-};
-
 // Pure arithmetic over corpus facts and options, like plan_search (and like it, it sets use_shadow, which the shape helpers read).
 nvdb_status plan_range(nvdb_hip_ctx& ctx, uint32_t nq, RangePlan& p) {
   ctx.use_shadow = shadow_preferred(&ctx);
@@ -63,6 +53,8 @@ nvdb_status plan_range(nvdb_hip_ctx& ctx, uint32_t nq, RangePlan& p) {
   p.perm_on = c->opt_tile_permute && c->fdim <= 768;
   return NVDB_OK;
 }
+
+namespace {
 
 // ---- exact route: ne queries at dev_q / dev_radius; qmap[i] = query i's number inside its sub-batch (ascending).  Fills cnt[qmap[i]]
 // and, while the call packs, emits query i's slice at base + (sum of cnt[] before qmap[i]) -- the counts of every earlier query of the
@@ -117,11 +109,7 @@ nvdb_status range_exact(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, cons
   return NVDB_OK;
 }
 
-// what the host reads of one filter pass
-struct FilterVerdict {
-  std::vector<uint32_t> kept, overflow, listcnt;
-  uint32_t misc[8] = {0};
-};
+}  // namespace
 
 // ---- filter route of one sub-batch: everything up to the ordered slabs in c->cand and their counts in c->rg_kept
 // dmask_of != nullptr: the masked search -- the keep step also requires the row's bit in the query's plane (everything before it is the unmasked pass)
@@ -182,8 +170,6 @@ nvdb_status range_filter_pass(nvdb_hip_ctx* c, hipStream_t s, const RangePlan& p
   HIPCHK(c, hipStreamSynchronize(s));
   return NVDB_OK;
 }
-
-}  // namespace
 
 nvdb_status range_search_flat(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, const float* radius, const MaskSel* msel, uint64_t* out_lims,
                               nvdb_hip_timing* timing) {

@@ -101,6 +101,27 @@ nvdb_status range_parts_core(nvdb_hip_ctx* c, hipStream_t s, const char* who, co
                              uint32_t nr, const uint32_t* probe, uint32_t nprobe, const MaskSel* msel, const uint32_t* qmap, std::vector<uint64_t>& cnt,
                              uint64_t base, RangeOut& out);
 
+// ---- the flat range search's plan and filter pass (nvdb_range.cpp), as the masked flat top-k (nvdb_masked_flat.cpp) calls them
+struct RangePlan {
+  const char* error = nullptr;
+  bool filter = false;                  // the filter route serves this call's sub-batches (else: the exact route alone)
+  bool prep_inits = false, perm_on = false, tail_exact = false;
+  uint32_t cap = 0, QPB = 0, QT = 0, nq_pad = 0, prog_words = 0, tile_rows = 0, n_al = 0;
+  uint32_t launch_rows = 0;             // rows per filter launch
+};
+// the route and shapes of one sub-batch of nq queries; p.error: why a forced route is refused
+nvdb_status plan_range(nvdb_hip_ctx& ctx, uint32_t nq, RangePlan& p);
+
+// what the host reads of one filter pass
+struct FilterVerdict {
+  std::vector<uint32_t> kept, overflow, listcnt;
+  uint32_t misc[8] = {0};
+};
+// filter route of one sub-batch: everything up to the ordered slabs in c->cand and their counts in c->rg_kept, then the verdict's
+// read-back (synchronises the stream).  dmask_of != nullptr: the keep step also requires the row's bit in the query's plane
+nvdb_status range_filter_pass(nvdb_hip_ctx* c, hipStream_t s, const RangePlan& p, const float* dq, const float* dradius, uint32_t nq, const uint32_t* dmask_of,
+                              FilterVerdict& v);
+
 // nvdb_hip_range_search and nvdb_hip_range_search_masked (msel != nullptr; nvdb_range.cpp)
 nvdb_status range_search_flat(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, const float* radius, const MaskSel* msel, uint64_t* out_lims,
                               nvdb_hip_timing* timing);

@@ -590,8 +590,10 @@ class HipContext:
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
     def search_masked(self, queries, k, mask_of=None, want_timing=False):
-        """The masked flat search (nvdb_hip_search_batch_masked): exact top-k over ALL live rows, k <= 64, on the partition scan --
-        the rows are read once per group of up to 32 queries; the MFMA filter route of search_batch takes no masks."""
+        """The masked flat search (nvdb_hip_search_batch_masked): exact top-k over ALL live rows, k <= 64.  Large corpora with an
+        MFMA filter (option path = 0: at least 262144 rows; path = 2: always) take the filter route -- a bar per query from a
+        prefix that holds enough live rows, then one stream of the corpus (stats path 2); the others the partition scan, which
+        reads the rows once per group of up to 32 queries (stats path 4).  The result does not depend on the route."""
         queries, nq, ids, scores, counts = self._probe_outputs(queries, k)
         mo = _mask_of_arg(mask_of, nq)
         t = Timing()

@@ -1,11 +1,13 @@
 """Masked searches against their unmasked twins on the same context in the same process.
 
-    python tools_dev/bench_masked.py [rows] [dim] [dtype] [nparts] [batch] [nprobe] [k] [calls] [warmup]
-                                     (defaults: 10000000 768 f16 4096 1024 8 10 20 3)
+    python tools_dev/bench_masked.py [rows] [dim] [dtype] [nparts] [batch] [nprobe] [k] [calls] [warmup] [flat_only]
+                                     (defaults: 10000000 768 f16 4096 1024 8 10 20 3 0)
 
 Equal partitions, random probes.  Reports the median wall ms per call of search_partitions (unmasked) beside
-search_partitions_masked under an all-live mask, a random 50 % and 1 % mask and a contiguous 10 % mask; then search_masked (the
-masked flat search) at batch 1 / 8 / 32 under the 50 % mask beside search_batch at the same batches; and one JSON line with all of it."""
+search_partitions_masked under an all-live mask, a random 50 % and 1 % mask and a contiguous 10 % mask (skipped with flat_only = 1);
+then search_masked (the masked flat search) at batch 1 / 8 / 32 / 128 / 1024 under the all-live, the 50 % and the 1 % mask beside
+search_batch at the same batches, with the route it took (stats path: 2 = MFMA filter route, 4 = partition scan); and one JSON line
+with all of it."""
 import json
 import os
 import sys
@@ -42,6 +44,7 @@ def main():
     k = int(a[6]) if len(a) > 6 else 10
     calls = int(a[7]) if len(a) > 7 else 20
     warmup = int(a[8]) if len(a) > 8 else 3
+    flat_only = int(a[9]) if len(a) > 9 else 0
     seed = 20240613
     ctx = nvdb_amd.HipContext(0)
     ctx.generate_corpus(seed, rows, dim, dtype)
@@ -58,31 +61,38 @@ def main():
     ctx.set_row_masks(planes)
     out = dict(rows=rows, dim=dim, dtype=dname, nparts=nparts, batch=batch, nprobe=nprobe, k=k, calls=calls, warmup=warmup)
 
-    uid, usc, ucnt = ctx.search_partitions(q, k, probe)
-    med, lo, hi = median_ms(lambda: ctx.search_partitions(q, k, probe), calls, warmup)
-    st = ctx.stats()
-    base = med
-    out["search_partitions"] = dict(median_ms=med, min_ms=lo, max_ms=hi, rows_scanned=st["rows_scanned"], launches=st["chunks"])
-    print(f"search_partitions                       : median {med:8.3f} ms  (min {lo:.3f}, max {hi:.3f})  rows read {st['rows_scanned']} launches {st['chunks']}")
-    for m, name in enumerate(names):
-        mo = np.full(batch, m, dtype=np.uint32)
-        ids, sc, cnt = ctx.search_partitions_masked(q, k, probe, mo)
-        same = bool(np.array_equal(ids, uid) and np.array_equal(sc.view(np.uint32), usc.view(np.uint32)) and np.array_equal(cnt, ucnt)) if m == 0 else None
-        med, lo, hi = median_ms(lambda: ctx.search_partitions_masked(q, k, probe, mo), calls, warmup)
-        out[f"search_partitions_masked/{name}"] = dict(median_ms=med, min_ms=lo, max_ms=hi, vs_unmasked=med / base, mean_count=float(cnt.mean()), equals_unmasked=same)
-        print(f"search_partitions_masked {name:15s}: median {med:8.3f} ms  (min {lo:.3f}, max {hi:.3f})  x{med / base:.3f} of unmasked  mean count {cnt.mean():.2f}"
-              + (f"  equals the unmasked result: {same}" if m == 0 else ""))
-    for b in (1, 8, 32):
+    if not flat_only:
+        uid, usc, ucnt = ctx.search_partitions(q, k, probe)
+        med, lo, hi = median_ms(lambda: ctx.search_partitions(q, k, probe), calls, warmup)
+        st = ctx.stats()
+        base = med
+        out["search_partitions"] = dict(median_ms=med, min_ms=lo, max_ms=hi, rows_scanned=st["rows_scanned"], launches=st["chunks"])
+        print(f"search_partitions                       : median {med:8.3f} ms  (min {lo:.3f}, max {hi:.3f})  rows read {st['rows_scanned']} launches {st['chunks']}")
+        for m, name in enumerate(names):
+            mo = np.full(batch, m, dtype=np.uint32)
+            ids, sc, cnt = ctx.search_partitions_masked(q, k, probe, mo)
+            same = bool(np.array_equal(ids, uid) and np.array_equal(sc.view(np.uint32), usc.view(np.uint32)) and np.array_equal(cnt, ucnt)) if m == 0 else None
+            med, lo, hi = median_ms(lambda: ctx.search_partitions_masked(q, k, probe, mo), calls, warmup)
+            out[f"search_partitions_masked/{name}"] = dict(median_ms=med, min_ms=lo, max_ms=hi, vs_unmasked=med / base, mean_count=float(cnt.mean()), equals_unmasked=same)
+            print(f"search_partitions_masked {name:15s}: median {med:8.3f} ms  (min {lo:.3f}, max {hi:.3f})  x{med / base:.3f} of unmasked  mean count {cnt.mean():.2f}"
+                  + (f"  equals the unmasked result: {same}" if m == 0 else ""))
+    for b in (1, 8, 32, 128, 1024):
+        if b > batch:
+            continue
         qb = np.ascontiguousarray(q[:b])
-        mo = np.full(b, 1, dtype=np.uint32)
         medf, lof, hif = median_ms(lambda: ctx.search_batch(qb, k), calls, warmup)
         pathf = ctx.stats()["path"]
-        medm, lom, him = median_ms(lambda: ctx.search_masked(qb, k, mo), calls, warmup)
-        st = ctx.stats()
-        out[f"flat/batch{b}"] = dict(search_batch_median_ms=medf, search_batch_path=pathf, search_masked_median_ms=medm, min_ms=lom, max_ms=him,
-                                     rows_scanned=st["rows_scanned"], launches=st["chunks"])
-        print(f"batch {b:3d}: search_batch median {medf:8.3f} ms (path {pathf})   search_masked (50 % live) median {medm:8.3f} ms  (min {lom:.3f}, max {him:.3f})  "
-              f"rows read {st['rows_scanned']}")
+        row = dict(search_batch_median_ms=medf, search_batch_min_ms=lof, search_batch_max_ms=hif, search_batch_path=pathf)
+        line = f"batch {b:4d}: search_batch median {medf:8.3f} ms (path {pathf})  search_masked"
+        for m, name in enumerate(names[:3]):
+            mo = np.full(b, m, dtype=np.uint32)
+            medm, lom, him = median_ms(lambda: ctx.search_masked(qb, k, mo), calls, warmup)
+            st = ctx.stats()
+            row[name] = dict(median_ms=medm, min_ms=lom, max_ms=him, path=st["path"], rows_scanned=st["rows_scanned"], launches=st["chunks"],
+                             overflow_queries=st["overflow_queries"], vs_search_batch=medm / medf)
+            line += f" | {name}: {medm:8.3f} ms (min {lom:.3f}, max {him:.3f}; path {st['path']}, rows read {st['rows_scanned']}, flagged {st['overflow_queries']})"
+        out[f"flat/batch{b}"] = row
+        print(line, flush=True)
     print(json.dumps(out))
     ctx.close()
 
