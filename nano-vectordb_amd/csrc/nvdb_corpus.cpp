@@ -418,6 +418,7 @@ nvdb_status nvdb_hip_set_option(nvdb_hip_ctx* c, const char* key, int64_t value)
   else if (k == "boot_tiles") { if (value < 0 || value > SELECT_MAX_CAP) return fail(c, NVDB_ERR_INVALID, "boot_tiles out of range"); c->opt_boot_tiles = value; }
 #ifdef NVDB_HIP_DEV
   else if (k == "debug_rows") { c->dbg_rows = value < 0 ? 0 : value; }
+  else if (k == "debug_bound_pct") { if (value < 1 || value > 100) return fail(c, NVDB_ERR_INVALID, "debug_bound_pct must be in [1,100]"); c->dbg_bound_pct = value; }
 #endif
   else if (k == "waves8") { c->opt_waves8 = value ? 1 : 0; }
   else if (k == "fuse") { c->opt_fuse = value ? 1 : 0; }

@@ -149,6 +149,7 @@ struct nvdb_hip_ctx {
   int64_t opt_boot_tiles = 0;                      // threshold bootstrap over this many 32-row tile maxima (0: max(64, 8k))
   int64_t opt_i8_small8 = 1;                       // int8 d = 512 / 768, batches <= 128: 1 = the 8-wave 16x16x64 logged build, 0 = filter_i8w_kernel<768, 1> (developer library)
   int64_t dbg_rows = 0;                            // developer build: rows the stamped launches of nvdb_hip_debug_clock_i8 cover (0: the corpus)
+  int64_t dbg_bound_pct = 100;                     // developer build: per cent of max_norm / filter_max_norm / resid_max the query prep is handed (tests/test_gpu_filter_bound.py: a case must fail under a short bound)
   DevBuf lk_scores, lk_sel, lk_hist, lk_state;     // any-k path (kernels_largek.h): score matrix of a query sub-batch, selected keys, radix state
   int64_t opt_refine_pinned = 0;                   // refine host call: stage queries / candidates / results through pinned host buffers (reference CUDA_PINNED)
   int64_t opt_refine_dbg_q = 0;                    // refine host call with a timing struct: the first min(this, Q) queries run the stamped twin kernel (reference CUDA_DBG_TIMING / CUDA_DBG_Q); 0 = off
@@ -339,6 +340,15 @@ nvdb_status score_matrix_batch(nvdb_hip_ctx* c, uint32_t nq, size_t per_query_by
 nvdb_status launch_score_matrix(nvdb_hip_ctx* c, hipStream_t s, const float* q32, uint32_t nq, float* scores, uint64_t ld, uint32_t n, uint32_t QG, bool mfma_ok);
 nvdb_status launch_sort_keys(nvdb_hip_ctx* c, hipStream_t s, unsigned long long* keys, uint32_t K2, uint32_t lists);
 // nvdb_launch_f16.cpp / nvdb_launch_i8.cpp
+// a corpus norm as the query prep kernels get it: the developer library scales it by option debug_bound_pct (100: unchanged, x * 1.0f)
+inline float prep_norm(const nvdb_hip_ctx* c, float v) {
+#ifdef NVDB_HIP_DEV
+  return v * (static_cast<float>(c->dbg_bound_pct) / 100.f);
+#else
+  (void)c;
+  return v;
+#endif
+}
 nvdb_status launch_prep_q16(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint32_t nq, uint32_t nq_pad, const PrepInit& pinit);
 nvdb_status launch_prep_q8(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint32_t nq, uint32_t nq_pad, const PrepInit& pinit);
 nvdb_status launch_filter_f16(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint32_t row_hi, uint32_t nq, uint32_t QT, uint32_t cap);

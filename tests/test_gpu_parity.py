@@ -1620,6 +1620,9 @@ def test_product_library_rejects_developer_variants(ctx):
             ctx.set_option(key, val)
         assert e.value.status == 3 and "developer-build" in str(e.value)
         ctx.set_option(key, 1 - val)                         # the default value is accepted
+    with pytest.raises(nvdb_amd.NvdbError) as e:             # the developer library's bound scale (tests/test_gpu_filter_bound.py): an unknown option here
+        ctx.set_option("debug_bound_pct", 100)
+    assert e.value.status == 1 and "unknown option" in str(e.value)
 
 
 def test_randomised_cross_check():
