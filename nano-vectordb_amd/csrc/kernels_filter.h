@@ -21,6 +21,18 @@
 // filter_i8w_kernel (int8 two-stage: hi plane always, lo plane on demand), filter_i8_kernel (int8 two-plane:
 // bootstrap build, A/B reference), prep_q16 / prep_q8 (query scaling, error bounds), shadow / generator / norm kernels.
 //
+// What the seven filter kernels (filter_i8s_kernel, kernels_filter_i8s.h, included) have in common that is NOT arithmetic is
+// written once, ahead of the first kernel ("shared pieces of the filter kernels" below): xcd_aware_grid (the one predicate
+// host and device share) and stream_place (workgroup -> row stream, query tile, tile range), piece_src_offsets (the swizzled
+// source offsets of a wave's direct-to-LDS pieces, swz_chunk), stamp_begin / stamp_store (STAMP builds), stream_exit (SYNC
+// release and XCD speed) and i8_stage1_bar (the int8 first-stage threshold).  Tile loops, MFMA schedules, rings, wait counts,
+// barriers and the survivor-log append stay with each kernel.  The two-stage int8 kernels (filter_i8w / i8p / i8s) also keep
+// placement and exit written out, around xcd_aware_grid: through stream_place they spill more scalar registers.
+// filter_i8s_kernel, the int8 flagship, shares xcd_aware_grid and i8_stage1_bar only, and the filing of a survivor under its
+// query stays written out in scatter_own_log and in verify_and_scatter_i8 (that kernel's tail): with filter_i8s_kernel on
+// piece_src_offsets and the stamps and both scatters on one filing function, the int8 flat search measured 0.2 - 0.45 % above
+// the parent's own spread in three alternating runs out of three (profiles/filter_shared_pieces_ab.txt); as it stands, inside.
+//
 // The MFMA result is only a FILTER: |filter - reference score| <= ebound[q] (prep kernels), every
 // survivor is re-scored in the reference's exact fp32 order afterwards (kernels_exact.h).
 #pragma once
@@ -254,6 +266,88 @@ __host__ __device__ __forceinline__ void perm_params(uint32_t T, uint32_t& mul, 
   mul = (static_cast<uint32_t>(0.6180339887 * m) | 1u) & mask;    // odd: a bijection modulo the power of two
 }
 
+// ------------------------------------------------------------------------------------------------
+// shared pieces of the filter kernels: placement, loader offsets, stamps, exit, the int8 first-stage bar
+// ------------------------------------------------------------------------------------------------
+// The XCD-aware mapping of a grid of nwg workgroups over QT query tiles is active: the QT workgroups of a row stream share an
+// XCD label.  The launchers ask this to decide whether the SYNC build runs and how `prog` is laid out (nvdb_ctx.h), the kernels
+// to place themselves (stream_place): one predicate for both.
+__host__ __device__ __forceinline__ bool xcd_aware_grid(uint32_t QT, uint32_t nwg) { return (nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0; }
+
+// Workgroup b of the grid -> row stream and query tile, and the stream's tiles [t_lo, t_lo + NT) of the launch's tiles_total.
+// XCD label = b % 8; under the XCD-aware mapping the QT workgroups that stream the same rows against different query tiles are
+// consecutive on the same label, so that they share that XCD's L2.  NT == 0: nothing to do, the kernel returns.
+struct StreamPlace { uint32_t stream, qt, t_lo, NT; bool xcd_map; };
+__device__ __forceinline__ StreamPlace stream_place(uint32_t QT, uint32_t tiles_total, const float* xcdw) {
+  const uint32_t nwg = gridDim.x, b = blockIdx.x;
+  StreamPlace p;
+  p.xcd_map = xcd_aware_grid(QT, nwg);
+  if (p.xcd_map) {
+    const uint32_t xcd = b & 7u, i = b >> 3;       // i-th workgroup of this XCD label
+    p.qt = i % QT;
+    p.stream = (i / QT) * 8u + xcd;
+  } else { p.qt = b % QT; p.stream = b / QT; }
+  uint32_t t_hi;
+  stream_tile_range(tiles_total, nwg / QT, p.stream, p.xcd_map, xcdw, p.t_lo, t_hi);
+  p.NT = t_hi - p.t_lo;
+  return p;
+}
+
+// LDS image of a tile: chunk c (16 bytes) of row r sits at chunk position swz_chunk(c, r) of its row, so that the 16 rows a
+// ds_read_b128 group touches at one k-offset fall into 16 different 16-byte bank groups.  Row strides that are multiples of 256
+// bytes (every fp16 build; int8 at d = 256, 512, 768) start every row in the same bank group: c ^ (r & 15), the XOR stays inside
+// a 16-chunk = 256-byte bank row.  Odd multiples of 128 bytes (int8 at d = 384, the reference's own data dimension) start
+// consecutive rows 8 bank groups apart -- (r & 1) already picks the half, (r >> 1) & 7 the place inside it.
+template <int ROW_BYTES> __device__ constexpr bool swz16() { return (ROW_BYTES / 16) % 16 == 0; }
+template <int ROW_BYTES> __device__ inline uint32_t swz_chunk(uint32_t c, uint32_t r) {
+  static_assert(ROW_BYTES % 128 == 0, "row stride of the LDS image: a multiple of 128 bytes");
+  return swz16<ROW_BYTES>() ? c ^ (r & 15u) : c ^ ((r >> 1) & 7u);
+}
+
+// Per-lane source offsets of a wave's PPW direct-to-LDS pieces (1 KB = 64 lanes x 16 bytes each).  The LDS side of such a load
+// is linear (M0 base + lane * 16), so the swizzle is applied to the per-lane GLOBAL address: LDS position P = piece * 64 + lane
+// of the stage takes row r = P / CPR, chunk swz_chunk(P % CPR, r), CPR = ROW_BYTES / 16 chunks per row of the image.
+// SRC_STRIDE: bytes between rows in memory where a stage holds only part of each row (filter_f16_k2_kernel's half-K stages).
+template <int ROW_BYTES, int PPW, int SRC_STRIDE = ROW_BYTES>
+__device__ __forceinline__ void piece_src_offsets(int wave, int lane, uint32_t (&src_off)[PPW]) {
+  constexpr uint32_t CPR = ROW_BYTES / 16;
+#pragma unroll
+  for (int i = 0; i < PPW; ++i) {
+    const uint32_t P = static_cast<uint32_t>((wave * PPW + i) * 64 + lane);
+    const uint32_t r = P / CPR, cpos = P % CPR;
+    src_off[i] = r * SRC_STRIDE + (swz_chunk<ROW_BYTES>(cpos, r) << 4);
+  }
+}
+
+// NOT shared: the append to a wave's survivor log (ballot, prefix count, `idx < FILTER_LOGCAP` store, count update).  As a
+// function it changes the register allocation around it (filter_f16_m16_kernel<768, .., WPB = 8> then spills a VGPR).  Every
+// copy keeps: the count runs on past FILTER_LOGCAP (how the scatter learns of the overflow), the stores do not.
+
+// STAMP builds (developer library only): clock and real-time stamps around the tile loop; wave 0 stores the two differences
+// behind the grid's progress counters, where nothing else reads them.
+__device__ __forceinline__ void stamp_begin(uint64_t& stamp_c, uint64_t& stamp_r) {
+  stamp_c = __builtin_amdgcn_s_memtime(); stamp_r = __builtin_amdgcn_s_memrealtime();
+}
+__device__ __forceinline__ void stamp_store(uint32_t* prog, uint64_t dc, uint64_t dr) {
+  uint64_t* out = reinterpret_cast<uint64_t*>(prog + static_cast<uint64_t>(gridDim.x) * 8) + static_cast<uint64_t>(blockIdx.x) * 2;
+  out[0] = dc; out[1] = dr;
+}
+
+// End of a workgroup's stream: a SYNC build releases its progress counter prog[stream * 8 + qt] (0xFFFFFFFF = "far ahead": the
+// siblings stop waiting for it), then wave 0 files the tile loop's time under the XCD label.  xw_t0: s_memrealtime before the
+// loop.  (The two-stage int8 kernels add up their stage counts BETWEEN these two steps and keep all three written out.)
+template <bool SYNC>
+__device__ __forceinline__ void stream_exit(uint32_t* prog, const StreamPlace& p, float* xcdw, int wave, int lane, uint32_t xw_t0) {
+  if constexpr (SYNC) { if (wave == 0 && lane == 0) __hip_atomic_store(prog + static_cast<uint64_t>(p.stream) * 8 + p.qt, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  if (wave == 0 && lane == 0) record_xcd_speed(xcdw, p.xcd_map, p.stream & 7u, p.NT, static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime()) - xw_t0);
+}
+
+// int8 two-stage builds: first-stage threshold for H * scale (the factor 2^lo_bits moved to this side, exactly, as lo_unit): a
+// little below T - delta, the margin covering the fp32 roundings of both stages' values.  A term of the documented error bound.
+__device__ __forceinline__ float i8_stage1_bar(float T, float qdelta, float lo_unit) {
+  return (T - (1.001f * qdelta + 2e-6f * fabsf(T) + 1e-5f)) * lo_unit;
+}
+
 // File this wave's logged survivors under their queries (cand[qid][slot], slot from an atomic counter).  Runs
 // once, after the tile loop: nothing is in flight any more, so the returning atomics cost nothing in the loop.
 __device__ __forceinline__ void scatter_own_log(const Hit* mylog, uint32_t wcnt, const ScatterArgs& a, int lane) {
@@ -298,13 +392,12 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
   constexpr int STAGE_BYTES = FILTER_ROWS * ROW_BYTES;
   constexpr int PIECES = STAGE_BYTES / 1024;       // 1 KB direct-to-LDS pieces per stage
   constexpr int PPW = PIECES / 4;                  // pieces per wave
-  constexpr int CHUNKS_PER_ROW = ROW_BYTES / 16;
   constexpr int NFRAG = NB * KSTEPS;               // B fragments per wave
   constexpr int NFRAG_A = NFRAG < 64 ? NFRAG : 64; // ... of which this many live in AGPRs
   constexpr int NFRAG_V = NFRAG - NFRAG_A;
   constexpr int QPW = 32 * NB, QPB = 4 * QPW;      // queries per wave / per workgroup
   static_assert(NB == 1 || NB == 2, "one or two 32-query blocks per wave");
-  static_assert(DIM % 128 == 0, "swizzle assumes row stride is a multiple of 256 bytes");
+  static_assert(DIM % 128 == 0 && swz16<ROW_BYTES>(), "a_base below assumes the c ^ (r & 15) image: row stride a multiple of 256 bytes");
   static_assert(PIECES % 4 == 0, "pieces must split evenly over 4 waves");
   static_assert(KSTEPS <= 64, "query block 0 must fit the AGPR-resident fragments");
   static_assert(FILTER_STAGES * STAGE_BYTES == filter_f16_lds_bytes<DIM>(), "the launchers size the dynamic LDS with filter_f16_lds_bytes");
@@ -316,19 +409,8 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
   const uint32_t wave_gid = blockIdx.x * 4 + wave;
 
   // ---- workgroup -> (row stream, query tile) ---------------------------------------------------
-  const uint32_t nwg = gridDim.x, b = blockIdx.x;
-  const uint32_t S = nwg / QT;
-  uint32_t stream, qt;
-  if ((nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0) {
-    const uint32_t xcd = b & 7u, i = b >> 3;       // i-th workgroup of this XCD label
-    qt = i % QT;
-    stream = (i / QT) * 8u + xcd;
-  } else { qt = b % QT; stream = b / QT; }
-  const uint32_t tiles_total = (row_hi - row_lo) / FILTER_ROWS;
-  const bool xcd_map = (nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0;
-  uint32_t t_lo, t_hi;
-  stream_tile_range(tiles_total, S, stream, xcd_map, sa.xcdw, t_lo, t_hi);
-  const uint32_t NT = t_hi - t_lo;
+  const StreamPlace sp = stream_place(QT, (row_hi - row_lo) / FILTER_ROWS, sa.xcdw);
+  const uint32_t qt = sp.qt, t_lo = sp.t_lo, NT = sp.NT;
   if (NT == 0) return;
 
   // ---- stationary operand: this wave's queries, all of K, in registers -------------------------
@@ -365,17 +447,9 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
   wave_has_queries = qbase < nq;                   // wave-uniform: padding-only waves skip their MFMAs
 
   // ---- per-lane source offsets of this wave's direct-to-LDS pieces -----------------------------
-  // LDS image of a stage: [32 rows][CHUNKS_PER_ROW 16-byte chunks], chunk c of row r stored at
-  // chunk position c ^ (r & 15) (XOR stays inside a 16-chunk = 256-byte bank row).  The LDS side of
-  // a direct-to-LDS load is linear (M0 base + lane*16), so the permutation is applied to the
-  // per-lane GLOBAL address: LDS position P = piece*64 + lane  <-  row P / CPR, chunk (P % CPR) ^ (row & 15).
+  // LDS image of a stage: [32 rows][ROW_BYTES / 16 chunks], chunk c of row r stored at chunk position c ^ (r & 15)
   uint32_t src_off[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const uint32_t P = static_cast<uint32_t>((wave * PPW + i) * 64 + lane);
-    const uint32_t r = P / CHUNKS_PER_ROW, cpos = P % CHUNKS_PER_ROW;
-    src_off[i] = r * ROW_BYTES + ((cpos ^ (r & 15u)) << 4);
-  }
+  piece_src_offsets<ROW_BYTES, PPW>(wave, lane, src_off);
   // A-fragment read offset: lane (r31,hsel) reads chunk 2s+hsel of row r31, stored at position
   // (2s+hsel) ^ (r31&15); since 2s+hsel == 2s ^ hsel this is a_base ^ ((s&7) << 5) + 256*(s>>3).
   const uint32_t a_base = r31 * ROW_BYTES + ((static_cast<uint32_t>(hsel) ^ (r31 & 15u)) << 4);
@@ -492,7 +566,7 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) asm volatile("" ::"v"(acc[nb]));
     } else {
-      // max tree per query block, then one compare (see filter_f16_m16_kernel)
+      // max tree per query block, then one compare (see filter_f16_m16_kernel's epilogue)
       float d[NB];
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
@@ -527,7 +601,7 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
       }
     }
   }
-  if (wave == 0 && lane == 0) record_xcd_speed(sa.xcdw, xcd_map, stream & 7u, NT, static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime()) - xw_t0);
+  stream_exit<false>(nullptr, sp, sa.xcdw, wave, lane, xw_t0);
   if constexpr (VAR == 0) scatter_own_log(mylog, wcnt, sa, lane);
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the two speculative stages before exit
 }
@@ -592,11 +666,11 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
   constexpr int TROWS = 16 * MB;                   // corpus rows per tile
   constexpr int STAGE_BYTES = TROWS * ROW_BYTES;
   constexpr int PIECES = STAGE_BYTES / 1024, PPW = PIECES / WPB;
-  constexpr int CHUNKS_PER_ROW = ROW_BYTES / 16;
   constexpr int NFRAG = NQB * KS, AMAX = WPB == 8 ? 32 : 64;      // two waves per SIMD: 128 AGPRs + 128 VGPRs each
   constexpr int NFRAG_A = NFRAG < AMAX ? NFRAG : AMAX, NFRAG_V = NFRAG - NFRAG_A;
   constexpr int NREAD = MB * KS;                   // A fragments per tile (MB row blocks x KS)
   static_assert(DIM % 128 == 0 && PIECES % WPB == 0 && NREAD % PPW == 0 && (WPB == 4 || WPB == 8), "shape");
+  static_assert(swz16<ROW_BYTES>(), "a16 below assumes the c ^ (r & 15) image: row stride a multiple of 256 bytes");
   static_assert((MB == 1 || MB == 2 || MB == 4) && (NQB == 1 || NQB == 2 || NQB == 4) && NQB * KS * 4 <= 384 && STAGE_BYTES * FILTER_STAGES <= 160 * 1024, "registers / LDS");
   static_assert(FILTER_STAGES * STAGE_BYTES == filter_f16_m16_lds_bytes<DIM, MB>(), "the launchers size the dynamic LDS with filter_f16_m16_lds_bytes");
 
@@ -605,16 +679,8 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
   const int x15 = lane & 15, g4 = lane >> 4;
   const uint32_t wave_gid = blockIdx.x * WPB + wave;
 
-  const uint32_t nwg = gridDim.x, b = blockIdx.x;
-  const uint32_t S = nwg / QT;
-  uint32_t stream, qt;
-  if ((nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0) { const uint32_t xcd = b & 7u, i = b >> 3; qt = i % QT; stream = (i / QT) * 8u + xcd; }
-  else { qt = b % QT; stream = b / QT; }
-  const uint32_t tiles_total = (row_hi - row_lo) / TROWS;
-  const bool xcd_map = (nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0;
-  uint32_t t_lo, t_hi;
-  stream_tile_range(tiles_total, S, stream, xcd_map, sa.xcdw, t_lo, t_hi);
-  const uint32_t NT = t_hi - t_lo;
+  const StreamPlace sp = stream_place(QT, (row_hi - row_lo) / TROWS, sa.xcdw);
+  const uint32_t stream = sp.stream, qt = sp.qt, t_lo = sp.t_lo, NT = sp.NT;
   if (NT == 0) return;
 
   // B fragment f = nb*KS + s: query block nb (16 queries), k-step s; lane (x15,g4) holds
@@ -645,12 +711,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
   const bool wave_has_queries = qbase < nq;
 
   uint32_t src_off[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const uint32_t P = static_cast<uint32_t>((wave * PPW + i) * 64 + lane);
-    const uint32_t r = P / CHUNKS_PER_ROW, cpos = P % CHUNKS_PER_ROW;
-    src_off[i] = r * ROW_BYTES + ((cpos ^ (r & 15u)) << 4);
-  }
+  piece_src_offsets<ROW_BYTES, PPW>(wave, lane, src_off);
   // A fragment (mb,s): lane (x15,g4) reads chunk 4s+g4 of row 16mb+x15, stored at position (4s+g4)^x15:
   //   a16 ^ ((s&3) << 6)  +  256*(s>>2)  +  16*ROW_BYTES*mb
   const uint32_t a16 = static_cast<uint32_t>(x15) * ROW_BYTES + ((static_cast<uint32_t>(g4) ^ static_cast<uint32_t>(x15)) << 4);
@@ -678,7 +739,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
 
   uint32_t sync_strikes = 0;                       // rendezvous that timed out; after 3 this workgroup stops waiting
   uint64_t stamp_c = 0, stamp_r = 0;
-  if constexpr (STAMP) { stamp_c = __builtin_amdgcn_s_memtime(); stamp_r = __builtin_amdgcn_s_memrealtime(); }
+  if constexpr (STAMP) stamp_begin(stamp_c, stamp_r);
   const uint32_t xw_t0 = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
   // 8-wave build: the two waves of a SIMD leave the per-tile barrier together, multiply together and would test together, with
   // the matrix pipe idle meanwhile.  Waves 4..7 therefore test a tile's accumulators AFTER the next barrier (LATE): their test
@@ -782,13 +843,9 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
   if (late && wave_has_queries) epilogue(NT - 1);
   if constexpr (STAMP) {
     const uint64_t dc = __builtin_amdgcn_s_memtime() - stamp_c, dr = __builtin_amdgcn_s_memrealtime() - stamp_r;
-    if (wave == 0 && lane == 0) {
-      uint64_t* out = reinterpret_cast<uint64_t*>(prog + static_cast<uint64_t>(gridDim.x) * 8) + static_cast<uint64_t>(blockIdx.x) * 2;
-      out[0] = dc; out[1] = dr;
-    }
+    if (wave == 0 && lane == 0) stamp_store(prog, dc, dr);
   }
-  if constexpr (SYNC) { if (wave == 0 && lane == 0) __hip_atomic_store(myprog + qt, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-  if (wave == 0 && lane == 0) record_xcd_speed(sa.xcdw, xcd_map, stream & 7u, NT, static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime()) - xw_t0);
+  stream_exit<SYNC>(prog, sp, sa.xcdw, wave, lane, xw_t0);
   scatter_own_log(mylog, wcnt, sa, lane);
 }
 
@@ -813,9 +870,9 @@ __global__ __launch_bounds__(256, 1) void filter_f16_k2_kernel(
   constexpr int TROWS = 16;
   constexpr int STAGE_BYTES = TROWS * SROW;
   constexpr int PIECES = STAGE_BYTES / 1024, PPW = PIECES / 4;
-  constexpr int CPR = SROW / 16;                   // 16-byte chunks per stage row
   constexpr int NFRAG = 2 * KS, NFRAG_A = NFRAG < 64 ? NFRAG : 64, NFRAG_V = NFRAG - NFRAG_A;
   static_assert(DIMS % 128 == 0 && PIECES % 4 == 0 && KS % PPW == 0 && NFRAG * 4 <= 384 && STAGE_BYTES * FILTER_STAGES <= 160 * 1024, "shape");
+  static_assert(swz16<SROW>(), "a16 below assumes the c ^ (r & 15) image: stage row stride a multiple of 256 bytes");
   static_assert(FILTER_STAGES * STAGE_BYTES == filter_f16_k2_lds_bytes<DIM>(), "the launchers size the dynamic LDS with filter_f16_k2_lds_bytes");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -823,16 +880,8 @@ __global__ __launch_bounds__(256, 1) void filter_f16_k2_kernel(
   const int x15 = lane & 15, g4 = lane >> 4;
   const uint32_t wave_gid = blockIdx.x * 4 + wave;
 
-  const uint32_t nwg = gridDim.x, b = blockIdx.x;
-  const uint32_t S = nwg / QT;
-  uint32_t stream, qt;
-  if ((nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0) { const uint32_t xcd = b & 7u, i = b >> 3; qt = i % QT; stream = (i / QT) * 8u + xcd; }
-  else { qt = b % QT; stream = b / QT; }
-  const uint32_t tiles_total = (row_hi - row_lo) / TROWS;
-  const bool xcd_map = (nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0;
-  uint32_t t_lo, t_hi;
-  stream_tile_range(tiles_total, S, stream, xcd_map, sa.xcdw, t_lo, t_hi);
-  const uint32_t NT = t_hi - t_lo;
+  const StreamPlace sp = stream_place(QT, (row_hi - row_lo) / TROWS, sa.xcdw);
+  const uint32_t stream = sp.stream, qt = sp.qt, t_lo = sp.t_lo, NT = sp.NT;
   if (NT == 0) return;
 
   // B fragment f = kh*KS + s: K-half kh, k-step s; lane (x15,g4) holds q16[query x15][kh*DIMS + 32 s + 8 g4 .. +8]
@@ -856,12 +905,7 @@ __global__ __launch_bounds__(256, 1) void filter_f16_k2_kernel(
   const bool wave_has_queries = qbase < nq;
 
   uint32_t src_off[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const uint32_t P = static_cast<uint32_t>((wave * PPW + i) * 64 + lane);
-    const uint32_t r = P / CPR, cpos = P % CPR;
-    src_off[i] = r * ROW_BYTES + ((cpos ^ (r & 15u)) << 4);
-  }
+  piece_src_offsets<SROW, PPW, ROW_BYTES>(wave, lane, src_off);     // the image holds half rows, memory whole ones
   const uint32_t a16 = static_cast<uint32_t>(x15) * SROW + ((static_cast<uint32_t>(g4) ^ static_cast<uint32_t>(x15)) << 4);
 
   const char* gbase = reinterpret_cast<const char*>(rows);
@@ -938,8 +982,7 @@ __global__ __launch_bounds__(256, 1) void filter_f16_k2_kernel(
       }
     }
   }
-  if constexpr (SYNC) { if (wave == 0 && lane == 0) __hip_atomic_store(myprog + qt, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-  if (wave == 0 && lane == 0) record_xcd_speed(sa.xcdw, xcd_map, stream & 7u, NT, static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime()) - xw_t0);
+  stream_exit<SYNC>(prog, sp, sa.xcdw, wave, lane, xw_t0);
   scatter_own_log(mylog, wcnt, sa, lane);
 }
 
@@ -1034,15 +1077,7 @@ static __global__ __launch_bounds__(256) void prep_q8_kernel(const float* __rest
   }
 }
 
-// LDS image of an int8 tile: chunk c (16 bytes) of row r sits at chunk position swz_chunk(c, r) of its row, so that the 16 rows a
-// ds_read_b128 group touches at one k-offset fall into 16 different 16-byte bank groups.  Row strides that are multiples of 256
-// bytes start every row in the same bank group: c ^ (r & 15).  Odd multiples of 128 bytes (d = 384, the reference's own data
-// dimension) start consecutive rows 8 bank groups apart -- (r & 1) already picks the half, (r >> 1) & 7 the place inside it.
-template <int ROW_BYTES> __device__ constexpr bool swz16() { return (ROW_BYTES / 16) % 16 == 0; }
-template <int ROW_BYTES> __device__ inline uint32_t swz_chunk(uint32_t c, uint32_t r) {
-  static_assert(ROW_BYTES % 128 == 0, "int8 row stride: a multiple of 128 bytes");
-  return swz16<ROW_BYTES>() ? c ^ (r & 15u) : c ^ ((r >> 1) & 7u);
-}
+// LDS image of an int8 tile: swz_chunk (shared pieces, above).
 // v_mfma_i32_32x32x32_i8 A fragment of k-step s: chunk 2 s + hsel of row r31; 2 s + hsel == 2 s ^ hsel, so the swizzled position is
 // a_base ^ (the k-step's bits inside the swizzle group) + the byte offset of the group
 template <int ROW_BYTES> __device__ inline uint32_t a_base_i8(uint32_t r31, uint32_t hsel) { return r31 * ROW_BYTES + (swz_chunk<ROW_BYTES>(hsel, r31) << 4); }
@@ -1070,7 +1105,6 @@ __global__ __launch_bounds__(256, 1) void filter_i8_kernel(
   constexpr int STAGE_BYTES = DATA_BYTES + 4 * 1024;   // + one 1 KB scales slot per wave
   constexpr int PIECES = DATA_BYTES / 1024;
   constexpr int PPW = PIECES / 4;                  // corpus pieces per wave
-  constexpr int CHUNKS_PER_ROW = ROW_BYTES / 16;
   static_assert(DIM % 128 == 0, "int8 row stride: a multiple of 128 bytes (swz_chunk)");
   static_assert(PIECES % 4 == 0 && KSTEPS % PPW == 0 && 2 * KSTEPS <= 64, "shape");
   static_assert(FILTER_STAGES_I8 * STAGE_BYTES == filter_i8_lds_bytes<DIM>(), "the launchers size the dynamic LDS with filter_i8_lds_bytes");
@@ -1080,16 +1114,8 @@ __global__ __launch_bounds__(256, 1) void filter_i8_kernel(
   const int r31 = lane & 31, hsel = lane >> 5;
   const uint32_t wave_gid = blockIdx.x * 4 + wave;
 
-  const uint32_t nwg = gridDim.x, b = blockIdx.x;
-  const uint32_t S = nwg / QT;
-  uint32_t stream, qt;
-  if ((nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0) { const uint32_t xcd = b & 7u, i = b >> 3; qt = i % QT; stream = (i / QT) * 8u + xcd; }
-  else { qt = b % QT; stream = b / QT; }
-  const uint32_t tiles_total = (row_hi - row_lo) / FILTER_ROWS;
-  const bool xcd_map = (nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0;
-  uint32_t t_lo, t_hi;
-  stream_tile_range(tiles_total, S, stream, xcd_map, sa.xcdw, t_lo, t_hi);
-  const uint32_t NT = t_hi - t_lo;
+  const StreamPlace sp = stream_place(QT, (row_hi - row_lo) / FILTER_ROWS, sa.xcdw);
+  const uint32_t stream = sp.stream, qt = sp.qt, t_lo = sp.t_lo, NT = sp.NT;
   if (NT == 0) return;
 
   // stationary operand: 32 queries x two int8 planes x all of K, in AGPRs.  Lane (r31,hsel) holds bytes
@@ -1112,12 +1138,7 @@ __global__ __launch_bounds__(256, 1) void filter_i8_kernel(
   const bool wave_has_queries = qbase < nq;
 
   uint32_t src_off[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const uint32_t P = static_cast<uint32_t>((wave * PPW + i) * 64 + lane);
-    const uint32_t r = P / CHUNKS_PER_ROW, cpos = P % CHUNKS_PER_ROW;
-    src_off[i] = r * ROW_BYTES + (swz_chunk<ROW_BYTES>(cpos, r) << 4);
-  }
+  piece_src_offsets<ROW_BYTES, PPW>(wave, lane, src_off);
   const uint32_t sc_off = (lane & 7) * 16;         // 32 row scales = 128 bytes; lanes >= 8 re-load the same chunks
   const uint32_t a_base = a_base_i8<ROW_BYTES>(static_cast<uint32_t>(r31), static_cast<uint32_t>(hsel));
 
@@ -1232,8 +1253,7 @@ __global__ __launch_bounds__(256, 1) void filter_i8_kernel(
       }
     }
   }
-  if constexpr (SYNC) { if (wave == 0 && lane == 0) __hip_atomic_store(prog + static_cast<uint64_t>(stream) * 8 + qt, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-  if (wave == 0 && lane == 0) record_xcd_speed(sa.xcdw, xcd_map, stream & 7u, NT, static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime()) - xw_t0);
+  stream_exit<SYNC>(prog, sp, sa.xcdw, wave, lane, xw_t0);
   if constexpr (!BOOT) scatter_own_log(mylog, wcnt, sa, lane);
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
@@ -1293,7 +1313,6 @@ __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
   constexpr int STAGE_BYTES = DATA_BYTES + 4 * 1024;
   constexpr int PIECES = DATA_BYTES / 1024;
   constexpr int PPW = PIECES / 4;
-  constexpr int CHUNKS_PER_ROW = ROW_BYTES / 16;
   // dims up to 1536 (768 < DIM: NB = 1, MB = 1 -- 32 queries per wave, 192 AGPRs of hi-plane fragments, 32-row tiles in three
   // 52 KB stages).  int32 range of (H << 7) + L at any dim: prep_q8_kernel keeps the L1 norm of a query's hi plane below
   // I8_HI_L1_MAX, so |H| < 2^23 whatever the dim.
@@ -1307,13 +1326,14 @@ __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
   const int r31 = lane & 31, hsel = lane >> 5;
   const uint32_t wave_gid = blockIdx.x * 4 + wave;
 
+  // written out, not stream_place: through the shared function these two-stage kernels spill more scalar registers
   const uint32_t nwg = gridDim.x, b = blockIdx.x;
   const uint32_t S = nwg / QT;
   uint32_t stream, qt;
-  if ((nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0) { const uint32_t xcd = b & 7u, i = b >> 3; qt = i % QT; stream = (i / QT) * 8u + xcd; }
+  if (xcd_aware_grid(QT, nwg)) { const uint32_t xcd = b & 7u, i = b >> 3; qt = i % QT; stream = (i / QT) * 8u + xcd; }
   else { qt = b % QT; stream = b / QT; }
   const uint32_t tiles_total = (row_hi - row_lo) / TROWS;
-  const bool xcd_map = (nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0;
+  const bool xcd_map = xcd_aware_grid(QT, nwg);
   uint32_t t_lo, t_hi;
   stream_tile_range(tiles_total, S, stream, xcd_map, sa.xcdw, t_lo, t_hi);
   const uint32_t NT = t_hi - t_lo;
@@ -1338,21 +1358,13 @@ __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
     const bool real = qid[nb] < nq;
     thr_s[nb] = real ? thr[qid[nb]] * qscale[qid[nb]] : __builtin_huge_valf();   // threshold in units of s_q
     inv_s[nb] = real ? qinv[qid[nb]] : 0.f;
-    // first-stage threshold for H * scale (the factor 128 moved to this side, exactly): a little below
-    // T - delta, the margin covering the fp32 roundings of both stages' values
-    const float T = thr_s[nb];
-    t1q[nb] = real ? (T - (1.001f * qdelta[qid[nb]] + 2e-6f * fabsf(T) + 1e-5f)) * lo_unit : __builtin_huge_valf();
+    t1q[nb] = real ? i8_stage1_bar(thr_s[nb], qdelta[qid[nb]], lo_unit) : __builtin_huge_valf();   // first-stage threshold for H * scale
     asm volatile("" ::"v"(thr_s[nb]), "v"(inv_s[nb]), "v"(t1q[nb]));
   }
   const bool wave_has_queries = qbase < nq;
 
   uint32_t src_off[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const uint32_t P = static_cast<uint32_t>((wave * PPW + i) * 64 + lane);
-    const uint32_t r = P / CHUNKS_PER_ROW, cpos = P % CHUNKS_PER_ROW;
-    src_off[i] = r * ROW_BYTES + (swz_chunk<ROW_BYTES>(cpos, r) << 4);
-  }
+  piece_src_offsets<ROW_BYTES, PPW>(wave, lane, src_off);
   const uint32_t sc_off = (lane & (8 * MB - 1)) * 16;   // TROWS row scales = 128 * MB bytes; the other lanes re-load the same chunks
   const uint32_t a_base = a_base_i8<ROW_BYTES>(static_cast<uint32_t>(r31), static_cast<uint32_t>(hsel));
 
@@ -1416,7 +1428,7 @@ __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
 
   uint32_t sync_strikes = 0;
   uint64_t stamp_c = 0, stamp_r = 0;
-  if constexpr (STAMP) { stamp_c = __builtin_amdgcn_s_memtime(); stamp_r = __builtin_amdgcn_s_memrealtime(); }
+  if constexpr (STAMP) stamp_begin(stamp_c, stamp_r);
   const uint32_t xw_t0 = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
   for (uint32_t t = 0; t < NT; ++t) {
     if constexpr (SYNC) {
@@ -1568,10 +1580,7 @@ __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
   if constexpr (DEFER) { if (pend) consume_pending(0); }
   if constexpr (STAMP) {
     const uint64_t dc = __builtin_amdgcn_s_memtime() - stamp_c, dr = __builtin_amdgcn_s_memrealtime() - stamp_r;
-    if (wave == 0 && lane == 0) {
-      uint64_t* out = reinterpret_cast<uint64_t*>(prog + static_cast<uint64_t>(gridDim.x) * 8) + static_cast<uint64_t>(blockIdx.x) * 2;
-      out[0] = dc; out[1] = dr;
-    }
+    if (wave == 0 && lane == 0) stamp_store(prog, dc, dr);
   }
   if constexpr (SYNC) { if (wave == 0 && lane == 0) __hip_atomic_store(prog + static_cast<uint64_t>(stream) * 8 + qt, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   if (stage_counts && lane == 0 && (n_stage1 | n_stage2)) { atomicAdd(stage_counts, n_stage1); atomicAdd(stage_counts + 1, n_stage2); }
@@ -1698,7 +1707,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
   constexpr int NSLOT_DEFER = 16 / WPB, SCRATCH_BYTES = DEFER ? NSLOT_DEFER * DIM : 0;   // per wave: lo-plane rows of up to 4 (2) deferred values
   constexpr int PIECES = DATA_BYTES / 1024;
   constexpr int PPW = PIECES / WPB;
-  constexpr int CHUNKS_PER_ROW = ROW_BYTES / 16;
   static_assert(DIM % 128 == 0 && DIM <= 768, "row stride multiple of 128 bytes (swz_chunk); int32 range of 128*H + L");
   static_assert(PIECES % WPB == 0 && KSTEPS % PPW == 0 && KSTEPS % 2 == 0 && KSTEPS >= 8, "shape");
   static_assert(NSTAGE * STAGE_BYTES + WPB * SCRATCH_BYTES <= 160 * 1024 && PPW + 1 < 64 && DIM % 16 == 0 && DIM / 16 <= 64, "LDS / vmcnt range");
@@ -1709,13 +1717,14 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
   const int r31 = lane & 31, hsel = lane >> 5;
   const uint32_t wave_gid = blockIdx.x * WPB + wave;
 
+  // written out, not stream_place: through the shared function these two-stage kernels spill more scalar registers
   const uint32_t nwg = gridDim.x, b = blockIdx.x;
   const uint32_t S = nwg / QT;
   uint32_t stream, qt;
-  if ((nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0) { const uint32_t xcd = b & 7u, i = b >> 3; qt = i % QT; stream = (i / QT) * 8u + xcd; }
+  if (xcd_aware_grid(QT, nwg)) { const uint32_t xcd = b & 7u, i = b >> 3; qt = i % QT; stream = (i / QT) * 8u + xcd; }
   else { qt = b % QT; stream = b / QT; }
   const uint32_t tiles_total = (row_hi - row_lo) / TROWS;
-  const bool xcd_map = (nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0;
+  const bool xcd_map = xcd_aware_grid(QT, nwg);
   uint32_t t_lo, t_hi;
   stream_tile_range(tiles_total, S, stream, xcd_map, sa.xcdw, t_lo, t_hi);
   const uint32_t NT = t_hi - t_lo;
@@ -1751,19 +1760,13 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
     const bool real = qid[nb] < nq;
     thr_s[nb] = real ? thr[qid[nb]] * qscale[qid[nb]] : __builtin_huge_valf();
     inv_s[nb] = real ? qinv[qid[nb]] : 0.f;
-    const float T = thr_s[nb];
-    t1q[nb] = real ? (T - (1.001f * qdelta[qid[nb]] + 2e-6f * fabsf(T) + 1e-5f)) * lo_unit : __builtin_huge_valf();   // as filter_i8w_kernel
+    t1q[nb] = real ? i8_stage1_bar(thr_s[nb], qdelta[qid[nb]], lo_unit) : __builtin_huge_valf();
     asm volatile("" ::"v"(thr_s[nb]), "v"(inv_s[nb]), "v"(t1q[nb]));
   }
   const bool wave_has_queries = qbase < nq;
 
   uint32_t src_off[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const uint32_t P = static_cast<uint32_t>((wave * PPW + i) * 64 + lane);
-    const uint32_t r = P / CHUNKS_PER_ROW, cpos = P % CHUNKS_PER_ROW;
-    src_off[i] = r * ROW_BYTES + (swz_chunk<ROW_BYTES>(cpos, r) << 4);
-  }
+  piece_src_offsets<ROW_BYTES, PPW>(wave, lane, src_off);
   const uint32_t sc_off = (lane & (8 * MB - 1)) * 16;
   const uint32_t a_base = a_base_i8<ROW_BYTES>(static_cast<uint32_t>(r31), static_cast<uint32_t>(hsel));
 
@@ -2041,7 +2044,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
   uint32_t sync_strikes = 0;
   uint64_t stamp_c = 0, stamp_r = 0;
   [[maybe_unused]] uint64_t rare_acc = 0, cons_acc = 0;     // VAR 5: cycles this wave spent inside rare_path / consume_slots
-  if constexpr (STAMP) { stamp_c = __builtin_amdgcn_s_memtime(); stamp_r = __builtin_amdgcn_s_memrealtime(); }
+  if constexpr (STAMP) stamp_begin(stamp_c, stamp_r);
   const uint32_t xw_t0 = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
   for (uint32_t t = 0; t < NT; ++t) {
     if constexpr (SYNC) {
@@ -2169,10 +2172,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
     uint64_t dc = __builtin_amdgcn_s_memtime() - stamp_c;
     const uint64_t dr = __builtin_amdgcn_s_memrealtime() - stamp_r;
     if constexpr (VAR == 5) dc = (rare_acc << 32) | (cons_acc & 0xFFFFFFFFull);   // this build reports those instead of the loop's cycles
-    if (wave == 0 && lane == 0) {
-      uint64_t* out = reinterpret_cast<uint64_t*>(prog + static_cast<uint64_t>(gridDim.x) * 8) + static_cast<uint64_t>(blockIdx.x) * 2;
-      out[0] = dc; out[1] = dr;
-    }
+    if (wave == 0 && lane == 0) stamp_store(prog, dc, dr);
   }
   if constexpr (SYNC) { if (wave == 0 && lane == 0) __hip_atomic_store(prog + static_cast<uint64_t>(stream) * 8 + qt, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   if (stage_counts && lane == 0 && (n_stage1 | n_stage2)) { atomicAdd(stage_counts, n_stage1); atomicAdd(stage_counts + 1, n_stage2); }

@@ -63,10 +63,10 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
   const uint32_t nwg = gridDim.x, b = blockIdx.x;
   const uint32_t S = nwg / QT;
   uint32_t stream, qt;
-  if ((nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0) { const uint32_t xcd = b & 7u, i = b >> 3; qt = i % QT; stream = (i / QT) * 8u + xcd; }
+  if (xcd_aware_grid(QT, nwg)) { const uint32_t xcd = b & 7u, i = b >> 3; qt = i % QT; stream = (i / QT) * 8u + xcd; }
   else { qt = b % QT; stream = b / QT; }
   const uint32_t tiles_total = (row_hi - row_lo) / TROWS;
-  const bool xcd_map = (nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0;
+  const bool xcd_map = xcd_aware_grid(QT, nwg);
   uint32_t t_lo, t_hi;
   stream_tile_range(tiles_total, S, stream, xcd_map, sa.xcdw, t_lo, t_hi);
   const uint32_t NT = t_hi - t_lo;
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
     qid[nb] = qbase + nb * 16 + x15;
     const bool real = qid[nb] < nq;
     const float T = real ? thr[qid[nb]] * qscale[qid[nb]] : __builtin_huge_valf();
-    t1q[nb] = real ? (T - (1.001f * qdelta[qid[nb]] + 2e-6f * fabsf(T) + 1e-5f)) * lo_unit : __builtin_huge_valf();   // as filter_i8w_kernel
+    t1q[nb] = real ? i8_stage1_bar(T, qdelta[qid[nb]], lo_unit) : __builtin_huge_valf();
     asm volatile("" ::"v"(t1q[nb]));
   }
   const bool wave_has_queries = qbase < nq;

@@ -384,9 +384,8 @@ inline uint32_t filter_grid(const nvdb_hip_ctx* c, uint32_t QT) {
   return nwg ? nwg : QT;
 }
 
-// the kernels' XCD-aware mapping is active: the QT workgroups of a row stream share an XCD label
-inline bool xcd_aware_grid(uint32_t QT, uint32_t nwg) { return (nwg & 7u) == 0 && ((nwg >> 3) % QT) == 0; }
-// ... only then, and with siblings to keep in step, does the rendezvous apply
+// xcd_aware_grid(QT, nwg) (kernels_filter.h: the predicate the kernels place themselves by): the XCD-aware mapping is active.
+// Only then, and with siblings to keep in step, does the rendezvous apply
 inline bool sibling_sync_grid(const nvdb_hip_ctx* c, uint32_t QT, uint32_t nwg) { return c->opt_sibling_sync && QT > 1 && QT <= 8 && xcd_aware_grid(QT, nwg); }
 
 // rendezvous arguments of a filter kernel: counters (unused / not-yet-started slots read 0xFFFFFFFF = "far ahead"),

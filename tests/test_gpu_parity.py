@@ -731,6 +731,35 @@ def test_overflow_falls_back_to_exact_path(ctx, oracle, permute):
     _check_against_oracle(oracle, base, po.DT_F16, None, q, ids, sc, k, "overflow")
 
 
+@pytest.mark.parametrize("tag,d,nq", [("f16", 128, 32), ("i8", 256, 32), ("i8", 256, 200)])
+def test_wave_log_overflow_is_handled_and_stays_exact(ctx, oracle, tag, d, nq):
+    """A wave's survivor log holds FILTER_LOGCAP = 4096 entries per launch (csrc/kernels_filter.h: the count runs on, the
+    stores stop).  131072 identical rows: every row ties, so every row reaches every query's bar.  Plan at one query tile on
+    256 workgroups (plan_search, filter_grid):
+      f16, d = 128, 32 queries (filter_f16_kernel, 32-row tiles, the 32 queries on wave 0): bootstrap 80 tiles, growth 8 -> chunks
+        [0, 20480) and [20480, 131072); the second gives a stream 13 or 14 tiles x 32 rows x 32 queries >= 13312 survivors;
+      i8, d = 256, 32 queries (filter_i8w_kernel, 64-row tiles; scatter_own_log's clamp): the same chunks, 6 or 7 tiles x 64 x 32
+        >= 12288;
+      i8, d = 256, 200 queries (the pipelined build that logs first-stage survivors, 64 queries per wave; verify_and_scatter_i8's
+        clamp): bootstrap 152 tiles, growth 3 -> last chunk [43776, 131072), 5 or 6 tiles x 64 x 64 >= 20480.
+    Three to five times the log either way.  The overflow is a handled condition: which queries lost entries is unknown, so all
+    of them are reported and the batch is redone; the answer is the CPU path's, ties in id order."""
+    n, k = 131072, 10
+    row = nvdb_amd.synth_rows_f32(SEED + 40, 0, 1, d)
+    base, dt, scales = _as_dtype(oracle, np.repeat(row, n, axis=0), tag)
+    queries = nvdb_amd.synth_rows_f32(SEED + 41, 0, nq, d)
+    ctx.upload_corpus(base, dt, scales)
+    ctx.set_option("path", 2)
+    ids, sc = ctx.search_batch(queries, k)                   # (raises unless the call returns NVDB_OK)
+    st = ctx.stats()
+    ctx.set_option("path", 0)
+    assert st["path"] == 2 and st["overflow_queries"] == nq and st["bound_violations"] == 0, st
+    oid, osc = oracle.flat_topk(base, dt, queries, k, scales)
+    assert np.array_equal(oid, np.tile(np.arange(k, dtype=oid.dtype), (nq, 1)))
+    assert np.array_equal(ids, oid)
+    assert np.array_equal(sc.view(np.uint32), osc.view(np.uint32))
+
+
 # ----------------------------------------------------------------------------- sharding (multi-GPU logic on one GPU)
 def test_row_sharded_search_merges_to_the_unsharded_answer(oracle):
     n, d, nq, k, shards = 120000, 768, 24, 10, 3
