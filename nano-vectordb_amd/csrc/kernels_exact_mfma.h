@@ -89,6 +89,132 @@ __device__ __forceinline__ void exact_load_bq(const float* __restrict__ q32, uin
   }
 }
 
+constexpr uint32_t EXACT_MFMA_ROWS = 16;                 // rows per tile (MFMA M)
+constexpr uint32_t EXACT_MFMA_QB = 16;                   // queries per wave (MFMA N)
+
+// ---- the pieces every kernel of this file is made of ----------------------------------------------
+
+// this workgroup's tiles [t_lo, t_hi) of the rows [row_lo, row_hi): the grid's x dimension splits the 16-row tiles evenly
+__device__ __forceinline__ void exact_tile_range(uint32_t row_lo, uint32_t row_hi, uint32_t& t_lo, uint32_t& t_hi) {
+  const uint32_t P = gridDim.x, p = blockIdx.x;
+  const uint32_t tiles = (row_hi - row_lo + EXACT_MFMA_ROWS - 1) / EXACT_MFMA_ROWS;
+  t_lo = static_cast<uint32_t>(static_cast<uint64_t>(tiles) * p / P);
+  t_hi = static_cast<uint32_t>(static_cast<uint64_t>(tiles) * (p + 1) / P);
+}
+
+// one K-step of chain j: acc = x * bq + (first step of a tile ? 0 : acc)
+__device__ __forceinline__ void exact_mfma_step(floatx4_t& acc, float x, float bq, bool first) {
+  if (first) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x, bq, floatx4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+  else acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x, bq, acc, 0, 0, 0);
+}
+
+// the eight chains -> s[v] = reference score of (row 4 * (lane / 16) + v of the tile, query lane % 16): (lo + hi), hadd, hadd  (simd_dot.cpp:38-44)
+__device__ __forceinline__ void exact_reduce(const floatx4_t (&acc)[8], float (&s)[4]) {
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    const float s0 = acc[0][v] + acc[4][v], s1 = acc[1][v] + acc[5][v], s2 = acc[2][v] + acc[6][v], s3 = acc[3][v] + acc[7][v];
+    s[v] = (s0 + s1) + (s2 + s3);
+  }
+}
+
+// Consume the stationary fragments and the bar in front of the tile loop: hipcc otherwise defers its wait for these loads to their first
+// use inside the loop, and that s_waitcnt vmcnt(0) would also wait for the direct-to-LDS prefetches it cannot see -- once per tile
+template <int T>
+__device__ __forceinline__ void exact_pin(const float (&bq)[T][8], float gthr) {
+#pragma unroll
+  for (int t = 0; t < T; ++t)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(bq[t][j]));
+  asm volatile("" ::"v"(gthr));
+}
+
+// score-matrix store of one lane's four rows row0 .. row0 + 3 of query qi (ld: a multiple of 4, so the 16-byte store is aligned)
+__device__ __forceinline__ void exact_store_scores(float* out, uint64_t ld, uint32_t qi, uint32_t row0, uint32_t row_hi, const float (&s)[4]) {
+  float* o = out + static_cast<uint64_t>(qi) * ld + row0;
+  if (row0 + 3 < row_hi) *reinterpret_cast<float4*>(o) = make_float4(s[0], s[1], s[2], s[3]);
+  else {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) if (row0 + v < row_hi) o[v] = s[v];
+  }
+}
+
+// Per lane: the k-th best (score, row) of ITS query (lane % 16) so far -- what a new row must beat --, the length of that query's list,
+// the bar handed in (gthr) and quick = what a score must reach to enter at all (gthr and, once the list is full, its k-th score).
+// real = false: a padding query of a partial group, which files nothing.
+struct ExactTopK {
+  float thr_s = NEG_INF;
+  uint32_t thr_id = 0xFFFFFFFFu, my_cnt = 0;
+  float quick, gthr;
+  bool real;
+  __device__ __forceinline__ ExactTopK(float gthr_, bool real_) : quick(gthr_), gthr(gthr_), real(real_) {}
+};
+
+// One tile's scores s[v] (this lane: rows row0 + v of its query; tile_row0 = the tile's first row) against the wave's lists
+// l_s / l_id[query of the block][entry e <-> lane e], best first.
+__device__ __forceinline__ void exact_topk_offer(ExactTopK& st, float (*l_s)[64], uint32_t (*l_id)[64], const float (&s)[4],
+                                                 uint32_t row0, uint32_t tile_row0, uint32_t row_hi, uint32_t k, int lane) {
+  // one compare per tile and lane in front of the full test: a row can only enter with a score >= quick (NaN scores never enter)
+  const float smax = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
+  if (!__ballot(st.real && smax >= st.quick)) return;
+  bool pass[4];
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    const uint32_t row = row0 + v;
+    pass[v] = st.real && row < row_hi && s[v] >= st.gthr && (st.my_cnt < k || better(s[v], row, st.thr_s, st.thr_id));
+  }
+  // rare: file the passing (row, query) pairs, one at a time, into the queries' lists
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    unsigned long long m = __ballot(pass[v]);
+    while (m) {
+      const int L = __builtin_ctzll(m);
+      m &= m - 1;
+      const uint32_t g = static_cast<uint32_t>(L) & 15u;                                  // the pair's query (block-relative)
+      const float cs = readlane_f(s[v], L);
+      const uint32_t cid = tile_row0 + 4u * (static_cast<uint32_t>(L) >> 4) + v;
+      const uint32_t c = readlane_u(st.my_cnt, static_cast<int>(g));                      // (lanes g, g + 16, .. hold query g's state)
+      const float ts = readlane_f(st.thr_s, static_cast<int>(g));
+      const uint32_t tid = readlane_u(st.thr_id, static_cast<int>(g));
+      if (!(c < k || better(cs, cid, ts, tid))) continue;                                  // an earlier pair of this tile raised the bar
+      float es = l_s[g][lane];
+      uint32_t eid = l_id[g][lane];
+      const bool ahead = static_cast<uint32_t>(lane) < c && better(es, eid, cs, cid);
+      const uint32_t pos = static_cast<uint32_t>(__builtin_popcountll(__ballot(ahead)));
+      const float up_s = __shfl_up(es, 1);
+      const uint32_t up_id = __shfl_up(eid, 1);
+      if (static_cast<uint32_t>(lane) > pos) { es = up_s; eid = up_id; }
+      else if (static_cast<uint32_t>(lane) == pos) { es = cs; eid = cid; }
+      const uint32_t c2 = c < k ? c + 1 : k;
+      if (static_cast<uint32_t>(lane) < c2) { l_s[g][lane] = es; l_id[g][lane] = eid; }
+      const float nts = readlane_f(es, static_cast<int>(k) - 1);
+      const uint32_t ntid = readlane_u(eid, static_cast<int>(k) - 1);
+      if ((static_cast<uint32_t>(lane) & 15u) == g) {
+        st.my_cnt = c2;
+        if (c2 == k) { st.thr_s = nts; st.thr_id = ntid; }
+      }
+    }
+  }
+  st.quick = st.my_cnt < k ? st.gthr : fmaxf(st.gthr, st.thr_s);
+}
+
+// append this wave's lists (queries qg_first .. + 15, those below nq) to the global candidate lists; select_kernel orders them
+__device__ __forceinline__ void exact_topk_flush(const ExactTopK& st, const float (*l_s)[64], const uint32_t (*l_id)[64], uint32_t qg_first, uint32_t nq,
+                                                 Cand* cand, uint32_t* cnt, uint32_t cap, uint32_t* overflow, int lane) {
+  for (uint32_t g = 0; g < EXACT_MFMA_QB; ++g) {
+    const uint32_t q = qg_first + g;
+    const uint32_t c = readlane_u(st.my_cnt, static_cast<int>(g));
+    if (q >= nq || c == 0) continue;
+    uint32_t slot0 = 0;
+    if (lane == 0) slot0 = atomicAdd(&cnt[q], c);
+    slot0 = readlane_u(slot0, 0);
+    if (static_cast<uint32_t>(lane) < c) {
+      const uint32_t slot = slot0 + lane;
+      if (slot < cap) cand[static_cast<uint64_t>(q) * cap + slot] = Cand{l_s[g][lane], l_id[g][lane]};
+      else overflow[q] = 1u;
+    }
+  }
+}
+
 // One 16-row tile against the wave's 16 queries.  `raw` holds this tile's K-steps (ring of RING steps, the rest is fetched as
 // the loop goes); while they are consumed the same registers receive the steps of the tile at `next` (lane's row pointer
 // + its kq offset; pass the current pointer again for the last tile: the bytes are loaded and never used).
@@ -106,24 +232,13 @@ __device__ __forceinline__ void exact_tile(const char* cur, const char* next, Ex
     if (t + RING < T) raw[t % RING] = exact_raw_load<DT>(cur + (t + RING) * STEP_BYTES);
     else raw[t % RING] = exact_raw_load<DT>(next + (t + RING - T) * STEP_BYTES);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (t == 0) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j], bq[0][j], floatx4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      else acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j], bq[t][j], acc[j], 0, 0, 0);
-    }
+    for (int j = 0; j < 8; ++j) exact_mfma_step(acc[j], x[j], bq[t][j], t == 0);
     // keep step t's refill load inside step t: left alone, the scheduler gathers all of a tile's loads behind its last MFMA
     // and the prefetch distance collapses to the epilogue
     __builtin_amdgcn_sched_barrier(0);
   }
-#pragma unroll
-  for (int v = 0; v < 4; ++v) {
-    // (lo + hi), hadd, hadd  (simd_dot.cpp:38-44)
-    const float s0 = acc[0][v] + acc[4][v], s1 = acc[1][v] + acc[5][v], s2 = acc[2][v] + acc[6][v], s3 = acc[3][v] + acc[7][v];
-    s[v] = (s0 + s1) + (s2 + s3);
-  }
+  exact_reduce(acc, s);
 }
-
-constexpr uint32_t EXACT_MFMA_ROWS = 16;                 // rows per tile (MFMA M)
-constexpr uint32_t EXACT_MFMA_QB = 16;                   // queries per wave (MFMA N)
 
 // wave -> (query block, row slice) of a workgroup that serves `nqb` (1..4) blocks of 16 queries
 __device__ __forceinline__ void exact_wave_role(uint32_t nqb, uint32_t wave, uint32_t& qb, uint32_t& slice, uint32_t& nslice) {
@@ -132,20 +247,22 @@ __device__ __forceinline__ void exact_wave_role(uint32_t nqb, uint32_t wave, uin
 }
 
 // ------------------------------------------------------------------------------------------------
-// scan: grid = (row splits P, ceil(nq / 64)), block = 256.  Same contract as scan_exact_kernel: every wave appends the <= k
-// best rows of its tiles (those that also clear the query's global threshold) to its queries' candidate lists; a query
-// receives at most P * nslice * k entries.
+// The register-direct kernels: grid = (row splits P, ceil(nq / 64)), block = 256.
+//   scan (SCORES = false): same contract as scan_exact_kernel: every wave appends the <= k best rows of its tiles (those that also
+//     clear the query's global threshold) to its queries' candidate lists; a query receives at most P * nslice * k entries.
+//     l_s / l_id: per wave and query a best-first list, entry e <-> lane e.
+//   scores (SCORES = true): out[q][row] for every (query, row) -- the any-k path's score matrix (kernels_largek.h);
+//     ld = row stride of `out` (a multiple of 4: 16-byte stores of 4 rows).
 // ------------------------------------------------------------------------------------------------
-template <int DT, int DIM>
-__global__ __launch_bounds__(256, 1) void scan_exact_mfma_kernel(
+template <int DT, int DIM, bool SCORES>
+__device__ __forceinline__ void exact_reg_body(
     const void* __restrict__ rows, const float* __restrict__ scales, uint32_t row_lo, uint32_t row_hi,
     const float* __restrict__ q32, uint32_t nq, uint32_t k, const float* __restrict__ thr,
-    Cand* __restrict__ cand, uint32_t* __restrict__ cnt, uint32_t cap, uint32_t* __restrict__ overflow) {
+    Cand* __restrict__ cand, uint32_t* __restrict__ cnt, uint32_t cap, uint32_t* __restrict__ overflow,
+    float* __restrict__ out, uint64_t ld, float (*l_s)[EXACT_MFMA_QB][64], uint32_t (*l_id)[EXACT_MFMA_QB][64]) {
   static_assert(DIM % 32 == 0 && DIM <= 768, "whole MFMA K-steps; 16 queries x DIM fp32 in registers");
   constexpr int BPE = exact_bpe<DT>(), RING = exact_ring<DT, DIM>(), STEP_BYTES = 32 * BPE;
   constexpr uint64_t ROW_BYTES = static_cast<uint64_t>(DIM) * BPE;
-  __shared__ float l_s[4][EXACT_MFMA_QB][64];            // per wave and query: best-first list, entry e <-> lane e
-  __shared__ uint32_t l_id[4][EXACT_MFMA_QB][64];
   const int lane = threadIdx.x & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n16 = lane & 15, kq = lane >> 4;
@@ -159,17 +276,9 @@ __global__ __launch_bounds__(256, 1) void scan_exact_mfma_kernel(
   float bq[DIM / 32][8];
   exact_load_bq<DIM>(q32, qi, nq, kq, bq);
 
-  // this workgroup's tiles, this wave's share of them
-  const uint32_t P = gridDim.x, p = blockIdx.x;
-  const uint32_t tiles = (row_hi - row_lo + EXACT_MFMA_ROWS - 1) / EXACT_MFMA_ROWS;
-  const uint32_t t_lo = static_cast<uint32_t>(static_cast<uint64_t>(tiles) * p / P), t_hi = static_cast<uint32_t>(static_cast<uint64_t>(tiles) * (p + 1) / P);
-
-  // per lane: the k-th best (score, row) of ITS query so far -- what a new row must beat -- and the list length
-  float thr_s = NEG_INF;
-  uint32_t thr_id = 0xFFFFFFFFu, my_cnt = 0;
-  const float gthr = (thr != nullptr && qi < nq) ? thr[qi] : NEG_INF;
-  const bool real = qi < nq;
-  float quick = gthr;
+  uint32_t t_lo, t_hi;                                    // this workgroup's tiles; the waves' slices interleave in them
+  exact_tile_range(row_lo, row_hi, t_lo, t_hi);
+  ExactTopK topk((!SCORES && thr != nullptr && qi < nq) ? thr[qi] : NEG_INF, qi < nq);
 
   const char* gbase = static_cast<const char*>(rows);
   auto lane_ptr = [&](uint32_t tile) -> const char* {     // row (tile, m = lane % 16), clamped into the range; + this lane's K offset
@@ -204,139 +313,31 @@ __global__ __launch_bounds__(256, 1) void scan_exact_mfma_kernel(
     float s[4];
     exact_tile<DT, DIM>(cur, next, raw, bq, s);
     cur = next;
-    const uint32_t row0 = row_lo + tile * EXACT_MFMA_ROWS + 4u * static_cast<uint32_t>(kq);     // this lane's rows: row0 + v
+    const uint32_t tile_row0 = row_lo + tile * EXACT_MFMA_ROWS, row0 = tile_row0 + 4u * static_cast<uint32_t>(kq);     // this lane's rows: row0 + v
     if constexpr (DT == DT_I8) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) { s[v] = s[v] * sc_cur[v]; sc_cur[v] = sc_nxt[v]; }                           // simd_dot.cpp:198
     }
-    // one compare per tile and lane in front of the full test: a row can only enter with a score >= quick (= the bar handed in and,
-    // once this query's list is full, its k-th score; NaN scores never enter)
-    const float smax = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
-    if (!__ballot(real && smax >= quick)) continue;
-    bool pass[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const uint32_t row = row0 + v;
-      pass[v] = real && row < row_hi && s[v] >= gthr && (my_cnt < k || better(s[v], row, thr_s, thr_id));
-    }
-    // rare: file the passing (row, query) pairs, one at a time, into the queries' lists
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      unsigned long long m = __ballot(pass[v]);
-      while (m) {
-        const int L = __builtin_ctzll(m);
-        m &= m - 1;
-        const uint32_t g = static_cast<uint32_t>(L) & 15u;                                  // the pair's query (block-relative)
-        const float cs = readlane_f(s[v], L);
-        const uint32_t cid = row_lo + tile * EXACT_MFMA_ROWS + 4u * (static_cast<uint32_t>(L) >> 4) + v;
-        const uint32_t c = readlane_u(my_cnt, static_cast<int>(g));                         // (lanes g, g + 16, .. hold query g's state)
-        const float ts = readlane_f(thr_s, static_cast<int>(g));
-        const uint32_t tid = readlane_u(thr_id, static_cast<int>(g));
-        if (!(c < k || better(cs, cid, ts, tid))) continue;                                  // an earlier pair of this tile raised the bar
-        float es = l_s[wave][g][lane];
-        uint32_t eid = l_id[wave][g][lane];
-        const bool ahead = static_cast<uint32_t>(lane) < c && better(es, eid, cs, cid);
-        const uint32_t pos = static_cast<uint32_t>(__builtin_popcountll(__ballot(ahead)));
-        const float up_s = __shfl_up(es, 1);
-        const uint32_t up_id = __shfl_up(eid, 1);
-        if (static_cast<uint32_t>(lane) > pos) { es = up_s; eid = up_id; }
-        else if (static_cast<uint32_t>(lane) == pos) { es = cs; eid = cid; }
-        const uint32_t c2 = c < k ? c + 1 : k;
-        if (static_cast<uint32_t>(lane) < c2) { l_s[wave][g][lane] = es; l_id[wave][g][lane] = eid; }
-        const float nts = readlane_f(es, static_cast<int>(k) - 1);
-        const uint32_t ntid = readlane_u(eid, static_cast<int>(k) - 1);
-        if (static_cast<uint32_t>(n16) == g) {
-          my_cnt = c2;
-          if (c2 == k) { thr_s = nts; thr_id = ntid; }
-        }
-      }
-    }
-    quick = my_cnt < k ? gthr : fmaxf(gthr, thr_s);
+    if constexpr (SCORES) { if (qi < nq) exact_store_scores(out, ld, qi, row0, row_hi, s); }
+    else exact_topk_offer(topk, l_s[wave], l_id[wave], s, row0, tile_row0, row_hi, k, lane);
   }
-  // append this wave's lists (global candidate lists; select_kernel orders them)
-  for (uint32_t g = 0; g < EXACT_MFMA_QB; ++g) {
-    const uint32_t q = qg0 + qb * EXACT_MFMA_QB + g;
-    const uint32_t c = readlane_u(my_cnt, static_cast<int>(g));
-    if (q >= nq || c == 0) continue;
-    uint32_t slot0 = 0;
-    if (lane == 0) slot0 = atomicAdd(&cnt[q], c);
-    slot0 = readlane_u(slot0, 0);
-    if (static_cast<uint32_t>(lane) < c) {
-      const uint32_t slot = slot0 + lane;
-      if (slot < cap) cand[static_cast<uint64_t>(q) * cap + slot] = Cand{l_s[wave][g][lane], l_id[wave][g][lane]};
-      else overflow[q] = 1u;
-    }
-  }
+  if constexpr (!SCORES) exact_topk_flush(topk, l_s[wave], l_id[wave], qg0 + qb * EXACT_MFMA_QB, nq, cand, cnt, cap, overflow, lane);
 }
 
-// ------------------------------------------------------------------------------------------------
-// scores: out[q][row] for every (query, row) -- the any-k path's score matrix (kernels_largek.h).
-// grid = (row splits, ceil(nq / 64)), block = 256; ld = row stride of `out` (a multiple of 4: 16-byte stores of 4 rows).
-// ------------------------------------------------------------------------------------------------
+template <int DT, int DIM>
+__global__ __launch_bounds__(256, 1) void scan_exact_mfma_kernel(
+    const void* __restrict__ rows, const float* __restrict__ scales, uint32_t row_lo, uint32_t row_hi,
+    const float* __restrict__ q32, uint32_t nq, uint32_t k, const float* __restrict__ thr,
+    Cand* __restrict__ cand, uint32_t* __restrict__ cnt, uint32_t cap, uint32_t* __restrict__ overflow) {
+  __shared__ float l_s[4][EXACT_MFMA_QB][64];
+  __shared__ uint32_t l_id[4][EXACT_MFMA_QB][64];
+  exact_reg_body<DT, DIM, false>(rows, scales, row_lo, row_hi, q32, nq, k, thr, cand, cnt, cap, overflow, nullptr, 0, l_s, l_id);
+}
+
 template <int DT, int DIM>
 __global__ __launch_bounds__(256, 1) void scores_exact_mfma_kernel(const void* __restrict__ rows, const float* __restrict__ scales, uint32_t n,
                                                                    const float* __restrict__ q32, uint32_t nq, float* __restrict__ out, uint64_t ld) {
-  static_assert(DIM % 32 == 0 && DIM <= 768, "whole MFMA K-steps; 16 queries x DIM fp32 in registers");
-  constexpr int BPE = exact_bpe<DT>(), RING = exact_ring<DT, DIM>(), STEP_BYTES = 32 * BPE;
-  constexpr uint64_t ROW_BYTES = static_cast<uint64_t>(DIM) * BPE;
-  const int lane = threadIdx.x & 63;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int n16 = lane & 15, kq = lane >> 4;
-  const uint32_t qg0 = blockIdx.y * 64u;
-  const uint32_t nqb_all = (nq - qg0 + EXACT_MFMA_QB - 1) / EXACT_MFMA_QB, nqb = nqb_all < 4u ? nqb_all : 4u;
-  uint32_t qb, slice, nslice;
-  exact_wave_role(nqb, wave, qb, slice, nslice);
-  if (qb >= nqb) return;
-  const uint32_t qi = qg0 + qb * EXACT_MFMA_QB + n16;
-  float bq[DIM / 32][8];
-  exact_load_bq<DIM>(q32, qi, nq, kq, bq);
-  const uint32_t P = gridDim.x, p = blockIdx.x;
-  const uint32_t tiles = (n + EXACT_MFMA_ROWS - 1) / EXACT_MFMA_ROWS;
-  const uint32_t t_lo = static_cast<uint32_t>(static_cast<uint64_t>(tiles) * p / P), t_hi = static_cast<uint32_t>(static_cast<uint64_t>(tiles) * (p + 1) / P);
-  const char* gbase = static_cast<const char*>(rows);
-  auto lane_ptr = [&](uint32_t tile) -> const char* {
-    uint32_t r = tile * EXACT_MFMA_ROWS + static_cast<uint32_t>(n16);
-    r = r < n ? r : n - 1;
-    return gbase + static_cast<uint64_t>(r) * ROW_BYTES + static_cast<uint32_t>(kq) * (8 * BPE);
-  };
-  uint32_t tile = t_lo + slice;
-  if (tile >= t_hi) return;
-  float sc_cur[4] = {1.f, 1.f, 1.f, 1.f};              // int8 row scales, one tile ahead (see scan_exact_mfma_kernel)
-  auto load_scales = [&](uint32_t tl, float (&dst)[4]) {
-    if constexpr (DT == DT_I8) {
-      const uint32_t r0 = tl * EXACT_MFMA_ROWS + 4u * static_cast<uint32_t>(kq);
-#pragma unroll
-      for (int v = 0; v < 4; ++v) dst[v] = scales[r0 + v < n ? r0 + v : n - 1];
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  load_scales(tile, sc_cur);
-  ExactRaw<DT> raw[RING];
-  const char* cur = lane_ptr(tile);
-#pragma unroll
-  for (int t = 0; t < RING; ++t) { raw[t] = exact_raw_load<DT>(cur + t * STEP_BYTES); __builtin_amdgcn_sched_barrier(0); }
-  for (; tile < t_hi; tile += nslice) {
-    const uint32_t nxt = tile + nslice < t_hi ? tile + nslice : tile;
-    const char* next = lane_ptr(nxt);
-    float sc_nxt[4] = {1.f, 1.f, 1.f, 1.f};
-    load_scales(nxt, sc_nxt);
-    float s[4];
-    exact_tile<DT, DIM>(cur, next, raw, bq, s);
-    cur = next;
-    const uint32_t row0 = tile * EXACT_MFMA_ROWS + 4u * static_cast<uint32_t>(kq);
-    if constexpr (DT == DT_I8) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v) { s[v] = s[v] * sc_cur[v]; sc_cur[v] = sc_nxt[v]; }
-    }
-    if (qi < nq) {
-      float* o = out + static_cast<uint64_t>(qi) * ld + row0;
-      if (row0 + 3 < n) *reinterpret_cast<float4*>(o) = make_float4(s[0], s[1], s[2], s[3]);
-      else {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) if (row0 + v < n) o[v] = s[v];
-      }
-    }
-  }
+  exact_reg_body<DT, DIM, true>(rows, scales, 0u, n, q32, nq, 0u, nullptr, nullptr, nullptr, 0u, nullptr, out, ld, nullptr, nullptr);
 }
 
 // ================================================================================================
@@ -393,18 +394,11 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_lds_kernel(
 
   float bq[T][8];
   exact_load_bq<DIM>(q32, qi, nq, kq, bq);
-  // consume the fragments HERE: hipcc otherwise defers its wait for these loads to their first use inside the tile loop, and that
-  // s_waitcnt vmcnt(0) would also wait for the direct-to-LDS prefetches it cannot see -- once per tile
-#pragma unroll
-  for (int t = 0; t < T; ++t)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(bq[t][j]));
   const float gthr = (!SCORES && thr != nullptr) ? thr[qi] : NEG_INF;
-  asm volatile("" ::"v"(gthr));
+  exact_pin(bq, gthr);
 
-  const uint32_t P = gridDim.x, p = blockIdx.x;
-  const uint32_t tiles = (row_hi - row_lo + EXACT_MFMA_ROWS - 1) / EXACT_MFMA_ROWS;
-  const uint32_t t_lo = static_cast<uint32_t>(static_cast<uint64_t>(tiles) * p / P), t_hi = static_cast<uint32_t>(static_cast<uint64_t>(tiles) * (p + 1) / P);
+  uint32_t t_lo, t_hi;
+  exact_tile_range(row_lo, row_hi, t_lo, t_hi);
   if (t_lo >= t_hi) return;
 
   // loader: piece i of this wave = linear 16-byte slots [(wave * PPW + i) * 64, +64) of the stage; slot L = row L / CHUNKS_PER_ROW,
@@ -433,8 +427,8 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_lds_kernel(
       if (lane < 16) glds4_v(scales + r, lds_base + (tl % NSTAGE) * STAGE_BYTES + DATA_BYTES + wave * 64);
     }
   };
-  // NOTE: a stage is chosen by the TILE index (tile % NSTAGE), so prefetches beyond t_hi land in the stage of the last tile --
-  // only after that tile has been consumed?  No: they are issued while it is being read.  Keep them out: see `have` below.
+  // a stage is chosen by the TILE index (tile % NSTAGE), so a prefetch beyond t_hi, clamped to the last tile, would overwrite that tile's
+  // stage while it is being read: none is issued -- issue_tile tests tile < t_hi here, the tile loop tests nxt < t_hi
   auto issue_tile = [&](uint32_t tile) {
     if (tile < t_hi) {
 #pragma unroll
@@ -465,9 +459,7 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_lds_kernel(
     return r;
   };
 
-  float thr_s = NEG_INF;
-  uint32_t thr_id = 0xFFFFFFFFu, my_cnt = 0;
-  float quick = gthr;
+  ExactTopK topk(gthr, true);
 
   // prologue: the first NSTAGE - 1 tiles
 #pragma unroll
@@ -490,6 +482,8 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_lds_kernel(
       float x[8];
       exact_raw_to_f32<DT>(ring[t % RING], x);
 #pragma unroll
+      // (exact_mfma_step and, below, exact_reduce written out in THIS kernel: through the helpers hipcc pulls the reduction's
+      // v_accvgpr_reads in between the last K-step's MFMAs of the fp32 d = 256 / 512 builds -- profiles/exact_shared_pieces_codegen.txt)
       for (int j = 0; j < 8; ++j) {
         if (t == 0) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j], bq[0][j], floatx4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         else acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j], bq[t][j], acc[j], 0, 0, 0);
@@ -511,76 +505,15 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_lds_kernel(
       const float s0 = acc[0][v] + acc[4][v], s1 = acc[1][v] + acc[5][v], s2 = acc[2][v] + acc[6][v], s3 = acc[3][v] + acc[7][v];
       s[v] = (s0 + s1) + (s2 + s3);
     }
-    const uint32_t row0 = row_lo + tile * EXACT_MFMA_ROWS + 4u * static_cast<uint32_t>(kq);
+    const uint32_t tile_row0 = row_lo + tile * EXACT_MFMA_ROWS, row0 = tile_row0 + 4u * static_cast<uint32_t>(kq);
     if constexpr (DT == DT_I8) {
       const float4 sc = *reinterpret_cast<const float4*>(stage + DATA_BYTES + wave * 64 + 16 * kq);
       s[0] *= sc.x; s[1] *= sc.y; s[2] *= sc.z; s[3] *= sc.w;                      // simd_dot.cpp:198
     }
-    if constexpr (SCORES) {
-      float* o = out + static_cast<uint64_t>(qi) * ld + row0;
-      if (row0 + 3 < row_hi) *reinterpret_cast<float4*>(o) = make_float4(s[0], s[1], s[2], s[3]);
-      else {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) if (row0 + v < row_hi) o[v] = s[v];
-      }
-    } else {
-      const float smax = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));       // (the quick test of scan_exact_mfma_kernel)
-      if (!__ballot(smax >= quick)) continue;
-      bool pass[4];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const uint32_t row = row0 + v;
-        pass[v] = row < row_hi && s[v] >= gthr && (my_cnt < k || better(s[v], row, thr_s, thr_id));
-      }
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        unsigned long long m = __ballot(pass[v]);
-        while (m) {
-          const int L = __builtin_ctzll(m);
-          m &= m - 1;
-          const uint32_t g = static_cast<uint32_t>(L) & 15u;
-          const float cs = readlane_f(s[v], L);
-          const uint32_t cid = row_lo + tile * EXACT_MFMA_ROWS + 4u * (static_cast<uint32_t>(L) >> 4) + v;
-          const uint32_t c = readlane_u(my_cnt, static_cast<int>(g));
-          const float ts = readlane_f(thr_s, static_cast<int>(g));
-          const uint32_t tid = readlane_u(thr_id, static_cast<int>(g));
-          if (!(c < k || better(cs, cid, ts, tid))) continue;
-          float es = l_s[SCORES ? 0 : wave][SCORES ? 0 : g][lane];
-          uint32_t eid = l_id[SCORES ? 0 : wave][SCORES ? 0 : g][lane];
-          const bool ahead = static_cast<uint32_t>(lane) < c && better(es, eid, cs, cid);
-          const uint32_t pos = static_cast<uint32_t>(__builtin_popcountll(__ballot(ahead)));
-          const float up_s = __shfl_up(es, 1);
-          const uint32_t up_id = __shfl_up(eid, 1);
-          if (static_cast<uint32_t>(lane) > pos) { es = up_s; eid = up_id; }
-          else if (static_cast<uint32_t>(lane) == pos) { es = cs; eid = cid; }
-          const uint32_t c2 = c < k ? c + 1 : k;
-          if (static_cast<uint32_t>(lane) < c2) { l_s[SCORES ? 0 : wave][SCORES ? 0 : g][lane] = es; l_id[SCORES ? 0 : wave][SCORES ? 0 : g][lane] = eid; }
-          const float nts = readlane_f(es, static_cast<int>(k) - 1);
-          const uint32_t ntid = readlane_u(eid, static_cast<int>(k) - 1);
-          if (static_cast<uint32_t>(x15) == g) {
-            my_cnt = c2;
-            if (c2 == k) { thr_s = nts; thr_id = ntid; }
-          }
-        }
-      }
-      quick = my_cnt < k ? gthr : fmaxf(gthr, thr_s);
-    }
+    if constexpr (SCORES) exact_store_scores(out, ld, qi, row0, row_hi, s);
+    else exact_topk_offer(topk, l_s[wave], l_id[wave], s, row0, tile_row0, row_hi, k, lane);
   }
-  if constexpr (!SCORES) {
-    for (uint32_t g = 0; g < EXACT_MFMA_QB; ++g) {
-      const uint32_t q = qg0 + wave * EXACT_MFMA_QB + g;
-      const uint32_t c = readlane_u(my_cnt, static_cast<int>(g));
-      if (c == 0) continue;
-      uint32_t slot0 = 0;
-      if (lane == 0) slot0 = atomicAdd(&cnt[q], c);
-      slot0 = readlane_u(slot0, 0);
-      if (static_cast<uint32_t>(lane) < c) {
-        const uint32_t slot = slot0 + lane;
-        if (slot < cap) cand[static_cast<uint64_t>(q) * cap + slot] = Cand{l_s[SCORES ? 0 : wave][SCORES ? 0 : g][lane], l_id[SCORES ? 0 : wave][SCORES ? 0 : g][lane]};
-        else overflow[q] = 1u;
-      }
-    }
-  }
+  if constexpr (!SCORES) exact_topk_flush(topk, l_s[wave], l_id[wave], qg0 + wave * EXACT_MFMA_QB, nq, cand, cnt, cap, overflow, lane);
 }
 
 // ================================================================================================
@@ -633,16 +566,11 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_img_kernel(
 
   float bq[T][8];
   exact_load_bq<DIM>(q32, qi, nq, kq, bq);
-#pragma unroll
-  for (int t = 0; t < T; ++t)          // consumed HERE (see exact_mfma_lds_kernel: a wait deferred into the loop would drain the asm loads)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(bq[t][j]));
   const float gthr = (!SCORES && thr != nullptr) ? thr[qi] : NEG_INF;
-  asm volatile("" ::"v"(gthr));
+  exact_pin(bq, gthr);
 
-  const uint32_t P = gridDim.x, p = blockIdx.x;
-  const uint32_t tiles = (row_hi - row_lo + EXACT_MFMA_ROWS - 1) / EXACT_MFMA_ROWS;
-  const uint32_t t_lo = static_cast<uint32_t>(static_cast<uint64_t>(tiles) * p / P), t_hi = static_cast<uint32_t>(static_cast<uint64_t>(tiles) * (p + 1) / P);
+  uint32_t t_lo, t_hi;
+  exact_tile_range(row_lo, row_hi, t_lo, t_hi);
   if (t_lo >= t_hi) return;
 
   // my quarter of a tile = rows 4 * wave .. + 3.  Raw chunk i of this lane is chunk `pc(i)` of row `pr(i)`, chosen so that the 16 lanes
@@ -778,9 +706,7 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_img_kernel(
     return r;
   };
 
-  float thr_s = NEG_INF;
-  uint32_t thr_id = 0xFFFFFFFFu, my_cnt = 0;
-  float quick = gthr;
+  ExactTopK topk(gthr, true);
   float sc_cur[4] = {1.f, 1.f, 1.f, 1.f};
 
   // prologue: image of the first tile; my quarter of the second on its way
@@ -815,8 +741,7 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_img_kernel(
       exact_raw_to_f32<DT_F32>(ring[t % RING], x);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        if (t == 0) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j], bq[0][j], floatx4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        else acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j], bq[t][j], acc[j], 0, 0, 0);
+        exact_mfma_step(acc[j], x[j], bq[t][j], t == 0);
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
           if (t == conv_step(i)) {
@@ -829,68 +754,14 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_img_kernel(
       staged_reads(tile, t);
     }
     float s[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const float s0 = acc[0][v] + acc[4][v], s1 = acc[1][v] + acc[5][v], s2 = acc[2][v] + acc[6][v], s3 = acc[3][v] + acc[7][v];
-      s[v] = (s0 + s1) + (s2 + s3);
-    }
-    const uint32_t row0 = row_lo + tile * EXACT_MFMA_ROWS + 4u * static_cast<uint32_t>(kq);
+    exact_reduce(acc, s);
+    const uint32_t tile_row0 = row_lo + tile * EXACT_MFMA_ROWS, row0 = tile_row0 + 4u * static_cast<uint32_t>(kq);
     if constexpr (DT == DT_I8) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) s[v] *= sc_cur[v];                               // simd_dot.cpp:198
     }
-    if constexpr (SCORES) {
-      float* o = out + static_cast<uint64_t>(qi) * ld + row0;
-      if (row0 + 3 < row_hi) *reinterpret_cast<float4*>(o) = make_float4(s[0], s[1], s[2], s[3]);
-      else {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) if (row0 + v < row_hi) o[v] = s[v];
-      }
-    } else {
-      // one compare per tile and lane in front of the full test: a row can only enter with a score >= quick (= the bar handed in
-      // and, once my list is full, its k-th score; NaN scores never enter, as before)
-      const float smax = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
-      if (__ballot(smax >= quick)) {
-        bool pass[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const uint32_t row = row0 + v;
-          pass[v] = row < row_hi && s[v] >= gthr && (my_cnt < k || better(s[v], row, thr_s, thr_id));
-        }
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          unsigned long long m = __ballot(pass[v]);
-          while (m) {
-            const int L = __builtin_ctzll(m);
-            m &= m - 1;
-            const uint32_t g = static_cast<uint32_t>(L) & 15u;
-            const float cs = readlane_f(s[v], L);
-            const uint32_t cid = row_lo + tile * EXACT_MFMA_ROWS + 4u * (static_cast<uint32_t>(L) >> 4) + v;
-            const uint32_t c = readlane_u(my_cnt, static_cast<int>(g));
-            const float ts = readlane_f(thr_s, static_cast<int>(g));
-            const uint32_t tid = readlane_u(thr_id, static_cast<int>(g));
-            if (!(c < k || better(cs, cid, ts, tid))) continue;
-            float es = l_s[SCORES ? 0 : wave][SCORES ? 0 : g][lane];
-            uint32_t eid = l_id[SCORES ? 0 : wave][SCORES ? 0 : g][lane];
-            const bool ahead = static_cast<uint32_t>(lane) < c && better(es, eid, cs, cid);
-            const uint32_t pos = static_cast<uint32_t>(__builtin_popcountll(__ballot(ahead)));
-            const float up_s = __shfl_up(es, 1);
-            const uint32_t up_id = __shfl_up(eid, 1);
-            if (static_cast<uint32_t>(lane) > pos) { es = up_s; eid = up_id; }
-            else if (static_cast<uint32_t>(lane) == pos) { es = cs; eid = cid; }
-            const uint32_t c2 = c < k ? c + 1 : k;
-            if (static_cast<uint32_t>(lane) < c2) { l_s[SCORES ? 0 : wave][SCORES ? 0 : g][lane] = es; l_id[SCORES ? 0 : wave][SCORES ? 0 : g][lane] = eid; }
-            const float nts = readlane_f(es, static_cast<int>(k) - 1);
-            const uint32_t ntid = readlane_u(eid, static_cast<int>(k) - 1);
-            if (static_cast<uint32_t>(x15) == g) {
-              my_cnt = c2;
-              if (c2 == k) { thr_s = nts; thr_id = ntid; }
-            }
-          }
-        }
-        quick = my_cnt < k ? gthr : fmaxf(gthr, thr_s);
-      }
-    }
+    if constexpr (SCORES) exact_store_scores(out, ld, qi, row0, row_hi, s);
+    else exact_topk_offer(topk, l_s[wave], l_id[wave], s, row0, tile_row0, row_hi, k, lane);
     if constexpr (DT == DT_I8) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) sc_cur[v] = sc_nxt[v];
@@ -901,21 +772,7 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_img_kernel(
   };
   for (uint32_t tile = t_lo; tile < t_hi; ++tile) one_tile(tile);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // (the prefetch that ran past my range)
-  if constexpr (!SCORES) {
-    for (uint32_t g = 0; g < EXACT_MFMA_QB; ++g) {
-      const uint32_t q = qg0 + wave * EXACT_MFMA_QB + g;
-      const uint32_t c = readlane_u(my_cnt, static_cast<int>(g));
-      if (c == 0) continue;
-      uint32_t slot0 = 0;
-      if (lane == 0) slot0 = atomicAdd(&cnt[q], c);
-      slot0 = readlane_u(slot0, 0);
-      if (static_cast<uint32_t>(lane) < c) {
-        const uint32_t slot = slot0 + lane;
-        if (slot < cap) cand[static_cast<uint64_t>(q) * cap + slot] = Cand{l_s[SCORES ? 0 : wave][SCORES ? 0 : g][lane], l_id[SCORES ? 0 : wave][SCORES ? 0 : g][lane]};
-        else overflow[q] = 1u;
-      }
-    }
-  }
+  if constexpr (!SCORES) exact_topk_flush(topk, l_s[wave], l_id[wave], qg0 + wave * EXACT_MFMA_QB, nq, cand, cnt, cap, overflow, lane);
 }
 
 }  // namespace nvdbhip

@@ -234,6 +234,8 @@ using F16Dims16 = DimList<896, 1024, 1152, 1280, 1408, 1536>;
 using F16DimsK2 = DimList<2048, 2560, 3072>;
 using I8Dims = DimList<768, 640, 512, 384, 256>;
 using I8DimsBig = DimList<896, 1024, 1152, 1280, 1408, 1536>;
+// the exact fp32-MFMA kernels (kernels_exact_mfma.h): dim % 32 == 0 (no scalar tail), 16 queries x dim floats in registers
+using ExactMfmaDims = DimList<768, 640, 512, 384, 256, 128>;
 
 // st = f(std::integral_constant<int, D>) for the D of the list that equals dim; false: the list does not hold dim
 template <int... D, typename F>
@@ -241,6 +243,13 @@ bool dispatch_dim(DimList<D...>, uint32_t dim, nvdb_status& st, F&& f) {
   return ((dim == static_cast<uint32_t>(D) && ((st = f(std::integral_constant<int, D>{})), true)) || ...);
 }
 template <int... D> bool has_dim(DimList<D...>, uint32_t dim) { return ((dim == static_cast<uint32_t>(D)) || ...); }
+// st = f(std::integral_constant<int, DT_*>) for the corpus dtype (anything that is neither fp32 nor fp16 is int8, as in every launcher)
+template <typename F>
+void dispatch_dtype(uint32_t dtype, nvdb_status& st, F&& f) {
+  if (dtype == NVDB_DTYPE_F32) st = f(std::integral_constant<int, DT_F32>{});
+  else if (dtype == NVDB_DTYPE_F16) st = f(std::integral_constant<int, DT_F16>{});
+  else st = f(std::integral_constant<int, DT_I8>{});
+}
 
 inline bool f16_filter_dim(uint32_t dim) { return has_dim(F16Dims{}, dim) || has_dim(F16Dims16{}, dim) || has_dim(F16DimsK2{}, dim); }
 inline bool i8_filter_dim(uint32_t dim) { return has_dim(I8Dims{}, dim) || has_dim(I8DimsBig{}, dim); }

@@ -27,18 +27,55 @@ nvdb_status launch_scan_exact_qg(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo
   const bool al = aligned_rows(c->dtype, c->dim);
   const uint32_t qstride = (c->dim + 3u) & ~3u;
   const size_t lds = static_cast<size_t>(QG) * qstride * 4 + static_cast<size_t>(4) * QG * 64 * 8 + 4 * QG * 4;
-#define NVDB_LAUNCH_SCAN(DT, AL) \
-  scan_exact_kernel<DT, QG, AL><<<grid, 256, lds, s>>>(c->rows, c->scales, c->dim, row_lo, row_hi, q32, nq, 0u, k, thr, cand, cnt, cap, ovf)
-  if (c->dtype == NVDB_DTYPE_F32) { if (al) NVDB_LAUNCH_SCAN(DT_F32, true); else NVDB_LAUNCH_SCAN(DT_F32, false); }
-  else if (c->dtype == NVDB_DTYPE_F16) { if (al) NVDB_LAUNCH_SCAN(DT_F16, true); else NVDB_LAUNCH_SCAN(DT_F16, false); }
-  else { if (al) NVDB_LAUNCH_SCAN(DT_I8, true); else NVDB_LAUNCH_SCAN(DT_I8, false); }
-#undef NVDB_LAUNCH_SCAN
+  nvdb_status st = NVDB_OK;
+  dispatch_dtype(c->dtype, st, [&](auto dt) {
+    auto go = [&](auto kern) { kern<<<grid, 256, lds, s>>>(c->rows, c->scales, c->dim, row_lo, row_hi, q32, nq, 0u, k, thr, cand, cnt, cap, ovf); };
+    if (al) go(scan_exact_kernel<decltype(dt)::value, QG, true>); else go(scan_exact_kernel<decltype(dt)::value, QG, false>);
+    return NVDB_OK;
+  });
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
 }
 
-// dims the fp32-MFMA exact kernels are instantiated for (dim % 32 == 0: no scalar tail; 16 queries x dim floats in registers)
-bool exact_mfma_dim(uint32_t dim) { return dim == 768 || dim == 640 || dim == 512 || dim == 384 || dim == 256 || dim == 128; }
+bool exact_mfma_dim(uint32_t dim) { return has_dim(ExactMfmaDims{}, dim); }
+
+// row splits of an exact MFMA grid of gy query groups: wgs workgroups in all, >= 8 tiles each, within the list capacity (pmax)
+static uint32_t exact_grid_p(uint32_t wgs, uint32_t gy, uint32_t tiles, uint32_t pmax) {
+  const uint32_t P = std::max<uint32_t>(1, wgs / gy);
+  return std::max<uint32_t>(1, std::min(std::min(P, std::max<uint32_t>(1, tiles / 8)), pmax));
+}
+
+// what the exact MFMA kernels take behind (rows, scales): the scan fills the list fields, the score matrix out / ld
+struct ExactMfmaArgs {
+  uint32_t row_lo, row_hi; const float* q32; uint32_t k; const float* thr; Cand* cand; uint32_t* cnt; uint32_t cap; uint32_t* ovf; float* out; uint64_t ld;
+};
+
+// The staged builds take the full groups of 64 queries: fp16 / int8 rows converted once per workgroup into an fp32 LDS image
+// (exact_mfma_img_kernel) first, else raw tiles staged through LDS (exact_mfma_lds_kernel), where the options ask for them and the
+// shape has a build.  Returns the number of queries served: [0, q0); the rest goes to the register-direct kernels.
+template <int DT, bool SCORES>
+uint32_t launch_exact_staged(nvdb_hip_ctx* c, hipStream_t s, const ExactMfmaArgs& a, uint32_t nq, uint32_t tiles, uint32_t wgs, uint32_t pmax, nvdb_status& st) {
+  if (nq < 64) return 0;
+  const bool want_img = c->opt_exact_img && c->opt_exact_lds != 2;
+  const bool want_lds = c->opt_exact_lds == 2 || (c->opt_exact_lds == 1 && DT == DT_F32);
+  const uint32_t gy = nq / 64;
+  const dim3 grid(exact_grid_p(wgs, gy, tiles, pmax), gy);
+  uint32_t q0 = 0;
+  auto launch = [&](auto kern, int lds) {
+    if (nvdb_status ls = raise_lds_limit(c, reinterpret_cast<const void*>(kern), lds)) return ls;
+    kern<<<grid, 256, lds, s>>>(c->rows, c->scales, a.row_lo, a.row_hi, a.q32, gy * 64, a.k, a.thr, a.cand, a.cnt, a.cap, a.ovf, a.out, a.ld);
+    HIPCHK(c, hipGetLastError());
+    q0 = gy * 64;
+    return NVDB_OK;
+  };
+  dispatch_dim(ExactMfmaDims{}, c->dim, st, [&](auto Dc) {
+    constexpr int D = decltype(Dc)::value;
+    if constexpr (exact_img_shape<DT, D>()) { if (want_img) return launch(exact_mfma_img_kernel<DT, D, SCORES>, exact_img_bytes<DT, D>()); }
+    if constexpr (exact_lds_shape<DT, D>()) { if (want_lds) return launch(exact_mfma_lds_kernel<DT, D, SCORES>, exact_lds_bytes<DT, D>()); }
+    return NVDB_OK;
+  });
+  return q0;
+}
 
 // The exact scan on the fp32 matrix cores (kernels_exact_mfma.h).  A query receives at most P * nslice * k list entries, nslice = 4 / (16-query
 // blocks of its group of 64, rounded up to 1, 2 or 4).
@@ -46,70 +83,26 @@ template <int DT>
 nvdb_status launch_scan_exact_mfma(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint32_t row_hi, const float* q32,
                                    uint32_t nq, uint32_t k, const float* thr, uint32_t cap, uint32_t reserve) {
   const uint32_t tiles = (row_hi - row_lo + EXACT_MFMA_ROWS - 1) / EXACT_MFMA_ROWS;
+  const uint32_t wgs = static_cast<uint32_t>(c->opt_exact_wgs) * static_cast<uint32_t>(c->num_cu);   // one workgroup per CU in all (see opt_exact_wgs)
   Cand* cand = static_cast<Cand*>(c->cand.p);
   uint32_t* cnt = static_cast<uint32_t*>(c->cnt.p);
   uint32_t* ovf = static_cast<uint32_t*>(c->overflow.p);
-  uint32_t q0 = 0;                                  // queries [0, q0) are served by the LDS-staged kernel (full groups of 64)
-  bool lds_done = false;
-#define NVDB_SCAN_LDS(D)                                                                                                           \
-  if constexpr (exact_lds_shape<DT, D>()) {                                                                                        \
-    if ((c->opt_exact_lds == 2 || (c->opt_exact_lds == 1 && DT == DT_F32)) && nq >= 64 && c->dim == D) {                          \
-      const uint32_t gy = nq / 64;                                                                                                 \
-      const uint32_t pmax = (cap > reserve + k) ? (cap - reserve) / k : 1;                                                         \
-      uint32_t P = std::max<uint32_t>(1, (static_cast<uint32_t>(c->opt_exact_wgs) * static_cast<uint32_t>(c->num_cu)) / gy);                                  \
-      P = std::max<uint32_t>(1, std::min(std::min(P, std::max<uint32_t>(1, tiles / 8)), pmax));                                    \
-      const void* fn = reinterpret_cast<const void*>(exact_mfma_lds_kernel<DT, D, false>);                                         \
-      if (nvdb_status ls = raise_lds_limit(c, fn, exact_lds_bytes<DT, D>())) return ls;                                            \
-      exact_mfma_lds_kernel<DT, D, false><<<dim3(P, gy), 256, exact_lds_bytes<DT, D>(), s>>>(c->rows, c->scales, row_lo, row_hi, q32, gy * 64, k, thr, \
-                                                                                             cand, cnt, cap, ovf, nullptr, 0);     \
-      HIPCHK(c, hipGetLastError());                                                                                                \
-      q0 = gy * 64; lds_done = true;                                                                                               \
-    }                                                                                                                              \
-  }
-  // fp16 / int8 rows, full groups of 64 queries: the tile converted once per workgroup into an fp32 LDS image (exact_mfma_img_kernel)
-#define NVDB_SCAN_IMG(D)                                                                                                           \
-  if constexpr (exact_img_shape<DT, D>()) {                                                                                        \
-    if (c->opt_exact_img && c->opt_exact_lds != 2 && nq >= 64 && c->dim == D) {                                                    \
-      const uint32_t gy = nq / 64;                                                                                                 \
-      const uint32_t pmax = (cap > reserve + k) ? (cap - reserve) / k : 1;                                                         \
-      uint32_t P = std::max<uint32_t>(1, (static_cast<uint32_t>(c->opt_exact_wgs) * static_cast<uint32_t>(c->num_cu)) / gy);                                  \
-      P = std::max<uint32_t>(1, std::min(std::min(P, std::max<uint32_t>(1, tiles / 8)), pmax));                                    \
-      const void* fn = reinterpret_cast<const void*>(exact_mfma_img_kernel<DT, D, false>);                                         \
-      if (nvdb_status ls = raise_lds_limit(c, fn, exact_img_bytes<DT, D>())) return ls;                                            \
-      exact_mfma_img_kernel<DT, D, false><<<dim3(P, gy), 256, exact_img_bytes<DT, D>(), s>>>(c->rows, c->scales, row_lo, row_hi, q32, gy * 64, k, thr, \
-                                                                                             cand, cnt, cap, ovf, nullptr, 0);     \
-      HIPCHK(c, hipGetLastError());                                                                                                \
-      q0 = gy * 64; lds_done = true;                                                                                               \
-    }                                                                                                                              \
-  }
-  NVDB_SCAN_IMG(768) NVDB_SCAN_IMG(640) NVDB_SCAN_IMG(512) NVDB_SCAN_IMG(384) NVDB_SCAN_IMG(256) NVDB_SCAN_IMG(128)
-#undef NVDB_SCAN_IMG
-  if (!lds_done) { NVDB_SCAN_LDS(768) NVDB_SCAN_LDS(640) NVDB_SCAN_LDS(512) NVDB_SCAN_LDS(384) NVDB_SCAN_LDS(256) NVDB_SCAN_LDS(128) }
-#undef NVDB_SCAN_LDS
-  (void)lds_done;
-  if (q0 >= nq) return NVDB_OK;
-  // the rest (fewer than 64 queries, or everything when the LDS-staged build does not take the shape): register-direct kernel
+  nvdb_status st = NVDB_OK;
+  const uint32_t q0 = launch_exact_staged<DT, false>(c, s, ExactMfmaArgs{row_lo, row_hi, q32, k, thr, cand, cnt, cap, ovf, nullptr, 0}, nq, tiles, wgs,
+                                                     (cap > reserve + k) ? (cap - reserve) / k : 1, st);
+  if (st || q0 >= nq) return st;
+  // the rest (fewer than 64 queries, or everything when no staged build takes the shape): register-direct kernel
   const uint32_t nr = nq - q0;
   const uint32_t gy = (nr + 63) / 64;
   const uint32_t last_blocks = (nr - (gy - 1) * 64 + 15) / 16;                    // 16-query blocks of the last (partial) group
   const uint32_t nslice_max = last_blocks >= 3 ? 1u : (last_blocks == 2 ? 2u : 4u);
   const uint32_t pmax = (cap > reserve + k * nslice_max) ? (cap - reserve) / (k * nslice_max) : 1;
-  uint32_t P = std::max<uint32_t>(1, (static_cast<uint32_t>(c->opt_exact_wgs) * static_cast<uint32_t>(c->num_cu)) / gy);   // one workgroup per CU in all (see opt_exact_wgs)
-  P = std::min(P, std::max<uint32_t>(1, tiles / 8));                                           // >= 8 tiles each
-  P = std::max<uint32_t>(1, std::min(P, pmax));
-  const dim3 grid(P, gy);
-  const float* qr = q32 + static_cast<size_t>(q0) * c->dim;
-  const float* thr_r = thr ? thr + q0 : nullptr;
-#define NVDB_SCAN_MFMA(D) scan_exact_mfma_kernel<DT, D><<<grid, 256, 0, s>>>(c->rows, c->scales, row_lo, row_hi, qr, nr, k, thr_r, cand + static_cast<size_t>(q0) * cap, cnt + q0, cap, ovf + q0)
-  switch (c->dim) {
-    case 768: NVDB_SCAN_MFMA(768); break;
-    case 640: NVDB_SCAN_MFMA(640); break;
-    case 512: NVDB_SCAN_MFMA(512); break;
-    case 384: NVDB_SCAN_MFMA(384); break;
-    case 256: NVDB_SCAN_MFMA(256); break;
-    default: NVDB_SCAN_MFMA(128); break;
-  }
-#undef NVDB_SCAN_MFMA
+  const dim3 grid(exact_grid_p(wgs, gy, tiles, pmax), gy);
+  dispatch_dim(ExactMfmaDims{}, c->dim, st, [&](auto D) {
+    scan_exact_mfma_kernel<DT, decltype(D)::value><<<grid, 256, 0, s>>>(c->rows, c->scales, row_lo, row_hi, q32 + static_cast<size_t>(q0) * c->dim, nr, k,
+                                                                      thr ? thr + q0 : nullptr, cand + static_cast<size_t>(q0) * cap, cnt + q0, cap, ovf + q0);
+    return NVDB_OK;
+  });
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
 }
@@ -120,9 +113,9 @@ nvdb_status launch_scan_exact(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, u
   if (k > WAVE_KMAX) return fail(c, NVDB_ERR_INTERNAL, "scan_exact: k beyond the wavefront-resident lists (64)");
   // more than 8 queries, whole MFMA K-steps and enough rows for the tiles: the fp32 matrix cores (same bits, ~4x the rate)
   if (c->opt_exact_mfma && nq > 8 && exact_mfma_dim(c->dim) && row_hi - row_lo >= 64u * EXACT_MFMA_ROWS) {
-    if (c->dtype == NVDB_DTYPE_F32) return launch_scan_exact_mfma<DT_F32>(c, s, row_lo, row_hi, q32, nq, k, thr, cap, reserve);
-    if (c->dtype == NVDB_DTYPE_F16) return launch_scan_exact_mfma<DT_F16>(c, s, row_lo, row_hi, q32, nq, k, thr, cap, reserve);
-    return launch_scan_exact_mfma<DT_I8>(c, s, row_lo, row_hi, q32, nq, k, thr, cap, reserve);
+    nvdb_status st = NVDB_OK;
+    dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_scan_exact_mfma<decltype(dt)::value>(c, s, row_lo, row_hi, q32, nq, k, thr, cap, reserve); });
+    return st;
   }
   uint32_t QG = nq >= 8 ? 8 : (nq >= 4 ? 4 : (nq >= 2 ? 2 : 1));
   while (QG > 1 && static_cast<size_t>(QG) * (((c->dim + 3u) & ~3u) * 4 + 4 * 64 * 8 + 16) > 60 * 1024) QG >>= 1;   // LDS budget
@@ -185,30 +178,35 @@ nvdb_status launch_rescore(nvdb_hip_ctx* c, hipStream_t s, const float* q32, uin
       while (cap2 < cap) cap2 <<= 1;
       lds = std::max(lds, cap2 * sizeof(Cand));                    // the folded select sorts the list in the same LDS
     }
-    const void* fn = c->dtype == NVDB_DTYPE_F32 ? reinterpret_cast<const void*>(rescore_lds_kernel<DT_F32>)
-                   : c->dtype == NVDB_DTYPE_F16 ? reinterpret_cast<const void*>(rescore_lds_kernel<DT_F16>) : reinterpret_cast<const void*>(rescore_lds_kernel<DT_I8>);
-    if (lds > 48 * 1024)
-      if (nvdb_status ls = raise_lds_limit(c, fn, SELECT_MAX_CAP * sizeof(Cand))) return ls;
-    if (c->dtype == NVDB_DTYPE_F32) rescore_lds_kernel<DT_F32><<<nq, 256, lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot, cpp, fs);
-    else if (c->dtype == NVDB_DTYPE_F16) rescore_lds_kernel<DT_F16><<<nq, 256, lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot, cpp, fs);
-    else rescore_lds_kernel<DT_I8><<<nq, 256, lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot, cpp, fs);
+    nvdb_status st = NVDB_OK;
+    dispatch_dtype(c->dtype, st, [&](auto dt) {
+      auto kern = rescore_lds_kernel<decltype(dt)::value>;
+      if (lds > 48 * 1024)
+        if (nvdb_status ls = raise_lds_limit(c, reinterpret_cast<const void*>(kern), SELECT_MAX_CAP * sizeof(Cand))) return ls;
+      kern<<<nq, 256, lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot, cpp, fs);
+      return NVDB_OK;
+    });
+    if (st) return st;
     HIPCHK(c, hipGetLastError());
     if (fused) *fused = fs.mode != 0;
     return NVDB_OK;
   }
   if (c->opt_rescore8) {
-    if (c->dtype == NVDB_DTYPE_F32) rescore8_kernel<DT_F32><<<nq, 256, rs_lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot);
-    else if (c->dtype == NVDB_DTYPE_F16) rescore8_kernel<DT_F16><<<nq, 256, rs_lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot);
-    else rescore8_kernel<DT_I8><<<nq, 256, rs_lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot);
+    nvdb_status st = NVDB_OK;
+    dispatch_dtype(c->dtype, st, [&](auto dt) {
+      rescore8_kernel<decltype(dt)::value><<<nq, 256, rs_lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot);
+      return NVDB_OK;
+    });
     HIPCHK(c, hipGetLastError());
     return NVDB_OK;
   }
   const bool al = aligned_rows(c->dtype, c->dim);
-#define NVDB_LAUNCH_RS(DT, AL) rescore_kernel<DT, AL><<<nq, 256, rs_lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot)
-  if (c->dtype == NVDB_DTYPE_F32) { if (al) NVDB_LAUNCH_RS(DT_F32, true); else NVDB_LAUNCH_RS(DT_F32, false); }
-  else if (c->dtype == NVDB_DTYPE_F16) { if (al) NVDB_LAUNCH_RS(DT_F16, true); else NVDB_LAUNCH_RS(DT_F16, false); }
-  else { if (al) NVDB_LAUNCH_RS(DT_I8, true); else NVDB_LAUNCH_RS(DT_I8, false); }
-#undef NVDB_LAUNCH_RS
+  nvdb_status st = NVDB_OK;
+  dispatch_dtype(c->dtype, st, [&](auto dt) {
+    auto go = [&](auto kern) { kern<<<nq, 256, rs_lds, s>>>(c->rows, c->scales, c->dim, q32, cand, cnt, cap, eb, viol, tot); };
+    if (al) go(rescore_kernel<decltype(dt)::value, true>); else go(rescore_kernel<decltype(dt)::value, false>);
+    return NVDB_OK;
+  });
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
 }
@@ -219,77 +217,39 @@ nvdb_status launch_scores_exact_qg(nvdb_hip_ctx* c, hipStream_t s, const float* 
   const dim3 grid(std::min<uint32_t>((n + 255u) / 256u, 8u * static_cast<uint32_t>(c->num_cu)), (nq + QG - 1) / QG);
   const bool al = aligned_rows(c->dtype, c->dim);
   const size_t lds = static_cast<size_t>(QG) * ((c->dim + 3u) & ~3u) * 4;
-#define NVDB_LAUNCH_SC(DT, AL) scores_exact_kernel<DT, QG, AL><<<grid, 256, lds, s>>>(c->rows, c->scales, c->dim, n, q32, nq, out, ld)
-  if (c->dtype == NVDB_DTYPE_F32) { if (al) NVDB_LAUNCH_SC(DT_F32, true); else NVDB_LAUNCH_SC(DT_F32, false); }
-  else if (c->dtype == NVDB_DTYPE_F16) { if (al) NVDB_LAUNCH_SC(DT_F16, true); else NVDB_LAUNCH_SC(DT_F16, false); }
-  else { if (al) NVDB_LAUNCH_SC(DT_I8, true); else NVDB_LAUNCH_SC(DT_I8, false); }
-#undef NVDB_LAUNCH_SC
+  nvdb_status st = NVDB_OK;
+  dispatch_dtype(c->dtype, st, [&](auto dt) {
+    auto go = [&](auto kern) { kern<<<grid, 256, lds, s>>>(c->rows, c->scales, c->dim, n, q32, nq, out, ld); };
+    if (al) go(scores_exact_kernel<decltype(dt)::value, QG, true>); else go(scores_exact_kernel<decltype(dt)::value, QG, false>);
+    return NVDB_OK;
+  });
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
 }
 
 // the same score matrix from the fp32 matrix cores (kernels_exact_mfma.h)
-nvdb_status launch_scores_exact_mfma(nvdb_hip_ctx* c, hipStream_t s, const float* q32, uint32_t nq, float* out, uint64_t ld) {
+template <int DT>
+nvdb_status launch_scores_exact_mfma_dt(nvdb_hip_ctx* c, hipStream_t s, const float* q32, uint32_t nq, float* out, uint64_t ld) {
   const uint32_t n = static_cast<uint32_t>(c->n);
   const uint32_t tiles = (n + EXACT_MFMA_ROWS - 1) / EXACT_MFMA_ROWS;
-  uint32_t q0 = 0;
-#define NVDB_SC_LDS(DT, D)                                                                                                          \
-  if constexpr (exact_lds_shape<DT, D>()) {                                                                                        \
-    if ((c->opt_exact_lds == 2 || (c->opt_exact_lds == 1 && DT == DT_F32)) && nq >= 64 && c->dim == D) {                          \
-      const uint32_t gy = nq / 64;                                                                                                 \
-      uint32_t P = std::max<uint32_t>(1, (2u * static_cast<uint32_t>(c->num_cu)) / gy);                                  \
-      P = std::max<uint32_t>(1, std::min(P, std::max<uint32_t>(1, tiles / 8)));                                                    \
-      const void* fn = reinterpret_cast<const void*>(exact_mfma_lds_kernel<DT, D, true>);                                          \
-      if (nvdb_status ls = raise_lds_limit(c, fn, exact_lds_bytes<DT, D>())) return ls;                                            \
-      exact_mfma_lds_kernel<DT, D, true><<<dim3(P, gy), 256, exact_lds_bytes<DT, D>(), s>>>(c->rows, c->scales, 0u, n, q32, gy * 64, 0u, nullptr, \
-                                                                                            nullptr, nullptr, 0u, nullptr, out, ld);   \
-      HIPCHK(c, hipGetLastError());                                                                                                \
-      q0 = gy * 64;                                                                                                                \
-    }                                                                                                                              \
-  }
-#define NVDB_SC_IMG(DT, D)                                                                                                          \
-  if constexpr (exact_img_shape<DT, D>()) {                                                                                        \
-    if (c->opt_exact_img && c->opt_exact_lds != 2 && nq >= 64 && c->dim == D && q0 == 0) {                                         \
-      const uint32_t gy = nq / 64;                                                                                                 \
-      uint32_t P = std::max<uint32_t>(1, (2u * static_cast<uint32_t>(c->num_cu)) / gy);                                  \
-      P = std::max<uint32_t>(1, std::min(P, std::max<uint32_t>(1, tiles / 8)));                                                    \
-      const void* fn = reinterpret_cast<const void*>(exact_mfma_img_kernel<DT, D, true>);                                          \
-      if (nvdb_status ls = raise_lds_limit(c, fn, exact_img_bytes<DT, D>())) return ls;                                            \
-      exact_mfma_img_kernel<DT, D, true><<<dim3(P, gy), 256, exact_img_bytes<DT, D>(), s>>>(c->rows, c->scales, 0u, n, q32, gy * 64, 0u, nullptr, \
-                                                                                            nullptr, nullptr, 0u, nullptr, out, ld);   \
-      HIPCHK(c, hipGetLastError());                                                                                                \
-      q0 = gy * 64;                                                                                                                \
-    }                                                                                                                              \
-  }
-#define NVDB_SC_LDS_DT(DT) NVDB_SC_IMG(DT, 768) NVDB_SC_IMG(DT, 640) NVDB_SC_IMG(DT, 512) NVDB_SC_IMG(DT, 384) NVDB_SC_IMG(DT, 256) NVDB_SC_IMG(DT, 128) \
-  if (q0 == 0) { NVDB_SC_LDS(DT, 768) NVDB_SC_LDS(DT, 640) NVDB_SC_LDS(DT, 512) NVDB_SC_LDS(DT, 384) NVDB_SC_LDS(DT, 256) NVDB_SC_LDS(DT, 128) }
-  if (c->dtype == NVDB_DTYPE_F32) { NVDB_SC_LDS_DT(DT_F32) } else if (c->dtype == NVDB_DTYPE_F16) { NVDB_SC_LDS_DT(DT_F16) } else { NVDB_SC_LDS_DT(DT_I8) }
-#undef NVDB_SC_LDS_DT
-#undef NVDB_SC_LDS
-#undef NVDB_SC_IMG
-  if (q0 >= nq) return NVDB_OK;
+  const uint32_t wgs = 2u * static_cast<uint32_t>(c->num_cu), no_pmax = 0xFFFFFFFFu;             // (no candidate lists: nothing caps the row splits)
+  nvdb_status st = NVDB_OK;
+  const uint32_t q0 = launch_exact_staged<DT, true>(c, s, ExactMfmaArgs{0u, n, q32, 0u, nullptr, nullptr, nullptr, 0u, nullptr, out, ld}, nq, tiles, wgs, no_pmax, st);
+  if (st || q0 >= nq) return st;
   const uint32_t nr = nq - q0;
   const uint32_t gy = (nr + 63) / 64;
-  uint32_t P = std::max<uint32_t>(1, (2u * static_cast<uint32_t>(c->num_cu)) / gy);
-  P = std::max<uint32_t>(1, std::min(P, tiles / 8));
-  const dim3 grid(P, gy);
-  const float* qr = q32 + static_cast<size_t>(q0) * c->dim;
-  float* outr = out + static_cast<size_t>(q0) * ld;
-#define NVDB_SC_MFMA(DT, D) scores_exact_mfma_kernel<DT, D><<<grid, 256, 0, s>>>(c->rows, c->scales, n, qr, nr, outr, ld)
-#define NVDB_SC_MFMA_DT(DT)                                                                                       \
-  switch (c->dim) {                                                                                              \
-    case 768: NVDB_SC_MFMA(DT, 768); break;                                                                      \
-    case 640: NVDB_SC_MFMA(DT, 640); break;                                                                      \
-    case 512: NVDB_SC_MFMA(DT, 512); break;                                                                      \
-    case 384: NVDB_SC_MFMA(DT, 384); break;                                                                      \
-    case 256: NVDB_SC_MFMA(DT, 256); break;                                                                      \
-    default: NVDB_SC_MFMA(DT, 128); break;                                                                       \
-  }
-  if (c->dtype == NVDB_DTYPE_F32) NVDB_SC_MFMA_DT(DT_F32) else if (c->dtype == NVDB_DTYPE_F16) NVDB_SC_MFMA_DT(DT_F16) else NVDB_SC_MFMA_DT(DT_I8)
-#undef NVDB_SC_MFMA_DT
-#undef NVDB_SC_MFMA
+  const dim3 grid(exact_grid_p(wgs, gy, tiles, no_pmax), gy);
+  dispatch_dim(ExactMfmaDims{}, c->dim, st, [&](auto D) {
+    scores_exact_mfma_kernel<DT, decltype(D)::value><<<grid, 256, 0, s>>>(c->rows, c->scales, n, q32 + static_cast<size_t>(q0) * c->dim, nr, out + static_cast<size_t>(q0) * ld, ld);
+    return NVDB_OK;
+  });
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
+}
+nvdb_status launch_scores_exact_mfma(nvdb_hip_ctx* c, hipStream_t s, const float* q32, uint32_t nq, float* out, uint64_t ld) {
+  nvdb_status st = NVDB_OK;
+  dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_scores_exact_mfma_dt<decltype(dt)::value>(c, s, q32, nq, out, ld); });
+  return st;
 }
 
 // queries per sub-batch: what the score matrix + whatever else a query needs (per_query_bytes) may take of HBM; held_bytes: already ours, counts as available
