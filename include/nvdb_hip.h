@@ -69,7 +69,7 @@ typedef struct nvdb_hip_timing {
 /* What the last flat search did (for tests, bench.py and the roofline arithmetic). */
 typedef struct nvdb_hip_scan_stats {
   uint32_t path;               /* 1 = exact fp32 scan, 2 = MFMA filter + exact rescore (k <= 1024), 3 = any-k (k > 64 off the filter path), 4 = partitioned probe search,
-                                  5 = range search, filter route, 6 = range search, exact route, 7 = range search, partition scan */
+                                  5 = range search, filter route, 6 = range search, exact route, 7 = range search, partition scan, 8 = probe search, any k */
   uint32_t chunks;             /* corpus chunks (kernel launches of the dominant kernel)          */
   uint64_t rows_scanned;       /* rows x query-tiles streamed by the dominant kernel              */
   uint64_t candidates;         /* (query,row) pairs that reached the exact rescore                */
@@ -294,11 +294,13 @@ nvdb_status nvdb_hip_search_ivf(nvdb_hip_ctx* ctx, const float* queries, uint32_
  * SearchParameters::sel with an IDSelectorBitmap.  A context holds nmasks bit planes over its resident corpus; plane m is
  * W = ceil(n / 32) uint32 words, LOCAL row r (global_row_base plays no part) is live in mask m iff bit r & 31 of word
  * m * W + (r >> 5) is 1.  Bits at positions >= n of a plane's last word are ignored on input and read back as 0.
- * Masked entry points: the top-k searches below (k <= 64) and the range searches of the next block (nvdb_hip_range_search_partitions /
- * _ivf with masked != 0, nvdb_hip_range_search_masked, nvdb_hip_ivf_range_search).
+ * Masked entry points: the top-k searches below (k <= 64), the range searches of the next block (nvdb_hip_range_search_partitions /
+ * _ivf with masked != 0, nvdb_hip_range_search_masked, nvdb_hip_ivf_range_search) and the probe searches for any k behind them
+ * (nvdb_hip_search_partitions_anyk / _ivf_anyk, nvdb_hip_ivf_search_anyk with masked != 0).
  * The masked flat top-k (nvdb_hip_search_batch_masked) rides the MFMA filter kernels where the corpus is large enough to pay for it.
  * NOT masked (out of scope so far): nvdb_hip_search_batch itself and its exact / any-k routes, nvdb_hip_range_search itself, the
- * device group, the _dev stream entry points, top-k with k > 64, the nvdb:: C++ host layer.  Those entry points, and the unmasked probe
+ * device group, the _dev stream entry points, the masked FLAT top-k with k > 64 (nvdb_hip_search_batch_masked; on the probe path any
+ * k is served, see "probe search for any k" below), the nvdb:: C++ host layer.  Those entry points, and the unmasked probe
  * searches above, ignore resident masks entirely: results, statistics and launches are what they are without masks.
  * ------------------------------------------------------------------------------------------- */
 
@@ -403,6 +405,52 @@ nvdb_status nvdb_hip_range_search_masked(nvdb_hip_ctx* ctx, const float* queries
                                          nvdb_hip_timing* timing /* may be NULL */);
 
 /* ---------------------------------------------------------------------------------------------
+ * probe search for any k: nvdb_hip_search_partitions' question for k beyond the 64 entries of its wavefront-resident lists --
+ * recall@100 on an IVF-Flat index, or the R candidates per query that nvdb_hip_refine_l2_topk takes.  The existing calls keep
+ * their k <= 64 contract; the capability has names of its own, with the argument shape of nvdb_hip_range_search_partitions.
+ * Result per query: the exact top-k by dot product over the rows of the probed union -- for masked != 0 only the rows that are
+ * live in the query's plane --, with the score bits and the (score desc, global id asc) order of nvdb_hip_search_partitions.
+ * Any k >= 1 is accepted and k is NOT clamped (as on the probe search, unlike nvdb_hip_search_batch): out_ids[nq][k],
+ * out_scores[nq][k]; out_counts[q] (optional) = min(k, live rows in the union), counted on the device; slots beyond the count
+ * hold id UINT64_MAX / -inf.  k <= 64: the call IS its twin (nvdb_hip_search_partitions / _masked, nvdb_hip_search_ivf / _masked)
+ * -- result, timing and statistics (path 4) bit for bit.
+ * masked == 0: mask_of is ignored, resident masks play no part.  masked != 0: mask_of[nq] as for the masked searches above --
+ * 0xFFFFFFFF = no mask, NULL = plane 0 for every query; an entry >= nmasks or no planes resident -> NVDB_ERR_INVALID before
+ * anything is launched, nothing written.
+ * k == 0 or nq == 0 -> NVDB_OK, nothing written.  nprobe == 0 -> every count 0, outputs all padding.  No partition table ->
+ * NVDB_ERR_INVALID; no corpus -> NVDB_ERR_NO_CORPUS.  Non-finite query or corpus values: no fault, no hang, order unspecified
+ * (for k > 64 a row whose score is NaN is no candidate, as in the range search: it is neither returned nor counted).
+ * Any nq: for k > 64 the batch is cut into query sub-batches whose candidate blocks (8 bytes per row of a query's probed union)
+ * stay within half of option "largek_budget_mb", the key slabs of lists longer than 8192 entries within the other half, and the
+ * device copy of the results within as many entries as the blocks may hold; one query is taken whatever the option says; the
+ * caller does not see the cut.  A single query whose union reaches 2^32 rows, or more than 2^31 results for one query ->
+ * NVDB_ERR_UNSUPPORTED.
+ * nvdb_hip_get_stats afterwards (k > 64): path = 8, chunks = scan launches, rows_scanned = rows of the work items (live or not),
+ * candidates = non-padding entries of the candidate blocks (the live rows of the unions).  timing (optional): kernel / total as for
+ * nvdb_hip_range_search_partitions (the work list's copies and the results' alternate with the launches and ride inside).
+ * Cost, plainly: the scan of nvdb_hip_range_search_partitions at radius -inf -- every live row of the union is scored and written
+ * once, nothing is pruned inside the scan --, then per query one workgroup that reads its block once per radix pass, and k results
+ * copied back instead of the union.
+ * Out of scope, unchanged: the masked flat search with k > 64 (nvdb_hip_search_batch_masked), the device group, _dev stream forms
+ * of these calls, any pruning inside the scan.
+ * ------------------------------------------------------------------------------------------- */
+
+/* probe[nq][nprobe]: nvdb_hip_search_partitions' rules (0xFFFFFFFF = empty slot, duplicates count once, an entry >= nparts ->
+ * NVDB_ERR_INVALID before anything is launched, nothing written). */
+nvdb_status nvdb_hip_search_partitions_anyk(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t k,
+                                            const uint32_t* probe /* [nq][nprobe] */, uint32_t nprobe,
+                                            const uint32_t* mask_of /* [nq], may be NULL */, int masked,
+                                            uint64_t* out_ids /* [nq][k] */, float* out_scores /* [nq][k] */,
+                                            uint32_t* out_counts /* [nq], may be NULL */, nvdb_hip_timing* timing /* may be NULL */);
+/* The coarse step, the clamp of nprobe and out_probe (optional, [nq][nprobe]) are nvdb_hip_search_ivf's; centroids are not masked.
+ * Without centroids -> NVDB_ERR_INVALID. */
+nvdb_status nvdb_hip_search_ivf_anyk(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+                                     const uint32_t* mask_of /* [nq], may be NULL */, int masked,
+                                     uint64_t* out_ids /* [nq][k] */, float* out_scores /* [nq][k] */,
+                                     uint32_t* out_counts /* [nq], may be NULL */, uint32_t* out_probe /* may be NULL */,
+                                     nvdb_hip_timing* timing /* may be NULL */);
+
+/* ---------------------------------------------------------------------------------------------
  * IVF-Flat build: from a resident corpus to an index the probe search above can serve -- centroids trained on the GPU
  * (the reference trains them with FAISS, apps/nvdb_ivf_build.cpp:59-64), every row assigned to its best centroid, the rows
  * copied into list order, results answered in the ORIGINAL ids.
@@ -479,6 +527,14 @@ nvdb_status nvdb_hip_ivf_search_masked(nvdb_hip_ivf* ivf, const float* queries, 
                                        const uint32_t* mask_of /* [nq], may be NULL */,
                                        uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                        uint32_t* out_probe, nvdb_hip_timing* timing);
+
+/* nvdb_hip_search_ivf_anyk on the index's context (any k; mask_of names planes set with nvdb_hip_ivf_set_row_masks, original rows),
+ * then the id mapping and the ORDER of nvdb_hip_ivf_search: every id that is not padding becomes src's global_row_base + perm[id];
+ * equal scores by (partition number, original id) -- the select orders equal scores by position in the lists, not by the mapped id. */
+nvdb_status nvdb_hip_ivf_search_anyk(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+                                     const uint32_t* mask_of /* [nq], may be NULL */, int masked,
+                                     uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                     uint32_t* out_probe, nvdb_hip_timing* timing);
 
 /* nvdb_hip_range_search_ivf on the index's context; mask_of names planes set with nvdb_hip_ivf_set_row_masks (original rows).
  * The lims are final; the slices are held by the index's context in list positions. */

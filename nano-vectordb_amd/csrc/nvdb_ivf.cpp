@@ -447,6 +447,19 @@ nvdb_status nvdb_hip_ivf_search_masked(nvdb_hip_ivf* ix, const float* queries, u
   return NVDB_OK;
 }
 
+nvdb_status nvdb_hip_ivf_search_anyk(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, const uint32_t* mask_of, int masked,
+                                     uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
+  if (!ix) return NVDB_ERR_INVALID;
+  const nvdb_status st = nvdb_hip_search_ivf_anyk(ix->ctx, queries, nq, k, nprobe, mask_of, masked, out_ids, out_scores, out_counts, out_probe, timing);
+  if (st) { ix->err = nvdb_hip_last_error(ix->ctx); return st; }
+  if (nq == 0 || k == 0) return NVDB_OK;            // nothing was written
+  // (as nvdb_hip_ivf_search: the select's keys carry positions in the list-ordered copy, so equal scores already stand by (list, original row))
+  const uint32_t* perm = ix->perm.data();
+  for (size_t i = 0; i < static_cast<size_t>(nq) * k; ++i)
+    if (out_ids[i] != ~0ull) out_ids[i] = ix->src_row_base + perm[out_ids[i]];
+  return NVDB_OK;
+}
+
 nvdb_status nvdb_hip_ivf_range_search(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, const float* radius, uint32_t nprobe, const uint32_t* mask_of, int masked,
                                       uint64_t* out_lims, uint32_t* out_probe, nvdb_hip_timing* timing) {
   if (!ix) return NVDB_ERR_INVALID;

@@ -101,6 +101,10 @@ nvdb_status range_parts_core(nvdb_hip_ctx* c, hipStream_t s, const char* who, co
                              uint32_t nr, const uint32_t* probe, uint32_t nprobe, const MaskSel* msel, const uint32_t* qmap, std::vector<uint64_t>& cnt,
                              uint64_t base, RangeOut& out);
 
+// one launch of range_parts_kernel's build for this corpus (qw queries per wave) over the items of `a`; radius: per query of the
+// launch set, on the device (the probe search for any k, nvdb_parts_anyk.cpp, passes -inf throughout)
+nvdb_status launch_range_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const float* radius, const ScanArgs& a);
+
 // ---- the flat range search's plan and filter pass (nvdb_range.cpp), as the masked flat top-k (nvdb_masked_flat.cpp) calls them
 struct RangePlan {
   const char* error = nullptr;

@@ -12,15 +12,11 @@
 
 namespace nvdbhip {
 
-namespace {
-
 nvdb_status launch_range_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const float* radius, const ScanArgs& a) {
   return parts_dispatch(c, qw, staged, a.mk.mask_of != nullptr, [&](auto dt, auto w, auto al, auto st, auto mk) {
     return parts_launch(c, s, range_parts_kernel<dt(), w(), al(), st(), mk()>, w(), st(), a.nitems, a.items, a.qidx, a.dst, a.q32, radius, a.cand, a.mk);
   });
 }
-
-}  // namespace
 
 nvdb_status range_parts_core(nvdb_hip_ctx* c, hipStream_t s, const char* who, const uint64_t* off, uint32_t nparts, const float* queries, const float* radius,
                              uint32_t nr, const uint32_t* probe, uint32_t nprobe, const MaskSel* msel, const uint32_t* qmap, std::vector<uint64_t>& cnt,

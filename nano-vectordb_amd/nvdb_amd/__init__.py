@@ -39,6 +39,7 @@ EXPORTS = [
     "nvdb_hip_ivf_set_row_masks", "nvdb_hip_ivf_update_row_mask", "nvdb_hip_ivf_search_masked",
     "nvdb_hip_range_search_partitions", "nvdb_hip_range_search_ivf", "nvdb_hip_range_search_masked",
     "nvdb_hip_ivf_range_search", "nvdb_hip_ivf_range_results",
+    "nvdb_hip_search_partitions_anyk", "nvdb_hip_search_ivf_anyk", "nvdb_hip_ivf_search_anyk",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_filter_variant", "nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -209,6 +210,9 @@ def _bind(L, dev):
     L.nvdb_hip_range_search_masked.argtypes = [vp, vp, u32, vp, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_ivf_range_search.argtypes = [vp, vp, u32, vp, u32, vp, C.c_int, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_ivf_range_results.argtypes = [vp, vp, vp]
+    L.nvdb_hip_search_partitions_anyk.argtypes = [vp, vp, u32, u32, vp, u32, vp, C.c_int, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_search_ivf_anyk.argtypes = [vp, vp, u32, u32, u32, vp, C.c_int, vp, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_ivf_search_anyk.argtypes = [vp, vp, u32, u32, u32, vp, C.c_int, vp, vp, vp, vp, C.POINTER(Timing)]
     for name in EXPORTS:
         getattr(L, name)
     if dev:
@@ -602,6 +606,31 @@ class HipContext:
                                                         C.byref(t) if want_timing else None))
         return (ids, scores, counts, t) if want_timing else (ids, scores, counts)
 
+    # -- probe search for any k (k <= 64: the twins above, bit for bit; beyond: scan, radix select, sort -- stats path 8)
+    def search_partitions_anyk(self, queries, k, probe, mask_of=None, masked=None, want_timing=False):
+        """search_partitions / search_partitions_masked for any k >= 1 (k is not clamped: counts[q] = min(k, live rows in the probed
+        union), padding behind it).  masked None: masked iff mask_of is given (masked=True with mask_of None: plane 0)."""
+        queries, nq, ids, scores, counts = self._probe_outputs(queries, k)
+        probe = np.ascontiguousarray(probe, dtype=np.uint32).reshape(nq, -1)
+        mo = _mask_of_arg(mask_of, nq)
+        masked = (mo is not None) if masked is None else bool(masked)
+        t = Timing()
+        self._chk(self.lib.nvdb_hip_search_partitions_anyk(self.h, queries.ctypes.data, nq, k, probe.ctypes.data, probe.shape[1],
+                                                           mo.ctypes.data if mo is not None else None, 1 if masked else 0, ids.ctypes.data,
+                                                           scores.ctypes.data, counts.ctypes.data, C.byref(t) if want_timing else None))
+        return (ids, scores, counts, t) if want_timing else (ids, scores, counts)
+
+    def search_ivf_anyk(self, queries, k, nprobe, mask_of=None, masked=None, want_probe=False):
+        """search_ivf / search_ivf_masked for any k >= 1; (ids, scores, counts[, probe])."""
+        queries, nq, ids, scores, counts = self._probe_outputs(queries, k)
+        probe = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
+        mo = _mask_of_arg(mask_of, nq)
+        masked = (mo is not None) if masked is None else bool(masked)
+        self._chk(self.lib.nvdb_hip_search_ivf_anyk(self.h, queries.ctypes.data, nq, k, nprobe, mo.ctypes.data if mo is not None else None,
+                                                    1 if masked else 0, ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
+                                                    probe.ctypes.data if want_probe else None, None))
+        return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
+
     # -- range search on the probe path (lims, ids, scores as range_search; over range_max_mb the NvdbError carries `.lims`)
     def _range(self, call, queries, radius, mask_of, masked):
         return _range_call(self, lambda: self.lib.nvdb_hip_last_error(self.h).decode(),
@@ -765,6 +794,24 @@ class IvfIndex:
         self._chk(self.lib.nvdb_hip_ivf_search_masked(self.h, queries.ctypes.data, nq, k, nprobe, mo.ctypes.data if mo is not None else None,
                                                       ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
                                                       probe.ctypes.data if want_probe else None, None))
+        return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
+
+    def search_anyk(self, queries, k, nprobe, mask_of=None, masked=None, want_probe=False):
+        """search() / search_masked() for any k >= 1 (k is not clamped): (ids in the source corpus' ids, scores, counts[, probe]);
+        equal scores by (partition, original id).  masked None: masked iff mask_of is given."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        nq = queries.shape[0]
+        ids = np.full((nq, k), np.iinfo(np.uint64).max, dtype=np.uint64)
+        scores = np.full((nq, k), -np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        probe = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
+        mo = _mask_of_arg(mask_of, nq)
+        masked = (mo is not None) if masked is None else bool(masked)
+        self._chk(self.lib.nvdb_hip_ivf_search_anyk(self.h, queries.ctypes.data, nq, k, nprobe, mo.ctypes.data if mo is not None else None,
+                                                    1 if masked else 0, ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
+                                                    probe.ctypes.data if want_probe else None, None))
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
     def range_search(self, queries, radius, nprobe, mask_of=None, masked=None, want_probe=False):
