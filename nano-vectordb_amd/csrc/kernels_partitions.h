@@ -29,19 +29,14 @@
 // order unspecified.
 #pragma once
 #include "kernels_exact.h"
+#include "parts_worklist.h"   // PartItem, PART_WAVES, PART_QW_MAX, PART_SEG_ROWS: what the host-side list builder shares with the kernels
 
 namespace nvdbhip {
 
 constexpr uint32_t PART_TILE_ROWS = 64;        // rows per tile = lanes per wave
-constexpr uint32_t PART_WAVES = 8;             // waves per workgroup (two per SIMD: one hides the other's LDS latency)
 constexpr uint32_t PART_THREADS = 64 * PART_WAVES;
 constexpr uint32_t PART_STAGE_MAX_ROW_BYTES = 1536;
 constexpr uint32_t PART_MAX_CHUNKS = PART_TILE_ROWS * PART_STAGE_MAX_ROW_BYTES / 16u / PART_THREADS;   // 16-byte chunks of a tile one thread prefetches
-constexpr uint32_t PART_QW_MAX = 4;            // queries per wave -> groups of at most PART_WAVES * 4 queries
-constexpr uint32_t PART_SEG_ROWS = 2048;       // a partition is cut into segments of at most this many rows
-
-// one workgroup's work; qoff indexes qidx[], doff indexes dst[] (both: one entry per query of the group)
-struct PartItem { uint32_t row_lo, row_hi, qoff, doff, nqg, pad; };
 
 // MASKED builds: mask_of[q] = the plane query q searches under (0xFFFFFFFF: none, every row live), planes = [nmasks][W] words,
 // local row r live in plane m iff bit r & 31 of word m * W + (r >> 5).  Unmasked builds ignore it.

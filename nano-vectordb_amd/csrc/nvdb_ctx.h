@@ -12,11 +12,14 @@
 //   nvdb_launch_i8.cpp     ... of the int8 kernels (kernels_filter.h, kernels_filter_i8s.h)
 //   nvdb_launch_exact.cpp  ... of the exact fp32-order kernels, select / rescore / merge, the any-k path (kernels_exact*.h, kernels_largek.h)
 //   nvdb_refine.cpp        exact-L2 refine (kernels_refine.h)
-//   nvdb_partitions.cpp    partitioned probe search: partition table, coarse quantiser, work list, launches; row masks and the masked searches
-//                          (kernels_partitions.h, row_mask.h)
+//   nvdb_partitions.cpp    partitioned probe search: partition table, coarse quantiser, the pass driver of every partition scan (nvdb_parts.h: work list ->
+//                          image -> copies -> launches by class), the top-k argument check; row masks and the masked searches (kernels_partitions.h, row_mask.h)
+//   parts_worklist.h       the work list itself and its image's layout, plain C++ with no HIP call (as nvdb_plan.h, range_plan.h, parts_anyk_plan.h, masked_plan.h)
+//   nvdb_parts_anyk.cpp    the probe search for any k: per sub-batch one pass at radius -inf, select, long slabs (kernels_parts_anyk.h, parts_anyk_plan.h)
 //   nvdb_masked_flat.cpp   the masked flat top-k on the MFMA filter route: prefix rank, bootstrap bar, the range search's filter pass, top-k of the kept
 //                          lists (kernels_masked_topk.h, masked_plan.h)
-//   nvdb_ivf.cpp           IVF-Flat build: row assignment, spherical k-means, list layout, the reordered index (kernels_ivf.h, ivf_layout.h)
+//   nvdb_ivf.cpp           IVF-Flat build: row assignment, spherical k-means, list layout, the reordered index and its searches (the context's, ids mapped
+//                          back by ivf_map_ids) (kernels_ivf.h, ivf_layout.h)
 //   nvdb_debug.cpp         developer entry points (libnvdb_hip_dev.so only)
 //   nvdb_group.cpp         device group, layered on the public ABI (does not include this header)
 // There is NO CPU fallback anywhere in these files: without a working HIP device every entry point that computes returns

@@ -179,6 +179,25 @@ struct nvdb_hip_ivf {
   std::string err;
 };
 
+namespace {
+
+// positions in the list-ordered copy -> ids of the source corpus, in place; what is no position ("no entry", ~0) stays.  The
+// order stays: equal scores stand by (list, original row)
+void ivf_map_ids(const nvdb_hip_ivf* ix, uint64_t* ids, uint64_t count) {
+  const uint32_t* perm = ix->perm.data();
+  const uint64_t n = ix->perm.size();
+  for (uint64_t i = 0; i < count; ++i)
+    if (ids[i] < n) ids[i] = ix->src_row_base + perm[ids[i]];
+}
+
+// a call forwarded to the index's context: its status, and on failure its error text
+nvdb_status ivf_forward(nvdb_hip_ivf* ix, nvdb_status st) {
+  if (st) ix->err = nvdb_hip_last_error(ix->ctx);
+  return st;
+}
+
+}  // namespace
+
 extern "C" {
 
 nvdb_status nvdb_ivf_layout_host(const uint32_t* assign, uint64_t n, uint32_t nparts, uint64_t* out_offsets, uint32_t* out_perm) {
@@ -394,13 +413,8 @@ nvdb_status nvdb_hip_ivf_info(const nvdb_hip_ivf* ix, uint64_t* n, uint32_t* npa
 nvdb_status nvdb_hip_ivf_search(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
                                 float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
   if (!ix) return NVDB_ERR_INVALID;
-  const nvdb_status st = nvdb_hip_search_ivf(ix->ctx, queries, nq, k, nprobe, out_ids, out_scores, out_counts, out_probe, timing);
-  if (st) { ix->err = nvdb_hip_last_error(ix->ctx); return st; }
-  if (nq == 0 || k == 0) return NVDB_OK;            // nothing was written
-  // positions in the list-ordered copy -> ids of the source corpus; the order stays: equal scores by (list, original row)
-  const uint32_t* perm = ix->perm.data();
-  for (size_t i = 0; i < static_cast<size_t>(nq) * k; ++i)
-    if (out_ids[i] != ~0ull) out_ids[i] = ix->src_row_base + perm[out_ids[i]];
+  if (nvdb_status st = ivf_forward(ix, nvdb_hip_search_ivf(ix->ctx, queries, nq, k, nprobe, out_ids, out_scores, out_counts, out_probe, timing))) return st;
+  if (nq && k) ivf_map_ids(ix, out_ids, static_cast<uint64_t>(nq) * k);      // (nq == 0 || k == 0: nothing was written)
   return NVDB_OK;
 }
 
@@ -438,45 +452,29 @@ nvdb_status nvdb_hip_ivf_update_row_mask(nvdb_hip_ivf* ix, uint32_t mask, const 
 nvdb_status nvdb_hip_ivf_search_masked(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, const uint32_t* mask_of,
                                        uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
   if (!ix) return NVDB_ERR_INVALID;
-  const nvdb_status st = nvdb_hip_search_ivf_masked(ix->ctx, queries, nq, k, nprobe, mask_of, out_ids, out_scores, out_counts, out_probe, timing);
-  if (st) { ix->err = nvdb_hip_last_error(ix->ctx); return st; }
-  if (nq == 0 || k == 0) return NVDB_OK;            // nothing was written
-  const uint32_t* perm = ix->perm.data();           // (as nvdb_hip_ivf_search: the order stays, equal scores by (list, original row))
-  for (size_t i = 0; i < static_cast<size_t>(nq) * k; ++i)
-    if (out_ids[i] != ~0ull) out_ids[i] = ix->src_row_base + perm[out_ids[i]];
+  if (nvdb_status st = ivf_forward(ix, nvdb_hip_search_ivf_masked(ix->ctx, queries, nq, k, nprobe, mask_of, out_ids, out_scores, out_counts, out_probe, timing))) return st;
+  if (nq && k) ivf_map_ids(ix, out_ids, static_cast<uint64_t>(nq) * k);
   return NVDB_OK;
 }
 
 nvdb_status nvdb_hip_ivf_search_anyk(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, const uint32_t* mask_of, int masked,
                                      uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
   if (!ix) return NVDB_ERR_INVALID;
-  const nvdb_status st = nvdb_hip_search_ivf_anyk(ix->ctx, queries, nq, k, nprobe, mask_of, masked, out_ids, out_scores, out_counts, out_probe, timing);
-  if (st) { ix->err = nvdb_hip_last_error(ix->ctx); return st; }
-  if (nq == 0 || k == 0) return NVDB_OK;            // nothing was written
-  // (as nvdb_hip_ivf_search: the select's keys carry positions in the list-ordered copy, so equal scores already stand by (list, original row))
-  const uint32_t* perm = ix->perm.data();
-  for (size_t i = 0; i < static_cast<size_t>(nq) * k; ++i)
-    if (out_ids[i] != ~0ull) out_ids[i] = ix->src_row_base + perm[out_ids[i]];
+  if (nvdb_status st = ivf_forward(ix, nvdb_hip_search_ivf_anyk(ix->ctx, queries, nq, k, nprobe, mask_of, masked, out_ids, out_scores, out_counts, out_probe, timing))) return st;
+  if (nq && k) ivf_map_ids(ix, out_ids, static_cast<uint64_t>(nq) * k);      // (the select's keys carry positions in the list-ordered copy)
   return NVDB_OK;
 }
 
 nvdb_status nvdb_hip_ivf_range_search(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, const float* radius, uint32_t nprobe, const uint32_t* mask_of, int masked,
                                       uint64_t* out_lims, uint32_t* out_probe, nvdb_hip_timing* timing) {
   if (!ix) return NVDB_ERR_INVALID;
-  const nvdb_status st = nvdb_hip_range_search_ivf(ix->ctx, queries, nq, radius, nprobe, mask_of, masked, out_lims, out_probe, timing);
-  if (st) ix->err = nvdb_hip_last_error(ix->ctx);
-  return st;
+  return ivf_forward(ix, nvdb_hip_range_search_ivf(ix->ctx, queries, nq, radius, nprobe, mask_of, masked, out_lims, out_probe, timing));
 }
 
 nvdb_status nvdb_hip_ivf_range_results(nvdb_hip_ivf* ix, uint64_t* out_ids, float* out_scores) {
   if (!ix) return NVDB_ERR_INVALID;
-  const nvdb_status st = nvdb_hip_range_results(ix->ctx, out_ids, out_scores);
-  if (st) { ix->err = nvdb_hip_last_error(ix->ctx); return st; }
-  // positions in the list-ordered copy -> ids of the source corpus; the order stays: equal scores by (list, original row)
-  const uint32_t* perm = ix->perm.data();
-  const uint64_t total = ix->ctx->range_total, n = ix->perm.size();
-  for (uint64_t i = 0; i < total; ++i)
-    if (out_ids[i] < n) out_ids[i] = ix->src_row_base + perm[out_ids[i]];
+  if (nvdb_status st = ivf_forward(ix, nvdb_hip_range_results(ix->ctx, out_ids, out_scores))) return st;
+  ivf_map_ids(ix, out_ids, ix->ctx->range_total);
   return NVDB_OK;
 }
 

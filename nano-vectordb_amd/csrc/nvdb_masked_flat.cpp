@@ -5,7 +5,9 @@
 //   1. prefix rank   per distinct plane of the sub-batch, the prefix [0, P) that holds L live rows (masked_plan.h; P = n where the
 //                    plane holds fewer) and the bootstrap's work items over it (masked_prefix_rank_kernel)
 //   2. bootstrap     the exact masked top-k over [0, P): the masked partition scan, every plane a partition of its own (queries of
-//                    different planes never share a group), then select_parts_kernel -- into the output staging
+//                    different planes never share a group), then select_parts_kernel -- into the output staging.  The pass is
+//                    parts_pass / parts_scan_classes (nvdb_parts.h) with the queries on the device already; its hook turns the
+//                    placeholder segments into what the prefix-rank kernel fills in
 //   3. bar           radius = the k-th bootstrap score; fewer than k live rows in [0, n), or a plane with too few for a bar
 //                    (mp_boot_final): NaN -- the bootstrap's answer is final, the query files nothing in the filter pass
 //   4. main pass     range_filter_pass (nvdb_range.cpp) at radius = bar under the queries' planes: every live row whose exact score
@@ -105,32 +107,35 @@ nvdb_status filter_sub(nvdb_hip_ctx* c, hipStream_t s, const RangePlan& p, const
   sc.off.resize(static_cast<size_t>(nslots) + 1);
   for (uint32_t j = 0; j <= nslots; ++j) sc.off[j] = j * span;
   if ((st = parts_probes(c, "search_batch_masked", sc.off.data(), nslots, b, ps->probe_tmp.data(), 1, nullptr))) return st;
-  PartList wl;
-  if ((st = parts_worklist(c, "search_batch_masked", sc.off.data(), nslots, 0, b, 1, qg_max, k, wl))) return st;
-  for (auto& items : ps->items)
-    for (PartItem& it : items) {
-      const uint32_t slot = static_cast<uint32_t>(it.row_lo / span);
-      it.row_lo = static_cast<uint32_t>((it.row_lo - slot * span) / PART_SEG_ROWS);
-      it.row_hi = nseg;
-      it.pad = slot + 1u;
-    }
   sc.extra.resize(static_cast<size_t>(nslots) * 2 + b);               // [slot table | every query's slot]
   for (uint32_t j = 0; j < nslots; ++j) { sc.extra[2 * j] = sc.slot_mask[j]; sc.extra[2 * j + 1] = nseg; }
   for (uint32_t q = 0; q < b; ++q) sc.extra[2 * static_cast<size_t>(nslots) + q] = ps->probe_tmp[q];
   const size_t ob_ids = static_cast<size_t>(b) * k * 8, ob_sc = static_cast<size_t>(b) * k * 4;
-  const size_t cand_bytes = std::max<uint64_t>(wl.total, 1) * sizeof(Cand);
-  if ((st = ensure(c, ps->cand, cand_bytes))) return st;
-  if ((st = ensure(c, ps->out_ids, ob_ids))) return st;
-  if ((st = ensure(c, ps->out_scores, ob_sc))) return st;
-  if ((st = ensure(c, ps->out_counts, static_cast<size_t>(b) * 4))) return st;
-  if ((st = ensure(c, c->rg_radius, static_cast<size_t>(b) * 4))) return st;
-  if ((st = ensure(c, c->rg_idx, static_cast<size_t>(nslots) * 8))) return st;     // [prefix | final] per slot
   const MaskSel msel{mask};
-  PartImage im;
-  if ((st = parts_stage(c, wl, b, &msel, sc.extra.data(), static_cast<uint32_t>(sc.extra.size()), im))) return st;
-  HIPCHK(c, hipMemcpyAsync(ps->meta.p, ps->pin, im.bytes, hipMemcpyHostToDevice, s));
+  PartPass pass;
+  pass.off = sc.off.data(); pass.nparts = nslots; pass.q0 = 0; pass.b = b; pass.nprobe = 1; pass.slot_cap = k;
+  pass.msel = &msel;                                                    // (queries: nullptr -- dq holds them)
+  pass.extra = sc.extra.data(); pass.extra_words = static_cast<uint32_t>(sc.extra.size());
+  st = parts_pass(c, s, "search_batch_masked", pb, pass, [&](PartPass&) -> nvdb_status {
+    for (auto& items : ps->list.items)                                  // a placeholder segment becomes (segment number, nseg, slot + 1)
+      for (PartItem& it : items) {
+        const uint32_t slot = static_cast<uint32_t>(it.row_lo / span);
+        it.row_lo = static_cast<uint32_t>((it.row_lo - slot * span) / PART_SEG_ROWS);
+        it.row_hi = nseg;
+        it.pad = slot + 1u;
+      }
+    nvdb_status e;
+    if ((e = ensure(c, ps->out_ids, ob_ids))) return e;
+    if ((e = ensure(c, ps->out_scores, ob_sc))) return e;
+    if ((e = ensure(c, ps->out_counts, static_cast<size_t>(b) * 4))) return e;
+    if ((e = ensure(c, c->rg_radius, static_cast<size_t>(b) * 4))) return e;
+    return ensure(c, c->rg_idx, static_cast<size_t>(nslots) * 8);       // [prefix | final] per slot
+  });
+  if (st) return st;
+  const PartList& wl = pass.wl;
+  const PartImage& im = pass.im;
   // a slot of a segment shorter than k is written in part: what is not written reads as "no entry" (row 0xFFFFFFFF)
-  HIPCHK(c, hipMemsetAsync(ps->cand.p, 0xFF, cand_bytes, s));
+  HIPCHK(c, hipMemsetAsync(ps->cand.p, 0xFF, std::max<uint64_t>(wl.total, 1) * sizeof(Cand), s));
   const uint32_t nitems = static_cast<uint32_t>(wl.nitems);
   unsigned long long* d_ids = static_cast<unsigned long long*>(ps->out_ids.p);
   float* d_sc = static_cast<float*>(ps->out_scores.p);
@@ -143,17 +148,7 @@ nvdb_status filter_sub(nvdb_hip_ctx* c, hipStream_t s, const RangePlan& p, const
 
   // 2. bootstrap: the masked scan over the prefixes, the select into the output staging
   uint32_t launches = 0;
-  {
-    const PartItem* it = im.items;
-    for (int cl = 2; cl >= 0; --cl) {
-      const uint32_t n_cl = static_cast<uint32_t>(ps->items[cl].size());
-      if (!n_cl) continue;
-      const ScanArgs a{it, n_cl, im.qidx, im.dst, dq, static_cast<Cand*>(ps->cand.p), im.mk};
-      if ((st = launch_scan_parts(c, s, std::min<uint32_t>(pb.qw_max, 1u << cl), pb.staged, k, a))) return st;
-      it += n_cl;
-      ++launches;
-    }
-  }
+  if ((st = parts_scan_classes(c, pb, im, dq, launches, [&](uint32_t qw, const ScanArgs& a) { return launch_scan_parts(c, s, qw, pb.staged, k, a); }))) return st;
   select_parts_kernel<<<b, 64, 0, s>>>(static_cast<const Cand*>(ps->cand.p), im.cbeg, k, c->row_base, d_ids, d_sc, d_cnt);
   HIPCHK(c, hipGetLastError());
   // 3. bar

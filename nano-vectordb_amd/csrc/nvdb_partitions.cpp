@@ -1,9 +1,9 @@
 // nvdb_partitions.cpp -- partitioned probe search: the partition table and the optional coarse quantiser of a context, the
-// host-side work list, the launches of kernels_partitions.h, and the entry points nvdb_hip_set_partitions / set_centroids /
+// pass driver every user of the partition scans shares (nvdb_parts.h), the launches of kernels_partitions.h, and the entry points nvdb_hip_set_partitions / set_centroids /
 // search_partitions / search_ivf, the row masks (nvdb_hip_set_row_masks / update_row_mask / get_row_masks) and the masked
 // searches (include/nvdb_hip.h).
 //
-// Work list (built per call from the probe table, all on the host):
+// Work list (built per pass from the probe table, all on the host, in plain C++: parts_worklist.h):
 //   1. every query's probes are de-duplicated; a counting sort by partition gives, per probed partition, the ascending list of
 //      the queries that probe it (qidx);
 //   2. that list is cut into groups of at most PART_WAVES * QW queries, the partition into balanced segments of at most PART_SEG_ROWS
@@ -12,9 +12,11 @@
 //      (dst); the blocks are laid out by a prefix sum (cbeg), so the capacity is exact and nothing can overflow.
 // Items are sorted by group size into classes (<= 8, <= 16, <= 32 queries) that run the QW = 1, 2, 4 builds of the kernel (the
 // widest one the LDS has room for): a remainder group of three queries does not pay for sixteen.
-// The list builder, its pinned image and the dispatch to a kernel build (parts_worklist / parts_stage / parts_dispatch,
-// nvdb_parts.h) are shared with the partition range scan (nvdb_range_parts.cpp), whose slots hold a segment's row count instead
-// of min(k, rows).
+// One pass = parts_pass (work list -> cand / q grown -> pinned image -> the image's and the queries' copies) and
+// parts_scan_classes (the three classes' launches, widest first); parts_search below, the partition range scan
+// (nvdb_range_parts.cpp) and the probe search for any k (nvdb_parts_anyk.cpp), whose slots hold a segment's row count instead of
+// min(k, rows), and the masked flat bootstrap (nvdb_masked_flat.cpp) add only what is theirs.  parts_call_begin / _end bracket
+// the calls that run several passes; parts_topk_args is the one argument check of the six top-k entry points.
 // A masked search is the same work list with every query's mask number appended to the pinned image; the MASKED builds of the
 // scan test a row's bit before they offer it, and the select kernel writes the counts the host can no longer derive.  The
 // masked flat search runs the corpus as one implicit partition that every query probes -- or, where its plan says so, rides the MFMA
@@ -74,101 +76,18 @@ PartBuild parts_build(const nvdb_hip_ctx* c) {
 
 nvdb_status parts_probes(nvdb_hip_ctx* c, const char* who, const uint64_t* off, uint32_t nparts, uint32_t nq, const uint32_t* probe, uint32_t nprobe,
                          uint64_t* rows_union) {
-  PartState* ps = c->parts;
-  ps->uniq.resize(static_cast<size_t>(nq) * nprobe);
-  ps->ucount.assign(nq, 0);
-  for (uint32_t q = 0; q < nq; ++q) {
-    uint32_t* u = ps->uniq.data() + static_cast<size_t>(q) * nprobe;
-    uint32_t m = 0;
-    for (uint32_t j = 0; j < nprobe; ++j) {
-      const uint32_t p = probe[static_cast<size_t>(q) * nprobe + j];
-      if (p == 0xFFFFFFFFu) continue;
-      if (p >= nparts) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": probe entry names a partition >= nparts");
-      u[m++] = p;
-    }
-    std::sort(u, u + m);
-    m = static_cast<uint32_t>(std::unique(u, u + m) - u);
-    ps->ucount[q] = m;
-    if (rows_union) {
-      uint64_t rows = 0;
-      for (uint32_t j = 0; j < m; ++j) rows += off[u[j] + 1] - off[u[j]];
-      rows_union[q] = rows;
-    }
-  }
+  if (const char* why = pw_probes(c->parts->list, off, nparts, nq, probe, nprobe, rows_union)) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": " + why);
   return NVDB_OK;
 }
 
-nvdb_status parts_worklist(nvdb_hip_ctx* c, const char* who, const uint64_t* off, uint32_t nparts, uint32_t q0, uint32_t nq, uint32_t nprobe,
-                           uint32_t qg_max, uint32_t slot_cap, PartList& wl) {
-  PartState* ps = c->parts;
-  // 1. the de-duplicated probes of queries q0 .. q0 + nq (parts_probes): per-partition query counts
-  const uint32_t* uniq = ps->uniq.data() + static_cast<size_t>(q0) * nprobe;
-  const uint32_t* ucount = ps->ucount.data() + q0;
-  ps->pcount.assign(nparts, 0);
-  for (uint32_t q = 0; q < nq; ++q)
-    for (uint32_t j = 0; j < ucount[q]; ++j) ++ps->pcount[uniq[static_cast<size_t>(q) * nprobe + j]];
-  // 2. counting sort: the queries of every partition, ascending
-  ps->pstart.assign(nparts + 1, 0);
-  for (uint32_t p = 0; p < nparts; ++p) ps->pstart[p + 1] = ps->pstart[p] + ps->pcount[p];
-  const uint32_t npairs = ps->pstart[nparts];
-  ps->qidx.resize(npairs);
-  ps->cursor.assign(ps->pstart.begin(), ps->pstart.end() - 1);
-  for (uint32_t q = 0; q < nq; ++q) {
-    const uint32_t* u = uniq + static_cast<size_t>(q) * nprobe;
-    for (uint32_t j = 0; j < ucount[q]; ++j) ps->qidx[ps->cursor[u[j]]++] = q;
-  }
-  // 3. candidate slots a probe of partition p costs a query; the queries' blocks
-  auto nseg_of = [](uint64_t size) { return static_cast<uint32_t>((size + PART_SEG_ROWS - 1) / PART_SEG_ROWS); };
-  ps->psum.assign(nparts, 0);
-  for (uint32_t p = 0; p < nparts; ++p) {
-    const uint64_t size = off[p + 1] - off[p];
-    if (!ps->pcount[p] || !size) continue;
-    const uint32_t nseg = nseg_of(size);
-    uint64_t sum = 0;
-    for (uint32_t sg = 0; sg < nseg; ++sg) sum += std::min<uint64_t>(slot_cap, size * (sg + 1) / nseg - size * sg / nseg);
-    ps->psum[p] = static_cast<uint32_t>(sum);
-  }
-  ps->cbeg.assign(nq + 1, 0);
-  uint64_t total = 0;
-  for (uint32_t q = 0; q < nq; ++q) {
-    const uint32_t* u = uniq + static_cast<size_t>(q) * nprobe;
-    for (uint32_t j = 0; j < ucount[q]; ++j) total += ps->psum[u[j]];
-    if (total >= 0xFFFFFFFFull) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 candidate slots in one call (split the batch)");
-    ps->cbeg[q + 1] = static_cast<uint32_t>(total);
-  }
-  // 4. work items, by class of group size
-  for (auto& v : ps->items) v.clear();
-  ps->dst.clear();
-  ps->cursor.assign(ps->cbeg.begin(), ps->cbeg.end() - 1);
-  uint64_t rows_read = 0;
-  for (uint32_t p = 0; p < nparts; ++p) {
-    const uint64_t size = off[p + 1] - off[p];
-    const uint32_t cnt = ps->pcount[p];
-    if (!cnt || !size) continue;
-    const uint32_t nseg = nseg_of(size);
-    for (uint32_t g0 = 0; g0 < cnt; g0 += qg_max) {
-      const uint32_t nqg = std::min(qg_max, cnt - g0);
-      const int cl = nqg <= PART_WAVES ? 0 : (nqg <= 2 * PART_WAVES ? 1 : 2);
-      for (uint32_t sg = 0; sg < nseg; ++sg) {
-        const uint32_t lo = static_cast<uint32_t>(off[p] + size * sg / nseg), hi = static_cast<uint32_t>(off[p] + size * (sg + 1) / nseg);
-        ps->items[cl].push_back(PartItem{lo, hi, ps->pstart[p] + g0, static_cast<uint32_t>(ps->dst.size()), nqg, 0u});
-        const uint32_t slot = std::min<uint32_t>(slot_cap, hi - lo);
-        for (uint32_t g = 0; g < nqg; ++g) { uint32_t& cur = ps->cursor[ps->qidx[ps->pstart[p] + g0 + g]]; ps->dst.push_back(cur); cur += slot; }
-        rows_read += hi - lo;
-      }
-    }
-  }
-  wl.npairs = npairs;
-  wl.total = total;
-  wl.rows_read = rows_read;
-  wl.nitems = ps->items[0].size() + ps->items[1].size() + ps->items[2].size();
-  return NVDB_OK;
-}
+namespace {
 
+// the HIP side of a work list's image: meta, the pinned buffer and the events grown / created, the image written (pw_write_image),
+// its parts as device addresses.  msel: the pass's own (nullptr: unmasked)
 nvdb_status parts_stage(nvdb_hip_ctx* c, const PartList& wl, uint32_t nq, const MaskSel* msel, const uint32_t* extra, uint32_t extra_words, PartImage& im) {
   PartState* ps = c->parts;
-  const size_t w_items = wl.nitems * (sizeof(PartItem) / 4), w_qidx = wl.npairs, w_dst = ps->dst.size(), w_cbeg = nq + 1, w_mask = msel ? nq : 0;
-  const size_t meta_bytes = (w_items + w_qidx + w_dst + w_cbeg + w_mask + extra_words) * 4;
+  const PartLayout l = pw_layout(ps->list, wl, nq, msel != nullptr, extra_words);
+  const size_t meta_bytes = l.words * 4;
   if (nvdb_status st = ensure(c, ps->meta, meta_bytes)) return st;
   if (ps->pin_bytes < meta_bytes) {
     if (ps->pin) (void)hipHostFree(ps->pin);
@@ -177,29 +96,64 @@ nvdb_status parts_stage(nvdb_hip_ctx* c, const PartList& wl, uint32_t nq, const 
     ps->pin_bytes = meta_bytes + meta_bytes / 2;
   }
   for (hipEvent_t& e : ps->ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-  uint32_t* w = static_cast<uint32_t*>(ps->pin);
-  for (int cl = 2; cl >= 0; --cl) {                                     // the widest groups first: the longest items start early
-    if (!ps->items[cl].empty()) std::memcpy(w, ps->items[cl].data(), ps->items[cl].size() * sizeof(PartItem));
-    w += ps->items[cl].size() * (sizeof(PartItem) / 4);
-  }
-  if (w_qidx) std::memcpy(w, ps->qidx.data(), w_qidx * 4);
-  w += w_qidx;
-  if (w_dst) std::memcpy(w, ps->dst.data(), w_dst * 4);
-  w += w_dst;
-  std::memcpy(w, ps->cbeg.data(), w_cbeg * 4);
-  w += w_cbeg;
-  for (uint32_t q = 0; q < w_mask; ++q) w[q] = msel->mask_of ? msel->mask_of[q] : 0u;
-  w += w_mask;
-  if (extra_words) std::memcpy(w, extra, static_cast<size_t>(extra_words) * 4);
-  uint32_t* dmeta = static_cast<uint32_t*>(ps->meta.p);
+  pw_write_image(ps->list, l, msel ? msel->mask_of : nullptr, extra, static_cast<uint32_t*>(ps->pin));
+  const uint32_t* dmeta = static_cast<const uint32_t*>(ps->meta.p);
   im.bytes = meta_bytes;
-  im.items = reinterpret_cast<const PartItem*>(dmeta);
-  im.qidx = dmeta + w_items;
-  im.dst = im.qidx + w_qidx;
-  im.cbeg = im.dst + w_dst;
-  im.extra = im.cbeg + w_cbeg + w_mask;
-  im.mk = msel ? PartMask{im.cbeg + w_cbeg, static_cast<const uint32_t*>(c->row_masks.p), static_cast<uint32_t>(rm_words(c->n))}
+  im.items = reinterpret_cast<const PartItem*>(dmeta + l.items);
+  im.qidx = dmeta + l.qidx;
+  im.dst = dmeta + l.dst;
+  im.cbeg = dmeta + l.cbeg;
+  im.extra = dmeta + l.extra;
+  im.mk = msel ? PartMask{dmeta + l.mask_of, static_cast<const uint32_t*>(c->row_masks.p), static_cast<uint32_t>(rm_words(c->n))}
                : PartMask{nullptr, nullptr, 0u};
+  return NVDB_OK;
+}
+
+}  // namespace
+
+nvdb_status parts_pass(nvdb_hip_ctx* c, hipStream_t s, const char* who, const PartBuild& pb, PartPass& p, const PartPassHook& between) {
+  PartState* ps = c->parts;
+  nvdb_status st;
+  if (const char* why = pw_worklist(ps->list, p.off, p.nparts, p.q0, p.b, p.nprobe, PART_WAVES * pb.qw_max, p.slot_cap, p.wl))
+    return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": " + why);
+  if (p.skip_empty && !p.wl.total) return NVDB_OK;
+  if (between && (st = between(p))) return st;
+  // device workspace (grow-only) and the pinned image of the work list
+  const size_t qbytes = static_cast<size_t>(p.b) * c->dim * 4;
+  if ((st = ensure(c, ps->cand, std::max<size_t>(p.wl.total, 1) * sizeof(Cand)))) return st;
+  if (p.queries && (st = ensure(c, ps->q, qbytes))) return st;
+  const MaskSel sub{p.msel && p.msel->mask_of ? p.msel->mask_of + p.q0 : nullptr};   // the one place a batch's mask_of becomes a pass's
+  if ((st = parts_stage(c, p.wl, p.b, p.msel ? &sub : nullptr, p.extra, p.extra_words, p.im))) return st;
+  if (p.time_copies) HIPCHK(c, hipEventRecord(ps->ev[0], s));
+  HIPCHK(c, hipMemcpyAsync(ps->meta.p, ps->pin, p.im.bytes, hipMemcpyHostToDevice, s));
+  if (p.queries) HIPCHK(c, hipMemcpyAsync(ps->q.p, p.queries + static_cast<size_t>(p.q0) * c->dim, qbytes, hipMemcpyHostToDevice, s));
+  if (p.time_copies) HIPCHK(c, hipEventRecord(ps->ev[1], s));
+  return NVDB_OK;
+}
+
+nvdb_status parts_call_begin(nvdb_hip_ctx* c, uint32_t path) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventRecord(get_event(c, 60), c->stream));
+  c->stats = nvdb_hip_scan_stats{};
+  c->stats.path = path;
+  c->stats_lazy = false;
+  c->last_nq = 0; c->last_cap = 0; c->last_filter = false;           // (nvdb_hip_search_check describes flat searches)
+  c->last_filter_kind = 0;
+  return NVDB_OK;
+}
+
+nvdb_status parts_call_end(nvdb_hip_ctx* c, nvdb_hip_timing* timing) {
+  HIPCHK(c, hipEventRecord(get_event(c, 62), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (timing) {
+    const PartBuild pb = parts_build(c);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, get_event(c, 60), get_event(c, 62));
+    timing->kernel_ms += ms;
+    timing->total_ms = timing->h2d_ms + timing->kernel_ms + timing->d2h_ms;
+    timing->threads = PART_THREADS; timing->nwarps = PART_WAVES;
+    timing->shmem_bytes = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), pb.qw_max, pb.staged);
+  }
   return NVDB_OK;
 }
 
@@ -231,52 +185,33 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, 
   PartState* ps = c->parts;
   const uint32_t row_bytes = c->dim * static_cast<uint32_t>(bpe_of(c->dtype));
   const PartBuild pb = parts_build(c);
-  const uint32_t qw_max = pb.qw_max;
-  const bool staged = pb.staged;
-  if (!qw_max) return fail(c, NVDB_ERR_UNSUPPORTED, "search_partitions: dim too large for the query staging");
+  if (!pb.qw_max) return fail(c, NVDB_ERR_UNSUPPORTED, "search_partitions: dim too large for the query staging");
   nvdb_status st;
   const bool host_counts = out_counts && !msel;                          // (masked: the select kernel counts)
   if (host_counts) ps->rows_union.resize(nq);
   if ((st = parts_probes(c, "search_partitions", off, nparts, nq, probe, nprobe, host_counts ? ps->rows_union.data() : nullptr))) return st;
-  PartList wl;
-  if ((st = parts_worklist(c, "search_partitions", off, nparts, 0, nq, nprobe, PART_WAVES * qw_max, k, wl))) return st;
-  if (host_counts)
-    for (uint32_t q = 0; q < nq; ++q) out_counts[q] = static_cast<uint32_t>(std::min<uint64_t>(k, ps->rows_union[q]));
-  const uint64_t total = wl.total, rows_read = wl.rows_read;
 
-  // device workspace (grow-only) and the pinned image of the work list: [items | qidx | dst | cbeg | masked: mask_of]
-  const size_t qbytes = static_cast<size_t>(nq) * c->dim * 4, ob_ids = static_cast<size_t>(nq) * k * 8, ob_sc = static_cast<size_t>(nq) * k * 4;
+  const size_t ob_ids = static_cast<size_t>(nq) * k * 8, ob_sc = static_cast<size_t>(nq) * k * 4;
   HIPCHK(c, hipSetDevice(c->device));
-  if ((st = ensure(c, ps->cand, std::max<size_t>(total, 1) * sizeof(Cand)))) return st;
-  if ((st = ensure(c, ps->q, qbytes))) return st;
-  if ((st = ensure(c, ps->out_ids, ob_ids))) return st;
-  if ((st = ensure(c, ps->out_scores, ob_sc))) return st;
-  if (msel && (st = ensure(c, ps->out_counts, static_cast<size_t>(nq) * 4))) return st;
-  PartImage im;
-  if ((st = parts_stage(c, wl, nq, msel, nullptr, 0, im))) return st;
   hipStream_t s = c->stream;
-  const PartItem* d_items = im.items;
-  const uint32_t *d_qidx = im.qidx, *d_dst = im.dst, *d_cbeg = im.cbeg;
-  const PartMask mk = im.mk;
+  PartPass p;
+  p.off = off; p.nparts = nparts; p.q0 = 0; p.b = nq; p.nprobe = nprobe; p.slot_cap = k;
+  p.msel = msel; p.queries = queries;
+  p.time_copies = timing != nullptr;
+  st = parts_pass(c, s, "search_partitions", pb, p, [&](PartPass&) -> nvdb_status {
+    if (host_counts)
+      for (uint32_t q = 0; q < nq; ++q) out_counts[q] = static_cast<uint32_t>(std::min<uint64_t>(k, ps->rows_union[q]));
+    if (nvdb_status e = ensure(c, ps->out_ids, ob_ids)) return e;
+    if (nvdb_status e = ensure(c, ps->out_scores, ob_sc)) return e;
+    return msel ? ensure(c, ps->out_counts, static_cast<size_t>(nq) * 4) : NVDB_OK;
+  });
+  if (st) return st;
   uint32_t* d_counts = msel ? static_cast<uint32_t*>(ps->out_counts.p) : nullptr;
-  if (timing) HIPCHK(c, hipEventRecord(ps->ev[0], s));
-  HIPCHK(c, hipMemcpyAsync(ps->meta.p, ps->pin, im.bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(ps->q.p, queries, qbytes, hipMemcpyHostToDevice, s));
-  if (timing) HIPCHK(c, hipEventRecord(ps->ev[1], s));
   uint32_t launches = 0;
-  {
-    const PartItem* it = d_items;
-    for (int cl = 2; cl >= 0; --cl) {
-      const uint32_t n_cl = static_cast<uint32_t>(ps->items[cl].size());
-      if (!n_cl) continue;
-      const uint32_t qw = std::min<uint32_t>(qw_max, 1u << cl);
-      const ScanArgs a{it, n_cl, d_qidx, d_dst, static_cast<const float*>(ps->q.p), static_cast<Cand*>(ps->cand.p), mk};
-      if ((st = launch_scan_parts(c, s, qw, staged, k, a))) return st;
-      it += n_cl;
-      ++launches;
-    }
-  }
-  select_parts_kernel<<<nq, 64, 0, s>>>(static_cast<const Cand*>(ps->cand.p), d_cbeg, k, c->row_base,
+  if ((st = parts_scan_classes(c, pb, p.im, static_cast<const float*>(ps->q.p), launches,
+                               [&](uint32_t qw, const ScanArgs& a) { return launch_scan_parts(c, s, qw, pb.staged, k, a); })))
+    return st;
+  select_parts_kernel<<<nq, 64, 0, s>>>(static_cast<const Cand*>(ps->cand.p), p.im.cbeg, k, c->row_base,
                                          static_cast<unsigned long long*>(ps->out_ids.p), static_cast<float*>(ps->out_scores.p), d_counts);
   HIPCHK(c, hipGetLastError());
   if (timing) HIPCHK(c, hipEventRecord(ps->ev[2], s));
@@ -289,8 +224,8 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, 
   c->stats = nvdb_hip_scan_stats{};
   c->stats.path = 4;
   c->stats.chunks = launches;
-  c->stats.rows_scanned = rows_read;
-  c->stats.candidates = total;
+  c->stats.rows_scanned = p.wl.rows_read;
+  c->stats.candidates = p.wl.total;
   c->stats_lazy = false;
   c->last_filter = false;
   if (timing) {
@@ -301,30 +236,42 @@ nvdb_status parts_search(nvdb_hip_ctx* c, const uint64_t* off, uint32_t nparts, 
     timing->h2d_ms += h2d; timing->kernel_ms += ker; timing->d2h_ms += d2h;
     timing->total_ms = timing->h2d_ms + timing->kernel_ms + timing->d2h_ms;
     timing->threads = PART_THREADS; timing->nwarps = PART_WAVES; timing->K = k;
-    timing->shmem_bytes = parts_lds(c->dim, row_bytes, qw_max, staged);
+    timing->shmem_bytes = parts_lds(c->dim, row_bytes, pb.qw_max, pb.staged);
   }
+  return NVDB_OK;
+}
+
+void pad_rows(uint32_t nq, uint32_t k, uint32_t from, uint64_t* out_ids, float* out_scores, uint32_t* counts) {
+  for (uint32_t q = 0; q < nq; ++q)
+    for (uint32_t j = from; j < k; ++j) { out_ids[static_cast<size_t>(q) * k + j] = ~0ull; out_scores[static_cast<size_t>(q) * k + j] = NEG_INF; }
+  if (counts) std::fill(counts, counts + nq, 0u);
+}
+
+nvdb_status parts_topk_args(nvdb_hip_ctx* c, const char* who, bool ivf, uint32_t kmax, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe,
+                            uint32_t nprobe, const MaskSel* msel, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing, bool* done) {
+  *done = true;
+  nvdb_status st = parts_args(c, who);
+  if (st) return st;
+  if (ivf && !c->parts->have_centroids) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no centroids (nvdb_hip_set_centroids)");
+  if (timing) std::memset(timing, 0, sizeof(*timing));
+  if (nq == 0 || k == 0) return NVDB_OK;
+  if (kmax && k > kmax) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": k <= " + std::to_string(kmax) + " (wavefront-resident lists)");
+  if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
+  if (msel && (st = mask_args(c, msel->mask_of, nq, who))) return st;
+  if (nprobe == 0) { pad_rows(nq, k, 0, out_ids, out_scores, out_counts); return NVDB_OK; }
+  if (!ivf && !probe) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": null probe table");
+  *done = false;
   return NVDB_OK;
 }
 
 namespace {
 
-void pad_outputs(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
-  for (size_t i = 0; i < static_cast<size_t>(nq) * k; ++i) { out_ids[i] = ~0ull; out_scores[i] = NEG_INF; }
-  if (out_counts) for (uint32_t q = 0; q < nq; ++q) out_counts[q] = 0;
-}
-
 // nvdb_hip_search_partitions and its masked twin (msel != nullptr)
 nvdb_status search_partitions_any(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe, uint32_t nprobe,
                                   const MaskSel* msel, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
-  nvdb_status st = parts_args(c, who);
-  if (st) return st;
-  if (timing) std::memset(timing, 0, sizeof(*timing));
-  if (nq == 0 || k == 0) return NVDB_OK;
-  if (k > WAVE_KMAX) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": k <= 64 (wavefront-resident lists)");
-  if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
-  if (msel && (st = mask_args(c, msel->mask_of, nq, who))) return st;
-  if (nprobe == 0) { pad_outputs(nq, k, out_ids, out_scores, out_counts); return NVDB_OK; }
-  if (!probe) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": null probe table");
+  bool done;
+  const nvdb_status st = parts_topk_args(c, who, false, WAVE_KMAX, queries, nq, k, probe, nprobe, msel, out_ids, out_scores, out_counts, timing, &done);
+  if (st || done) return st;
   PartState* ps = c->parts;
   return parts_search(c, ps->offsets.data(), static_cast<uint32_t>(ps->offsets.size() - 1), queries, nq, k, probe, nprobe, msel, out_ids, out_scores,
                       out_counts, timing);
@@ -333,16 +280,10 @@ nvdb_status search_partitions_any(nvdb_hip_ctx* c, const char* who, const float*
 // nvdb_hip_search_ivf and its masked twin: the coarse step knows no masks
 nvdb_status search_ivf_any(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, const MaskSel* msel,
                            uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
-  nvdb_status st = parts_args(c, who);
-  if (st) return st;
+  bool done;
+  nvdb_status st = parts_topk_args(c, who, true, WAVE_KMAX, queries, nq, k, nullptr, nprobe, msel, out_ids, out_scores, out_counts, timing, &done);
+  if (st || done) return st;
   PartState* ps = c->parts;
-  if (!ps->have_centroids) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no centroids (nvdb_hip_set_centroids)");
-  if (timing) std::memset(timing, 0, sizeof(*timing));
-  if (nq == 0 || k == 0) return NVDB_OK;
-  if (k > WAVE_KMAX) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": k <= 64 (wavefront-resident lists)");
-  if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
-  if (msel && (st = mask_args(c, msel->mask_of, nq, who))) return st;
-  if (nprobe == 0) { pad_outputs(nq, k, out_ids, out_scores, out_counts); return NVDB_OK; }
   uint32_t np = 0;
   if ((st = parts_coarse(c, who, queries, nq, nprobe, out_probe, timing, np))) return st;
   const uint32_t nparts = static_cast<uint32_t>(ps->offsets.size() - 1);

@@ -1,7 +1,11 @@
-// nvdb_parts.h -- what the probe search (nvdb_partitions.cpp) and the partition range scan (nvdb_range_parts.cpp) share: the
-// state behind nvdb_hip_ctx::parts, the kernel build a corpus takes and the dispatch to it (parts_dispatch), the host-side work list
-// and its pinned image.  Internal.
+// nvdb_parts.h -- what the drivers of the probe path share (nvdb_partitions.cpp holds the definitions; the users are the probe
+// search there, the partition range scan nvdb_range_parts.cpp, the probe search for any k nvdb_parts_anyk.cpp and the masked flat
+// bootstrap nvdb_masked_flat.cpp): the state behind nvdb_hip_ctx::parts, the kernel build a corpus takes and the dispatch to it
+// (parts_dispatch), one pass's set-up (parts_pass: work list, workspace, pinned image, copies), the launches of a pass by class
+// (parts_scan_classes), the bracket of a call that runs several passes (parts_call_begin / parts_call_end) and the argument
+// checks of the top-k entry points (parts_topk_args).  The work list itself is plain C++: parts_worklist.h.  Internal.
 #pragma once
+#include <functional>
 #include <type_traits>
 
 #include "nvdb_ctx.h"
@@ -20,10 +24,10 @@ struct PartState {
   size_t pin_bytes = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   // host scratch, reused across calls
-  std::vector<uint32_t> uniq, ucount, pcount, pstart, cursor, qidx, dst, cbeg, psum, probe_tmp;
+  PartScratch list;                                // the work list of the current pass (parts_worklist.h)
+  std::vector<uint32_t> probe_tmp;
   std::vector<uint64_t> coarse_ids, rows_union;
   std::vector<float> coarse_scores;
-  std::vector<PartItem> items[3];
 };
 
 constexpr size_t PART_LDS_LIMIT = 160 * 1024;
@@ -88,28 +92,75 @@ nvdb_status parts_launch(nvdb_hip_ctx* c, hipStream_t s, K kernel, uint32_t qw, 
   return NVDB_OK;
 }
 
-// The probe table of a call, checked and de-duplicated, into the PartState's host scratch (uniq / ucount): 0xFFFFFFFF slots dropped,
-// a partition named twice counted once, an entry >= nparts -> NVDB_ERR_INVALID.  rows_union (optional, nq entries): the rows of
-// every query's probed union.
+// pw_probes (parts_worklist.h) into the PartState's scratch; an entry >= nparts -> NVDB_ERR_INVALID.  rows_union (optional, nq
+// entries): the rows of every query's probed union.
 nvdb_status parts_probes(nvdb_hip_ctx* c, const char* who, const uint64_t* off, uint32_t nparts, uint32_t nq, const uint32_t* probe, uint32_t nprobe,
                          uint64_t* rows_union);
 
-// The work list of queries q0 .. q0 + nq of that table (numbered from 0 inside the list; nvdb_partitions.cpp describes it): the
-// counting sort by partition, query groups of at most qg_max queries, segments of at most PART_SEG_ROWS rows, classes by group
-// size.  slot_cap: an (item, query) gets min(slot_cap, segment rows) candidate slots (the top-k search: k; the range scan: no cap).
-struct PartList { uint32_t npairs = 0; uint64_t total = 0, rows_read = 0; size_t nitems = 0; };
-nvdb_status parts_worklist(nvdb_hip_ctx* c, const char* who, const uint64_t* off, uint32_t nparts, uint32_t q0, uint32_t nq, uint32_t nprobe,
-                           uint32_t qg_max, uint32_t slot_cap, PartList& wl);
-
-// The pinned image of the work list [items | qidx | dst | cbeg | masked: mask_of | extra] and the device workspace it is copied
-// to (meta, grown here; the copy itself is the caller's: hipMemcpyAsync(ps->meta.p, ps->pin, image.bytes)).
+// The image of a work list on the device (meta): [items | qidx | dst | cbeg | masked: mask_of | extra], as device addresses.
 struct PartImage {
   size_t bytes = 0;
-  const PartItem* items = nullptr;                 // device addresses
+  const PartItem* items = nullptr;
   const uint32_t *qidx = nullptr, *dst = nullptr, *cbeg = nullptr, *extra = nullptr;
   PartMask mk{nullptr, nullptr, 0u};
 };
-nvdb_status parts_stage(nvdb_hip_ctx* c, const PartList& wl, uint32_t nq, const MaskSel* msel, const uint32_t* extra, uint32_t extra_words, PartImage& im);
+
+// One pass: queries q0 .. q0 + b of a batch whose probe table parts_probes has taken, over the table off[0 .. nparts].
+struct PartPass {
+  // what the caller sets
+  const uint64_t* off = nullptr;
+  uint32_t nparts = 0, q0 = 0, b = 0, nprobe = 0;
+  uint32_t slot_cap = 0;                           // an (item, query) gets min(slot_cap, segment rows) candidate slots
+  const MaskSel* msel = nullptr;                   // the BATCH's (nullptr: unmasked): the pass takes mask_of + q0
+  const float* queries = nullptr;                  // the BATCH's, host memory: rows q0 .. go to ps->q; nullptr: they are on the device already
+  const uint32_t* extra = nullptr;                 // words behind the work list in the image (the hook may set them)
+  uint32_t extra_words = 0;
+  bool skip_empty = false;                         // a list without candidate slots: return after building it (wl.total == 0), nothing staged
+  bool time_copies = false;                        // record ps->ev[0] / ev[1] around the two copies
+  // what parts_pass leaves
+  PartList wl;
+  PartImage im;
+};
+
+// The set-up of a pass on stream s: build the work list (qg_max = PART_WAVES * pb.qw_max), run `between` (optional: what a caller
+// does between list and image -- grow buffers of its own, rewrite items, set p.extra), grow cand and q, stage the pinned image,
+// enqueue its copy to meta and, where p.queries is given, the queries' copy to ps->q.
+using PartPassHook = std::function<nvdb_status(PartPass&)>;
+nvdb_status parts_pass(nvdb_hip_ctx* c, hipStream_t s, const char* who, const PartBuild& pb, PartPass& p, const PartPassHook& between = nullptr);
+
+// The launches of a staged pass: the three classes of group size, widest first (the longest items start early), class cl on the
+// QW = min(pb.qw_max, 1 << cl) build.  launch(qw, ScanArgs) -> nvdb_status is launch_scan_parts or launch_range_parts with the
+// caller's k or radius; q32: the pass's queries on the device.  Adds the launches made to `launches`.
+template <class Launch>
+nvdb_status parts_scan_classes(nvdb_hip_ctx* c, const PartBuild& pb, const PartImage& im, const float* q32, uint32_t& launches, Launch&& launch) {
+  const PartState* ps = c->parts;
+  const PartItem* it = im.items;
+  for (int cl = 2; cl >= 0; --cl) {
+    const uint32_t n_cl = static_cast<uint32_t>(ps->list.items[cl].size());
+    if (!n_cl) continue;
+    const ScanArgs a{it, n_cl, im.qidx, im.dst, q32, static_cast<Cand*>(ps->cand.p), im.mk};
+    if (nvdb_status st = launch(std::min<uint32_t>(pb.qw_max, 1u << cl), a)) return st;
+    it += n_cl;
+    ++launches;
+  }
+  return NVDB_OK;
+}
+
+// The bracket of a call that runs its passes between two events on c->stream (the range scan, the any-k search).  begin: sets
+// the device, records event 60, replaces c->stats by an empty record of `path`, clears what nvdb_hip_search_check reads (it
+// describes flat searches).  end: records event 62, synchronises, adds the span to timing->kernel_ms (the passes' copies ride
+// inside: they alternate with the launches) and fills total_ms / threads / nwarps / shmem_bytes.
+nvdb_status parts_call_begin(nvdb_hip_ctx* c, uint32_t path);
+nvdb_status parts_call_end(nvdb_hip_ctx* c, nvdb_hip_timing* timing);
+
+// entries from .. k of nq output rows become "no entry" (~0, -inf); counts (optional, nq entries) become 0
+void pad_rows(uint32_t nq, uint32_t k, uint32_t from, uint64_t* out_ids, float* out_scores, uint32_t* counts = nullptr);
+
+// What the top-k entry points of the probe path check alike, in one order (an earlier failure wins): corpus and table, ivf:
+// centroids, timing zeroed, nq == 0 || k == 0 answered, k <= kmax (kmax = 0: any k), null pointers, masked: mask_of, nprobe == 0
+// answered with padding, !ivf: null probe table.  *done: the call is answered (an error, or nothing to search).
+nvdb_status parts_topk_args(nvdb_hip_ctx* c, const char* who, bool ivf, uint32_t kmax, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe,
+                            uint32_t nprobe, const MaskSel* msel, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing, bool* done);
 
 // nvdb_hip_ctx::parts, created where a call needs the workspace only (no table is set, a table that is set stays as it is)
 PartState* parts_workspace(nvdb_hip_ctx* c);

@@ -1,8 +1,9 @@
 // nvdb_parts_anyk.cpp -- the probe search for any k (DESIGN.md section 4 "probe search, any k"): the exact top-k of every query's
 // probed union, live rows only under a mask, for k beyond the wavefront-resident lists of nvdb_hip_search_partitions.  k <= 64 IS
 // that call.  Otherwise, per sub-batch of queries:
-//   work list     parts_worklist (nvdb_partitions.cpp) with uncapped slots, as the range scan: an (item, query) slab holds as many entries as its segment has rows
-//   scan          range_parts_kernel with every radius -inf appends Cand{score, row} of every live row and pads the slabs (kernels_range_parts.h)
+//   pass          parts_pass (nvdb_parts.h) with uncapped slots, as the range scan: an (item, query) slab holds as many entries as its segment has rows;
+//                 between list and image: the sub-batch's plan (pa_plan), its words behind the work list, the device output grown
+//   scan          parts_scan_classes: range_parts_kernel with every radius -inf appends Cand{score, row} of every live row and pads the slabs (kernels_range_parts.h)
 //   select        parts_anyk_select_kernel: count, radix select of the k-th key, collect, and for slabs that fit the LDS sort + emit (kernels_parts_anyk.h)
 //   long slabs    bitonic_global_step_kernel launches per slab length, parts_anyk_emit_kernel
 //   copy          the sub-batch's rows of the device output into the caller's arrays
@@ -18,11 +19,6 @@ namespace {
 
 constexpr uint32_t PARTS_STAT_ANYK = 8;                              // nvdb_hip_scan_stats::path
 
-void pad_rows(uint32_t nq, uint32_t k, uint32_t from, uint64_t* out_ids, float* out_scores) {
-  for (uint32_t q = 0; q < nq; ++q)
-    for (uint32_t j = from; j < k; ++j) { out_ids[static_cast<size_t>(q) * k + j] = ~0ull; out_scores[static_cast<size_t>(q) * k + j] = NEG_INF; }
-}
-
 // the search proper for k > 64: the arguments are validated, nq > 0 and nprobe > 0
 nvdb_status parts_anyk_search(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, uint32_t k, const uint32_t* probe, uint32_t nprobe,
                               const MaskSel* msel, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
@@ -36,15 +32,8 @@ nvdb_status parts_anyk_search(nvdb_hip_ctx* c, const char* who, const float* que
   std::vector<uint64_t> block(nq, 0);
   if ((st = parts_probes(c, who, off, nparts, nq, probe, nprobe, block.data()))) return st;
 
-  HIPCHK(c, hipSetDevice(c->device));
+  if ((st = parts_call_begin(c, PARTS_STAT_ANYK))) return st;
   hipStream_t s = c->stream;
-  const hipEvent_t e[2] = {get_event(c, 60), get_event(c, 62)};
-  HIPCHK(c, hipEventRecord(e[0], s));
-  c->stats = nvdb_hip_scan_stats{};
-  c->stats.path = PARTS_STAT_ANYK;
-  c->stats_lazy = false;
-  c->last_nq = 0; c->last_cap = 0; c->last_filter = false;           // (nvdb_hip_search_check describes flat searches)
-  c->last_filter_kind = 0;
 
   const uint64_t budget_entries = (static_cast<uint64_t>(c->opt_largek_budget_mb) << 20) / (2 * sizeof(Cand));
   std::vector<uint32_t> extra, hcnt, hraw;
@@ -55,33 +44,36 @@ nvdb_status parts_anyk_search(nvdb_hip_ctx* c, const char* who, const float* que
     const uint32_t b = q1 - q0;
     uint64_t* ids0 = out_ids + static_cast<size_t>(q0) * k;
     float* sc0 = out_scores + static_cast<size_t>(q0) * k;
-    PartList wl;
-    if ((st = parts_worklist(c, who, off, nparts, q0, b, nprobe, PART_WAVES * pb.qw_max, 0xFFFFFFFFu, wl))) return st;
+    uint32_t nlong = 0;
+    size_t out_entries = 0;
+    PartPass p;
+    p.off = off; p.nparts = nparts; p.q0 = q0; p.b = b; p.nprobe = nprobe; p.slot_cap = 0xFFFFFFFFu;
+    p.msel = msel; p.queries = queries;
+    p.skip_empty = true;
+    st = parts_pass(c, s, who, pb, p, [&](PartPass& pp) -> nvdb_status {
+      if (!pa_plan(block.data() + q0, b, k, plan)) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 results for one query");
+      nlong = static_cast<uint32_t>(plan.longs.size());
+      // behind the work list in the pinned image: [radius (-inf) b | slab_off 2 b | long lists 4 nlong]
+      extra.assign(static_cast<size_t>(b) * 3 + static_cast<size_t>(nlong) * 4, 0xFF800000u);
+      std::copy(plan.slab_off.begin(), plan.slab_off.end(), extra.begin() + b);
+      if (nlong) std::memcpy(extra.data() + static_cast<size_t>(b) * 3, plan.longs.data(), static_cast<size_t>(nlong) * sizeof(PaLong));
+      pp.extra = extra.data(); pp.extra_words = static_cast<uint32_t>(extra.size());
+      out_entries = static_cast<size_t>(b) * plan.out_k;
+      nvdb_status e;
+      if ((e = ensure(c, ps->out_ids, out_entries * 8))) return e;
+      if ((e = ensure(c, ps->out_scores, out_entries * 4))) return e;
+      if ((e = ensure(c, ps->out_counts, static_cast<size_t>(b) * 4))) return e;
+      if ((e = ensure(c, c->rg_pcnt, static_cast<size_t>(b) * 4))) return e;
+      return ensure(c, c->rg_slab, static_cast<size_t>(plan.slab_keys) * 8);
+    });
+    if (st) return st;
+    const PartList& wl = p.wl;
+    const PartImage& im = p.im;
     if (!wl.total) {                                                   // no row in any union of the sub-batch
-      pad_rows(b, k, 0, ids0, sc0);
-      if (out_counts) std::fill(out_counts + q0, out_counts + q1, 0u);
+      pad_rows(b, k, 0, ids0, sc0, out_counts ? out_counts + q0 : nullptr);
       q0 = q1;
       continue;
     }
-    if (!pa_plan(block.data() + q0, b, k, plan)) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 results for one query");
-    const uint32_t nlong = static_cast<uint32_t>(plan.longs.size());
-    // behind the work list in the pinned image: [radius (-inf) b | slab_off 2 b | long lists 4 nlong]
-    extra.assign(static_cast<size_t>(b) * 3 + static_cast<size_t>(nlong) * 4, 0xFF800000u);
-    std::copy(plan.slab_off.begin(), plan.slab_off.end(), extra.begin() + b);
-    if (nlong) std::memcpy(extra.data() + static_cast<size_t>(b) * 3, plan.longs.data(), static_cast<size_t>(nlong) * sizeof(PaLong));
-    const size_t qbytes = static_cast<size_t>(b) * c->dim * 4, out_entries = static_cast<size_t>(b) * plan.out_k;
-    if ((st = ensure(c, ps->cand, static_cast<size_t>(wl.total) * sizeof(Cand)))) return st;
-    if ((st = ensure(c, ps->q, qbytes))) return st;
-    if ((st = ensure(c, ps->out_ids, out_entries * 8))) return st;
-    if ((st = ensure(c, ps->out_scores, out_entries * 4))) return st;
-    if ((st = ensure(c, ps->out_counts, static_cast<size_t>(b) * 4))) return st;
-    if ((st = ensure(c, c->rg_pcnt, static_cast<size_t>(b) * 4))) return st;
-    if ((st = ensure(c, c->rg_slab, static_cast<size_t>(plan.slab_keys) * 8))) return st;
-    const MaskSel sub{msel && msel->mask_of ? msel->mask_of + q0 : nullptr};
-    PartImage im;
-    if ((st = parts_stage(c, wl, b, msel ? &sub : nullptr, extra.data(), static_cast<uint32_t>(extra.size()), im))) return st;
-    HIPCHK(c, hipMemcpyAsync(ps->meta.p, ps->pin, im.bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(ps->q.p, queries + static_cast<size_t>(q0) * c->dim, qbytes, hipMemcpyHostToDevice, s));
     const float* d_radius = reinterpret_cast<const float*>(im.extra);
     const uint32_t* d_slab_off = im.extra + b;
     const PaLong* d_longs = reinterpret_cast<const PaLong*>(im.extra + static_cast<size_t>(b) * 3);
@@ -90,15 +82,11 @@ nvdb_status parts_anyk_search(nvdb_hip_ctx* c, const char* who, const float* que
     float* d_scores = static_cast<float*>(ps->out_scores.p);
     uint32_t* d_counts = static_cast<uint32_t*>(ps->out_counts.p);
     unsigned long long* slab = static_cast<unsigned long long*>(c->rg_slab.p);
-    const PartItem* it = im.items;
-    for (int cl = 2; cl >= 0; --cl) {
-      const uint32_t n_cl = static_cast<uint32_t>(ps->items[cl].size());
-      if (!n_cl) continue;
-      const ScanArgs a{it, n_cl, im.qidx, im.dst, static_cast<const float*>(ps->q.p), static_cast<Cand*>(ps->cand.p), im.mk};
-      if ((st = launch_range_parts(c, s, std::min<uint32_t>(pb.qw_max, 1u << cl), pb.staged, d_radius, a))) return st;
-      it += n_cl;
-      c->stats.chunks++;
-    }
+    uint32_t launches = 0;
+    if ((st = parts_scan_classes(c, pb, im, static_cast<const float*>(ps->q.p), launches,
+                                 [&](uint32_t qw, const ScanArgs& a) { return launch_range_parts(c, s, qw, pb.staged, d_radius, a); })))
+      return st;
+    c->stats.chunks += launches;
     const size_t lds = PA_LDS_HEAD + static_cast<size_t>(plan.lds_keys) * 8;
     if (lds > 64 * 1024)
       if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(parts_anyk_select_kernel), PA_LDS_HEAD + static_cast<size_t>(PA_LDS_KEYS) * 8))) return st;
@@ -136,36 +124,8 @@ nvdb_status parts_anyk_search(nvdb_hip_ctx* c, const char* who, const float* que
     c->stats.rows_scanned += wl.rows_read;
     q0 = q1;
   }
-  HIPCHK(c, hipEventRecord(e[1], s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (timing) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e[0], e[1]);
-    timing->kernel_ms += ms;                                           // (the work list's copies and the results' ride inside: they alternate with the launches)
-    timing->total_ms = timing->h2d_ms + timing->kernel_ms + timing->d2h_ms;
-    timing->threads = PART_THREADS; timing->nwarps = PART_WAVES; timing->K = k;
-    timing->shmem_bytes = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), pb.qw_max, pb.staged);
-  }
-  return NVDB_OK;
-}
-
-// what the two forms check alike, in the order of their k <= 64 twins; *done: the call is answered
-nvdb_status parts_anyk_args(nvdb_hip_ctx* c, const char* who, bool ivf, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, const MaskSel* msel,
-                            uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing, bool* done) {
-  *done = true;
-  nvdb_status st = parts_args(c, who);
-  if (st) return st;
-  if (ivf && !c->parts->have_centroids) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no centroids (nvdb_hip_set_centroids)");
-  if (timing) std::memset(timing, 0, sizeof(*timing));
-  if (nq == 0 || k == 0) return NVDB_OK;
-  if (!queries || !out_ids || !out_scores) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
-  if (msel && (st = mask_args(c, msel->mask_of, nq, who))) return st;
-  if (nprobe == 0) {
-    pad_rows(nq, k, 0, out_ids, out_scores);
-    if (out_counts) std::fill(out_counts, out_counts + nq, 0u);
-    return NVDB_OK;
-  }
-  *done = false;
+  if ((st = parts_call_end(c, timing))) return st;
+  if (timing) timing->K = k;
   return NVDB_OK;
 }
 
@@ -183,9 +143,8 @@ nvdb_status nvdb_hip_search_partitions_anyk(nvdb_hip_ctx* c, const float* querie
   const char* who = "search_partitions_anyk";
   const MaskSel msel{mask_of};
   bool done;
-  nvdb_status st = parts_anyk_args(c, who, false, queries, nq, k, nprobe, masked ? &msel : nullptr, out_ids, out_scores, out_counts, timing, &done);
+  const nvdb_status st = parts_topk_args(c, who, false, 0, queries, nq, k, probe, nprobe, masked ? &msel : nullptr, out_ids, out_scores, out_counts, timing, &done);
   if (st || done) return st;
-  if (!probe) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": null probe table");
   return parts_anyk_search(c, who, queries, nq, k, probe, nprobe, masked ? &msel : nullptr, out_ids, out_scores, out_counts, timing);
 }
 
@@ -197,7 +156,7 @@ nvdb_status nvdb_hip_search_ivf_anyk(nvdb_hip_ctx* c, const float* queries, uint
   const char* who = "search_ivf_anyk";
   const MaskSel msel{mask_of};
   bool done;
-  nvdb_status st = parts_anyk_args(c, who, true, queries, nq, k, nprobe, masked ? &msel : nullptr, out_ids, out_scores, out_counts, timing, &done);
+  nvdb_status st = parts_topk_args(c, who, true, 0, queries, nq, k, nullptr, nprobe, masked ? &msel : nullptr, out_ids, out_scores, out_counts, timing, &done);
   if (st || done) return st;
   uint32_t np = 0;
   if ((st = parts_coarse(c, who, queries, nq, nprobe, out_probe, timing, np))) return st;

@@ -1,6 +1,7 @@
 // nvdb_range.h -- what the flat range search (nvdb_range.cpp) and the range search on the probe path (nvdb_range_parts.cpp) share:
 // the packed result arrays of a call and their budget, the tail that turns downloaded counts into sorted, emitted slices
-// (range_tail), and the partition range scan as the flat masked search calls it.  Internal.
+// (range_tail), and the partition range scan as the flat masked search calls it (range_parts_core: per sub-batch one parts_pass
+// of nvdb_parts.h, the count, the tail).  Internal.
 #pragma once
 #include "nvdb_parts.h"
 #include "kernels_range.h"

@@ -1,7 +1,8 @@
 // nvdb_range_parts.cpp -- range search on the probe path (DESIGN.md section 4 "range search"): every row of a query's probed
 // partitions that is live in its mask and whose reference-order score reaches its radius.  Per sub-batch of queries:
-//   work list     parts_worklist (nvdb_partitions.cpp) with uncapped slots: an (item, query) slab holds as many entries as its segment has rows
-//   scan          range_parts_kernel appends Cand{score, row} to the slabs and pads them (kernels_range_parts.h)
+//   pass          parts_pass (nvdb_parts.h) with uncapped slots -- an (item, query) slab holds as many entries as its segment has rows -- and the
+//                 sub-batch's radii behind the work list in the image
+//   scan          parts_scan_classes: range_parts_kernel appends Cand{score, row} to the slabs and pads them (kernels_range_parts.h)
 //   tail          count per query -> host: exclusive scan -> range_tail (nvdb_range.h): slab runs, collect keys (score, position), sort, emit
 // The host cuts a batch into consecutive query sub-batches whose candidate blocks stay within half of largek_budget_mb (the other
 // half is the key slabs') and below 2^32 entries (rp_cut); packed results are appended in query order, so the caller never sees the cut.
@@ -42,28 +43,22 @@ nvdb_status range_parts_core(nvdb_hip_ctx* c, hipStream_t s, const char* who, co
     const uint32_t q1 = rp_cut(block.data(), nr, q0, budget_entries);
     if (q1 == q0) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": one query's probed union holds 2^32 rows or more");
     const uint32_t b = q1 - q0;
-    PartList wl;
-    if ((st = parts_worklist(c, who, off, nparts, q0, b, nprobe, PART_WAVES * pb.qw_max, 0xFFFFFFFFu, wl))) return st;
+    PartPass p;
+    p.off = off; p.nparts = nparts; p.q0 = q0; p.b = b; p.nprobe = nprobe; p.slot_cap = 0xFFFFFFFFu;
+    p.msel = msel; p.queries = queries;
+    p.extra = reinterpret_cast<const uint32_t*>(radius + q0); p.extra_words = b;
+    p.skip_empty = true;
+    if ((st = parts_pass(c, s, who, pb, p, [&](PartPass&) { return ensure(c, c->rg_pcnt, static_cast<size_t>(b) * 4); }))) return st;
+    const PartList& wl = p.wl;
+    const PartImage& im = p.im;
     hc.assign(b, 0u);
-    PartImage im;
     if (wl.total) {
-      const size_t qbytes = static_cast<size_t>(b) * c->dim * 4;
-      if ((st = ensure(c, ps->cand, static_cast<size_t>(wl.total) * sizeof(Cand)))) return st;
-      if ((st = ensure(c, ps->q, qbytes))) return st;
-      if ((st = ensure(c, c->rg_pcnt, static_cast<size_t>(b) * 4))) return st;
-      const MaskSel sub{msel && msel->mask_of ? msel->mask_of + q0 : nullptr};
-      if ((st = parts_stage(c, wl, b, msel ? &sub : nullptr, reinterpret_cast<const uint32_t*>(radius + q0), b, im))) return st;
-      HIPCHK(c, hipMemcpyAsync(ps->meta.p, ps->pin, im.bytes, hipMemcpyHostToDevice, s));
-      HIPCHK(c, hipMemcpyAsync(ps->q.p, queries + static_cast<size_t>(q0) * c->dim, qbytes, hipMemcpyHostToDevice, s));
-      const PartItem* it = im.items;
-      for (int cl = 2; cl >= 0; --cl) {
-        const uint32_t n_cl = static_cast<uint32_t>(ps->items[cl].size());
-        if (!n_cl) continue;
-        const ScanArgs a{it, n_cl, im.qidx, im.dst, static_cast<const float*>(ps->q.p), static_cast<Cand*>(ps->cand.p), im.mk};
-        if ((st = launch_range_parts(c, s, std::min<uint32_t>(pb.qw_max, 1u << cl), pb.staged, reinterpret_cast<const float*>(im.extra), a))) return st;
-        it += n_cl;
-        c->stats.chunks++;
-      }
+      uint32_t launches = 0;
+      if ((st = parts_scan_classes(c, pb, im, static_cast<const float*>(ps->q.p), launches, [&](uint32_t qw, const ScanArgs& a) {
+            return launch_range_parts(c, s, qw, pb.staged, reinterpret_cast<const float*>(im.extra), a);
+          })))
+        return st;
+      c->stats.chunks += launches;
       rparts_count_kernel<<<b, 256, 0, s>>>(static_cast<const Cand*>(ps->cand.p), im.cbeg, static_cast<uint32_t*>(c->rg_pcnt.p));
       HIPCHK(c, hipGetLastError());
       HIPCHK(c, hipMemcpyAsync(hc.data(), c->rg_pcnt.p, static_cast<size_t>(b) * 4, hipMemcpyDeviceToHost, s));
@@ -88,7 +83,7 @@ nvdb_status range_parts_core(nvdb_hip_ctx* c, hipStream_t s, const char* who, co
         [&](const std::vector<RangeDesc>& run, const RangeDesc* desc, uint32_t* taken, unsigned long long* slab) {
           const uint32_t nrun = static_cast<uint32_t>(run.size());
           uint32_t max_len = 0;                          // the longest block of the run
-          for (const RangeDesc& d : run) max_len = std::max(max_len, ps->cbeg[d.q + 1] - ps->cbeg[d.q]);
+          for (const RangeDesc& d : run) max_len = std::max(max_len, ps->list.cbeg[d.q + 1] - ps->list.cbeg[d.q]);
           const uint32_t G = std::max<uint32_t>(1, std::min<uint32_t>((max_len + 1023u) / 1024u, (8u * static_cast<uint32_t>(c->num_cu) + nrun - 1) / nrun));
           rparts_collect_kernel<<<dim3(G, nrun), 256, 0, s>>>(cand, im.cbeg, desc, taken, slab);
         },
@@ -108,15 +103,8 @@ namespace {
 nvdb_status range_parts_search(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, const float* radius, const uint32_t* probe, uint32_t nprobe,
                                const MaskSel* msel, uint64_t* out_lims, nvdb_hip_timing* timing) {
   PartState* ps = c->parts;
-  HIPCHK(c, hipSetDevice(c->device));
+  if (nvdb_status st = parts_call_begin(c, RANGE_STAT_PARTS)) return st;
   hipStream_t s = c->stream;
-  const hipEvent_t e[2] = {get_event(c, 60), get_event(c, 62)};
-  HIPCHK(c, hipEventRecord(e[0], s));
-  c->stats = nvdb_hip_scan_stats{};
-  c->stats.path = RANGE_STAT_PARTS;
-  c->stats_lazy = false;
-  c->last_nq = 0; c->last_cap = 0; c->last_filter = false;           // (nvdb_hip_search_check describes flat searches)
-  c->last_filter_kind = 0;
   RangeOut out;
   out.budget_entries = (static_cast<uint64_t>(c->opt_range_max_mb) << 20) / 12;
   std::vector<uint64_t> cnt(nq, 0);
@@ -124,16 +112,7 @@ nvdb_status range_parts_search(nvdb_hip_ctx* c, const char* who, const float* qu
                                         cnt, 0, out))
     return st;
   const uint64_t total = rp_scan(cnt.data(), nq, 0, nullptr, out_lims + 1);
-  HIPCHK(c, hipEventRecord(e[1], s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (timing) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e[0], e[1]);
-    timing->kernel_ms += ms;                                         // (the work list's and the queries' copies ride inside: they alternate with the launches)
-    timing->total_ms = timing->h2d_ms + timing->kernel_ms + timing->d2h_ms;
-    timing->threads = PART_THREADS; timing->nwarps = PART_WAVES;
-    timing->shmem_bytes = parts_lds(c->dim, c->dim * static_cast<uint32_t>(bpe_of(c->dtype)), parts_build(c).qw_max, parts_build(c).staged);
-  }
+  if (nvdb_status st = parts_call_end(c, timing)) return st;
   if (!out.pack)
     return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": " + std::to_string(total) + " results (" + std::to_string((total * 12 + (1u << 20) - 1) >> 20) +
                                             " MB packed) exceed option range_max_mb = " + std::to_string(c->opt_range_max_mb) + "; out_lims is complete");

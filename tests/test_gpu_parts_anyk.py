@@ -314,6 +314,33 @@ def test_search_ivf_anyk(cases):
     assert np.array_equal(ids, fid) and np.array_equal(sc.view(np.uint32), fsc.view(np.uint32))
 
 
+def test_search_ivf_anyk_sub_batch_cut(cases):
+    """The IVF form under largek_budget_mb = 1, masked, with the probe table asked for: the coarse step's probes feed several
+    sub-batches (each takes its own window of mask_of), the bytes are the default budget's and the table is search_ivf's."""
+    c = cases(F16, 768)
+    c.ctx.set_centroids(_centroids(c))
+    nq, nprobe = 20, 5
+    mo = (np.arange(nq) % (NMASKS + 1)).astype(np.uint32)
+    mo[mo == NMASKS] = SENT
+    *_, want_probe = c.ctx.search_ivf(c.queries[:nq], 10, nprobe, want_probe=True)
+    assert sum(len(union_rows(want_probe[q])) for q in range(nq)) > 3 * 65536          # (several sub-batches under a 1 MB budget)
+    want = {k: c.ctx.search_ivf_anyk(c.queries[:nq], k, nprobe, mo, want_probe=True) for k in (100, 8193)}
+    chunks = c.ctx.stats()["chunks"]
+    for k in (100, 8193):                                               # (the default-budget run itself: the oracle's rows over that table)
+        pid, psc, pcnt = c.check(want_probe, k, mo, what="ivf, default budget")
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(want[k][:3], (pid, psc, pcnt))), k
+    try:
+        c.ctx.set_option("largek_budget_mb", 1)
+        for k in (100, 8193):
+            got = c.ctx.search_ivf_anyk(c.queries[:nq], k, nprobe, mo, want_probe=True)
+            st = c.ctx.stats()
+            assert all(x.tobytes() == y.tobytes() for x, y in zip(got, want[k])), k
+            assert np.array_equal(got[3], want_probe), k
+            assert st["path"] == 8 and st["chunks"] > chunks, st
+    finally:
+        c.ctx.set_option("largek_budget_mb", 8192)
+
+
 IVF_N, IVF_SEED, IVF_NPARTS = 2113, 20250611, 37
 
 

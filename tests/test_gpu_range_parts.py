@@ -257,6 +257,28 @@ def test_grouping_and_sizes(cases, dtype, dim):
         c.ctx.set_option("range_max_mb", 4096)
 
 
+def test_masked_cut_keeps_every_querys_plane_and_radius(cases):
+    """largek_budget_mb = 1 (65536 candidate entries per launch set) with 20 queries on the 20000-row partition: sub-batches of at
+    most three queries.  Every query has a plane and a radius of its own, so a sub-batch that read another window's mask numbers
+    or radii (the offsets by its first query) answers with other rows: the bytes of the default-budget run, and the oracle's."""
+    c = cases(F16, 768)
+    nq = 20
+    probe = np.array([[BIG, q % NPARTS, SENT] for q in range(nq)], dtype=np.uint32)
+    mo = cycle(nq, 3)                                                   # planes 3 .. 8, "no mask", 0 .. : they change inside every sub-batch and across the cuts
+    radius = np.array([kth_best(c.scores(q)[c.union(probe[q])], 1 + 37 * q) for q in range(nq)], dtype=np.float32)
+    assert len(set(radius.tolist())) == nq and len(set(mo[:3].tolist())) == 3 and not np.array_equal(mo[:3], mo[3:6])
+    whole = c.check(probe, radius, mo, what="default budget")
+    chunks = c.ctx.stats()["chunks"]
+    try:
+        c.ctx.set_option("largek_budget_mb", 1)
+        cut = c.check(probe, radius, mo, what="largek_budget_mb = 1, masked, own radii")
+        for a, b in zip(whole, cut):
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+        assert c.ctx.stats()["chunks"] >= (nq + 2) // 3 and c.ctx.stats()["chunks"] > chunks     # (at least one launch per sub-batch)
+    finally:
+        c.ctx.set_option("largek_budget_mb", 8192)
+
+
 def test_probe_table_edge_cases(cases):
     c = cases(I8, 100)
     probe = np.array([[SENT, 5, SENT, 2],          # sentinel slots
