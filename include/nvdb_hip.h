@@ -362,6 +362,56 @@ nvdb_status nvdb_hip_search_batch_masked(nvdb_hip_ctx* ctx, const float* queries
                                          nvdb_hip_timing* timing);
 
 /* ---------------------------------------------------------------------------------------------
+ * compaction: the other half of the tombstones.  A row that nvdb_hip_update_row_mask has marked dead still takes its HBM and is
+ * still fetched, and only the masked entry points leave it out.  Compaction squeezes the dead rows of ONE plane out of the
+ * resident corpus, on the device, in place; afterwards every unmasked entry point -- nvdb_hip_search_batch and its _dev form,
+ * nvdb_hip_range_search, the probe searches -- serves exactly the live set at the cost of a corpus of that many rows.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Removes from the resident corpus every row that is dead in plane `mask`, on the device, in place.  Stable: live rows keep
+ * their order.  New local row j is old local row out_old_rows[j]; global ids are global_row_base + the NEW local row.
+ * What moves, all by the same order-preserving map: the rows, the scales of an int8 corpus, the int8 shadow and its scales (the
+ * padded-dim shadow of an int8 corpus as well as the filter shadow of option "q8_shadow"), the fp16 shadow.  Behind the new end
+ * every one of them reads as zeros again for the padding rows and the vector-load slack an upload leaves; the scale buffers are
+ * zero up to their padded length.  The buffers keep their capacity: HBM is NOT given back.
+ * What follows the move: n becomes the live count; global_row_base, dtype, dim, options, statistics and what the context has
+ * learnt about the corpus (the list capacity it needed, a demoted shadow) are kept.  The norm bounds of the filters (the largest
+ * row norm, the shadow's, its residual, the sign of the int8 scales) are kept too: maxima over a superset of the remaining rows, so
+ * every filter bound still holds -- nvdb_hip_corpus_info's max_row_norm is an UPPER BOUND after a compaction.  All resident planes
+ * go through the map and are repacked to W' = ceil(n' / 32) words with tail bits 0: plane `mask` becomes all live, every other
+ * plane keeps, for each surviving row, the bit it had; the live counts the library keeps per plane become exact.  A resident
+ * partition table becomes offsets'[p] = live rows below the old offsets[p] (empty partitions are legal); the centroids stay, no row
+ * has changed its partition.  A held range result is invalidated (nvdb_hip_range_results -> NVDB_ERR_INVALID until the next search).
+ * The walk: ascending slabs of option "compact_slab_rows" rows (a multiple of 64 in [64, 2^24], default 65536).  A slab whose
+ * destination ends at or before its start is moved by one launch; any other is gathered into a bounce buffer of one slab and
+ * copied from there, so no launch writes bytes that it reads.  Rows before the first dead row are neither read nor written.  Peak
+ * extra HBM: one slab of the widest array, 4 bytes per 64 rows, the new planes (and 4 bytes per live row where out_old_rows is given).
+ *   NVDB_ERR_INVALID      ctx == NULL, no planes resident, mask >= nmasks, or no row live in the plane (an empty corpus is not
+ *                         representable): nothing changed, nothing written
+ *   NVDB_ERR_NO_CORPUS    nothing resident: nothing changed
+ *   NVDB_ERR_UNSUPPORTED  an adopted corpus (the caller's memory, unpadded): nothing changed
+ *   NVDB_OK               also where no row is dead: *out_n = n, the identity map, nothing launched beyond the count
+ *   NVDB_ERR_HIP          a HIP error.  One before the first row has moved (an allocation of the workspace, the rank step): nothing
+ *                         changed.  One after it leaves no half-moved corpus: the context drops its corpus, table and planes as a
+ *                         load does before it loads; the next call sees NVDB_ERR_NO_CORPUS.
+ * Synchronous.  A context is single-owner, as everywhere. */
+nvdb_status nvdb_hip_compact_rows(nvdb_hip_ctx* ctx, uint32_t mask, uint64_t* out_n /* may be NULL */,
+                                  uint32_t* out_old_rows /* may be NULL; room for the OLD n entries, the first *out_n are written */);
+
+/* The same for an index (nvdb_hip_ivf_build, below): `mask` names a plane set with nvdb_hip_ivf_set_row_masks.  The lists shrink in
+ * place and stay contiguous: offsets' = the cumulative sum of the lists' live counts, perm'[j] = perm[old position of j], and
+ * nvdb_hip_ivf_info reports the new n, offsets and perm.  Results keep coming in ORIGINAL ids -- the caller's ids do not change --
+ * and, the move being stable, equal scores stay ordered by (partition, original id).  nvdb_hip_ivf_set_row_masks and
+ * nvdb_hip_ivf_update_row_mask afterwards still speak of ORIGINAL rows (planes of ceil(n / 32) words over the n rows the index
+ * was built from); the bit or the update of a row that a compaction has removed is ignored.  Statuses as above (ivf == NULL ->
+ * NVDB_ERR_INVALID).  A failure before the first row has moved -- any status but NVDB_ERR_HIP, and NVDB_ERR_HIP from the workspace's
+ * allocations or the rank step -- leaves the index exactly as it was; only where the index's context has dropped its corpus (a HIP
+ * error during the move: nvdb_hip_corpus_info on nvdb_hip_ivf_ctx then returns NVDB_ERR_NO_CORPUS) does the index hold no rows.
+ * No row dead -> NVDB_OK, nothing changed. */
+struct nvdb_hip_ivf;
+nvdb_status nvdb_hip_ivf_compact(struct nvdb_hip_ivf* ivf, uint32_t mask, uint64_t* out_n /* may be NULL */);
+
+/* ---------------------------------------------------------------------------------------------
  * range search on the probe path: nvdb_hip_range_search's question -- every row whose score reaches a per-query radius -- asked of
  * a per-query choice of partitions, of an IVF index, and of the rows that are live in a query's mask.  FAISS users know the
  * combination as IndexIVF::range_search with SearchParameters::sel.
@@ -553,7 +603,7 @@ nvdb_status nvdb_hip_ivf_range_results(nvdb_hip_ivf* ivf, uint64_t* out_ids, flo
  * "q8_auto_min_rows", "q8_auto_max_mb" (all set before the upload), "shadow_exact_thr" (1: a search that streams the int8 shadow
  * takes its thresholds from exact scores of its best 2k candidates, one error bound under them; 0: two bounds under the k-th filter score), "exact_mfma" (exact scores on the fp32
  * matrix cores), "exact_lds", "i8_dense8" (int8 filter, d = 768, batches > 128: 1 = 8 waves of 32 queries per workgroup, 0 = 4 of 64; same results), "i8_defer", "i8_lo_bits", "boot_tiles", "xcd_balance", "rescore8", "refine_v2", "refine_pinned" (reference CUDA_PINNED:
- * pinned host staging in nvdb_hip_refine_l2_topk), "largek_budget_mb" (HBM for the any-k path's score matrix), "range_max_mb" (packed results a range search may hold), "time_kernels" (1: start /
+ * pinned host staging in nvdb_hip_refine_l2_topk), "largek_budget_mb" (HBM for the any-k path's score matrix), "range_max_mb" (packed results a range search may hold), "compact_slab_rows" (rows per slab of nvdb_hip_compact_rows' walk: a multiple of 64 in [64, 2^24], default 65536), "time_kernels" (1: start /
  * stop events attached to every launch of the dominant kernel, read by nvdb_hip_collect_kernel_times), "time_launches" (the same for one host-API
  * call with a timing struct -> stats.filter_kernel_ms).  "mfma16", "i8_wide", "i8_pipe", "i8_waves8", "i8_mfma16", "i8_small8" select kernel
  * variants that exist in libnvdb_hip_dev.so only: the product accepts their default values (1, 1, 1, 0, 1) and returns

@@ -1,6 +1,7 @@
 // nvdb_corpus.cpp -- the context and its resident corpus: create / destroy, upload / adopt / generate (fp16 / int8 shadow copies,
 // row-norm pass), options, statistics, host-side helpers of the C ABI (include/nvdb_hip.h).
 #include "nvdb_ctx.h"
+#include "compact_plan.h"
 #include "kernels_corpus.h"
 
 namespace {
@@ -230,6 +231,8 @@ nvdb_status corpus_take_ownership(nvdb_hip_ctx* c, void* dev_rows, float* dev_sc
   return compute_max_norm(c);
 }
 
+void corpus_drop(nvdb_hip_ctx* c) { free_corpus(c); }
+
 }  // namespace nvdbhip
 
 extern "C" {
@@ -287,7 +290,8 @@ void nvdb_hip_destroy(nvdb_hip_ctx* c) {
   if (c->hostblock.p) c->misc.p = nullptr;         // (misc lives inside the host API's result block)
   for (DevBuf* b : {&c->q32, &c->q16, &c->qscale, &c->qinv, &c->ebound, &c->slack, &c->thr, &c->cnt, &c->overflow, &c->cand,
                     &c->out_ids, &c->out_scores, &c->misc, &c->hostblock, &c->hitlog, &c->prog, &c->qdelta, &c->rq, &c->rcand, &c->rout_ids, &c->rout_dist, &c->rdbg, &c->lk_scores, &c->lk_sel, &c->lk_hist, &c->lk_state, &c->xcdw, &c->tickets,
-                    &c->rg_radius, &c->rg_kept, &c->rg_off, &c->rg_idx, &c->rg_q, &c->rg_desc, &c->rg_taken, &c->rg_slab, &c->rg_pcnt, &c->rg_maskof, &c->rg_ids, &c->rg_scores, &c->row_masks, &c->mask_rows})
+                    &c->rg_radius, &c->rg_kept, &c->rg_off, &c->rg_idx, &c->rg_q, &c->rg_desc, &c->rg_taken, &c->rg_slab, &c->rg_pcnt, &c->rg_maskof, &c->rg_ids, &c->rg_scores, &c->row_masks, &c->mask_rows,
+                    &c->cp_rank, &c->cp_sums, &c->cp_bounce, &c->cp_map, &c->cp_live, &c->row_masks_alt})
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   for (auto& k : c->klaunch) { (void)hipEventDestroy(k.e0); (void)hipEventDestroy(k.e1); }
@@ -438,6 +442,7 @@ nvdb_status nvdb_hip_set_option(nvdb_hip_ctx* c, const char* key, int64_t value)
   else if (k == "refine_dbg_q") { if (value < 0) return fail(c, NVDB_ERR_INVALID, "refine_dbg_q must be >= 0"); c->opt_refine_dbg_q = value; }
   else if (k == "largek_budget_mb") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "largek_budget_mb must be >= 1"); c->opt_largek_budget_mb = value; }
   else if (k == "range_max_mb") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "range_max_mb must be >= 1"); c->opt_range_max_mb = value; }
+  else if (k == "compact_slab_rows") { if (!cp_slab_rows_valid(value)) return fail(c, NVDB_ERR_INVALID, "compact_slab_rows must be a multiple of 64 in [64, 2^24]"); c->opt_compact_slab_rows = value; }
   else if (k == "chunk_growth") { if (value != 0 && (value < 2 || value > 64)) return fail(c, NVDB_ERR_INVALID, "chunk_growth must be 0 (automatic) or in [2,64]"); c->opt_growth = value; }
   else if (k == "min_filter_batch") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "min_filter_batch must be >= 1"); c->opt_min_filter_batch = value; }
   else return fail(c, NVDB_ERR_INVALID, "unknown option: " + k);

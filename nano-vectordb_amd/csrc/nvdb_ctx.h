@@ -18,6 +18,8 @@
 //   nvdb_parts_anyk.cpp    the probe search for any k: per sub-batch one pass at radius -inf, select, long slabs (kernels_parts_anyk.h, parts_anyk_plan.h)
 //   nvdb_masked_flat.cpp   the masked flat top-k on the MFMA filter route: prefix rank, bootstrap bar, the range search's filter pass, top-k of the kept
 //                          lists (kernels_masked_topk.h, masked_plan.h)
+//   nvdb_compact.cpp       in-place compaction of tombstoned rows: rank, slab walk (direct / bounce), planes, partition table (kernels_compact.h, compact_plan.h);
+//                          nvdb_hip_compact_rows here, nvdb_hip_ivf_compact beside the index in nvdb_ivf.cpp
 //   nvdb_ivf.cpp           IVF-Flat build: row assignment, spherical k-means, list layout, the reordered index and its searches (the context's, ids mapped
 //                          back by ivf_map_ids) (kernels_ivf.h, ivf_layout.h)
 //   nvdb_debug.cpp         developer entry points (libnvdb_hip_dev.so only)
@@ -192,7 +194,11 @@ struct nvdb_hip_ctx {
   uint32_t nmasks = 0;                             // ... planes resident (0: none; any corpus load drops them, the buffer stays)
   std::vector<uint64_t> mask_live;                 // ... and their live rows as the host knows them: counted when the planes are set, moved by the length of every
                                                    // update's row list (an ESTIMATE -- a list may name a row twice or a row already in that state); read by the masked
-                                                   // flat search's automatic route only, never by a result
+                                                   // flat search's automatic route only, never by a result; exact after nvdb_hip_compact_rows
+  // compaction (nvdb_compact.cpp): grow-only workspace -- tile ranks, their block sums / bases, one slab of the widest array, the map, the planes' live counts --
+  // and the spare the repacked planes are written to before it is swapped with row_masks
+  DevBuf cp_rank, cp_sums, cp_bounce, cp_map, cp_live, row_masks_alt;
+  int64_t opt_compact_slab_rows = 65536;           // rows per slab of the walk (a multiple of 64; compact_plan.h): profiles/compact_bench_10M.txt
 };
 
 #define HIPCHK(ctx, call)                                                                        \
@@ -370,6 +376,7 @@ nvdb_status launch_boot_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t n0, uint32_t
 // nvdb_corpus.cpp
 nvdb_status corpus_alloc_padded(nvdb_hip_ctx* c, uint64_t n, uint32_t dim, uint32_t dtype, void** rows, float** scales);
 nvdb_status corpus_take_ownership(nvdb_hip_ctx* c, void* dev_rows, float* dev_scales, uint64_t n, uint32_t dim, uint32_t dtype, uint64_t global_row_base);
+void corpus_drop(nvdb_hip_ctx* c);       // the context forgets its corpus, shadows, partition table and planes (what a load does before it loads)
 // nvdb_partitions.cpp
 void parts_drop(nvdb_hip_ctx* c);        // the corpus changes: forget the partition table and the centroids (the workspace stays)
 void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace

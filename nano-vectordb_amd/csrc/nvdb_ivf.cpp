@@ -7,6 +7,7 @@
 // API ranks it with k = 1 on the caller's stream, narrow_ids_kernel keeps the u32 part; a batch whose self-check trips goes
 // through the child's host API, which retries by itself -- the device group's pattern (nvdb_group.cpp).
 #include "nvdb_ctx.h"
+#include "compact_plan.h"
 #include "ivf_layout.h"
 #include "row_mask.h"
 #include "kernels_ivf.h"
@@ -176,6 +177,7 @@ struct nvdb_hip_ivf {
   std::vector<uint32_t> inv;                       // inv[row of the source corpus] = position; built by the first nvdb_hip_ivf_update_row_mask
   std::vector<uint64_t> offsets;                   // nparts + 1
   uint64_t src_row_base = 0;
+  uint64_t src_n = 0;                              // rows of the source corpus (perm.size() until nvdb_hip_ivf_compact removes rows)
   std::string err;
 };
 
@@ -352,6 +354,7 @@ nvdb_status nvdb_hip_ivf_build(nvdb_hip_ctx* src, const float* centroids, uint32
   ix->perm.resize(n);
   ix->offsets.resize(static_cast<size_t>(nparts) + 1);
   ix->src_row_base = src->row_base;
+  ix->src_n = n;
   if (!ivf_layout(assign.data(), n, nparts, ix->offsets.data(), ix->perm.data())) return bail(NVDB_ERR_INTERNAL, "ivf_build: assignment out of range");
 
   // 3. - 5. the list-ordered copy, owned by a fresh context on the same device
@@ -424,9 +427,10 @@ nvdb_status nvdb_hip_ivf_set_row_masks(nvdb_hip_ivf* ix, const uint32_t* bits, u
   if (!bits || nmasks == 0 || nmasks == 0xFFFFFFFFu) st = nvdb_hip_set_row_masks(ix->ctx, nullptr, nmasks);   // nothing to permute
   else {
     // position j of the index is live iff bit perm[j] of the caller's plane is set
-    const uint64_t n = ix->perm.size(), W = rm_words(n);
+    // (the caller's planes are over the source corpus' rows, the index's over the positions a compaction has left)
+    const uint64_t n = ix->perm.size(), W = rm_words(n), Wsrc = rm_words(ix->src_n);
     std::vector<uint32_t> planes(static_cast<size_t>(nmasks) * W);
-    for (uint32_t m = 0; m < nmasks; ++m) rm_permute(bits + static_cast<size_t>(m) * W, ix->perm.data(), n, planes.data() + static_cast<size_t>(m) * W);
+    for (uint32_t m = 0; m < nmasks; ++m) rm_permute(bits + static_cast<size_t>(m) * Wsrc, ix->perm.data(), n, planes.data() + static_cast<size_t>(m) * W);
     st = nvdb_hip_set_row_masks(ix->ctx, planes.data(), nmasks);
   }
   if (st) ix->err = nvdb_hip_last_error(ix->ctx);
@@ -435,18 +439,48 @@ nvdb_status nvdb_hip_ivf_set_row_masks(nvdb_hip_ivf* ix, const uint32_t* bits, u
 
 nvdb_status nvdb_hip_ivf_update_row_mask(nvdb_hip_ivf* ix, uint32_t mask, const uint64_t* rows, uint64_t nrows, int live) {
   if (!ix) return NVDB_ERR_INVALID;
-  const uint64_t n = ix->perm.size();
+  const uint64_t n = ix->src_n;                      // rows are named as the source corpus numbers them, before and after a compaction
   if (nrows && !rows) { ix->err = "ivf_update_row_mask: null row list"; return NVDB_ERR_INVALID; }
   if (!rm_rows_valid(rows, nrows, n)) { ix->err = "ivf_update_row_mask: a listed row is >= the row count"; return NVDB_ERR_INVALID; }
   if (ix->inv.empty() && nrows) {
     ix->inv.resize(n);
-    if (!rm_inverse(ix->perm.data(), n, ix->inv.data())) { ix->inv.clear(); ix->err = "ivf_update_row_mask: the index's permutation is damaged"; return NVDB_ERR_INTERNAL; }
+    if (!cp_inverse(ix->perm.data(), ix->perm.size(), n, ix->inv.data())) { ix->inv.clear(); ix->err = "ivf_update_row_mask: the index's permutation is damaged"; return NVDB_ERR_INTERNAL; }
   }
-  std::vector<uint64_t> pos(nrows);
-  for (uint64_t i = 0; i < nrows; ++i) pos[i] = ix->inv[rows[i]];
-  const nvdb_status st = nvdb_hip_update_row_mask(ix->ctx, mask, pos.data(), nrows, live);
+  std::vector<uint64_t> pos;
+  pos.reserve(nrows);
+  for (uint64_t i = 0; i < nrows; ++i)
+    if (ix->inv[rows[i]] != 0xFFFFFFFFu) pos.push_back(ix->inv[rows[i]]);   // (a row that a compaction removed has no position: nothing to update)
+  const nvdb_status st = nvdb_hip_update_row_mask(ix->ctx, mask, pos.data(), pos.size(), live);
   if (st) ix->err = nvdb_hip_last_error(ix->ctx);
   return st;
+}
+
+nvdb_status nvdb_hip_ivf_compact(nvdb_hip_ivf* ix, uint32_t mask, uint64_t* out_n) {
+  if (!ix) return NVDB_ERR_INVALID;
+  std::vector<uint32_t> old_rows(ix->perm.size());   // positions of the list-ordered copy: new position j was position old_rows[j]
+  uint64_t n_new = 0;
+  const nvdb_status st = nvdb_hip_compact_rows(ix->ctx, mask, &n_new, old_rows.data());
+  if (st) {
+    ix->err = nvdb_hip_last_error(ix->ctx);
+    // A failure before the first row moved (an allocation of the workspace, say) has changed nothing: the index stays as it was.
+    // Only where the context has DROPPED its corpus -- a HIP error during the move -- is this an index of no rows
+    if (!ix->ctx->rows) {
+      ix->perm.clear(); ix->inv.clear();
+      std::fill(ix->offsets.begin(), ix->offsets.end(), 0);
+    }
+    return st;
+  }
+  if (n_new == ix->perm.size()) {                    // no row was dead: nothing moved, perm, offsets and inv stand
+    if (out_n) *out_n = n_new;
+    return NVDB_OK;
+  }
+  // lists shrink in place and stay contiguous: the entries of the map below an old offset are the live positions before that list
+  cp_offsets_from_map(old_rows.data(), n_new, ix->offsets.data(), ix->offsets.size(), ix->offsets.data());
+  cp_perm(ix->perm.data(), old_rows.data(), n_new);
+  ix->perm.resize(n_new);
+  ix->inv.clear();                                   // rebuilt by the next nvdb_hip_ivf_update_row_mask
+  if (out_n) *out_n = n_new;
+  return NVDB_OK;
 }
 
 nvdb_status nvdb_hip_ivf_search_masked(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, const uint32_t* mask_of,

@@ -40,6 +40,7 @@ EXPORTS = [
     "nvdb_hip_range_search_partitions", "nvdb_hip_range_search_ivf", "nvdb_hip_range_search_masked",
     "nvdb_hip_ivf_range_search", "nvdb_hip_ivf_range_results",
     "nvdb_hip_search_partitions_anyk", "nvdb_hip_search_ivf_anyk", "nvdb_hip_ivf_search_anyk",
+    "nvdb_hip_compact_rows", "nvdb_hip_ivf_compact",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_filter_variant", "nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -213,6 +214,8 @@ def _bind(L, dev):
     L.nvdb_hip_search_partitions_anyk.argtypes = [vp, vp, u32, u32, vp, u32, vp, C.c_int, vp, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_search_ivf_anyk.argtypes = [vp, vp, u32, u32, u32, vp, C.c_int, vp, vp, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_ivf_search_anyk.argtypes = [vp, vp, u32, u32, u32, vp, C.c_int, vp, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_compact_rows.argtypes = [vp, u32, C.POINTER(u64), vp]
+    L.nvdb_hip_ivf_compact.argtypes = [vp, u32, C.POINTER(u64)]
     for name in EXPORTS:
         getattr(L, name)
     if dev:
@@ -571,6 +574,15 @@ class HipContext:
             self._chk(self.lib.nvdb_hip_get_row_masks(self.h, None, None, out.ctypes.data))
         return out
 
+    def compact_rows(self, mask=0):
+        """Remove the rows that are dead in plane `mask` from the resident corpus, on the device, in place (stable) ->
+        (n_new, old_rows [n_new] u32: new local row j was old local row old_rows[j])."""
+        n_old = self.corpus_info()["n"]
+        old = np.zeros(max(n_old, 1), dtype=np.uint32)
+        n_new = C.c_uint64(0)
+        self._chk(self.lib.nvdb_hip_compact_rows(self.h, mask, C.byref(n_new), old.ctypes.data))
+        return n_new.value, old[:n_new.value].copy()
+
     def search_partitions_masked(self, queries, k, probe, mask_of=None, want_timing=False):
         """search_partitions over the rows live in each query's mask: mask_of[q] = plane number (0xFFFFFFFF: none; None: plane 0
         for every query) -> (ids, scores, counts); counts[q] = min(k, live rows in the probed union)."""
@@ -726,6 +738,7 @@ class IvfIndex:
             raise NvdbError(st, self.lib.nvdb_hip_ivf_last_error(None).decode())
         self.h = h
         self.ctx = _BorrowedContext(self.lib, C.c_void_p(self.lib.nvdb_hip_ivf_ctx(h)), src_ctx.device)
+        self.src_n = self.info()["n"]                    # rows of the source corpus: what the planes stay indexed by after compact()
 
     def close(self):
         if getattr(self, "h", None):
@@ -773,12 +786,19 @@ class IvfIndex:
         if masks is None or (isinstance(masks, (int, np.integer)) and not isinstance(masks, (bool, np.bool_))):
             self._chk(self.lib.nvdb_hip_ivf_set_row_masks(self.h, None, int(masks or 0)))
             return
-        packed = pack_row_masks(masks, self.info()["n"])
+        packed = pack_row_masks(masks, self.src_n)
         self._chk(self.lib.nvdb_hip_ivf_set_row_masks(self.h, packed.ctypes.data, packed.shape[0]))
 
     def update_row_mask(self, mask, rows, live):
         rows = np.ascontiguousarray(rows, dtype=np.uint64).ravel()
         self._chk(self.lib.nvdb_hip_ivf_update_row_mask(self.h, mask, rows.ctypes.data if rows.size else None, rows.size, 1 if live else 0))
+
+    def compact(self, mask=0):
+        """Remove the rows that are dead in plane `mask` from the index, on the device, in place -> n_new.  The lists shrink and
+        stay contiguous; ids stay the source corpus' ids; info() reports the new n, offsets and perm."""
+        n_new = C.c_uint64(0)
+        self._chk(self.lib.nvdb_hip_ivf_compact(self.h, mask, C.byref(n_new)))
+        return n_new.value
 
     def search_masked(self, queries, k, nprobe, mask_of=None, want_probe=False):
         """search() over the rows live in each query's mask (mask_of as HipContext.search_partitions_masked)."""
