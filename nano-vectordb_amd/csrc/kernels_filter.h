@@ -17,9 +17,13 @@
 //
 // Kernels: filter_f16_m16_kernel (production fp16, v_mfma_f32_16x16x32_f16; MB/NQB pick the tile shape),
 // filter_f16_k2_kernel (1536 < DIM <= 3072: a tile streamed as two half-K stages),
-// filter_f16_kernel (32x32x16 build: batches <= 128, the bootstrap build VAR 7, timing ablations),
+// filter_f16_kernel (32x32x16 build: batches <= 128, the bootstrap build BOOT),
 // filter_i8w_kernel (int8 two-stage: hi plane always, lo plane on demand), filter_i8_kernel (int8 two-plane:
 // bootstrap build, A/B reference), prep_q16 / prep_q8 (query scaling, error bounds), shadow / generator / norm kernels.
+// Every build of every kernel here returns right results: the only diagnostic template switch is STAMP (the in-kernel clock pair
+// around the tile loop, developer library).  The timing-only knock-out builds (no direct-to-LDS loads, no LDS reads, no barrier,
+// no test, rare path cut short) that these loops carried as a VAR parameter were retired once their answers were recorded;
+// profiles/README.md ("Retired ablation builds") lists what each knocked out, for rebuilding one in a scratch tree.
 //
 // What the seven filter kernels (filter_i8s_kernel, kernels_filter_i8s.h, included) have in common that is NOT arithmetic is
 // written once, ahead of the first kernel ("shared pieces of the filter kernels" below): xcd_aware_grid (the one predicate
@@ -367,9 +371,7 @@ __device__ __forceinline__ void scatter_own_log(const Hit* mylog, uint32_t wcnt,
   }
 }
 
-// VAR selects timing-only ablation builds (results are wrong for VAR != 0; used by
-// nvdb_hip_debug_filter_variant): 1 = no direct-to-LDS loads in the loop, 2 = 1 + no barrier,
-// 3 = no MFMA (loads + LDS reads only), 4 = no epilogue compare, 5 = no LDS reads (MFMA on a constant).
+// BOOT = true: the bootstrap build (launch_boot_dim) -- best (score, row) per tile and query -> candidate lists, no thresholds.
 // NB = 32-query blocks per wave: 2 -> 256 queries per workgroup (MFMA-bound batches), 1 -> 128 queries
 // per workgroup (half the MFMA work per streamed byte: the HBM-bound regime, nq <= 128).
 // RING = A fragments in flight LDS -> VGPR.
@@ -381,12 +383,12 @@ __device__ __forceinline__ void glds16_v(const void* gptr, uint32_t lds_off) {
 }
 
 template <int DIM> constexpr size_t filter_f16_lds_bytes() { return static_cast<size_t>(FILTER_STAGES) * FILTER_ROWS * DIM * 2; }   // dynamic LDS of filter_f16_kernel
-template <int DIM, int NB, int VAR = 0, int RING = 6>
+template <int DIM, int NB, bool BOOT = false, int RING = 6>
 __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
     const _Float16* __restrict__ rows, uint32_t row_lo, uint32_t row_hi, const _Float16* __restrict__ q16,
     uint32_t nq, uint32_t QT, const float* __restrict__ thr, const float* __restrict__ qscale,
     const float* __restrict__ qinv, Hit* __restrict__ hitlog, ScatterArgs sa, uint32_t aux) {
-  // aux: VAR 7 (bootstrap build) only -- hitlog then points at the candidate lists and aux is their stride
+  // aux: BOOT only -- hitlog then points at the candidate lists and aux is their stride
   constexpr int KSTEPS = DIM / 16;                 // MFMA k-steps per tile
   constexpr int ROW_BYTES = DIM * 2;
   constexpr int STAGE_BYTES = FILTER_ROWS * ROW_BYTES;
@@ -460,7 +462,6 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
   const uint32_t g_lo = row_lo / FILTER_ROWS + t_lo;          // logical index of my first tile in the whole corpus
   auto tile_phys = [&](uint32_t t_rel) -> uint32_t { return perm_tile(g_lo + (t_rel < NT ? t_rel : NT - 1), sa); };
   auto tile_ptr = [&](uint32_t t_rel) -> const char* {
-    if constexpr (VAR == 6) return gbase + static_cast<uint64_t>(row_lo + (t_lo + (t_rel & 7u)) * FILTER_ROWS) * ROW_BYTES;   // ablation: 8 tiles per stream, L2-resident
     return gbase + static_cast<uint64_t>(tile_phys(t_rel)) * FILTER_ROWS * ROW_BYTES;
   };
   auto issue_piece = [&](const char* tile, uint32_t buf, int i) {
@@ -480,8 +481,8 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
   const uint32_t xw_t0 = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
   for (uint32_t t = 0; t < NT; ++t) {
     // my pieces of tile t have landed once all but the newest stage's PPW loads are complete
-    if constexpr (VAR != 1 && VAR != 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-    if constexpr (VAR != 2) __builtin_amdgcn_s_barrier();   // everyone's pieces landed; buffer (t+2)%3 is free
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
+    __builtin_amdgcn_s_barrier();   // everyone's pieces landed; buffer (t+2)%3 is free
 
     const char* next_tile = tile_ptr(t + 2);
     const uint32_t next_buf = (t + 2) % FILTER_STAGES;
@@ -495,45 +496,33 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
       return *reinterpret_cast<const float4_t*>(stage + (a_base ^ ((s & 7) << 5)) + (s >> 3) * 256);
     };
     float4_t ar[RING];
-    if constexpr (VAR == 5) {
 #pragma unroll
-      for (int s = 0; s < RING; ++s) ar[s] = float4_t{1.f, 2.f, 3.f, 4.f};
-    }
-#pragma unroll
-    for (int s = 0; s < RING - 1; ++s) if constexpr (VAR != 5) ar[s] = read_a(s);
+    for (int s = 0; s < RING - 1; ++s) ar[s] = read_a(s);
     floatx16 acc[NB];
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
       // keep RING-1 fragment reads ahead of the MFMAs; the slot written here was consumed by step s-1
-      if constexpr (VAR != 5) { if (s + RING - 1 < KSTEPS) ar[(s + RING - 1) % RING] = read_a(s + RING - 1); }
+      if (s + RING - 1 < KSTEPS) ar[(s + RING - 1) % RING] = read_a(s + RING - 1);
       const float4_t a = ar[s % RING];
-      if constexpr (VAR == 3) {
-        asm volatile("" ::"v"(a));
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        const int f = nb * KSTEPS + s;
         if (s == 0) {
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb) acc[nb] = floatx16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        }
-      } else {
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-          const int f = nb * KSTEPS + s;
-          if (s == 0) {
-            if (f < NFRAG_A) NVDB_MFMA_F16_ZERO_A(acc[nb], a, bqa[f < NFRAG_A ? f : 0]);
-            else NVDB_MFMA_F16_ZERO_V(acc[nb], a, bqv[f >= NFRAG_A ? f - NFRAG_A : 0]);
-          } else {
-            if (f < NFRAG_A) NVDB_MFMA_F16_ACC_A(acc[nb], a, bqa[f < NFRAG_A ? f : 0]);
-            else NVDB_MFMA_F16_ACC_V(acc[nb], a, bqv[f >= NFRAG_A ? f - NFRAG_A : 0]);
-          }
+          if (f < NFRAG_A) NVDB_MFMA_F16_ZERO_A(acc[nb], a, bqa[f < NFRAG_A ? f : 0]);
+          else NVDB_MFMA_F16_ZERO_V(acc[nb], a, bqv[f >= NFRAG_A ? f - NFRAG_A : 0]);
+        } else {
+          if (f < NFRAG_A) NVDB_MFMA_F16_ACC_A(acc[nb], a, bqa[f < NFRAG_A ? f : 0]);
+          else NVDB_MFMA_F16_ACC_V(acc[nb], a, bqv[f >= NFRAG_A ? f - NFRAG_A : 0]);
         }
       }
       // stream tile t+2 in behind the MFMAs, one 1 KB piece every PIECE_EVERY k-steps
-      if constexpr (VAR != 1 && VAR != 2) { if (s % PIECE_EVERY == PIECE_EVERY - 1) issue_piece(next_tile, next_buf, s / PIECE_EVERY); }
+      if (s % PIECE_EVERY == PIECE_EVERY - 1) issue_piece(next_tile, next_buf, s / PIECE_EVERY);
     }
     // 32 wait states: MFMA result -> VALU read (the compiler does not see inside the asm)
     if constexpr (NB == 2) asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc[0]), "+v"(acc[1]));
     else asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc[0]));
 
-    if constexpr (VAR == 7) {
+    if constexpr (BOOT) {
       // ---- bootstrap epilogue: best row of this tile for every query -> cand[qid][tile] -----------
       // (a lower bound generator for the first thresholds: the k-th largest of T tile maxima is <= the
       //  k-th largest score overall; the host discards these entries after the threshold is taken and
@@ -561,23 +550,17 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
       continue;
     }
     // ---- epilogue: threshold filter ------------------------------------------------------------
-    bool any = false;
-    if constexpr (VAR == 4) {
+    // max tree per query block, then one compare (see filter_f16_m16_kernel's epilogue)
+    float d[NB];
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) asm volatile("" ::"v"(acc[nb]));
-    } else {
-      // max tree per query block, then one compare (see filter_f16_m16_kernel's epilogue)
-      float d[NB];
+    for (int nb = 0; nb < NB; ++nb) {
+      float m = vmax3(acc[nb][0], acc[nb][1], acc[nb][2]);
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        float m = vmax3(acc[nb][0], acc[nb][1], acc[nb][2]);
-#pragma unroll
-        for (int r = 3; r < 15; r += 2) m = vmax3(m, acc[nb][r], acc[nb][r + 1]);
-        m = vmax3(m, acc[nb][15], acc[nb][15]);
-        d[nb] = m - thr_s[nb];
-      }
-      any = (NB == 2 ? vmax3(d[0], d[NB - 1], d[NB - 1]) : d[0]) >= 0.f;
+      for (int r = 3; r < 15; r += 2) m = vmax3(m, acc[nb][r], acc[nb][r + 1]);
+      m = vmax3(m, acc[nb][15], acc[nb][15]);
+      d[nb] = m - thr_s[nb];
     }
+    const bool any = (NB == 2 ? vmax3(d[0], d[NB - 1], d[NB - 1]) : d[0]) >= 0.f;
     if (__builtin_amdgcn_ballot_w64(any)) {
       // rare path: log the survivors in this wave's own region (plain 16-byte stores, no atomics,
       // nothing to wait for); scatter_own_log files them under their queries when the stream is done.
@@ -602,7 +585,7 @@ __global__ __launch_bounds__(256, 1) void filter_f16_kernel(
     }
   }
   stream_exit<false>(nullptr, sp, sa.xcdw, wave, lane, xw_t0);
-  if constexpr (VAR == 0) scatter_own_log(mylog, wcnt, sa, lane);
+  if constexpr (!BOOT) scatter_own_log(mylog, wcnt, sa, lane);
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the two speculative stages before exit
 }
 
@@ -646,16 +629,14 @@ __device__ __forceinline__ void sibling_rendezvous(uint32_t* myprog, uint32_t qt
 
 
 // STAMP: diagnostic build only (nvdb_hip_debug_clock): wave 0 stamps s_memtime / s_memrealtime around the tile
-// loop and stores the two differences behind the progress counters, where nothing else reads them.
-// VAR (with STAMP only; results are wrong): 1 = no direct-to-LDS loads in the loop, 5 = no LDS reads (MFMA on whatever
-// the ring registers hold), 15 = neither (bare MFMA stream + barrier + epilogue), 16 = 15 without the epilogue compares, 17 = 16 without the barrier.
+// loop and stores the two differences behind the progress counters, where nothing else reads them.  Same loop, same results.
 // MB x NQB = 16-row blocks per tile x 16-query blocks per wave: 2 x 4 (32-row tiles, 64 queries per wave) for
 // DIM <= 768; 1 x 2 (16-row tiles, 32 queries per wave) for DIM up to 1536 -- the wave's B fragments are NQB*DIM/8
 // registers either way (384 at the two corners), and a stage stays 48 KB.
 // WPB = waves per workgroup: 4 (one per SIMD, 512 registers each) or 8 (two per SIMD, 256 registers each, NQB = 2:
 // the second wave of a SIMD fills the gaps the first leaves at tile boundaries; twice the LDS reads per MFMA)
 template <int DIM, int MB = 2> constexpr size_t filter_f16_m16_lds_bytes() { return static_cast<size_t>(FILTER_STAGES) * 16 * MB * DIM * 2; }   // dynamic LDS of filter_f16_m16_kernel
-template <int DIM, int RING = 6, bool SYNC = false, bool STAMP = false, int VAR = 0, int MB = 2, int NQB = 4, int WPB = 4>
+template <int DIM, int RING = 6, bool SYNC = false, bool STAMP = false, int MB = 2, int NQB = 4, int WPB = 4>
 __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
     const _Float16* __restrict__ rows, uint32_t row_lo, uint32_t row_hi, const _Float16* __restrict__ q16,
     uint32_t nq, uint32_t QT, const float* __restrict__ thr, const float* __restrict__ qscale,
@@ -744,7 +725,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
   // 8-wave build: the two waves of a SIMD leave the per-tile barrier together, multiply together and would test together, with
   // the matrix pipe idle meanwhile.  Waves 4..7 therefore test a tile's accumulators AFTER the next barrier (LATE): their test
   // runs beside the partner wave's ring priming and first MFMAs, the partner's test beside their last MFMAs.
-  const bool late = (WPB == 8) && (VAR == 0 || VAR == 21) && wave >= 4;
+  const bool late = (WPB == 8) && wave >= 4;
   float4_t acc[MB][NQB];
   auto epilogue = [&](uint32_t te) {
     // "does any of my 32 scores reach its query's threshold": a max tree per query block (v_max3_f32), one subtract
@@ -790,9 +771,8 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
       // wave 0 only; the per-tile barrier holds the other waves back
       if (wave == 0 && (t & sync_mask) == 0) sibling_rendezvous(myprog, qt, t, sync_lead, sync_strikes, lane);
     }
-    constexpr bool NO_GLDS = (VAR == 1 || VAR >= 15), NO_READ = (VAR == 5 || VAR >= 15), NO_EPI = (VAR >= 16), NO_BAR = (VAR >= 17);
-    if constexpr (!NO_GLDS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-    if constexpr (!NO_BAR) __builtin_amdgcn_s_barrier();
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
+    __builtin_amdgcn_s_barrier();
     const char* next_tile = tile_ptr(t + 2);
     const uint32_t next_buf = (t + 2) % FILTER_STAGES;
     const char* stage = smem + (t % FILTER_STAGES) * STAGE_BYTES;
@@ -807,15 +787,11 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
       return *reinterpret_cast<const float4_t*>(stage + (a16 ^ ((s & 3) << 6)) + (s >> 2) * 256 + mb * 16 * ROW_BYTES);
     };
     float4_t ar[RING];
-    if constexpr (NO_READ) {
 #pragma unroll
-      for (int u = 0; u < RING; ++u) ar[u] = bqv[u];          // random, non-trivial operand bits
-    }
-#pragma unroll
-    for (int u = 0; u < RING - 1; ++u) if constexpr (!NO_READ) ar[u] = read_a(u);
+    for (int u = 0; u < RING - 1; ++u) ar[u] = read_a(u);
 #pragma unroll
     for (int u = 0; u < NREAD; ++u) {
-      if constexpr (!NO_READ) { if (u + RING - 1 < NREAD) ar[(u + RING - 1) % RING] = read_a(u + RING - 1); }
+      if (u + RING - 1 < NREAD) ar[(u + RING - 1) % RING] = read_a(u + RING - 1);
       const float4_t a = ar[u % RING];
       const int s = u / MB, mb = u % MB;
 #pragma unroll
@@ -829,7 +805,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
           else NVDB_MFMA16_ACC_V(acc[mb][nb], a, bqv[f >= NFRAG_A ? f - NFRAG_A : 0]);
         }
       }
-      if constexpr (!NO_GLDS) { if (u % PIECE_EVERY == PIECE_EVERY - 1) issue_piece(next_tile, next_buf, u / PIECE_EVERY); }
+      if (u % PIECE_EVERY == PIECE_EVERY - 1) issue_piece(next_tile, next_buf, u / PIECE_EVERY);
     }
     // 32 wait states: MFMA result -> VALU read (the compiler does not see inside the asm)
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -837,7 +813,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_f16_m16_kernel(
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
       for (int nb = 0; nb < NQB; ++nb) asm volatile("" : "+v"(acc[mb][nb]));
-    if constexpr (NO_EPI) continue;
     if (!late) epilogue(t);
   }
   if (late && wave_has_queries) epilogue(NT - 1);
@@ -1090,7 +1065,7 @@ template <int ROW_BYTES> __device__ inline uint32_t a_addr_i8(uint32_t a_base, i
 // first k-step of a block whose accumulators start at a constant (16 VGPRs holding it: srcC and vDst share a register class)
 #define NVDB_MFMA_I8_FROM(acc, a, b, c0) asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %3" : "=&v"(acc) : "v"(a), "a"(b), "v"(c0))
 
-// BOOT = true: bootstrap build (see filter_f16_kernel VAR 7): best (score,row) per tile and query -> cand lists
+// BOOT = true: bootstrap build (see filter_f16_kernel BOOT): best (score,row) per tile and query -> cand lists
 // (hitlog then points at the candidate lists, aux is their stride).
 template <int DIM> constexpr size_t filter_i8_lds_bytes() { return static_cast<size_t>(FILTER_STAGES_I8) * (FILTER_ROWS * DIM + 4 * 1024); }   // dynamic LDS of filter_i8_kernel
 template <int DIM, bool BOOT = false, int RING = 6, bool SYNC = false>
@@ -1291,14 +1266,13 @@ __device__ __forceinline__ int imax3(int a, int b, int c) {
 // ------------------------------------------------------------------------------------------------
 // MB = 32-row blocks per tile: 2 -> 64-row tiles (a 52 KB stage, three of them) halve the per-tile costs (barrier,
 // loop-top scalar code, rendezvous, MFMA drain) per row; 1 -> 32-row tiles, five stages (debug / A-B only).
-// STAMP / VAR: diagnostic builds only (libnvdb_hip_dev.so, nvdb_hip_debug_clock_i8; results are wrong for VAR != 0):
-// STAMP = s_memtime / s_memrealtime around the tile loop (written behind the rendezvous counters); VAR 1 = never run
-// stage 2 (no lo-plane pass), 2 = no stage-1 test either (MFMAs + stream only), 3 = 2 + no per-tile barrier.
+// STAMP: diagnostic build only (libnvdb_hip_dev.so, nvdb_hip_debug_clock_i8): s_memtime / s_memrealtime around the tile loop
+// (written behind the rendezvous counters); same loop, same results.
 // dynamic LDS of filter_i8w_kernel: its stages, and behind them (64-row tiles) 1 KB of lo-plane scratch per wave
 template <int DIM, int MB = 2> constexpr size_t filter_i8w_lds_bytes() {
   return static_cast<size_t>((MB == 2 || DIM > 768) ? 3 : FILTER_STAGES_I8) * (FILTER_ROWS * MB * DIM + 4 * 1024) + (MB == 2 ? 4 * 1024 : 0);
 }
-template <int DIM, int NB = 2, int RING = 6, bool SYNC = false, int MB = 2, bool STAMP = false, int VAR = 0>
+template <int DIM, int NB = 2, int RING = 6, bool SYNC = false, int MB = 2, bool STAMP = false>
 __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
     const signed char* __restrict__ rows, const float* __restrict__ scales, uint32_t row_lo, uint32_t row_hi,
     const signed char* __restrict__ qhi, const signed char* __restrict__ qlo, uint32_t nq, uint32_t QT,
@@ -1436,7 +1410,7 @@ __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
     }
     // my pieces of tile t have landed once all but the newest NSTAGE-2 tiles' loads are complete
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSTAGE - 2) * (PPW + 1)) : "memory");
-    if constexpr (VAR < 3) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     const uint32_t next_row0 = tile_row0(t + NSTAGE - 1), next_buf = (t + NSTAGE - 1) % NSTAGE;
     const char* stage = smem + (t % NSTAGE) * STAGE_BYTES;
     if (!wave_has_queries) {
@@ -1483,7 +1457,6 @@ __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) asm volatile("" : "+v"(acc[mb][nb]));
 
-    if constexpr (VAR >= 2) continue;
     // ---- stage 1: can any of my NB x 16 hi-plane values H_r * scale_r reach its first-stage threshold? ----------
     // (exact per value: cvt + mul, then a max tree per block and one compare; a cheaper bound such as
     //  max(H) * max(scale) lets a quarter of the tiles through, and a tile costs what its slowest wave costs)
@@ -1505,7 +1478,6 @@ __global__ __launch_bounds__(256, 1) void filter_i8w_kernel(
     if constexpr (DEFER) { if (pend) consume_pending(1); }             // issued one tile ago: PPW + 1 younger loads in flight
     if (!__builtin_amdgcn_ballot_w64(dall >= 0.f)) continue;
     ++n_stage1;
-    if constexpr (VAR == 1) continue;
     const uint32_t row0 = tile_row0(t);
     if constexpr (DEFER) {
       // rare path: which values pass?  (the same comparison as the max tree, value by value)
@@ -1676,9 +1648,7 @@ __device__ __forceinline__ void verify_and_scatter_i8(const Hit* mylog, uint32_t
 //     Barrier B is what it costs: block 1 of tile t-1 is tested during tile t, and its rare path still reads that tile's LDS
 //     stage, so the loads that overwrite it (tile t+2, same buffer) are issued only after every wave has passed B.
 // ------------------------------------------------------------------------------------------------
-// VAR (diagnostic builds, STAMP only; wrong results): 1 = no test and no rare path (the pipelined structure alone), 2 = test but no rare path,
-// 3 = rare path without consuming the deferred values, 4 = rare path entered and left at once; 5 = the production loop (right results) reporting
-// the cycles wave 0 spent inside rare_path (high word) and consume_slots (low word) instead of the loop's cycle count
+// STAMP: diagnostic build only (nvdb_hip_debug_clock_i8), the same loop with the clock pair around it.
 // WPB = 8: the same 256 queries per workgroup on 8 waves of 32 (NB = 1), two waves per SIMD with 256 registers each: a wave's
 // LDS-DMA issue, ring priming, barrier waits and rare path run beside its SIMD partner's MFMAs.
 // DEFER = false (the default build): a value that passes the first stage is only logged in the loop and finished after the stream
@@ -1687,7 +1657,7 @@ __device__ __forceinline__ void verify_and_scatter_i8(const Hit* mylog, uint32_t
 template <int DIM, int WPB = 4, bool DEFER = true> constexpr size_t filter_i8p_lds_bytes() {
   return static_cast<size_t>(3) * (2 * FILTER_ROWS * DIM + (WPB == 4 ? 4 : 1) * 256) + (DEFER ? WPB * (16 / WPB) * DIM : 0);
 }
-template <int DIM, bool SYNC = false, bool STAMP = false, int RING = 6, int VAR = 0, int WPB = 4, bool DEFER = true>
+template <int DIM, bool SYNC = false, bool STAMP = false, int RING = 6, int WPB = 4, bool DEFER = true>
 __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
     const signed char* __restrict__ rows, const float* __restrict__ scales, uint32_t row_lo, uint32_t row_hi,
     const signed char* __restrict__ qhi, const signed char* __restrict__ qlo, uint32_t nq, uint32_t QT,
@@ -1808,7 +1778,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
   for (int i = 0; i < NSLOT_DEFER; ++i) { pend_x[i] = make_uint4(0, 0, 0, 0); pend_H[i] = 0; pend_scale[i] = pend_thr[i] = pend_inv[i] = 0.f; pend_qid[i] = pend_row[i] = 0; }
   // finish the slots in `which`: their lo-plane rows have landed once all but the `younger` newest loads are complete
   auto consume_slots = [&](uint32_t which, uint32_t younger) {
-    if constexpr (VAR == 3) { pend_mask &= ~which; return; }
     switch (younger) {                             // s_waitcnt takes an immediate
       case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
       case PPW + 1: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW + 1) : "memory"); break;
@@ -1869,7 +1838,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
   // multiply one of them each by -2^23 (the test's v_fma constant).  Block 0's set is filled during the tile's first half (used in
   // the second), block 1's during the second half (used in the next tile's first half).
   auto scale_step = [&](const char* stage, int mb, int set, int w) {
-    if constexpr (VAR == 1) return;
     if (w == 0) {
       const float* sc_lds = reinterpret_cast<const float*>(stage + DATA_BYTES + (wave % SC_COPIES) * 256);
 #pragma unroll
@@ -1888,7 +1856,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
   // of step j, multiplies those of step j - 1 by their row scales and folds those of step j - 2 into the running maxima.
   float tc[NV], tm[NV];
   auto test_step = [&](const intx16 (&a)[NB], const float (&sc)[16], int j, int vps) {
-    if constexpr (VAR == 1) return;
     if constexpr (BIASED) {
       // one v_fma per value: (2^23 + H) * scale - 2^23 * scale = H * scale, rounded once like float(H) * scale (the constant is
       // exact: a power of two times the scale); slot j multiplies the values of step j, folds those of step j - 1
@@ -1919,7 +1886,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
   };
   float flagv = -1.f;                              // >= 0 iff some value of the tested block reaches its first-stage threshold
   auto combine_flags = [&]() {                     // behind the half's last MFMA
-    if constexpr (VAR == 1) return;
     float m[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) m[nb] = vmax3(vmax3(mx[nb][0], mx[nb][1], mx[nb][2]), mx[nb][3], mx[nb][3]) - t1q[nb];
@@ -1932,7 +1898,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
   auto rare_path = [&](const intx16 (&a)[NB], const char* stage, uint32_t row0, int mb) -> uint32_t {
     ++n_stage1;
     uint32_t issued = 0;
-    if constexpr (VAR == 4) return issued;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const uint32_t before = pend_mask;
@@ -2019,7 +1984,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
   // finish after the stream.  Per flagged group of 4 accumulator registers one ballot per value; lanes compact into the log.
   auto rare_log = [&](const intx16 (&a)[NB], const float (&sc)[16], uint32_t row0, int mb) {
     ++n_stage1;
-    if constexpr (VAR == 4) return;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
@@ -2043,7 +2007,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
 
   uint32_t sync_strikes = 0;
   uint64_t stamp_c = 0, stamp_r = 0;
-  [[maybe_unused]] uint64_t rare_acc = 0, cons_acc = 0;     // VAR 5: cycles this wave spent inside rare_path / consume_slots
   if constexpr (STAMP) stamp_begin(stamp_c, stamp_r);
   const uint32_t xw_t0 = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
   for (uint32_t t = 0; t < NT; ++t) {
@@ -2109,12 +2072,9 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
       }
     }
     young_loads = 0;
-    if ((VAR == 0 || VAR >= 3) && t > 0 && any_flag()) {
-      const uint64_t r0 = VAR == 5 ? __builtin_amdgcn_s_memtime() : 0;
+    if (t > 0 && any_flag()) {
       if constexpr (DEFER) young_loads = rare_path(acc1, prev_stage, tile_row0(t - 1), 1); else rare_log(acc1, sc_first, tile_row0(t - 1), 1);
-      if constexpr (VAR == 5) rare_acc += __builtin_amdgcn_s_memtime() - r0;
     }
-    if constexpr (VAR == 1 || VAR == 2) { asm volatile("" ::"v"(flagv)); }   // keep this half's test alive
     if constexpr (DEFER) __builtin_amdgcn_s_barrier();                     // B: nobody reads the stage of tile t-1 any more
     // ---- second half: block 1 of tile t  ||  loads of tile t+2, test of block 0 of tile t ---------------------------
     if constexpr (DEFER) load_scales(stage, 0, scv2[0]);                   // (!DEFER: block 0's set was filled during the first half)
@@ -2143,18 +2103,11 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
       __builtin_amdgcn_sched_barrier(0);
     }
     // what was deferred during the PREVIOUS tile is at least one tile old now; behind it: this tile's deferred loads and its PPW + 1 pieces
-    {
-      const uint64_t r0 = VAR == 5 ? __builtin_amdgcn_s_memtime() : 0;
-      if (pend_old) consume_slots(pend_old, PPW + 1 + young_loads);
-      if constexpr (VAR == 5) { const uint64_t r1 = __builtin_amdgcn_s_memtime(); cons_acc += r1 - r0; }
-    }
-    if ((VAR == 0 || VAR >= 3) && any_flag()) {
-      const uint64_t r0 = VAR == 5 ? __builtin_amdgcn_s_memtime() : 0;
+    if (pend_old) consume_slots(pend_old, PPW + 1 + young_loads);
+    if (any_flag()) {
       if constexpr (DEFER) rare_path(acc0, stage, tile_row0(t), 0); else rare_log(acc0, scv2[0], tile_row0(t), 0);
-      if constexpr (VAR == 5) rare_acc += __builtin_amdgcn_s_memtime() - r0;
     }
     pend_old = pend_mask;                                                  // everything deferred during this tile: due at the end of the next
-    if constexpr (VAR == 1 || VAR == 2) { asm volatile("" ::"v"(flagv)); }
   }
   if (wave_has_queries) {                          // block 1 of the last tile
     const char* last_stage = smem + ((NT - 1) % NSTAGE) * STAGE_BYTES;
@@ -2165,13 +2118,11 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8p_kernel(
     for (int j = 0; j < NV + 2; ++j) test_step(acc1, scv2[0], j, 1);       // (biased build: NV / 2 + 2 of them do something)
     combine_flags();
     if (pend_mask) consume_slots(pend_mask, 0);
-    if ((VAR == 0 || VAR >= 3) && any_flag()) { if constexpr (DEFER) rare_path(acc1, last_stage, tile_row0(NT - 1), 1); else rare_log(acc1, scv2[0], tile_row0(NT - 1), 1); }
+    if (any_flag()) { if constexpr (DEFER) rare_path(acc1, last_stage, tile_row0(NT - 1), 1); else rare_log(acc1, scv2[0], tile_row0(NT - 1), 1); }
     if (pend_mask) consume_slots(pend_mask, 0);
   }
   if constexpr (STAMP) {
-    uint64_t dc = __builtin_amdgcn_s_memtime() - stamp_c;
-    const uint64_t dr = __builtin_amdgcn_s_memrealtime() - stamp_r;
-    if constexpr (VAR == 5) dc = (rare_acc << 32) | (cons_acc & 0xFFFFFFFFull);   // this build reports those instead of the loop's cycles
+    const uint64_t dc = __builtin_amdgcn_s_memtime() - stamp_c, dr = __builtin_amdgcn_s_memrealtime() - stamp_r;
     if (wave == 0 && lane == 0) stamp_store(prog, dc, dr);
   }
   if constexpr (SYNC) { if (wave == 0 && lane == 0) __hip_atomic_store(prog + static_cast<uint64_t>(stream) * 8 + qt, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

@@ -25,12 +25,12 @@ typedef int intx4_t __attribute__((ext_vector_type(4)));
 #define NVDB_MFMA_I8S_FROM(acc, a, b, c0) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %3" : "=&v"(acc) : "v"(a), "a"(b), "v"(c0))
 #define NVDB_MFMA_I8S_ACC(acc, a, b) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b))
 
-// VAR (STAMP builds only; wrong results): 1 = no test, no logging (structure alone), 2 = test, nothing logged,
-// 3 = structure alone without the in-loop LDS-DMA issue (the stages keep the first tiles), 4 = structure alone without the A-fragment LDS reads.
+// STAMP: diagnostic build only (nvdb_hip_debug_clock_i8), the same loop with the clock pair around it.  The knock-out builds this
+// kernel once carried (no test, no logging, no LDS-DMA issue, no A-fragment reads) were retired; profiles/README.md has their recipes.
 // WPB = 8: the same 256 queries per workgroup on 8 waves of 32 (two waves per SIMD, 128 + 128 registers each): a wave's LDS-DMA issue,
 // ring priming and barrier waits run beside its SIMD partner's MFMAs.
 template <int DIM, int WPB = 4> constexpr size_t filter_i8s_lds_bytes() { return static_cast<size_t>(3) * (2 * FILTER_ROWS * DIM + WPB * 256); }   // dynamic LDS of filter_i8s_kernel
-template <int DIM, bool SYNC = false, bool STAMP = false, int RING = 6, int VAR = 0, int WPB = 4>
+template <int DIM, bool SYNC = false, bool STAMP = false, int RING = 6, int WPB = 4>
 __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
     const signed char* __restrict__ rows, const float* __restrict__ scales, uint32_t row_lo, uint32_t row_hi,
     const signed char* __restrict__ qhi, const signed char* __restrict__ qlo, uint32_t nq, uint32_t QT,
@@ -38,7 +38,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
     const float* __restrict__ qdelta, Hit* __restrict__ hitlog, ScatterArgs sa, uint32_t* __restrict__ prog,
     uint32_t sync_mask, uint32_t sync_lead, uint32_t* __restrict__ stage_counts) {
   static_assert(WPB == 4 || WPB == 8, "4 waves x 64 queries or 8 waves x 32 queries");
-  constexpr bool NOTEST = VAR == 1 || VAR == 3 || VAR == 4;
   constexpr int NB = 16 / WPB, MB = 2;                       // blocks of 16 queries per wave; 2 blocks of 32 rows per tile
   constexpr int NV = 8 * NB;                                 // values a lane tests per 32-row block
   constexpr int KS = DIM / 64;                               // k-steps of 64 bytes
@@ -123,8 +122,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
   auto issue_scales = [&](uint32_t row0, uint32_t buf) {
     if (lane < 8 * MB) glds16(sc_off, reinterpret_cast<const char*>(scales + row0), lds_base + buf * STAGE_BYTES + DATA_BYTES + wave * 256);
   };
-  auto loop_piece = [&](uint32_t row0, uint32_t buf, int i) { if constexpr (VAR != 3) issue_piece(row0, buf, i); };
-  auto loop_scales = [&](uint32_t row0, uint32_t buf) { if constexpr (VAR != 3) issue_scales(row0, buf); };
 #pragma unroll
   for (int st = 0; st < NSTAGE - 1; ++st) {
 #pragma unroll
@@ -151,14 +148,12 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
 
   auto read_a = [&](const char* stage, int u, int mb) -> float4_t {         // u = 2 s + h: k-step s, 16-row half h of row block mb
     const int s = u >> 1, h = u & 1;
-    if constexpr (VAR == 4) { float4_t z = {0.f, 1.f, 2.f, 3.f}; asm volatile("" : "+v"(z)); return z; }
     const uint32_t off = swz16<ROW_BYTES>() ? (a16 ^ ((s & 3) << 6)) + (s >> 2) * 256 : (a16 ^ ((s & 1) << 6)) + (s >> 1) * 128;
     return *reinterpret_cast<const float4_t*>(stage + off + (2 * mb + h) * 16 * ROW_BYTES);
   };
   // in the shadow of the MFMAs: slot 0 reads the 8 scales of block mb of `stage` into set `set`, slots SW0.. multiply one each by -2^23
   constexpr int SW0 = NSLOT >= 64 ? 8 : 4;         // (d = 384: 48 slots per half; the 32 test units need 34 of them)
   auto scale_step = [&](const char* stage, int mb, int set, int w) {
-    if constexpr (NOTEST) return;
     if (w == 0) {
       const float* sc_lds = reinterpret_cast<const float*>(stage + DATA_BYTES + wave * 256);
 #pragma unroll
@@ -178,7 +173,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
   constexpr int SPU = (NSLOT - W0 - 4) / NV >= 2 ? 2 : 1;   // slots per unit
   static_assert(W0 + NV * SPU + 2 <= NSLOT, "the test ends before the half's last MFMA");
   auto test_step = [&](const intx4_t (&a)[2][NB], const float (&sc)[8], const float (&sccs)[8], int w) {
-    if constexpr (NOTEST) return;
     const int rel = w - W0;
     if (rel < 0 || rel % SPU != 0) return;
     const int v = rel / SPU;
@@ -196,7 +190,6 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
   };
   float flagv = -1.f;                              // >= 0 iff some value of the tested block reaches its first-stage threshold
   auto combine_flags = [&]() {
-    if constexpr (NOTEST) return;
     float m[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) m[nb] = vmax3(mx[nb][0], mx[nb][1], mx[nb][1]) - t1q[nb];
@@ -255,7 +248,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
 #pragma unroll
     for (int u = 0; u < RING - 1; ++u) ar[u] = read_a(stage, u, 0);
 #pragma unroll
-    for (int i = 0; i < HP0; ++i) loop_piece(next_row0, next_buf, i);
+    for (int i = 0; i < HP0; ++i) issue_piece(next_row0, next_buf, i);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < NFRAG; ++u) {
@@ -274,12 +267,11 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (HP > HP0) {
-        if (u % EV1 == EV1 - 1) loop_piece(next_row0, next_buf, HP0 + u / EV1);
+        if (u % EV1 == EV1 - 1) issue_piece(next_row0, next_buf, HP0 + u / EV1);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if (VAR == 0 && t > 0 && any_flag()) rare_log(acc1, scv[1], tile_row0(t - 1), 1);
-    if constexpr (VAR != 0) { asm volatile("" ::"v"(flagv)); }
+    if (t > 0 && any_flag()) rare_log(acc1, scv[1], tile_row0(t - 1), 1);
     // ---- second half: block 1 of tile t  ||  rest of the loads of tile t + 2, test of block 0 of tile t ---------------------
     reset_max();
     constexpr int R0 = NFRAG % RING;                                       // ring slot of block 1's first fragment
@@ -298,12 +290,11 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
         if (w == NSLOT - 1) combine_flags();
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (u % EV2 == EV2 - 1) loop_piece(next_row0, next_buf, HP + u / EV2);
-      if (u == 0) loop_scales(next_row0, next_buf);
+      if (u % EV2 == EV2 - 1) issue_piece(next_row0, next_buf, HP + u / EV2);
+      if (u == 0) issue_scales(next_row0, next_buf);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (VAR == 0 && any_flag()) rare_log(acc0, scv[0], tile_row0(t), 0);
-    if constexpr (VAR != 0) { asm volatile("" ::"v"(flagv)); }
+    if (any_flag()) rare_log(acc0, scv[0], tile_row0(t), 0);
   }
   if (wave_has_queries) {                          // block 1 of the last tile
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -311,7 +302,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void filter_i8s_kernel(
 #pragma unroll
     for (int w = W0; w < W0 + (NV + 1) * SPU; ++w) test_step(acc1, scv[1], scc[1], w);
     combine_flags();
-    if (VAR == 0 && any_flag()) rare_log(acc1, scv[1], tile_row0(NT - 1), 1);
+    if (any_flag()) rare_log(acc1, scv[1], tile_row0(NT - 1), 1);
   }
   if constexpr (STAMP) {
     const uint64_t dc = __builtin_amdgcn_s_memtime() - stamp_c, dr = __builtin_amdgcn_s_memrealtime() - stamp_r;

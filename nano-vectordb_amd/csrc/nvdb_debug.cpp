@@ -1,4 +1,4 @@
-// nvdb_debug.cpp -- developer entry points (include/nvdb_hip_dev.h): stamped / ablation builds of the filter kernels, the device's
+// nvdb_debug.cpp -- developer entry points (include/nvdb_hip_dev.h): stamped builds of the filter kernels, the device's
 // tile partition function, the plan of a search for a shape given as plain numbers (no device).  Compiled into libnvdb_hip_dev.so only; the product library does not contain this file's code.
 #ifdef NVDB_HIP_DEV
 #include "nvdb_plan.h"
@@ -10,68 +10,67 @@ __global__ void fill_u32_kernel(uint32_t* p, uint32_t v, size_t n) {
   if (i < n) p[i] = v;
 }
 
+// What the two clock entry points share.  `launch` enqueues one stamped launch; they run back to back in bursts of CLOCK_BURST (the
+// rendezvous counters, the first prog_bytes of c->prog, reset ahead of each) until `seconds` have passed, and the last burst is timed
+// (`before_timed` is enqueued ahead of it).  Then the stamp pairs every workgroup's wave 0 left behind the counters are read back.
+constexpr uint32_t CLOCK_BURST = 8;
+struct ClockStats {
+  float ms = 0.f;                                  // per launch of the timed burst
+  float ghz[3] = {0.f, 0.f, 0.f};                  // median, min, max over the workgroups that stamped: delta(s_memtime) / delta(s_memrealtime) x 100 MHz
+  std::vector<double> us;                          // the tile loop's duration per workgroup (realtime ticks at 100 MHz; 0: no stamp)
+  uint32_t stamped = 0;
+  double sum_us = 0.0, max_us = 0.0;               // over the workgroups that stamped
+};
+template <typename Launch, typename BeforeTimed>
+nvdb_status clock_bursts(nvdb_hip_ctx* c, uint32_t nwg, size_t prog_bytes, float seconds, Launch launch, BeforeTimed before_timed, ClockStats& out) {
+  hipEvent_t e0, e1;
+  HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
+  // a workgroup without tiles (a corpus of fewer tiles than row streams) leaves no stamp: its pair reads 0, not what the buffer held
+  HIPCHK(c, hipMemsetAsync(static_cast<char*>(c->prog.p) + prog_bytes, 0, static_cast<size_t>(nwg) * 16, c->stream));
+  const auto t_start = std::chrono::steady_clock::now();
+  for (;;) {
+    const bool last = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_start).count() >= seconds;
+    if (last) { if (nvdb_status st = before_timed()) return st; HIPCHK(c, hipEventRecord(e0, c->stream)); }
+    for (uint32_t r = 0; r < CLOCK_BURST; ++r) {
+      HIPCHK(c, hipMemsetAsync(c->prog.p, 0xFF, prog_bytes, c->stream));
+      if (nvdb_status st = launch()) return st;
+    }
+    if (last) break;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  HIPCHK(c, hipEventRecord(e1, c->stream));
+  HIPCHK(c, hipEventSynchronize(e1));
+  HIPCHK(c, hipEventElapsedTime(&out.ms, e0, e1));
+  out.ms /= static_cast<float>(CLOCK_BURST);
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  std::vector<uint64_t> stamps(static_cast<size_t>(nwg) * 2);
+  HIPCHK(c, hipMemcpy(stamps.data(), static_cast<const char*>(c->prog.p) + prog_bytes, stamps.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<float> ghz;
+  out.us.assign(nwg, 0.0);
+  for (uint32_t w = 0; w < nwg; ++w) {
+    if (!stamps[2 * w + 1]) continue;
+    ghz.push_back(static_cast<float>(static_cast<double>(stamps[2 * w]) / static_cast<double>(stamps[2 * w + 1]) * 0.1));
+    out.us[w] = static_cast<double>(stamps[2 * w + 1]) * 0.01;
+    out.sum_us += out.us[w]; out.max_us = std::max(out.max_us, out.us[w]); ++out.stamped;
+  }
+  std::sort(ghz.begin(), ghz.end());
+  if (!ghz.empty()) { out.ghz[0] = ghz[ghz.size() / 2]; out.ghz[1] = ghz.front(); out.ghz[2] = ghz.back(); }
+  return NVDB_OK;
+}
 }  // namespace
 
 extern "C" {
 
-// Developer aid (not part of the drop-in surface): time ablation builds of the filter kernel on the
-// resident fp16 d=768 corpus with the query workspace left by the previous path-2 search.  Thresholds
-// are +inf (no survivors), so only the streaming/MFMA machinery is timed.
-nvdb_status nvdb_hip_debug_filter_variant(nvdb_hip_ctx* c, int variant, uint32_t nq, uint32_t reps, float* ms_per_launch) {
-  if (!c || !ms_per_launch) return NVDB_ERR_INVALID;
-  if (!c->rows || c->dtype != NVDB_DTYPE_F16 || c->dim != 768 || !c->q16.p) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: run a path-2 search on an fp16 d=768 corpus first");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (nq <= 128) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: variants are built for nq > 128 (NB = 2)");
-  const uint32_t QT = (nq + 255) / 256, nq_pad = QT * 256;
-  DevBuf inf;
-  nvdb_status st = ensure(c, inf, nq_pad * 4);
-  if (st) return st;
-  fill_u32_kernel<<<(nq_pad + 255) / 256, 256, 0, c->stream>>>(static_cast<uint32_t*>(inf.p), 0x7F800000u, nq_pad);
-  const uint32_t n_al = static_cast<uint32_t>(c->n / FILTER_ROWS * FILTER_ROWS);
-  const uint32_t nwg = filter_grid(c, QT);
-  const FilterCall f{c->stream, 0, n_al, nq, QT, c->last_cap, static_cast<const float*>(inf.p)};
-  hipEvent_t e0, e1;
-  HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-  auto run = [&](auto kern) -> nvdb_status {       // one untimed launch, then `reps` timed ones (tiles in identity order)
-    for (uint32_t r = 0; r <= reps; ++r) {
-      if (r == 1) HIPCHK(c, hipEventRecord(e0, c->stream));
-      if ((st = launch_filter_f16_kernel(c, f, kern, nwg, FilterGeom{256, filter_f16_lds_bytes<768>(), 4, false}, &c->hitlog, 0, 0u))) return st;
-    }
-    return NVDB_OK;
-  };
-  switch (variant) {
-    case 0: st = run(filter_f16_kernel<768, 2, 0, 4>); break;
-    case 1: st = run(filter_f16_kernel<768, 2, 1, 4>); break;
-    case 2: st = run(filter_f16_kernel<768, 2, 2, 4>); break;
-    case 3: st = run(filter_f16_kernel<768, 2, 3, 4>); break;
-    case 5: st = run(filter_f16_kernel<768, 2, 5, 4>); break;
-    case 6: st = run(filter_f16_kernel<768, 2, 0, 6>); break;
-    case 10: st = run(filter_f16_kernel<768, 2, 6, 6>); break;
-    case 7: st = run(filter_f16_kernel<768, 2, 0, 8>); break;
-    case 8: st = run(filter_f16_kernel<768, 2, 0, 3>); break;
-    case 9: st = run(filter_f16_kernel<768, 2, 0, 12>); break;
-    default: return fail(c, NVDB_ERR_INVALID, "debug: unknown variant");
-  }
-  if (st) return st;
-  HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-  *ms_per_launch = ms / static_cast<float>(reps ? reps : 1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(inf.p);
-  return NVDB_OK;
-}
-
 nvdb_status nvdb_hip_debug_clock(nvdb_hip_ctx* c, int variant, uint32_t nq, float seconds, float* out4) {
   if (!c || !out4) return NVDB_ERR_INVALID;
+  if (variant != 0 && variant != 20) return fail(c, NVDB_ERR_INVALID, "debug: unknown variant");
   if (!c->rows || c->dtype != NVDB_DTYPE_F16 || c->dim != 768 || !c->q16.p) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: run a path-2 search on an fp16 d=768 corpus first");
   if (nq <= 128 || nq > (c->last_nq + 255u) / 256u * 256u) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: 128 < nq <= the last search's padded batch");
   HIPCHK(c, hipSetDevice(c->device));
   const uint32_t QT = (nq + 255) / 256, nq_pad = QT * 256;
   const uint32_t nwg = filter_grid(c, QT);
   if (!xcd_aware_grid(QT, nwg)) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: batch does not map onto the XCD-aware grid");
-  DevBuf inf;
+  DevBuf inf;                                      // thresholds +inf: no survivors, the streaming / MFMA machinery alone
   nvdb_status st = ensure(c, inf, nq_pad * 4);
   if (st) return st;
   fill_u32_kernel<<<(nq_pad + 255) / 256, 256, 0, c->stream>>>(static_cast<uint32_t*>(inf.p), 0x7F800000u, nq_pad);
@@ -79,72 +78,43 @@ nvdb_status nvdb_hip_debug_clock(nvdb_hip_ctx* c, int variant, uint32_t nq, floa
   if ((st = ensure(c, c->prog, prog_bytes + stamp_bytes))) return st;
   const uint32_t n_al = static_cast<uint32_t>(c->n / FILTER_ROWS * FILTER_ROWS);
   const FilterCall f{c->stream, 0, n_al, nq, QT, c->last_cap, static_cast<const float*>(inf.p)};
-  hipEvent_t e0, e1;
-  HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-  const auto t_start = std::chrono::steady_clock::now();
-  float ms = 0.f;
-  const uint32_t burst = 8;
-  auto burst_of = [&](auto kern, uint32_t waves) -> nvdb_status {      // stamped builds on `waves` waves per workgroup (tiles in identity order)
-    for (uint32_t r = 0; r < burst; ++r) {
-      HIPCHK(c, hipMemsetAsync(c->prog.p, 0xFF, prog_bytes, c->stream));
-      if ((st = launch_filter_f16_kernel(c, f, kern, nwg, FilterGeom{64 * waves, filter_f16_m16_lds_bytes<768>(), waves, false}, &c->hitlog, 0,
-                                         static_cast<uint32_t*>(c->prog.p), static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead)))) return st;
-    }
-    return NVDB_OK;
-  };
-  for (;;) {                                       // back-to-back launches until `seconds` have passed, the last 8 timed
-    const bool last = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_start).count() >= seconds;
-    if (last) HIPCHK(c, hipEventRecord(e0, c->stream));
-    switch (variant) {
-      case 0: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 0>, 4); break;
-      case 1: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 1>, 4); break;
-      case 5: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 5>, 4); break;
-      case 15: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 15>, 4); break;
-      case 16: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 16>, 4); break;
-      case 17: st = burst_of(filter_f16_m16_kernel<768, 6, true, true, 17>, 4); break;
-      case 20: st = burst_of(filter_f16_m16_kernel<768, 4, true, true, 0, 2, 2, 8>, 8); break;   // the 8-wave production build (two waves per SIMD, 32 queries each), stamped
-      default: return fail(c, NVDB_ERR_INVALID, "debug: unknown variant");
-    }
-    if (st) return st;
-    if (last) {
-      HIPCHK(c, hipEventRecord(e1, c->stream));
-      HIPCHK(c, hipEventSynchronize(e1));
-      HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-      ms /= static_cast<float>(burst);
-      break;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  std::vector<uint64_t> stamps(static_cast<size_t>(nwg) * 2);
-  HIPCHK(c, hipMemcpy(stamps.data(), static_cast<const char*>(c->prog.p) + prog_bytes, stamp_bytes, hipMemcpyDeviceToHost));
-  std::vector<float> ghz;
-  for (uint32_t w = 0; w < nwg; ++w)
-    if (stamps[2 * w + 1]) ghz.push_back(static_cast<float>(static_cast<double>(stamps[2 * w]) / static_cast<double>(stamps[2 * w + 1]) * 0.1));   // realtime ticks at 100 MHz
-  std::sort(ghz.begin(), ghz.end());
-  out4[0] = ms;
-  out4[1] = ghz.empty() ? 0.f : ghz[ghz.size() / 2];
-  out4[2] = ghz.empty() ? 0.f : ghz.front();
-  out4[3] = ghz.empty() ? 0.f : ghz.back();
-  // how long the workgroups' tile loops ran (100 MHz ticks -> us): mean and max -- the launch ends with the slowest
-  double sum_us = 0.0, max_us = 0.0;
-  for (uint32_t w = 0; w < nwg; ++w) { const double us = static_cast<double>(stamps[2 * w + 1]) * 0.01; sum_us += us; max_us = std::max(max_us, us); }
-  out4[4] = static_cast<float>(sum_us / nwg);
-  out4[5] = static_cast<float>(max_us);
+  // 0: the 4-wave build; 20: the 8-wave production build (two waves per SIMD, 32 queries each); tiles in identity order
+  const auto kern = variant == 0 ? filter_f16_m16_kernel<768, 6, true, true> : filter_f16_m16_kernel<768, 4, true, true, 2, 2, 8>;
+  const uint32_t waves = variant == 0 ? 4 : 8;
+  ClockStats cs;
+  st = clock_bursts(c, nwg, prog_bytes, seconds, [&] {
+    return launch_filter_f16_kernel(c, f, kern, nwg, FilterGeom{64 * waves, filter_f16_m16_lds_bytes<768>(), waves, false}, &c->hitlog, 0,
+                                    static_cast<uint32_t*>(c->prog.p), static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead));
+  }, [] { return NVDB_OK; }, cs);
+  (void)hipFree(inf.p);
+  if (st) return st;
+  out4[0] = cs.ms; out4[1] = cs.ghz[0]; out4[2] = cs.ghz[1]; out4[3] = cs.ghz[2];
+  // how long the workgroups' tile loops ran: mean and max -- the launch ends with the slowest
+  out4[4] = static_cast<float>(cs.sum_us / nwg);
+  out4[5] = static_cast<float>(cs.max_us);
   // per XCD label (blockIdx % 8): mean duration, and the spread inside the label (max - min)
   for (uint32_t x = 0; x < 8; ++x) {
     double sx = 0.0, mn = 1e30, mxv = 0.0; uint32_t cnt = 0;
-    for (uint32_t w = x; w < nwg; w += 8) { const double us = static_cast<double>(stamps[2 * w + 1]) * 0.01; sx += us; mn = std::min(mn, us); mxv = std::max(mxv, us); ++cnt; }
+    for (uint32_t w = x; w < nwg; w += 8) { sx += cs.us[w]; mn = std::min(mn, cs.us[w]); mxv = std::max(mxv, cs.us[w]); ++cnt; }
     out4[6 + 2 * x] = cnt ? static_cast<float>(sx / cnt) : 0.f;
     out4[7 + 2 * x] = cnt ? static_cast<float>(mxv - mn) : 0.f;
   }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(inf.p);
   return NVDB_OK;
 }
 
-
 nvdb_status nvdb_hip_debug_clock_i8(nvdb_hip_ctx* c, int variant, uint32_t nq, float seconds, float* out4) {
   if (!c || !out4) return NVDB_ERR_INVALID;
+  // the stamped builds (the log sized for 8 waves per workgroup, as the product's launches)
+  using Kern = decltype(&filter_i8w_kernel<768, 2, 6, true, 2, true>);
+  Kern kern; uint32_t waves = 4; size_t lds;
+  switch (variant) {
+    case 0: kern = filter_i8w_kernel<768, 2, 6, true, 2, true>; lds = filter_i8w_lds_bytes<768, 2>(); break;
+    case 10: kern = filter_i8p_kernel<768, true, true, 6, 4, true>; lds = filter_i8p_lds_bytes<768, 4, true>(); break;    // the software-pipelined build with the in-loop second stage
+    case 20: kern = filter_i8p_kernel<768, true, true, 6, 4, false>; lds = filter_i8p_lds_bytes<768, 4, false>(); break;  // ... first-stage survivors logged, finished after the stream
+    case 30: kern = filter_i8s_kernel<768, true, true, 6, 4>; lds = filter_i8s_lds_bytes<768, 4>(); break;                // the 16x16x64 build (kernels_filter_i8s.h)
+    case 35: kern = filter_i8s_kernel<768, true, true, 6, 8>; lds = filter_i8s_lds_bytes<768, 8>(); waves = 8; break;     // ... on 8 waves
+    default: return fail(c, NVDB_ERR_INVALID, "debug: unknown variant");
+  }
   if (!c->rows || c->dtype != NVDB_DTYPE_I8 || c->dim != 768 || !c->q16.p || !c->opt_i8_wide) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: run a path-2 search on an int8 d=768 corpus first");
   if (nq <= 128 || nq > (c->last_nq + 255u) / 256u * 256u) return fail(c, NVDB_ERR_UNSUPPORTED, "debug: 128 < nq <= the last search's padded batch");
   HIPCHK(c, hipSetDevice(c->device));
@@ -159,80 +129,19 @@ nvdb_status nvdb_hip_debug_clock_i8(nvdb_hip_ctx* c, int variant, uint32_t nq, f
   const uint32_t n_al = static_cast<uint32_t>(n_dbg / I8W_TILE_ROWS * I8W_TILE_ROWS);
   const FilterCall f{c->stream, 0, n_al, nq, QT, c->last_cap, static_cast<const float*>(c->thr.p)};
   const SyncArgs sy{static_cast<uint32_t*>(c->prog.p), static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead)};
-  hipEvent_t e0, e1;
-  HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-  const auto t_start = std::chrono::steady_clock::now();
-  float ms = 0.f;
-  const uint32_t burst = 8;
-  auto burst_of = [&](auto kern, uint32_t waves, size_t lds) -> nvdb_status {      // stamped builds (the log sized for 8 waves per workgroup, as the product's launches)
-    for (uint32_t r = 0; r < burst; ++r) {
-      HIPCHK(c, hipMemsetAsync(c->prog.p, 0xFF, prog_bytes, c->stream));
-      if ((st = launch_filter_i8w_kernel(c, f, kern, nwg, FilterGeom{64 * waves, lds, 8, false}, static_cast<size_t>(nq_pad) * 768, I8W_TILE_ROWS, sy))) return st;
-    }
-    return NVDB_OK;
-  };
-  for (;;) {
-    const bool last = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_start).count() >= seconds;
-    if (last) { HIPCHK(c, hipMemsetAsync(static_cast<uint32_t*>(c->misc.p) + 4, 0, 8, c->stream)); HIPCHK(c, hipEventRecord(e0, c->stream)); }
-    switch (variant) {
-      case 0: st = burst_of(filter_i8w_kernel<768, 2, 6, true, 2, true, 0>, 4, filter_i8w_lds_bytes<768, 2>()); break;
-      case 1: st = burst_of(filter_i8w_kernel<768, 2, 6, true, 2, true, 1>, 4, filter_i8w_lds_bytes<768, 2>()); break;
-      case 2: st = burst_of(filter_i8w_kernel<768, 2, 6, true, 2, true, 2>, 4, filter_i8w_lds_bytes<768, 2>()); break;
-      case 3: st = burst_of(filter_i8w_kernel<768, 2, 6, true, 2, true, 3>, 4, filter_i8w_lds_bytes<768, 2>()); break;
-      case 10: st = burst_of(filter_i8p_kernel<768, true, true, 6, 0, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // the software-pipelined production build, stamped
-      case 11: st = burst_of(filter_i8p_kernel<768, true, true, 6, 1, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // ... its structure alone: no test, no rare path
-      case 12: st = burst_of(filter_i8p_kernel<768, true, true, 6, 2, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // ... test in the MFMA shadow, rare path never taken
-      case 13: st = burst_of(filter_i8p_kernel<768, true, true, 6, 3, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // ... rare path, deferred values never consumed
-      case 14: st = burst_of(filter_i8p_kernel<768, true, true, 6, 4, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // ... rare path entered and left at once
-      case 15: st = burst_of(filter_i8p_kernel<768, true, true, 6, 5, 4, true>, 4, filter_i8p_lds_bytes<768, 4, true>()); break;   // ... production loop, cycles inside rare_path / consume_slots (wave 0 of every workgroup)
-      case 30: st = burst_of(filter_i8s_kernel<768, true, true, 6, 0, 4>, 4, filter_i8s_lds_bytes<768, 4>()); break;   // the 16x16x64 build (kernels_filter_i8s.h), stamped
-      case 31: st = burst_of(filter_i8s_kernel<768, true, true, 6, 1, 4>, 4, filter_i8s_lds_bytes<768, 4>()); break;   // ... its structure alone: no test, nothing logged
-      case 32: st = burst_of(filter_i8s_kernel<768, true, true, 6, 2, 4>, 4, filter_i8s_lds_bytes<768, 4>()); break;   // ... test, nothing logged
-      case 33: st = burst_of(filter_i8s_kernel<768, true, true, 6, 3, 4>, 4, filter_i8s_lds_bytes<768, 4>()); break;   // ... structure alone without the in-loop LDS-DMA issue
-      case 34: st = burst_of(filter_i8s_kernel<768, true, true, 6, 4, 4>, 4, filter_i8s_lds_bytes<768, 4>()); break;   // ... structure alone without the A-fragment LDS reads
-      case 35: st = burst_of(filter_i8s_kernel<768, true, true, 6, 0, 8>, 8, filter_i8s_lds_bytes<768, 8>()); break;   // the 8-wave 16x16x64 build, stamped
-      case 36: st = burst_of(filter_i8s_kernel<768, true, true, 6, 1, 8>, 8, filter_i8s_lds_bytes<768, 8>()); break;   // ... its structure alone
-      case 20: st = burst_of(filter_i8p_kernel<768, true, true, 6, 0, 4, false>, 4, filter_i8p_lds_bytes<768, 4, false>()); break;   // the default build (first-stage survivors logged, finished after the stream), stamped
-      case 22: st = burst_of(filter_i8p_kernel<768, true, true, 6, 2, 4, false>, 4, filter_i8p_lds_bytes<768, 4, false>()); break;   // ... test, nothing logged
-      case 24: st = burst_of(filter_i8p_kernel<768, true, true, 6, 4, 4, false>, 4, filter_i8p_lds_bytes<768, 4, false>()); break;   // ... logging entered and left at once
-      default: return fail(c, NVDB_ERR_INVALID, "debug: unknown variant");
-    }
-    if (st) return st;
-    if (last) {
-      HIPCHK(c, hipEventRecord(e1, c->stream));
-      HIPCHK(c, hipEventSynchronize(e1));
-      HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-      ms /= static_cast<float>(burst);
-      break;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  std::vector<uint64_t> stamps(static_cast<size_t>(nwg) * 2);
-  HIPCHK(c, hipMemcpy(stamps.data(), static_cast<const char*>(c->prog.p) + prog_bytes, stamp_bytes, hipMemcpyDeviceToHost));
-  std::vector<float> ghz;
-  double rare_cyc = 0.0, cons_cyc = 0.0;
-  for (uint32_t w = 0; w < nwg; ++w) {
-    if (!stamps[2 * w + 1]) continue;
-    if (variant == 15) { rare_cyc += static_cast<double>(stamps[2 * w] >> 32); cons_cyc += static_cast<double>(stamps[2 * w] & 0xFFFFFFFFull); }
-    else ghz.push_back(static_cast<float>(static_cast<double>(stamps[2 * w]) / static_cast<double>(stamps[2 * w + 1]) * 0.1));
-  }
-  if (variant == 15) { ghz.assign(3, static_cast<float>(rare_cyc / nwg)); ghz[2] = static_cast<float>(cons_cyc / nwg); }   // out[2] / out[3]: mean cycles of a workgroup's wave 0 inside rare_path / consume_slots
-  else std::sort(ghz.begin(), ghz.end());
-  out4[0] = ms;
-  out4[1] = ghz.empty() ? 0.f : ghz[ghz.size() / 2];
-  out4[2] = ghz.empty() ? 0.f : ghz.front();
-  out4[3] = ghz.empty() ? 0.f : ghz.back();
-  uint32_t counts[2] = {0, 0};                      // rare-path entries / lo-plane MFMA blocks of the timed burst
-  HIPCHK(c, hipMemcpy(counts, static_cast<uint32_t*>(c->misc.p) + 4, 8, hipMemcpyDeviceToHost));
-  out4[4] = static_cast<float>(counts[0]) / burst;
-  out4[5] = static_cast<float>(counts[1]) / burst;
-  double sum_us = 0.0, max_us = 0.0;                // the tile loop alone, per workgroup (100 MHz ticks)
-  uint32_t nstamped = 0;
-  for (uint32_t w = 0; w < nwg; ++w)
-    if (stamps[2 * w + 1]) { const double us = static_cast<double>(stamps[2 * w + 1]) * 0.01; sum_us += us; max_us = std::max(max_us, us); ++nstamped; }
-  out4[6] = nstamped ? static_cast<float>(sum_us / nstamped) : 0.f;
-  out4[7] = static_cast<float>(max_us);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  uint32_t* counts_dev = static_cast<uint32_t*>(c->misc.p) + 4;   // rare-path entries / lo-plane MFMA blocks: of the timed burst only
+  ClockStats cs;
+  st = clock_bursts(c, nwg, prog_bytes, seconds, [&] {
+    return launch_filter_i8w_kernel(c, f, kern, nwg, FilterGeom{64 * waves, lds, 8, false}, static_cast<size_t>(nq_pad) * 768, I8W_TILE_ROWS, sy);
+  }, [&]() -> nvdb_status { HIPCHK(c, hipMemsetAsync(counts_dev, 0, 8, c->stream)); return NVDB_OK; }, cs);
+  if (st) return st;
+  out4[0] = cs.ms; out4[1] = cs.ghz[0]; out4[2] = cs.ghz[1]; out4[3] = cs.ghz[2];
+  uint32_t counts[2] = {0, 0};
+  HIPCHK(c, hipMemcpy(counts, counts_dev, 8, hipMemcpyDeviceToHost));
+  out4[4] = static_cast<float>(counts[0]) / CLOCK_BURST;
+  out4[5] = static_cast<float>(counts[1]) / CLOCK_BURST;
+  out4[6] = cs.stamped ? static_cast<float>(cs.sum_us / cs.stamped) : 0.f;   // the tile loop alone, per workgroup that stamped
+  out4[7] = static_cast<float>(cs.max_us);
   return NVDB_OK;
 }
 

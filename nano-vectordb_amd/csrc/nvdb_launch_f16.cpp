@@ -41,9 +41,9 @@ nvdb_status launch_filter_dim(nvdb_hip_ctx* c, const FilterCall& f) {
   if ((st = sibling_sync_args(c, f.s, f.QT, nwg, sy))) return st;
   if constexpr (DIM <= 768)
     if (sy.prog && c->opt_waves8)
-      return launch_filter_f16_kernel(c, f, filter_f16_m16_kernel<DIM, 4, true, false, 0, MBK, 2, 8>, nwg, FilterGeom{512, lds, 8, true}, &c->hitlog, TROWS,
+      return launch_filter_f16_kernel(c, f, filter_f16_m16_kernel<DIM, 4, true, false, MBK, 2, 8>, nwg, FilterGeom{512, lds, 8, true}, &c->hitlog, TROWS,
                                       sy.prog, sy.mask, sy.lead);
-  return launch_filter_f16_kernel(c, f, sy.prog ? filter_f16_m16_kernel<DIM, 6, true, false, 0, MBK> : filter_f16_m16_kernel<DIM, 6, false, false, 0, MBK>, nwg,
+  return launch_filter_f16_kernel(c, f, sy.prog ? filter_f16_m16_kernel<DIM, 6, true, false, MBK> : filter_f16_m16_kernel<DIM, 6, false, false, MBK>, nwg,
                                   FilterGeom{256, lds, 4, true}, &c->hitlog, TROWS, sy.prog, sy.mask, sy.lead);
 }
 
@@ -72,9 +72,9 @@ nvdb_status launch_filter_k_dim(nvdb_hip_ctx* c, const FilterCall& f) {
   if ((st = sibling_sync_args(c, f.s, f.QT, nwg, sy))) return st;
   if constexpr (DIM % 256 == 0)
     if (sy.prog && c->opt_waves8)
-      return launch_filter_f16_kernel(c, f, filter_f16_m16_kernel<DIM, 4, true, false, 0, 1, 1, 8>, nwg, FilterGeom{512, lds, 8, true}, &c->hitlog, 16, sy.prog,
+      return launch_filter_f16_kernel(c, f, filter_f16_m16_kernel<DIM, 4, true, false, 1, 1, 8>, nwg, FilterGeom{512, lds, 8, true}, &c->hitlog, 16, sy.prog,
                                       sy.mask, sy.lead);
-  return launch_filter_f16_kernel(c, f, sy.prog ? filter_f16_m16_kernel<DIM, 6, true, false, 0, 1, 2> : filter_f16_m16_kernel<DIM, 6, false, false, 0, 1, 2>, nwg,
+  return launch_filter_f16_kernel(c, f, sy.prog ? filter_f16_m16_kernel<DIM, 6, true, false, 1, 2> : filter_f16_m16_kernel<DIM, 6, false, false, 1, 2>, nwg,
                                   FilterGeom{256, lds, 4, true}, &c->hitlog, 16, sy.prog, sy.mask, sy.lead);
 }
 
@@ -82,7 +82,7 @@ nvdb_status launch_filter_k_dim(nvdb_hip_ctx* c, const FilterCall& f) {
 // -> cand[q][tile]; the caller then runs select(mode 2) to turn the k-th largest tile maximum into thr[q].
 template <int DIM, int NB>
 nvdb_status launch_boot_dim(nvdb_hip_ctx* c, const FilterCall& f) {
-  return launch_filter_f16_kernel(c, f, filter_f16_kernel<DIM, NB, 7>, filter_grid(c, f.QT), FilterGeom{256, filter_f16_lds_bytes<DIM>(), 0, false}, &c->cand,
+  return launch_filter_f16_kernel(c, f, filter_f16_kernel<DIM, NB, true>, filter_grid(c, f.QT), FilterGeom{256, filter_f16_lds_bytes<DIM>(), 0, false}, &c->cand,
                                   FILTER_ROWS, f.cap);
 }
 

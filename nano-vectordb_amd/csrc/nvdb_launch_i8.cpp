@@ -31,8 +31,8 @@ nvdb_status launch_filter_i8_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t 
 
 // the builds of the two-stage kernel; SYNC is the last choice made (both instantiations of a build have one type)
 template <int DIM, int NB, int MB> auto i8w_build(bool sync) { return sync ? filter_i8w_kernel<DIM, NB, 6, true, MB> : filter_i8w_kernel<DIM, NB, 6, false, MB>; }
-template <int DIM, int WPB, bool DEFER> auto i8p_build(bool sync) { return sync ? filter_i8p_kernel<DIM, true, false, 6, 0, WPB, DEFER> : filter_i8p_kernel<DIM, false, false, 6, 0, WPB, DEFER>; }
-template <int DIM, int WPB> auto i8s_build(bool sync) { return sync ? filter_i8s_kernel<DIM, true, false, 6, 0, WPB> : filter_i8s_kernel<DIM, false, false, 6, 0, WPB>; }
+template <int DIM, int WPB, bool DEFER> auto i8p_build(bool sync) { return sync ? filter_i8p_kernel<DIM, true, false, 6, WPB, DEFER> : filter_i8p_kernel<DIM, false, false, 6, WPB, DEFER>; }
+template <int DIM, int WPB> auto i8s_build(bool sync) { return sync ? filter_i8s_kernel<DIM, true, false, 6, WPB> : filter_i8s_kernel<DIM, false, false, 6, WPB>; }
 
 // int8, dims up to 768, 64-row tiles: which build streams which batch.  The product library holds
 //   batches <= 128 (NB = 1)  filter_i8w_kernel at 32 queries per wave; d = 512 / 768 and more than 8 queries (d = 384: more than 64): the
@@ -72,10 +72,10 @@ nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t
   // One query tile has no siblings: the SYNC = false instantiation alone.
   if constexpr (NB == 1 && (DIM == 768 || DIM == 512))
     if (c->opt_i8_small8 && !defer && f.QT == 1 && f.nq > 8)       // (a handful of queries: equal within noise, the old kernel stays)
-      return launch(filter_i8s_kernel<DIM, false, false, 6, 0, 8>, 8, filter_i8s_lds_bytes<DIM, 8>());
+      return launch(filter_i8s_kernel<DIM, false, false, 6, 8>, 8, filter_i8s_lds_bytes<DIM, 8>());
   if constexpr (NB == 1 && DIM == 384)               // d = 384 has no 8-wave schedule: 64 < batch <= 128 on the 4-wave build, two waves without queries (+4 % at 128; equal at 64)
     if (c->opt_i8_small8 && !defer && f.QT == 1 && f.nq > 64)
-      return launch(filter_i8s_kernel<DIM, false, false, 6, 0, 4>, 4, filter_i8s_lds_bytes<DIM, 4>());
+      return launch(filter_i8s_kernel<DIM, false, false, 6, 4>, 4, filter_i8s_lds_bytes<DIM, 4>());
   if (logs && c->opt_i8_mfma16) {
     // d = 768: on 8 waves of 32 queries, two per SIMD (option i8_dense8).  A flagged block runs rare_log, serial work during which a lone wave's
     // MFMA pipe idles; with two waves per SIMD the partner's MFMAs fill it.  Per launch of the N = 10M ladder the 8-wave build wins 10 / 10 / 5 %

@@ -43,7 +43,7 @@ EXPORTS = [
     "nvdb_hip_compact_rows", "nvdb_hip_ivf_compact",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
-DEV_EXPORTS = ["nvdb_hip_debug_filter_variant", "nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
+DEV_EXPORTS = ["nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
                "nvdb_hip_debug_plan"]
 
 
@@ -219,7 +219,6 @@ def _bind(L, dev):
     for name in EXPORTS:
         getattr(L, name)
     if dev:
-        L.nvdb_hip_debug_filter_variant.argtypes = [vp, C.c_int, u32, u32, f32p]
         L.nvdb_hip_debug_clock.argtypes = [vp, C.c_int, u32, C.c_float, f32p]
         L.nvdb_hip_debug_clock_i8.argtypes = [vp, C.c_int, u32, C.c_float, f32p]
         L.nvdb_permuted_tile.argtypes = [u32, u32]

@@ -34,7 +34,7 @@ def product_usage():
 
 @pytest.mark.parametrize("sync", ["true", "false"])
 def test_product_holds_the_eight_wave_build(product_usage, sync):
-    name = f"filter_i8s_kernel<768, {sync}, false, 6, 0, 8>"
+    name = f"filter_i8s_kernel<768, {sync}, false, 6, 8>"
     assert name in product_usage, sorted(k for k in product_usage if "filter_i8s" in k)
     u = product_usage[name]
     assert int(u["VGPRs"]) <= 128 and int(u["AGPRs"]) <= 128 and int(u["Occupancy"]) == 2, u
@@ -43,6 +43,6 @@ def test_product_holds_the_eight_wave_build(product_usage, sync):
 
 def test_product_still_holds_the_four_wave_build(product_usage):
     for sync in ("true", "false"):
-        assert f"filter_i8s_kernel<768, {sync}, false, 6, 0, 4>" in product_usage
+        assert f"filter_i8s_kernel<768, {sync}, false, 6, 4>" in product_usage
     # the developer-only stamped build stays out of the product
     assert not [k for k in product_usage if k.startswith("filter_i8s_kernel<768, true, true")]

@@ -68,27 +68,27 @@ def test_no_kernel_uses_scratch_or_spills(codegen):
 def test_register_budgets_of_the_production_kernels(codegen):
     by_name, _ = codegen
     # headline kernel: 8 waves per workgroup, two per SIMD -> 128 VGPRs + 128 AGPRs, no more
-    k = _find(by_name, "filter_f16_m16_kernelILi768ELi4ELb1ELb0ELi0ELi2ELi2ELi8E")
+    k = _find(by_name, "filter_f16_m16_kernelILi768ELi4ELb1ELb0ELi2ELi2ELi8E")
     assert k["vgpr"] <= 128 and k["agpr"] <= 128 and k["occ"] == 2, k
     # one-wave-per-SIMD builds: the whole 512-entry file, never beyond
     for key, v in by_name.items():
         if "filter_" in key or "filter_" in v["mangled"]:
             assert v["vgpr"] + v["agpr"] <= 512 and v["occ"] >= 1, (key, v)
-    k = _find(by_name, "filter_i8w_kernel<768, 2, 6, true, 2, false, 0>")
+    k = _find(by_name, "filter_i8w_kernel<768, 2, 6, true, 2, false>")
     assert k["agpr"] >= 192 and k["occ"] == 1, k                      # the hi plane of 64 queries stays resident in AGPRs
-    k = _find(by_name, "filter_i8p_kernel<768, true, false, 6, 0, 4, false>")
+    k = _find(by_name, "filter_i8p_kernel<768, true, false, 6, 4, false>")
     assert k["agpr"] >= 192 and k["occ"] == 1 and k["sspill"] == 0, k  # the pipelined build (default: first-stage survivors logged): same residency, no scratch (checked above)
-    k = _find(by_name, "filter_i8p_kernel<768, true, false, 6, 0, 4, true>")
+    k = _find(by_name, "filter_i8p_kernel<768, true, false, 6, 4, true>")
     assert k["agpr"] >= 192 and k["occ"] == 1, k                      # ... with the in-loop second stage (option i8_defer)
-    k = _find(by_name, "filter_i8p_kernel<768, true, false, 6, 0, 8, true>")
+    k = _find(by_name, "filter_i8p_kernel<768, true, false, 6, 8, true>")
     assert k["vgpr"] <= 128 and k["agpr"] <= 128 and k["agpr"] >= 96 and k["occ"] == 2, k   # its 8-wave variant (option i8_waves8): 32 queries per wave, two waves per SIMD
-    k = _find(by_name, "filter_i8s_kernel<768, true, false, 6, 0, 4>")
+    k = _find(by_name, "filter_i8s_kernel<768, true, false, 6, 4>")
     assert k["agpr"] >= 192 and k["occ"] == 1 and k["sspill"] == 0, k  # the product's int8 batch-1024 kernel (16x16x64 MFMA): hi plane of 64 queries in AGPRs
     # exact fp32-order scores on the fp32 matrix cores: 16 queries x 768 floats stationary (192 registers) + a tile of raw rows in flight
     for name in ("scan_exact_mfma_kernel<2, 768>", "scan_exact_mfma_kernel<1, 768>", "scan_exact_mfma_kernel<3, 768>", "scores_exact_mfma_kernel<2, 768>"):
         k = _find(by_name, name)
         assert k["vgpr"] + k["agpr"] <= 512 and k["occ"] == 1, (name, k)
-    k = _find(by_name, "filter_f16_kernelILi768ELi1ELi0ELi6E")
+    k = _find(by_name, "filter_f16_kernelILi768ELi1ELb0ELi6E")
     assert k["agpr"] >= 192, k
     # refine v3: two workgroups of three waves per CU -> at most 256 registers per lane
     k = _find(by_name, "refine_l2_rows_kernel<768>")
@@ -115,7 +115,7 @@ def test_rendezvous_registers_and_hand_placed_instructions(codegen):
     assert all(f'"s{r}"' in blk for r in range(88, 96)), "clobber list of the sibling rendezvous"
     # headline kernel: 192 MFMAs per tile and wave pair -> 96 in the 8-wave build's loop body, fed from AGPRs; the
     # compiler must not have copied fragments into VGPRs (v_accvgpr_read inside the loop)
-    k = _find(by_name, "filter_f16_m16_kernelILi768ELi4ELb1ELb0ELi0ELi2ELi2ELi8E")
+    k = _find(by_name, "filter_f16_m16_kernelILi768ELi4ELb1ELb0ELi2ELi2ELi8E")
     body = _body(asm, k["mangled"])
     assert body.count("v_mfma_f32_16x16x32_f16") >= 96
     assert body.count("global_load_lds_dwordx4") >= 6 and "s_nop 15" in body
@@ -126,7 +126,7 @@ def test_rendezvous_registers_and_hand_placed_instructions(codegen):
     k = _find(by_name, "scan_exact_mfma_kernel<2, 768>")
     body = _body(asm, k["mangled"])
     assert body.count("v_mfma_f32_16x16x4_f32") == 192 and body.count("s_waitcnt vmcnt(23)") >= 24, (body.count("v_mfma_f32_16x16x4_f32"), body.count("s_waitcnt vmcnt(23)"))
-    k = _find(by_name, "filter_i8s_kernel<768, true, false, 6, 0, 4>")
+    k = _find(by_name, "filter_i8s_kernel<768, true, false, 6, 4>")
     body = _body(asm, k["mangled"])
     assert body.count("v_mfma_i32_16x16x64_i8") == 192 and "v_mfma_i32_32x32x32_i8" not in body
     # refine v3: q - half as ONE v_fma_mix_f32 per element (hipcc folds the C++ form back into cvt + sub)

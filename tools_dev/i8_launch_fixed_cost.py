@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""What a launch of the int8 pipelined kernel costs beyond its tiles: stamped production build (variant 10) and its bare
-structure (11) over the first R rows of the corpus, R = 1 .. 256 tiles per row stream, at the thresholds the preceding
+"""What a launch of the int8 pipelined kernel costs beyond its tiles: the stamped default build (variant 20) and the build with
+the in-loop second stage (10) over the first R rows of the corpus, R = 1 .. 256 tiles per row stream, at the thresholds the preceding
 search ended with.  launch = event time per launch (includes a 3-us memset of the rendezvous words), loop = the tile loop
 alone inside the kernel (mean / longest workgroup).  Developer tool (libnvdb_hip_dev.so); run on the GPU box."""
 import ctypes as C, os, sys
@@ -17,7 +17,7 @@ ctx.set_option("path", 2); ctx.search_batch(q, 10)
 for tiles in (1, 2, 4, 8, 16, 32, 64, 128, 256):
     rows = 64 * 64 * tiles                               # 64 row streams x 64-row tiles
     ctx.set_option("debug_rows", rows)
-    for var in (10, 11):
+    for var in (20, 10):
         out = (C.c_float * 8)()
         rc = lib.nvdb_hip_debug_clock_i8(ctx.h, var, nq, 0.3, out)
         assert rc == 0, lib.nvdb_hip_last_error(ctx.h)
