@@ -50,7 +50,7 @@ typedef struct nvdb_hip_ctx nvdb_hip_ctx;
  * path fills h2d/kernel/d2h/total and leaves the rest zero.  dbg_*: the refine call's in-kernel
  * phase split (reference CUDA_DBG_TIMING, src/cuda_refine.cu:416-418, 495-500, 1116-1144), filled
  * when option "refine_dbg_q" > 0 and a timing struct is passed: the first dbg_q = min(option, Q)
- * queries run the stamped twin of the refine kernel, and dbg_*_cycles_avg are their average
+ * queries run the STAMP build of the refine kernel's template, and dbg_*_cycles_avg are their average
  * shader-clock cycles (s_memtime) per phase -- dist (gather + distances + top-K insertion), write
  * (list to LDS + barrier), merge (wave 0 merges the lists, stores the result).  dbg_*_pct are
  * FRACTIONS of the three averages' sum (0 when it is 0).  Otherwise all dbg_* are zero. */

@@ -40,17 +40,17 @@ __device__ __forceinline__ void wmin_insert(WaveTopKMin& t, uint32_t K, float d,
 __device__ __forceinline__ bool wmin_accepts(const WaveTopKMin& t, uint32_t K, float d, uint32_t id) {
   return t.cnt < K || closer(d, id, t.thr_d, t.thr_id);
 }
+__device__ __forceinline__ WaveTopKMin wmin_init() { return {1e30f, 0xFFFFFFFFu, 0u, 1e30f, 0xFFFFFFFFu}; }
 
-// ---- phase stamps of the refine twins (option refine_dbg_q; reference CUDA_DBG_TIMING, cuda_refine.cu:416-418, 442, 453, 495-500)
-// The stamped twin of each refine kernel runs the same body with STAMP = true: wave 0 of workgroup q < dbg_q reads the shader
-// clock at entry (t0), after its candidate loop (t1: dist), after the list write to LDS + the workgroup barrier (t2: write) and
-// after the merge and the output stores (t3: merge); lane 0 writes [t1-t0, t2-t1, t3-t2] to dbg_out[3q ..] with vector stores.
-// One asm statement reads the clock AND waits for it (s_memtime returns through lgkmcnt), fenced against the scheduler, so a
-// stamp closes exactly the code before it.  Stamps sit outside the candidate loops (and their hand-counted vmcnt waits).
-// Each body is written once, in kernels_refine_v{1,2,3}_body.h, and #included as the body of both __global__ kernels with a
-// constexpr STAMP.  A force-inlined __device__ body function would be the plainer form, but hipcc simplifies such a function
-// on its own before inlining it, and that changed the product kernels' ISA (v3's ballot lost a branch); textual inclusion
-// keeps the product kernels (STAMP = false) instruction for instruction what they were.
+// ---- phase stamps (option refine_dbg_q; reference CUDA_DBG_TIMING, cuda_refine.cu:416-418, 442, 453, 495-500)
+// Every refine kernel is one template with a trailing `bool STAMP = false`; the option launches the STAMP = true build of the same
+// template.  There wave 0 of workgroup q < dbg_q reads the shader clock at entry (t0), after its candidate loop (t1: dist), after
+// the list write to LDS + the workgroup barrier (t2: write) and after the merge and the output stores (t3: merge); lane 0 writes
+// [t1-t0, t2-t1, t3-t2] to dbg_out[3q ..] with vector stores.  One asm statement reads the clock AND waits for it (s_memtime
+// returns through lgkmcnt), fenced against the scheduler, so a stamp closes exactly the code before it.  Stamps sit outside the
+// candidate loops (and their hand-counted vmcnt waits).  The STAMP = false build ignores its last two arguments (nullptr, 0) and
+// holds no stamp: `if constexpr` drops them, and the two unread kernel arguments cost no instruction
+// (profiles/refine_one_template_codegen.txt, step 1).
 __device__ __forceinline__ uint64_t refine_stamp() {
   uint64_t t;
   __builtin_amdgcn_sched_barrier(0);
@@ -61,6 +61,49 @@ __device__ __forceinline__ uint64_t refine_stamp() {
 __device__ __forceinline__ void refine_stamp_store(uint64_t* __restrict__ dbg_out, uint32_t q, uint64_t t0, uint64_t t1, uint64_t t2, uint64_t t3) {
   uint64_t* o = dbg_out + 3ull * q;
   o[0] = t1 - t0; o[1] = t2 - t1; o[2] = t3 - t2;
+}
+
+// The end of every refine kernel: the waves' lists go to LDS, wave 0 merges them into its own and writes the K results
+// (padded with id 0xFFFFFFFF / dist 1e30); the STAMP build takes t1 .. t3 here and stores the three phases.  The list comes BY VALUE:
+// with a reference every kernel grew by 15-24 instructions behind its loop; by value the v1 / v3 builds keep their instruction
+// count (one pair of v_cndmask swaps places), v2 loses 3, and every candidate loop is the parent's
+// (profiles/refine_one_template_codegen.txt, step 2; timed in profiles/refine_one_template_ab.txt).
+// The ballot loop that offers a step's distances to the list stays written out in the three bodies: as a helper it sits inside
+// the candidate loop, took v3<768> from 215 to 216 VGPRs and moved its time outside the parent's own spread (same files).
+constexpr size_t refine_merge_bytes(int waves) { return waves * (64 * (sizeof(float) + sizeof(uint32_t)) + sizeof(uint32_t)); }   // the three arrays below
+template <int WAVES, bool STAMP>
+__device__ __forceinline__ void refine_finish(WaveTopKMin tk, uint32_t K, uint32_t q, int lane, int wave, uint32_t* __restrict__ out_ids,
+                                              float* __restrict__ out_dist, [[maybe_unused]] bool stamp, [[maybe_unused]] uint64_t t0,
+                                              [[maybe_unused]] uint64_t* __restrict__ dbg_out) {
+  __shared__ float lds_d[WAVES][64];
+  __shared__ uint32_t lds_id[WAVES][64];
+  __shared__ uint32_t lds_cnt[WAVES];
+  [[maybe_unused]] uint64_t t1 = 0, t2 = 0, t3 = 0;
+  if constexpr (STAMP) { if (stamp) t1 = refine_stamp(); }
+  lds_d[wave][lane] = tk.d; lds_id[wave][lane] = tk.id;
+  if (lane == 0) lds_cnt[wave] = tk.cnt;
+  __syncthreads();
+  if (wave != 0) return;
+  if constexpr (STAMP) { if (stamp) t2 = refine_stamp(); }
+  for (int w = 1; w < WAVES; ++w) {
+    const uint32_t c = lds_cnt[w];
+    for (uint32_t j = 0; j < c; ++j) {
+      const float cd = lds_d[w][j];
+      const uint32_t cid = lds_id[w][j];
+      if (wmin_accepts(tk, K, cd, cid)) wmin_insert(tk, K, cd, cid, lane);
+    }
+  }
+  if (static_cast<uint32_t>(lane) < K) {
+    const bool have = static_cast<uint32_t>(lane) < tk.cnt;
+    out_ids[static_cast<uint64_t>(q) * K + lane] = have ? tk.id : 0xFFFFFFFFu;
+    if (out_dist) out_dist[static_cast<uint64_t>(q) * K + lane] = have ? tk.d : 1e30f;
+  }
+  if constexpr (STAMP) {
+    if (stamp) {
+      t3 = refine_stamp();
+      if (lane == 0) refine_stamp_store(dbg_out, q, t0, t1, t2, t3);
+    }
+  }
 }
 
 // fp16 rows: cuda_refine.cu:326-382
@@ -105,21 +148,39 @@ __device__ __forceinline__ float l2_f32_ref_order(const float* __restrict__ x, c
   return acc;
 }
 
-// grid = Q, block = 256.  out_dist may be null.
-#define NVDB_REFINE_ARGS const void* __restrict__ rows, uint64_t n, uint32_t dim, const float* __restrict__ queries, \
-                         const uint32_t* __restrict__ cand, uint32_t R, uint32_t K, uint32_t* __restrict__ out_ids, float* __restrict__ out_dist
-template <int DT, bool ALIGNED>
-__global__ __launch_bounds__(256) void refine_l2_kernel(NVDB_REFINE_ARGS) {
-  constexpr bool STAMP = false;
-  [[maybe_unused]] uint64_t* const dbg_out = nullptr;
-  [[maybe_unused]] const uint32_t dbg_q = 0;
-#include "kernels_refine_v1_body.h"
-}
-// stamped twin (option refine_dbg_q)
-template <int DT, bool ALIGNED>
-__global__ __launch_bounds__(256) void refine_dbg_kernel(NVDB_REFINE_ARGS, uint64_t* __restrict__ dbg_out, uint32_t dbg_q) {
-  constexpr bool STAMP = true;
-#include "kernels_refine_v1_body.h"
+// grid = Q, block = 256.  out_dist may be null; dbg_out / dbg_q are read by the STAMP build only (the product build gets nullptr, 0).
+template <int DT, bool ALIGNED, bool STAMP = false>
+__global__ __launch_bounds__(256) void refine_l2_kernel(const void* __restrict__ rows, uint64_t n, uint32_t dim, const float* __restrict__ queries,
+                                                        const uint32_t* __restrict__ cand, uint32_t R, uint32_t K, uint32_t* __restrict__ out_ids,
+                                                        float* __restrict__ out_dist, uint64_t* __restrict__ dbg_out, uint32_t dbg_q) {
+  const uint32_t q = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  [[maybe_unused]] const bool stamp = STAMP && q < dbg_q && __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0;
+  [[maybe_unused]] uint64_t t0 = 0;
+  if constexpr (STAMP) { if (stamp) t0 = refine_stamp(); }
+  const float* __restrict__ qv = queries + static_cast<uint64_t>(q) * dim;
+  const uint32_t* __restrict__ cq = cand + static_cast<uint64_t>(q) * R;
+
+  WaveTopKMin tk = wmin_init();
+
+  for (uint32_t r0 = wave * 64u; r0 < R; r0 += 256u) {
+    const uint32_t r = r0 + lane;
+    const uint32_t id = (r < R) ? cq[r] : 0xFFFFFFFFu;
+    const bool valid = (id != 0xFFFFFFFFu) && (static_cast<uint64_t>(id) < n);     // cuda_refine.cu:437
+    const uint32_t rid = valid ? id : 0u;
+    float d;
+    if constexpr (DT == DT_F16) d = l2_f16_ref_order<ALIGNED>(static_cast<const unsigned short*>(rows) + static_cast<uint64_t>(rid) * dim, qv, dim);
+    else d = l2_f32_ref_order<ALIGNED>(static_cast<const float*>(rows) + static_cast<uint64_t>(rid) * dim, qv, dim);
+    unsigned long long m = __ballot(valid && wmin_accepts(tk, K, d, id));
+    while (m) {
+      const int L = __builtin_ctzll(m);
+      m &= m - 1;
+      const float cd = readlane_f(d, L);
+      const uint32_t cid = readlane_u(id, L);
+      if (wmin_accepts(tk, K, cd, cid)) wmin_insert(tk, K, cd, cid, lane);
+    }
+  }
+  refine_finish<4, STAMP>(tk, K, q, lane, wave, out_ids, out_dist, stamp, t0, dbg_out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -136,24 +197,94 @@ __global__ __launch_bounds__(256) void refine_dbg_kernel(NVDB_REFINE_ARGS, uint6
 // accumulation order exactly where the previous chunk stopped -- results are bit-identical to v1.
 // LDS: 4 waves x 2 buffers x 16 KB = 128 KB, one workgroup per CU, 64 KB of gathers in flight per CU.
 // ------------------------------------------------------------------------------------------------
-template <int DT>
-__global__ __launch_bounds__(256, 1) void refine_l2_lds_kernel(NVDB_REFINE_ARGS) {
-  constexpr bool STAMP = false;
-  [[maybe_unused]] uint64_t* const dbg_out = nullptr;
-  [[maybe_unused]] const uint32_t dbg_q = 0;
-#include "kernels_refine_v2_body.h"
-}
-// stamped twin (option refine_dbg_q)
-template <int DT>
-__global__ __launch_bounds__(256, 1) void refine_dbg_lds_kernel(NVDB_REFINE_ARGS, uint64_t* __restrict__ dbg_out, uint32_t dbg_q) {
-  constexpr bool STAMP = true;
-#include "kernels_refine_v2_body.h"
-}
-#undef NVDB_REFINE_ARGS
+template <int DT, bool STAMP = false>
+__global__ __launch_bounds__(256, 1) void refine_l2_lds_kernel(const void* __restrict__ rows, uint64_t n, uint32_t dim, const float* __restrict__ queries,
+                                                               const uint32_t* __restrict__ cand, uint32_t R, uint32_t K, uint32_t* __restrict__ out_ids,
+                                                               float* __restrict__ out_dist, uint64_t* __restrict__ dbg_out, uint32_t dbg_q) {
+  constexpr int BPE = (DT == DT_F16) ? 2 : 4;
+  constexpr int CH_BYTES = 256, CH_ELEMS = CH_BYTES / BPE, BUF_BYTES = 64 * CH_BYTES;   // 16 KB per wave buffer
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const uint32_t q = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const float* __restrict__ qv = queries + static_cast<uint64_t>(q) * dim;
+  const uint32_t* __restrict__ cq = cand + static_cast<uint64_t>(q) * R;
+  const uint32_t row_bytes = dim * BPE;
+  const uint32_t nchunks = (row_bytes + CH_BYTES - 1) / CH_BYTES;
+  char* mybuf = smem + wave * 2 * BUF_BYTES;
+  const uint32_t lds_mine = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(NVDB_LPTR(mybuf)));
+  const char* gbase = static_cast<const char*>(rows);
+  [[maybe_unused]] const bool stamp = STAMP && q < dbg_q && wave == 0;
+  [[maybe_unused]] uint64_t t0 = 0;
+  if constexpr (STAMP) { if (stamp) t0 = refine_stamp(); }
 
-}  // namespace nvdbhip
+  WaveTopKMin tk = wmin_init();
 
-namespace nvdbhip {
+  const uint32_t sub = lane >> 4, pos = lane & 15;           // piece p stages rows 4p..4p+3; this lane: row 4p+sub, slot pos
+  for (uint32_t r0 = wave * 64u; r0 < R; r0 += 256u) {
+    const uint32_t r = r0 + lane;
+    const uint32_t id = (r < R) ? cq[r] : 0xFFFFFFFFu;
+    const bool valid = (id != 0xFFFFFFFFu) && (static_cast<uint64_t>(id) < n);     // cuda_refine.cu:437
+    const uint32_t rid = valid ? id : 0u;                    // invalid lanes gather row 0 and are dropped below
+    // row ids this lane gathers for: rows 4p+sub, p = 0..15
+    uint32_t src_row_off_lo[16], src_row_off_hi[16];
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {
+      const uint32_t rr = static_cast<uint32_t>(__shfl(static_cast<int>(rid), 4 * p + static_cast<int>(sub)));
+      const uint64_t off = static_cast<uint64_t>(rr) * row_bytes;
+      src_row_off_lo[p] = static_cast<uint32_t>(off); src_row_off_hi[p] = static_cast<uint32_t>(off >> 32);
+    }
+    auto issue_chunk = [&](uint32_t c, uint32_t buf) {
+#pragma unroll
+      for (int p = 0; p < 16; ++p) {
+        const uint32_t rowi = 4u * p + sub;
+        uint32_t coff = c * CH_BYTES + ((pos ^ (rowi & 15u)) << 4);          // source chunk for LDS slot `pos`
+        if (coff + 16 > row_bytes) coff = row_bytes - 16;                     // ragged last chunk: any in-row bytes (unused)
+        const uint64_t off = ((static_cast<uint64_t>(src_row_off_hi[p]) << 32) | src_row_off_lo[p]) + coff;
+        glds16_v(gbase + off, lds_mine + buf * BUF_BYTES + p * 1024);
+      }
+    };
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    issue_chunk(0, 0);
+    for (uint32_t c = 0; c < nchunks; ++c) {
+      if (c + 1 < nchunks) { issue_chunk(c + 1, (c + 1) & 1u); asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); }
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const char* rowc = mybuf + (c & 1u) * BUF_BYTES + lane * CH_BYTES;
+      const uint32_t e0 = c * CH_ELEMS;
+      const uint32_t ne = (dim - e0 < static_cast<uint32_t>(CH_ELEMS)) ? dim - e0 : static_cast<uint32_t>(CH_ELEMS);
+      if constexpr (DT == DT_F16) {
+        for (uint32_t j = 0; j * 8 < ne; ++j) {                              // 8 dims = 4 pairs per 16-byte slot
+          const uint4 v = *reinterpret_cast<const uint4*>(rowc + ((j ^ (static_cast<uint32_t>(lane) & 15u)) << 4));
+          const float* qq = qv + e0 + 8 * j;
+          float dx, dy;
+          dx = qq[0] - half_bits_to_float(v.x & 0xFFFFu); dy = qq[1] - half_bits_to_float(v.x >> 16); a0 = __builtin_fmaf(dx, dx, a0); a0 = __builtin_fmaf(dy, dy, a0);
+          dx = qq[2] - half_bits_to_float(v.y & 0xFFFFu); dy = qq[3] - half_bits_to_float(v.y >> 16); a1 = __builtin_fmaf(dx, dx, a1); a1 = __builtin_fmaf(dy, dy, a1);
+          dx = qq[4] - half_bits_to_float(v.z & 0xFFFFu); dy = qq[5] - half_bits_to_float(v.z >> 16); a2 = __builtin_fmaf(dx, dx, a2); a2 = __builtin_fmaf(dy, dy, a2);
+          dx = qq[6] - half_bits_to_float(v.w & 0xFFFFu); dy = qq[7] - half_bits_to_float(v.w >> 16); a3 = __builtin_fmaf(dx, dx, a3); a3 = __builtin_fmaf(dy, dy, a3);
+        }
+      } else {
+        for (uint32_t j = 0; j * 4 < ne; ++j) {                              // single accumulator, one fma per element
+          const float4 v = *reinterpret_cast<const float4*>(rowc + ((j ^ (static_cast<uint32_t>(lane) & 15u)) << 4));
+          const float* qq = qv + e0 + 4 * j;
+          float dd;
+          dd = qq[0] - v.x; a0 = __builtin_fmaf(dd, dd, a0);
+          dd = qq[1] - v.y; a0 = __builtin_fmaf(dd, dd, a0);
+          dd = qq[2] - v.z; a0 = __builtin_fmaf(dd, dd, a0);
+          dd = qq[3] - v.w; a0 = __builtin_fmaf(dd, dd, a0);
+        }
+      }
+    }
+    const float d = (DT == DT_F16) ? (a0 + a1) + (a2 + a3) : a0;
+    unsigned long long m = __ballot(valid && wmin_accepts(tk, K, d, id));
+    while (m) {
+      const int L = __builtin_ctzll(m);
+      m &= m - 1;
+      const float cd = readlane_f(d, L);
+      const uint32_t cid = readlane_u(id, L);
+      if (wmin_accepts(tk, K, cd, cid)) wmin_insert(tk, K, cd, cid, lane);
+    }
+  }
+  refine_finish<4, STAMP>(tk, K, q, lane, wave, out_ids, out_dist, stamp, t0, dbg_out);
+}
 
 // ------------------------------------------------------------------------------------------------
 // refine, version 3 (fp16 rows, dim in {256, 384, 512, 768}): WHOLE rows per request, four lanes per row.
@@ -211,22 +342,95 @@ template <int DIM> constexpr int refine3_slot_bytes() {
   return REFINE3_ROWS * (LA * 16 + 16) + (REM ? (REFINE3_ROWS / 2) * 1040 : 0);
 }
 
-#define NVDB_REFINE3_ARGS const void* __restrict__ rows, uint64_t n, const float* __restrict__ queries, const uint32_t* __restrict__ cand, \
-                          uint32_t R, uint32_t K, uint32_t* __restrict__ out_ids, float* __restrict__ out_dist
-template <int DIM>
-__global__ __launch_bounds__(64 * REFINE3_WAVES) void refine_l2_rows_kernel(NVDB_REFINE3_ARGS) {
-  constexpr bool STAMP = false;
-  [[maybe_unused]] uint64_t* const dbg_out = nullptr;
-  [[maybe_unused]] const uint32_t dbg_q = 0;
-#include "kernels_refine_v3_body.h"
+template <int DIM, bool STAMP = false>
+__global__ __launch_bounds__(64 * REFINE3_WAVES) void refine_l2_rows_kernel(const void* __restrict__ rows, uint64_t n, const float* __restrict__ queries,
+                                                                            const uint32_t* __restrict__ cand, uint32_t R, uint32_t K, uint32_t* __restrict__ out_ids,
+                                                                            float* __restrict__ out_dist, uint64_t* __restrict__ dbg_out, uint32_t dbg_q) {
+  constexpr int RB = DIM * 2;                       // row bytes
+  constexpr int LA = refine3_la<DIM>();             // lanes of piece A (16 bytes each): the whole row up to 1 KB
+  constexpr int REM = RB - LA * 16;                 // 0, or 512 for 1536-byte rows: remainder, two rows per piece
+  static_assert(DIM % 8 == 0 && (REM == 0 || REM == 512), "rows of up to 1 KB, or of 1536 bytes");
+  constexpr int NPAIR = DIM / 8;                    // pairs per lane = 16-byte pieces per row
+  constexpr int SLOT = refine3_slot_bytes<DIM>();
+  constexpr int ABLOCK = LA * 16 + 16, BBLOCK = 1040;
+  constexpr int BOFF = REFINE3_ROWS * ABLOCK;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const uint32_t q = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane >> 2, c = lane & 3;
+  const uint32_t* __restrict__ cq = cand + static_cast<uint64_t>(q) * R;
+  char* myslot = smem + wave * SLOT;
+  const uint32_t lds_mine = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(NVDB_LPTR(myslot)));
+  const char* gbase = static_cast<const char*>(rows);
+  [[maybe_unused]] const bool stamp = STAMP && q < dbg_q && wave == 0;
+  [[maybe_unused]] uint64_t t0 = 0;
+  if constexpr (STAMP) { if (stamp) t0 = refine_stamp(); }
+
+  // this lane's query elements: pairs c, c + 4, c + 8, ... (two floats each), resident for the whole query
+  float2 qv[NPAIR];
+  {
+    const float2* qp = reinterpret_cast<const float2*>(queries + static_cast<uint64_t>(q) * DIM) + c;
+#pragma unroll
+    for (int i = 0; i < NPAIR; ++i) qv[i] = qp[4 * i];
+  }
+
+  WaveTopKMin tk = wmin_init();
+
+  const uint32_t voffA = static_cast<uint32_t>(lane) * 16u;                                 // piece A: lane l <- bytes [16 l, 16 l + 16) of the row
+  const uint32_t lane_lo = static_cast<uint32_t>(lane & 31) * 16u + LA * 16u;               // piece B: 32 lanes per row, after the A part
+  const char* rdA = myslot + r * ABLOCK + c * 4;                                            // this lane's read bases
+  const char* rdB = myslot + BOFF + (r & 7) * BBLOCK + (r >> 3) * 512 + c * 4;
+
+  uint32_t idx = wave * REFINE3_ROWS + (lane & 15);
+  uint32_t ids_next = (idx < R) ? cq[idx] : 0xFFFFFFFFu;
+  for (uint32_t s0 = wave * REFINE3_ROWS; s0 < R; s0 += REFINE3_WAVES * REFINE3_ROWS) {
+    const uint32_t ids = ids_next;                  // lanes 0..15 (and their copies in 16..63): candidate of row lane & 15
+    idx += REFINE3_WAVES * REFINE3_ROWS;
+    ids_next = (idx < R) ? cq[idx] : 0xFFFFFFFFu;   // next step's ids travel while this step's rows do
+    // ---- issue: 16 whole rows (rows j and j + 8 together: they share the remainder piece) ----
+#pragma unroll
+    for (int j = 0; j < REFINE3_ROWS / 2; ++j) {
+      const uint32_t sid0 = readlane_u(ids, j), sid1 = readlane_u(ids, j + 8);
+      const bool ok0 = (sid0 != 0xFFFFFFFFu) && (static_cast<uint64_t>(sid0) < n);         // cuda_refine.cu:437
+      const bool ok1 = (sid1 != 0xFFFFFFFFu) && (static_cast<uint64_t>(sid1) < n);
+      const uint64_t off0 = static_cast<uint64_t>(ok0 ? sid0 : 0u) * RB;                   // skipped candidates: row 0, dropped below
+      const uint64_t off1 = static_cast<uint64_t>(ok1 ? sid1 : 0u) * RB;
+      if (lane < LA) {                               // (all 64 lanes for rows of 1 KB and more); ok0 / ok1: wave-uniform branches
+        if (ok0) glds16_imm<0>(voffA, gbase + off0, lds_mine + j * ABLOCK);
+        if (ok1) glds16_imm<0>(voffA, gbase + off1, lds_mine + (j + 8) * ABLOCK);
+      }
+      if constexpr (REM != 0) {
+        const uint64_t o = (lane < 32 ? off0 : off1) + lane_lo;                            // the two rows are read by different half-waves
+        if (ok0 || ok1) glds16_v(gbase + o, lds_mine + BOFF + j * BBLOCK);
+      }
+    }
+    const uint32_t my_id = static_cast<uint32_t>(__shfl(static_cast<int>(ids), r));
+    const bool valid = (my_id != 0xFFFFFFFFu) && (static_cast<uint64_t>(my_id) < n);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // ---- consume: accumulator c of row r ----
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < NPAIR; ++i) {
+      const char* src = (i < LA) ? rdA + i * 16 : rdB + (i - LA) * 16;
+      const uint32_t x = *reinterpret_cast<const uint32_t*>(src);                          // half2 pair (x[2p], x[2p+1])
+      const float dx = q_minus_half_lo(x, qv[i].x);
+      const float dy = q_minus_half_hi(x, qv[i].y);
+      acc = __builtin_fmaf(dx, dx, acc);
+      acc = __builtin_fmaf(dy, dy, acc);
+    }
+    const float s1 = acc + __shfl_xor(acc, 1);      // a0 + a1 | a2 + a3
+    const float d = s1 + __shfl_xor(s1, 2);         // (a0 + a1) + (a2 + a3): the same bits in all four lanes
+    unsigned long long m = __ballot(valid && c == 0 && wmin_accepts(tk, K, d, my_id));
+    while (m) {
+      const int L = __builtin_ctzll(m);
+      m &= m - 1;
+      const float cd = readlane_f(d, L);
+      const uint32_t cid = readlane_u(my_id, L);
+      if (wmin_accepts(tk, K, cd, cid)) wmin_insert(tk, K, cd, cid, lane);
+    }
+  }
+  refine_finish<REFINE3_WAVES, STAMP>(tk, K, q, lane, wave, out_ids, out_dist, stamp, t0, dbg_out);
 }
-// stamped twin (option refine_dbg_q)
-template <int DIM>
-__global__ __launch_bounds__(64 * REFINE3_WAVES) void refine_dbg_rows_kernel(NVDB_REFINE3_ARGS, uint64_t* __restrict__ dbg_out, uint32_t dbg_q) {
-  constexpr bool STAMP = true;
-#include "kernels_refine_v3_body.h"
-}
-#undef NVDB_REFINE3_ARGS
 
 // Long fp16 rows (d = 1024 / 1536: 2 KB / 3 KB) stay on refine_l2_lds_kernel (v2).  A whole-row build of this kernel for them was
 // measured in round 3 (query in LDS, 8 or 16 rows per wave and step): 4.28 TB/s at d = 1024 and 3.77 TB/s at d = 1536 against v2's

@@ -157,7 +157,7 @@ struct nvdb_hip_ctx {
   int64_t dbg_bound_pct = 100;                     // developer build: per cent of max_norm / filter_max_norm / resid_max the query prep is handed (tests/test_gpu_filter_bound.py: a case must fail under a short bound)
   DevBuf lk_scores, lk_sel, lk_hist, lk_state;     // any-k path (kernels_largek.h): score matrix of a query sub-batch, selected keys, radix state
   int64_t opt_refine_pinned = 0;                   // refine host call: stage queries / candidates / results through pinned host buffers (reference CUDA_PINNED)
-  int64_t opt_refine_dbg_q = 0;                    // refine host call with a timing struct: the first min(this, Q) queries run the stamped twin kernel (reference CUDA_DBG_TIMING / CUDA_DBG_Q); 0 = off
+  int64_t opt_refine_dbg_q = 0;                    // refine host call with a timing struct: the first min(this, Q) queries run the STAMP build of the same kernel template (reference CUDA_DBG_TIMING / CUDA_DBG_Q); 0 = off
   void* rpinned = nullptr;                         // ... [queries | candidates | out ids | out dist]
   size_t rpinned_bytes = 0;
   int64_t opt_largek_budget_mb = 8192;             // HBM the any-k path may use for its score matrix
@@ -245,6 +245,8 @@ using I8Dims = DimList<768, 640, 512, 384, 256>;
 using I8DimsBig = DimList<896, 1024, 1152, 1280, 1408, 1536>;
 // the exact fp32-MFMA kernels (kernels_exact_mfma.h): dim % 32 == 0 (no scalar tail), 16 queries x dim floats in registers
 using ExactMfmaDims = DimList<768, 640, 512, 384, 256, 128>;
+// fp16 dims of the whole-row refine kernel (kernels_refine.h, v3): rows of 512 bytes to 1 KB, or of 1536 bytes
+using Refine3Dims = DimList<768, 512, 384, 256>;
 
 // st = f(std::integral_constant<int, D>) for the D of the list that equals dim; false: the list does not hold dim
 template <int... D, typename F>
@@ -262,7 +264,6 @@ void dispatch_dtype(uint32_t dtype, nvdb_status& st, F&& f) {
 
 inline bool f16_filter_dim(uint32_t dim) { return has_dim(F16Dims{}, dim) || has_dim(F16Dims16{}, dim) || has_dim(F16DimsK2{}, dim); }
 inline bool i8_filter_dim(uint32_t dim) { return has_dim(I8Dims{}, dim) || has_dim(I8DimsBig{}, dim); }
-inline bool refine3_dim(uint32_t dim) { return dim == 768 || dim == 512 || dim == 384 || dim == 256; }   // fp16 dims of the whole-row refine kernel
 
 // what the fp16 MFMA kernels stream: the corpus itself, or the fp16 shadow of an fp32 corpus
 inline const signed char* filter_rows_i8(const nvdb_hip_ctx* c) { return c->shadow8 ? c->shadow8 : static_cast<const signed char*>(c->rows); }

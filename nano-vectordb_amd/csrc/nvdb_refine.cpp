@@ -2,8 +2,6 @@
 #include "nvdb_ctx.h"
 #include "kernels_refine.h"
 
-extern "C" {
-
 // ---- refine -----------------------------------------------------------------------------------------
 static nvdb_status refine_args(nvdb_hip_ctx* c, const void* q, const void* cand, uint32_t K, const void* out_ids) {
   if (!c) return NVDB_ERR_INVALID;
@@ -15,73 +13,50 @@ static nvdb_status refine_args(nvdb_hip_ctx* c, const void* q, const void* cand,
   return NVDB_OK;
 }
 
-// what launch_refine launched, for the timing struct: the report is filled from the launch itself, not from a second reading
-// of the options
+// the kernel build of one refine call and how it is launched.  lds: its dynamic LDS.  takes_dim: v1 / v2 take the row length as
+// their third argument, v3 has it as a template parameter and takes none (an ignored argument would move its kernarg offsets)
+struct RefineChoice { const void* fn; uint32_t threads, waves; size_t lds; bool takes_dim; };
+// ... and what the timing struct reports of it
 struct RefineLaunch { uint32_t threads = 0, nwarps = 0; size_t lds = 0; };
 
-// dbg != nullptr: the stamped twin of the kernel chosen below (same arithmetic, same results; wave 0 of the first dbg_q
-// workgroups writes its phase cycles to dbg[3q ..]).
+template <typename... A> static const void* kernel_ptr(void (*k)(A...)) { return reinterpret_cast<const void*>(k); }
+
+// STAMP: the stamped build of the same template (same arithmetic, same results; option refine_dbg_q)
+template <bool STAMP>
+static RefineChoice choose_refine(const nvdb_hip_ctx* c) {
+  const bool f16 = c->dtype == NVDB_DTYPE_F16, al = aligned_rows(c->dtype, c->dim);
+  RefineChoice k{};
+  nvdb_status st = NVDB_OK;
+  // v3 (whole rows per request, four lanes per row): fp16 rows of 512 / 768 / 1024 / 1536 bytes
+  if (c->opt_refine_v2 >= 2 && f16 && dispatch_dim(Refine3Dims{}, c->dim, st, [&](auto D) {
+        constexpr int DIM = decltype(D)::value;
+        k = {kernel_ptr(refine_l2_rows_kernel<DIM, STAMP>), 64 * REFINE3_WAVES, REFINE3_WAVES, static_cast<size_t>(REFINE3_WAVES) * refine3_slot_bytes<DIM>(), false};
+        return NVDB_OK;
+      }))
+    return k;
+  // v2 (coalesced gather through LDS): whole 16-byte steps only (f16: dim % 8 == 0, f32: dim % 4 == 0)
+  if (al && c->opt_refine_v2 && static_cast<uint64_t>(c->dim) * bpe_of(c->dtype) >= 256)
+    return {kernel_ptr(f16 ? refine_l2_lds_kernel<DT_F16, STAMP> : refine_l2_lds_kernel<DT_F32, STAMP>), 256, 4, 4 * 2 * 64 * 256, true};
+  if (f16) return {kernel_ptr(al ? refine_l2_kernel<DT_F16, true, STAMP> : refine_l2_kernel<DT_F16, false, STAMP>), 256, 4, 0, true};
+  return {kernel_ptr(al ? refine_l2_kernel<DT_F32, true, STAMP> : refine_l2_kernel<DT_F32, false, STAMP>), 256, 4, 0, true};
+}
+
+// dbg != nullptr: wave 0 of the first dbg_q workgroups writes its phase cycles to dbg[3q ..]
 static nvdb_status launch_refine(nvdb_hip_ctx* c, hipStream_t s, const float* dq, const uint32_t* dc, uint32_t Q, uint32_t R,
                                  uint32_t K, uint32_t* doi, float* dod, uint64_t* dbg = nullptr, uint32_t dbg_q = 0,
                                  RefineLaunch* launched = nullptr) {
-  const bool al = aligned_rows(c->dtype, c->dim);
+  const RefineChoice k = dbg ? choose_refine<true>(c) : choose_refine<false>(c);
+  if (launched) *launched = {k.threads, k.waves, k.lds ? k.lds : refine_merge_bytes(k.waves)};   // v1 has the merge lists only
   nvdb_status st;
-  // v3 (whole rows per request, four lanes per row): fp16 rows of 512 / 1024 / 1536 bytes
-  if (c->opt_refine_v2 >= 2 && c->dtype == NVDB_DTYPE_F16 && refine3_dim(c->dim)) {
-#define NVDB_REFINE3(D)                                                                                                        \
-    {                                                                                                                          \
-      constexpr size_t lds = static_cast<size_t>(REFINE3_WAVES) * refine3_slot_bytes<D>();                                      \
-      if (launched) *launched = {64 * REFINE3_WAVES, REFINE3_WAVES, lds};                                                      \
-      if (dbg) {                                                                                                               \
-        if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(refine_dbg_rows_kernel<D>), lds))) return st;               \
-        refine_dbg_rows_kernel<D><<<Q, 64 * REFINE3_WAVES, lds, s>>>(c->rows, c->n, dq, dc, R, K, doi, dod, dbg, dbg_q);        \
-      } else {                                                                                                                 \
-        if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(refine_l2_rows_kernel<D>), lds))) return st;                \
-        refine_l2_rows_kernel<D><<<Q, 64 * REFINE3_WAVES, lds, s>>>(c->rows, c->n, dq, dc, R, K, doi, dod);                     \
-      }                                                                                                                        \
-    }
-    if (c->dim == 768) NVDB_REFINE3(768) else if (c->dim == 512) NVDB_REFINE3(512) else if (c->dim == 384) NVDB_REFINE3(384) else NVDB_REFINE3(256)
-#undef NVDB_REFINE3
-    HIPCHK(c, hipGetLastError());
-    return NVDB_OK;
-  }
-  // v2 (coalesced gather through LDS): whole 16-byte steps only (f16: dim % 8 == 0, f32: dim % 4 == 0)
-  if (al && c->opt_refine_v2 && static_cast<uint64_t>(c->dim) * bpe_of(c->dtype) >= 256) {
-    constexpr size_t lds = 4 * 2 * 64 * 256;
-    if (launched) *launched = {256, 4, lds};
-    const bool f16 = c->dtype == NVDB_DTYPE_F16;
-    const void* fn = dbg ? (f16 ? reinterpret_cast<const void*>(refine_dbg_lds_kernel<DT_F16>) : reinterpret_cast<const void*>(refine_dbg_lds_kernel<DT_F32>))
-                         : (f16 ? reinterpret_cast<const void*>(refine_l2_lds_kernel<DT_F16>) : reinterpret_cast<const void*>(refine_l2_lds_kernel<DT_F32>));
-    if ((st = raise_lds_limit(c, fn, lds))) return st;
-    if (dbg) {
-      if (f16) refine_dbg_lds_kernel<DT_F16><<<Q, 256, lds, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
-      else refine_dbg_lds_kernel<DT_F32><<<Q, 256, lds, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
-    } else {
-      if (f16) refine_l2_lds_kernel<DT_F16><<<Q, 256, lds, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
-      else refine_l2_lds_kernel<DT_F32><<<Q, 256, lds, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
-    }
-    HIPCHK(c, hipGetLastError());
-    return NVDB_OK;
-  }
-  if (launched) *launched = {256, 4, sizeof(float) * 4 * 64 + sizeof(uint32_t) * 4 * 64 + sizeof(uint32_t) * 4};   // v1: the merge lists only
-  if (dbg) {
-    if (c->dtype == NVDB_DTYPE_F16) {
-      if (al) refine_dbg_kernel<DT_F16, true><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
-      else refine_dbg_kernel<DT_F16, false><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
-    } else {
-      if (al) refine_dbg_kernel<DT_F32, true><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
-      else refine_dbg_kernel<DT_F32, false><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod, dbg, dbg_q);
-    }
-  } else if (c->dtype == NVDB_DTYPE_F16) {
-    if (al) refine_l2_kernel<DT_F16, true><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
-    else refine_l2_kernel<DT_F16, false><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
-  } else {
-    if (al) refine_l2_kernel<DT_F32, true><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
-    else refine_l2_kernel<DT_F32, false><<<Q, 256, 0, s>>>(c->rows, c->n, c->dim, dq, dc, R, K, doi, dod);
-  }
-  HIPCHK(c, hipGetLastError());
+  if (k.lds && (st = raise_lds_limit(c, k.fn, k.lds))) return st;
+  std::vector<void*> args = {&c->rows, &c->n};
+  if (k.takes_dim) args.push_back(&c->dim);
+  args.insert(args.end(), {&dq, &dc, &R, &K, &doi, &dod, &dbg, &dbg_q});
+  HIPCHK(c, hipLaunchKernel(k.fn, dim3(Q), dim3(k.threads), args.data(), k.lds, s));
   return NVDB_OK;
 }
+
+extern "C" {
 
 nvdb_status nvdb_hip_refine_l2_topk_dev(nvdb_hip_ctx* c, const float* dq, const uint32_t* dc, uint32_t Q, uint32_t R, uint32_t K,
                                         uint32_t* doi, float* dod, void* hip_stream) {

@@ -24,7 +24,7 @@ struct CudaRefineTiming {
 // (pointer, N, D, dtype), like the reference (src/cuda_refine.cu:188-203).  Errors: std::exit with the
 // reference's codes (1 runtime error, 2 bad dtype, 3 K > 64).  Env: CUDA_RETURN_DIST=0 -> ids only; CUDA_PINNED=1 -> the
 // call's host buffers are staged through pinned memory (reference src/cuda_refine.cu:875, 902-914); CUDA_DBG_TIMING=1 ->
-// the first CUDA_DBG_Q queries (default 32, at most Q) run the stamped twin of the refine kernel and timing->dbg_* hold the
+// the first CUDA_DBG_Q queries (default 32, at most Q) run the STAMP build of the refine kernel template and timing->dbg_* hold the
 // average shader-clock cycles of its three phases (dist / write / merge) and their shares as fractions (:863-872, 1116-1144).
 // Both are read on every call.
 void cuda_l2_topk_batch(const void* base_ptr, uint32_t base_dtype, uint64_t N, uint32_t D, const float* queries_f32,

@@ -91,7 +91,7 @@ def test_register_budgets_of_the_production_kernels(codegen):
     k = _find(by_name, "filter_f16_kernelILi768ELi1ELb0ELi6E")
     assert k["agpr"] >= 192, k
     # refine v3: two workgroups of three waves per CU -> at most 256 registers per lane
-    k = _find(by_name, "refine_l2_rows_kernel<768>")
+    k = _find(by_name, "refine_l2_rows_kernel<768, false>")
     assert k["vgpr"] + k["agpr"] <= 256 and k["occ"] >= 2, k
 
 
@@ -130,7 +130,7 @@ def test_rendezvous_registers_and_hand_placed_instructions(codegen):
     body = _body(asm, k["mangled"])
     assert body.count("v_mfma_i32_16x16x64_i8") == 192 and "v_mfma_i32_32x32x32_i8" not in body
     # refine v3: q - half as ONE v_fma_mix_f32 per element (hipcc folds the C++ form back into cvt + sub)
-    k = _find(by_name, "refine_l2_rows_kernel<768>")
+    k = _find(by_name, "refine_l2_rows_kernel<768, false>")
     body = _body(asm, k["mangled"])
     assert body.count("v_fma_mix_f32") == 192 and body.count("v_cvt_f32_f16") == 0 and body.count("global_load_lds_dwordx4") == 24
 

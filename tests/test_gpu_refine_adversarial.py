@@ -4,7 +4,7 @@ The other refine tests draw candidates at random, which never yields equal dista
 best inside one wave or inside the last partial step, a skipped slot behind a very close row, R at a step boundary, the first
 and last row of the allocation, or a valid candidate at or beyond the padding distance 1e30.  Here every list is BUILT from
 fp64 distances computed in this module, and every list runs on each row of BUILDS, which together reach all product kernels
-(v3 whole rows, v2 column chunks through LDS, v1 lane per row; kernels_refine_v{1,2,3}_body.h).
+(v3 whole rows, v2 column chunks through LDS, v1 lane per row; the three kernel templates of kernels_refine.h).
 
 Every finite case asserts
   * ids and distance bits == oracle.refine(mode=0), the restatement of the reference kernel's fp32 order;
@@ -376,13 +376,10 @@ def check_fp64(bd, key, qsel, cand, K, ids, dist, strict=True):
 # ----------------------------------------------------------------------------- CPU checks of the generators (no GPU)
 def test_slot_geometry_matches_the_kernel_bodies():
     """GEOM restates what the bodies do: v1 / v2 walk `r0 = wave * 64; r0 += 256`, v3 `s0 = wave * ROWS; s0 += WAVES * ROWS`."""
-    for v in ("v1", "v2"):
-        body = open(os.path.join(CSRC, f"kernels_refine_{v}_body.h")).read()
-        assert re.search(r"for \(uint32_t r0 = wave \* 64u; r0 < R; r0 \+= 256u\)", body), v
-        assert GEOM[v] == (4, 64)
-    body = open(os.path.join(CSRC, "kernels_refine_v3_body.h")).read()
     head = open(os.path.join(CSRC, "kernels_refine.h")).read()
-    assert re.search(r"for \(uint32_t s0 = wave \* REFINE3_ROWS; s0 < R; s0 \+= REFINE3_WAVES \* REFINE3_ROWS\)", body)
+    assert len(re.findall(r"for \(uint32_t r0 = wave \* 64u; r0 < R; r0 \+= 256u\)", head)) == 2       # v1 and v2
+    assert GEOM["v1"] == (4, 64) and GEOM["v2"] == (4, 64)
+    assert re.search(r"for \(uint32_t s0 = wave \* REFINE3_ROWS; s0 < R; s0 \+= REFINE3_WAVES \* REFINE3_ROWS\)", head)
     m = re.search(r"constexpr int REFINE3_WAVES = (\d+), REFINE3_ROWS = (\d+);", head)
     assert m and GEOM["v3"] == (int(m.group(1)), int(m.group(2)))
     for k, (w, g) in GEOM.items():

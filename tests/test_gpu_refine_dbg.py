@@ -1,6 +1,6 @@
 """Refine phase timing on the GPU (option refine_dbg_q; reference CUDA_DBG_TIMING / CUDA_DBG_Q and the eval app's dbg TSV).
 
-The stamped twin of every refine kernel must return the product kernel's ids and distance bits, and the timing struct's seven
+The STAMP build of every refine kernel template must return the product kernel's ids and distance bits, and the timing struct's seven
 dbg_* fields must carry the reference's reduction (averages over dbg_q = min(option, Q) queries, shares as fractions);
 with the option off they stay zero.  The CLI writes the reference's one-row TSV under CUDA_DBG_TIMING=1 and nothing without it."""
 import os
@@ -55,7 +55,7 @@ def _assert_split(t, dbg_q):
     assert all(abs(p - a / tot) < 1e-12 for a, p in zip(avgs, pcts))
 
 
-# (tag, d, R, K, refine_v2): together they launch all ten stamped twins
+# (tag, d, R, K, refine_v2): together they launch all ten STAMP builds
 SHAPES = [("f16", 768, 1024, 10, 2), ("f16", 768, 1024, 10, 1), ("f16", 768, 1024, 10, 0), ("f16", 512, 300, 10, 2),
           ("f16", 384, 500, 10, 2), ("f16", 256, 200, 10, 2), ("f16", 100, 77, 5, 2), ("f16", 1536, 1024, 10, 2),
           ("f16", 1024, 333, 64, 2), ("f32", 768, 300, 64, 2), ("f32", 768, 300, 64, 0), ("f32", 37, 40, 3, 2)]

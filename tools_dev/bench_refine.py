@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """BASELINE config 5: exact-L2 refine, N=2.9M fp16 d=768, Q=10000, R=1024, K=10 (synthetic candidates).
 
-REFINE_DBG_Q=n: for every refine build it runs, also time the stamped twin (option refine_dbg_q = n, the reference's
+REFINE_DBG_Q=n: for every refine build it runs, also time the STAMP build of the same template (option refine_dbg_q = n, the reference's
 CUDA_DBG_TIMING / CUDA_DBG_Q) interleaved with the product kernel, and print the phase split (average shader-clock cycles and
 shares of dist / write / merge over the first n queries) beside kernel_ms with the stamps off and on."""
 import json, os, sys
@@ -25,7 +25,7 @@ for v2 in [int(x) for x in os.environ.get("REFINE_V2", "2,1").split(",")]:
     for it in range(4):
         ids, dist, t = ctx.refine_l2_topk(queries, cand, K, want_timing=True)
         if best is None or t.kernel_ms < best.kernel_ms: best = t
-        if DBG_Q:                                      # stamped twin, interleaved with the product kernel
+        if DBG_Q:                                      # STAMP build, interleaved with the product kernel
             ctx.set_option("refine_dbg_q", DBG_Q)
             _, _, t = ctx.refine_l2_topk(queries, cand, K, want_timing=True)
             ctx.set_option("refine_dbg_q", 0)
