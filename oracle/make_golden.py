@@ -19,7 +19,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 import pyoracle as po  # noqa: E402
-from golden_inputs import (CASES, DOT_DIMS, make_case_inputs, make_dot_inputs, make_f16_specials,  # noqa: E402
+from golden_inputs import (CASES, DOT_DIMS, TAIL_DIMS, make_case_inputs, make_dot_inputs, make_f16_specials,  # noqa: E402
                            sha)
 
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
@@ -131,9 +131,35 @@ def main_refine_conv():
     print(f"wrote tests/golden/refine_conv_golden.npz: {len(g)} arrays, {sz} bytes")
 
 
+def ref_simd_dots(ref, d):
+    """The reference's SIMD dot kernels on make_dot_inputs(d) -> (input sha, f32 bits, f16 bits, int8 bits), 48 pairs each."""
+    q, x32, x16, x8, sc = make_dot_inputs(d)
+    ref.lib.ref_set_force_scalar(0)
+    f32 = np.array([ref.lib.ref_dot_f32(po._p(q[i], po._f32p), po._p(x32[i], po._f32p), d) for i in range(len(q))], dtype=np.float32)
+    f16 = np.array([ref.lib.ref_dot_f32_f16base(po._p(q[i], po._f32p), x16[i].ctypes.data, d) for i in range(len(q))], dtype=np.float32)
+    i8 = np.array([ref.lib.ref_dot_f32_i8base(po._p(q[i], po._f32p), x8[i].ctypes.data, d, float(sc[i])) for i in range(len(q))], dtype=np.float32)
+    return np.frombuffer(bytes.fromhex(sha(q, x32, x16, x8, sc)), dtype=np.uint8), bits(f32), bits(f16), bits(i8)
+
+
+def main_dot_tails():
+    """tests/golden/dot_tails_golden.npz: the SIMD dot kernels (simd_dot.cpp) at every dim of TAIL_DIMS -- all residues mod 16
+    behind a non-empty vector body, and three long bodies.  flat_golden.npz and DOT_DIMS stay as they are."""
+    os.makedirs(OUT, exist_ok=True)
+    ref = po.Reference()
+    g = {}
+    for d in TAIL_DIMS:
+        g[f"dot{d}_sha"], g[f"dot{d}_simd_f32"], g[f"dot{d}_simd_f16"], g[f"dot{d}_simd_i8"] = ref_simd_dots(ref, d)
+    np.savez_compressed(os.path.join(OUT, "dot_tails_golden.npz"), **g)
+    sz = os.path.getsize(os.path.join(OUT, "dot_tails_golden.npz"))
+    print(f"wrote tests/golden/dot_tails_golden.npz: {len(g)} arrays, {sz} bytes")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "refine_conv":
         main_refine_conv()
+    elif len(sys.argv) > 1 and sys.argv[1] == "dot_tails":
+        main_dot_tails()
     else:
         main()
         main_refine_conv()
+        main_dot_tails()

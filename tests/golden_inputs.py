@@ -1,4 +1,4 @@
-"""Deterministic inputs for the golden fixtures (tests/golden/flat_golden.npz).
+"""Deterministic inputs for the golden fixtures (tests/golden/flat_golden.npz, dot_tails_golden.npz).
 
 Used by oracle/make_golden.py (to feed the real reference) and by the tests (to re-create the
 same inputs; every array's sha256 is checked against the fixture before use).  Only numpy's
@@ -9,6 +9,11 @@ import hashlib
 import numpy as np
 
 DOT_DIMS = (768, 384, 300, 100, 37, 31, 16, 15, 13, 8, 7, 5, 3)
+# tests/golden/dot_tails_golden.npz: every residue mod 16 twice behind a non-empty vector body, and three long bodies
+# (384 + 7, 768 + 9, 1536 + 9) whose tails follow many unrolled steps
+TAIL_SWEEP_DIMS = tuple(range(17, 49))
+TAIL_LONG_DIMS = (391, 777, 1545)
+TAIL_DIMS = TAIL_SWEEP_DIMS + TAIL_LONG_DIMS
 
 # name -> shape of the flat-scan case.  "dup": rows duplicated so exact-score ties exist.
 CASES = {

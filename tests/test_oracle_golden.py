@@ -1,10 +1,12 @@
 """CPU tests: the C restatement (oracle/nvdb_oracle.c) against golden vectors produced by the REAL
 reference (oracle/make_golden.py -> tests/golden/flat_golden.npz).  This is what "pins" the oracle."""
+import os
+
 import numpy as np
 import pytest
 
 import pyoracle as po
-from golden_inputs import CASES, DOT_DIMS, make_case_inputs, make_dot_inputs, make_f16_specials, sha
+from golden_inputs import CASES, DOT_DIMS, TAIL_DIMS, make_case_inputs, make_dot_inputs, make_f16_specials, sha
 from parity import assert_topk_equal
 
 
@@ -30,6 +32,27 @@ def test_dot_kernels_bitexact(oracle, golden, d):
     assert np.array_equal(s32.view(np.uint32), golden[f"dot{d}_scalar_f32"])
     assert np.array_equal(s8.view(np.uint32), golden[f"dot{d}_scalar_i8"])
     assert np.array_equal(golden[f"dot{d}_scalar_f16"], golden[f"dot{d}_simd_f16"])
+
+
+@pytest.fixture(scope="module")
+def tails_golden():
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dot_tails_golden.npz"))
+
+
+@pytest.mark.parametrize("d", TAIL_DIMS)
+def test_dot_kernels_bitexact_at_every_tail(oracle, tails_golden, d):
+    """The SIMD kernels' restatement against the real reference at every residue mod 16 behind a non-empty vector body
+    (17 .. 48) and behind long bodies (391, 777, 1545): tests/golden/dot_tails_golden.npz."""
+    q, x32, x16, x8, sc = make_dot_inputs(d)
+    _sha_ok(tails_golden, f"dot{d}_sha", q, x32, x16, x8, sc)
+    L = oracle.lib
+    m = len(q)
+    f32 = np.array([L.oracle_dot_f32(po._p(q[i], po._f32p), po._p(x32[i], po._f32p), d) for i in range(m)], dtype=np.float32)
+    f16 = np.array([L.oracle_dot_f32_f16base(po._p(q[i], po._f32p), x16[i].ctypes.data, d) for i in range(m)], dtype=np.float32)
+    i8 = np.array([L.oracle_dot_f32_i8base(po._p(q[i], po._f32p), x8[i].ctypes.data, d, float(sc[i])) for i in range(m)], dtype=np.float32)
+    assert np.array_equal(f32.view(np.uint32), tails_golden[f"dot{d}_simd_f32"])
+    assert np.array_equal(f16.view(np.uint32), tails_golden[f"dot{d}_simd_f16"])
+    assert np.array_equal(i8.view(np.uint32), tails_golden[f"dot{d}_simd_i8"])
 
 
 def test_f16_conversion_specials(oracle, golden):
