@@ -19,7 +19,7 @@ void free_corpus(nvdb_hip_ctx* c) {
   c->rows = nullptr; c->scales = nullptr; c->owned = false; c->n = 0; c->dim = 0; c->fdim = 0; c->dtype = 0; c->max_norm = 0.f;
   c->cap_hint = 0;
   c->q8shadow = false; c->resid_max = 0.f; c->filter_max_norm = 0.f;
-  c->shadow_demoted = false; c->last_filter_kind = 0;
+  c->shadow_demoted = false; c->last_filter_kind = FILTER_NONE;
   c->range_valid = false; c->range_total = 0;      // the held range results describe the rows they were found in
   parts_drop(c);                                   // a partition table describes the rows it was set for
   c->nmasks = 0;                                   // ... and so do the row masks

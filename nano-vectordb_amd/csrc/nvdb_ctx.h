@@ -3,8 +3,8 @@
 //
 //   nvdb_corpus.cpp        create / destroy, corpus upload / adopt / generate (+ shadow copies, row-norm pass), options, statistics
 //   nvdb_plan.h            what one flat search will do (plan_search): route, list capacity, query tiling, bootstrap, chunk boundaries -- decided
-//                          before anything is enqueued, from corpus facts, options and the launchers' shape facts below; no HIP call
-//   nvdb_search.cpp        one flat search: plan -> workspace -> launches (search_core); the search entry points, their self-checks and retry ladder
+//                          before anything is enqueued, from a CONST context, no HIP call; the filter choice (filter_kind) travels in the plan, then in the flow's FilterRun
+//   nvdb_search.cpp        one flat search: plan -> prologue (begin_filter_run, the range search's too) -> launches (search_core); entry points, self-checks, retry ladder
 //   nvdb_range.cpp         range search (every row whose score reaches a per-query radius): plan, filter route, exact route, packing (kernels_range.h)
 //   nvdb_range_parts.cpp   range search on the probe path: the partition range scan, its per-query tail, the probe / IVF / masked entry points
 //                          (kernels_range_parts.h, range_plan.h; nvdb_range.h and nvdb_parts.h are what it shares with its two neighbours)
@@ -69,6 +69,8 @@ constexpr uint32_t I8W_TILE_ROWS = 64;        // rows per tile of the int8 two-s
 constexpr uint32_t PAD_ROWS = 64;             // zero rows every library-owned corpus / shadow is padded with: the largest tile
 constexpr uint32_t I8_FILTER_MAX_DIM = 1536;
 
+// what a search's filter launches stream: nothing (exact / any-k route), fp16 rows (the corpus or its fp16 shadow), the int8 shadow of an fp16 / fp32 corpus, an int8 corpus
+enum FilterKind : uint32_t { FILTER_NONE = 0, FILTER_F16 = 1, FILTER_SHADOW8 = 2, FILTER_I8 = 3 };
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -95,9 +97,7 @@ struct nvdb_hip_ctx {
   bool i8_scales_signed = false;                   // int8 corpus with a negative or NaN row scale: the in-loop second-stage build (no biased accumulators)
   signed char* shadow8 = nullptr;                  // int8 corpus with a dim the kernels are not instantiated for: rows zero-padded to fdim; or (q8shadow) the int8 FILTER shadow of an fp16 / fp32 corpus
   bool q8shadow = false;                           // fp16 / fp32 corpus with a resident int8 FILTER shadow (option q8_shadow): the int8 MFMA kernels can stream shadow8, every survivor is re-scored from the original rows
-  bool use_shadow = true;                          // ... and this search's filter launches stream it (plan_search's choice, which the shape helpers below read); false: the corpus' own fp16 filter
   bool shadow_demoted = false;                     // the shadow's lists or wave logs overflowed on this corpus (host API's retry ladder): searches start on the fp16 filter, in the spirit of cap_hint; a reload clears it
-  uint32_t last_filter_kind = 0;                   // what the last search's filter launches streamed: 0 none (exact / any-k route), 1 fp16 rows, 2 the int8 shadow, 3 an int8 corpus
   float filter_max_norm = 0.f;                     // max row norm of what the int8 filter streams (== max_norm for an int8 corpus; the shadow's for q8shadow -- max_norm stays the fp16 filter's)
   float resid_max = 0.f;                           // q8shadow: largest ||x - scale * x_q|| over the rows -- the corpus side of the filter's error bound
   int64_t opt_q8_shadow = -1;                      // set before the corpus is loaded: 1 = build the int8 filter shadow for fp16 / fp32 corpora whose dim the int8 kernels take, 0 = never (set later: also stop
@@ -120,13 +120,10 @@ struct nvdb_hip_ctx {
   void* pinned = nullptr;                           // pinned host staging of small calls: status words, results, queries
   void* pinned_dev = nullptr;                       // ... as the device addresses it (hipHostGetDevicePointer)
   size_t pinned_bytes = 0;
-  bool perm_on = false;                             // this search streams tiles in permuted order (search_core, from its plan)
   int64_t opt_tile_permute = 1;
   uint32_t cap_hint = 0;                            // this corpus has needed the longest candidate lists before: start with them
   bool stats_lazy = false;                          // stats.candidates not read back yet (nvdb_hip_get_stats does it)
-  hipEvent_t launch_e0 = nullptr, launch_e1 = nullptr;   // attached to the next filter launch (hipExtLaunchKernelGGL): its own start/stop timestamps, no extra packets
   std::vector<hipEvent_t> kl_pool;                  // recycled events of collected launches
-  uint32_t prog_slot = 0;                          // next free region of the rendezvous counters (reset per search)
   int64_t opt_time_launches = 0;                   // host API with a timing struct: 1 = also attach start / stop events to every filter launch (stats.filter_kernel_ms); costs ~0.1 ms per launch-rich pass
   int64_t opt_exact_lds = 1;                       // exact MFMA kernels: full groups of 64 queries stage their row tiles through LDS once per workgroup: 1 = for fp32 rows (101 vs 75 TFLOP/s; fp16 / int8 rows are faster register-direct: 86 vs 77), 2 = always, 0 = never
   int64_t opt_exact_img = 1;                       // exact MFMA kernels, fp16 / int8 rows, full groups of 64 queries: tile converted once per workgroup into an fp32 LDS image (exact_mfma_img_kernel); 0: register-direct / raw-staged builds
@@ -176,6 +173,8 @@ struct nvdb_hip_ctx {
   nvdb_hip_scan_stats stats{};
   uint32_t last_nq = 0, last_cap = 0;
   bool last_filter = false;
+  FilterKind last_filter_kind = FILTER_NONE;       // what its filter launches streamed
+  bool last_perm = false;                          // ... in permuted tile order (of the last search that filtered: nvdb_hip_debug_clock_i8 streams the same way)
   std::vector<hipEvent_t> ev_pool;
   std::vector<std::pair<int, int>> ev_filter;      // (start,stop) event indices of filter launches (last search)
   // kernel-time accounting across searches ("time_kernels" option): one entry per dominant-kernel launch
@@ -265,19 +264,21 @@ void dispatch_dtype(uint32_t dtype, nvdb_status& st, F&& f) {
 inline bool f16_filter_dim(uint32_t dim) { return has_dim(F16Dims{}, dim) || has_dim(F16Dims16{}, dim) || has_dim(F16DimsK2{}, dim); }
 inline bool i8_filter_dim(uint32_t dim) { return has_dim(I8Dims{}, dim) || has_dim(I8DimsBig{}, dim); }
 
-// what the fp16 MFMA kernels stream: the corpus itself, or the fp16 shadow of an fp32 corpus
+// what the int8 MFMA kernels stream: an int8 corpus (its zero-padded copy, where the dim needed one), or the int8 filter shadow of an fp16 / fp32 corpus
 inline const signed char* filter_rows_i8(const nvdb_hip_ctx* c) { return c->shadow8 ? c->shadow8 : static_cast<const signed char*>(c->rows); }
 inline const float* filter_scales_i8(const nvdb_hip_ctx* c) { return c->shadow8 ? c->shadow8_scales : c->scales; }
+// what the fp16 MFMA kernels stream: the corpus itself, or the fp16 shadow of an fp32 corpus
 inline const _Float16* filter_rows_f16(const nvdb_hip_ctx* c) {
   return c->shadow16 ? c->shadow16 : static_cast<const _Float16*>(c->rows);
 }
 
-// the int8 MFMA kernels do the filtering: an int8 corpus, or an fp16 / fp32 corpus with an int8 filter shadow
-inline bool filter_is_i8(const nvdb_hip_ctx* c) { return c->dtype == NVDB_DTYPE_I8 || (c->q8shadow && c->use_shadow); }
 // a shadow context whose corpus the fp16 filter streams as it is (every int8 dim is an fp16 dim too): both filters are available
 inline bool f16_beside_shadow(const nvdb_hip_ctx* c) { return c->q8shadow && c->dtype == NVDB_DTYPE_F16 && f16_filter_dim(c->dim); }
 // which of the two a search starts on: the shadow, unless it was switched off after the load or has overflowed on this corpus
 inline bool shadow_preferred(const nvdb_hip_ctx* c) { return c->q8shadow && !(f16_beside_shadow(c) && (c->opt_q8_shadow == 0 || c->shadow_demoted)); }
+// THE filter choice.  The planners call it once and carry the value in their plan: every shape helper below and every launcher takes it from there
+inline FilterKind filter_kind(const nvdb_hip_ctx* c) { return c->dtype == NVDB_DTYPE_I8 ? FILTER_I8 : shadow_preferred(c) ? FILTER_SHADOW8 : FILTER_F16; }
+constexpr bool filter_is_i8(FilterKind kind) { return kind == FILTER_I8 || kind == FILTER_SHADOW8; }
 // HBM the int8 filter shadow of a corpus takes: a byte per element and a scale per row (padding aside)
 inline uint64_t q8_shadow_bytes(uint64_t n, uint32_t dim) { return n * (static_cast<uint64_t>(dim) + 4u); }
 // Does a corpus get the shadow when it becomes resident?  free_hbm: what hipMemGetInfo reports free with the corpus resident.
@@ -299,12 +300,12 @@ inline bool filter_supported(const nvdb_hip_ctx* c) {
 }
 
 // int8: the two-stage kernel (hi plane resident, lo plane on demand); option i8_wide = 0 selects the two-plane kernel
-inline bool i8_two_stage(const nvdb_hip_ctx* c) { return filter_is_i8(c) && c->opt_i8_wide; }
+inline bool i8_two_stage(const nvdb_hip_ctx* c, FilterKind kind) { return filter_is_i8(kind) && c->opt_i8_wide; }
 
 // NB = 32-query blocks per wave: 1 for nq <= 128 (HBM-bound regime) and for the two-plane int8 kernel, else 2
-inline uint32_t filter_nb(const nvdb_hip_ctx* c, uint32_t nq) {
-  if (filter_is_i8(c) && (!i8_two_stage(c) || c->fdim > 768)) return 1u;   // two-plane kernel; dims > 768: 32 queries per wave
-  if (!filter_is_i8(c) && c->fdim > 768) return 1u;          // 16-row-tile build: 128 queries per workgroup
+inline uint32_t filter_nb(const nvdb_hip_ctx* c, FilterKind kind, uint32_t nq) {
+  if (filter_is_i8(kind) && (!i8_two_stage(c, kind) || c->fdim > 768)) return 1u;   // two-plane kernel; dims > 768: 32 queries per wave
+  if (!filter_is_i8(kind) && c->fdim > 768) return 1u;       // 16-row-tile build: 128 queries per workgroup
   return nq <= 128 ? 1u : 2u;
 }
 
@@ -312,7 +313,7 @@ inline uint32_t filter_nb(const nvdb_hip_ctx* c, uint32_t nq) {
 // AND by plan_search (nvdb_plan.h), which sizes the query tiles and aligns the chunk boundaries with them ----
 // a corpus this library allocated (a shadow copy always is) is zero-padded to whole tiles
 // (as far as the filter that streams this search goes: the fp16 filter beside an int8 shadow reads the corpus itself)
-inline bool corpus_padded(const nvdb_hip_ctx* c) { return c->owned || c->shadow16 != nullptr || (c->shadow8 != nullptr && filter_is_i8(c)); }
+inline bool corpus_padded(const nvdb_hip_ctx* c, FilterKind kind) { return c->owned || c->shadow16 != nullptr || (c->shadow8 != nullptr && filter_is_i8(kind)); }
 // fp16, dims <= 768: batches > 128 (NB == 2) run the 16x16x32 build (developer library: unless option mfma16 = 0) ...
 inline bool f16_m16_build(const nvdb_hip_ctx* c, uint32_t nb) { return nb == 2 && c->opt_mfma16; }
 // ... whose tiles are MB 16-row blocks: 64-row tiles up to d = 384, 32-row tiles beyond
@@ -321,26 +322,41 @@ constexpr uint32_t f16_m16_tile_rows(uint32_t dim) { return dim <= 384 ? 64u : 3
 constexpr uint32_t i8w_tile_rows(uint32_t dim) { return dim <= 768 ? I8W_TILE_ROWS : FILTER_ROWS; }
 // rows per tile of the build that streams this batch, as far as chunk boundaries care (the 16-row-tile fp16 builds of
 // dims > 768 take any multiple of 32)
-inline uint32_t filter_tile_rows(const nvdb_hip_ctx* c, uint32_t nq) {
-  if (filter_is_i8(c)) return i8_two_stage(c) ? i8w_tile_rows(c->fdim) : FILTER_ROWS;
-  return (c->fdim <= 768 && f16_m16_build(c, filter_nb(c, nq))) ? f16_m16_tile_rows(c->fdim) : FILTER_ROWS;
+inline uint32_t filter_tile_rows(const nvdb_hip_ctx* c, FilterKind kind, uint32_t nq) {
+  if (filter_is_i8(kind)) return i8_two_stage(c, kind) ? i8w_tile_rows(c->fdim) : FILTER_ROWS;
+  return (c->fdim <= 768 && f16_m16_build(c, filter_nb(c, kind, nq))) ? f16_m16_tile_rows(c->fdim) : FILTER_ROWS;
 }
 // queries per workgroup: fp16 64 on the K-split build (dims > 1536), 128 on the 16-row-tile build (768 < dim <= 1536), else and
 // for every int8 build 128 per 32-query block of a wave
 constexpr uint32_t f16_filter_qpb(uint32_t dim, uint32_t nb) { return dim > 1536 ? 64u : dim > 768 ? 128u : 128u * nb; }
 constexpr uint32_t f16_m16_qpb(uint32_t nqb, uint32_t wpb) { return 16u * nqb * wpb; }   // filter_f16_m16_kernel<.., NQB, WPB>: WPB waves x NQB 16-query blocks
-inline uint32_t filter_qpb(const nvdb_hip_ctx* c, uint32_t nq) { return filter_is_i8(c) ? 128u * filter_nb(c, nq) : f16_filter_qpb(c->fdim, filter_nb(c, nq)); }
+inline uint32_t filter_qpb(const nvdb_hip_ctx* c, FilterKind kind, uint32_t nq) { return filter_is_i8(kind) ? 128u * filter_nb(c, kind, nq) : f16_filter_qpb(c->fdim, filter_nb(c, kind, nq)); }
 // int8 two-stage, dims <= 768: batches > 128 run a software-pipelined build (developer library: unless option i8_pipe = 0), which
 // logs the first stage's survivors and finishes them after the stream unless the second stage has to stay in the tile loop
-inline bool i8_pipelined(const nvdb_hip_ctx* c, uint32_t nb) { return nb == 2 && c->opt_i8_pipe; }
+inline bool i8_pipelined(const nvdb_hip_ctx* c, FilterKind kind, uint32_t nb) { return i8_two_stage(c, kind) && nb == 2 && c->opt_i8_pipe; }
 inline bool i8_stage2_in_loop(const nvdb_hip_ctx* c) { return c->opt_i8_defer != 0 || c->i8_scales_signed; }
-inline bool i8_logs_survivors(const nvdb_hip_ctx* c, uint32_t nb) { return i8_pipelined(c, nb) && !i8_stage2_in_loop(c); }
+inline bool i8_logs_survivors(const nvdb_hip_ctx* c, FilterKind kind, uint32_t nb) { return i8_pipelined(c, kind, nb) && !i8_stage2_in_loop(c); }
 
 inline hipEvent_t get_event(nvdb_hip_ctx* c, size_t idx) {
   while (c->ev_pool.size() <= idx) { hipEvent_t e; (void)hipEventCreate(&e); c->ev_pool.push_back(e); }
   return c->ev_pool[idx];
 }
 
+// ---- a filter flow: what the plans of both (SearchPlan, nvdb_plan.h; RangePlan, nvdb_range.h) share -- all that begin_filter_run reads
+struct FilterPlan {
+  FilterKind kind = FILTER_NONE;        // filter_kind(c) when the plan was made: the shapes below are that filter's
+  bool filter = false, perm_on = false;    // filter launches follow the prologue; ... streaming tiles in permuted order
+  bool prep = false, prep_inits = false;   // the prep launch runs; ... and does the per-search resets itself (option fuse), else init_search_kernel
+  uint32_t cap = 0, QPB = 0, QT = 0, nq_pad = 0, prog_words = 0;
+};
+// ... and the flow as its launchers see it: built once by begin_filter_run, handed to every launch helper with the rows of that launch
+struct FilterRun {
+  hipStream_t s; FilterKind kind; bool perm;   // perm: tiles in permuted order (else identity)
+  uint32_t nq, QT, nq_pad, cap; const float* thr;
+  uint32_t prog_slot = 0;               // next free region of the rendezvous counters (next_prog_region)
+  hipEvent_t e0 = nullptr, e1 = nullptr;   // the next timed filter launch takes them (hipExtLaunchKernelGGL: its own start / stop timestamps, no extra packets)
+};
+struct RowRange { uint32_t lo, hi; };
 // ---- defined in one translation unit, called from another ----------------------------------------------------------
 // nvdb_launch_exact.cpp
 nvdb_status launch_init_search(nvdb_hip_ctx* c, hipStream_t s, uint32_t nq_pad, uint32_t prog_words);
@@ -370,10 +386,10 @@ inline float prep_norm(const nvdb_hip_ctx* c, float v) {
 }
 nvdb_status launch_prep_q16(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint32_t nq, uint32_t nq_pad, const PrepInit& pinit);
 nvdb_status launch_prep_q8(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint32_t nq, uint32_t nq_pad, const PrepInit& pinit);
-nvdb_status launch_filter_f16(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint32_t row_hi, uint32_t nq, uint32_t QT, uint32_t cap);
-nvdb_status launch_filter_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint32_t row_hi, uint32_t nq, uint32_t QT, uint32_t cap);
-nvdb_status launch_boot_f16(nvdb_hip_ctx* c, hipStream_t s, uint32_t n0, uint32_t nq, uint32_t QT, uint32_t cap, uint32_t nb);
-nvdb_status launch_boot_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t n0, uint32_t nq, uint32_t QT, uint32_t cap);
+nvdb_status launch_filter_f16(nvdb_hip_ctx* c, FilterRun& run, RowRange rows);
+nvdb_status launch_filter_i8(nvdb_hip_ctx* c, FilterRun& run, RowRange rows);
+nvdb_status launch_boot_f16(nvdb_hip_ctx* c, FilterRun& run, uint32_t n0);      // tile maxima of rows [0, n0)
+nvdb_status launch_boot_i8(nvdb_hip_ctx* c, FilterRun& run, uint32_t n0);
 // nvdb_corpus.cpp
 nvdb_status corpus_alloc_padded(nvdb_hip_ctx* c, uint64_t n, uint32_t dim, uint32_t dtype, void** rows, float** scales);
 nvdb_status corpus_take_ownership(nvdb_hip_ctx* c, void* dev_rows, float* dev_scales, uint64_t n, uint32_t dim, uint32_t dtype, uint64_t global_row_base);
@@ -384,8 +400,12 @@ void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace
 // nvdb_search.cpp
 nvdb_status ensure_q32(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes);          // the host API's query buffer: qbytes + 8 rows; a new buffer starts all zero
 nvdb_status zero_q32_pad(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes);        // ... and the 8 rows behind this call's queries read as zeros
-nvdb_status next_prog_region(nvdb_hip_ctx* c, hipStream_t s, uint32_t nwg, uint32_t** out);
-ScatterArgs scatter_args(nvdb_hip_ctx* c, uint32_t cap, uint32_t trows = 0);
+// prologue of search_core (whatever its route) and range_filter_pass: workspace (+ extra: a per-query word array), last filter state, init or prep, the run value
+nvdb_status begin_filter_run(nvdb_hip_ctx* c, hipStream_t s, const FilterPlan& p, const float* dev_q, const float* host_q, uint32_t nq, DevBuf* extra, FilterRun& run);
+nvdb_status launch_boot(nvdb_hip_ctx* c, FilterRun& run, uint32_t n0);
+nvdb_status launch_filter(nvdb_hip_ctx* c, FilterRun& run, RowRange rows);
+nvdb_status next_prog_region(nvdb_hip_ctx* c, FilterRun& run, uint32_t nwg, uint32_t** out);
+ScatterArgs scatter_args(nvdb_hip_ctx* c, const FilterRun& run, uint32_t trows = 0);
 float filter_events_ms(const nvdb_hip_ctx* c);                                 // sum over the last search's timed filter launches (ev_filter)
 nvdb_status sum_candidates(nvdb_hip_ctx* c, unsigned long long* total);         // list lengths the last thresholding select left, each capped at last_cap
 
@@ -411,18 +431,16 @@ inline bool sibling_sync_grid(const nvdb_hip_ctx* c, uint32_t QT, uint32_t nwg) 
 // rendezvous arguments of a filter kernel: counters (unused / not-yet-started slots read 0xFFFFFFFF = "far ahead"),
 // period mask, allowed lead; prog == nullptr: the SYNC = false build runs
 struct SyncArgs { uint32_t* prog = nullptr; uint32_t mask = 0, lead = 0; };
-inline nvdb_status sibling_sync_args(nvdb_hip_ctx* c, hipStream_t s, uint32_t QT, uint32_t nwg, SyncArgs& out) {
+inline nvdb_status sibling_sync_args(nvdb_hip_ctx* c, FilterRun& run, uint32_t nwg, SyncArgs& out) {
   out = SyncArgs{};
-  if (!sibling_sync_grid(c, QT, nwg)) return NVDB_OK;
+  if (!sibling_sync_grid(c, run.QT, nwg)) return NVDB_OK;
   out.mask = static_cast<uint32_t>(c->opt_sync_every - 1);
   out.lead = static_cast<uint32_t>(c->opt_sync_lead);
-  return next_prog_region(c, s, nwg, &out.prog);
+  return next_prog_region(c, run, nwg, &out.prog);
 }
 
-// one filter pass as its caller describes it
-struct FilterCall { hipStream_t s; uint32_t row_lo, row_hi, nq, QT, cap; const float* thr; };
-// ... and as one kernel build wants it launched; log_waves: waves per workgroup the survivor log is sized for (0: the
-// build writes no log); timed: the context's launch events attach (hipExtLaunchKernelGGL)
+// one filter launch as one kernel build wants it; log_waves: waves per workgroup the survivor log is sized for (0: the
+// build writes no log); timed: the run's launch events attach (hipExtLaunchKernelGGL)
 struct FilterGeom { uint32_t block; size_t lds; uint32_t log_waves; bool timed; };
 
 // A DevBuf* in a kernel's argument list stands for the Hit* it holds at launch time: the survivor log may move when
@@ -431,12 +449,12 @@ template <typename T> inline T launch_arg(T a) { return a; }
 inline Hit* launch_arg(DevBuf* b) { return static_cast<Hit*>(b->p); }
 
 template <typename... KA, typename... A>
-nvdb_status launch_filter_kernel(nvdb_hip_ctx* c, hipStream_t s, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, A... args) {
+nvdb_status launch_filter_kernel(nvdb_hip_ctx* c, FilterRun& run, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, A... args) {
   nvdb_status st;
   if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(kern), g.lds))) return st;
   if (g.log_waves && (st = ensure(c, c->hitlog, static_cast<size_t>(nwg) * g.log_waves * FILTER_LOGCAP * sizeof(Hit)))) return st;
-  if (g.timed) hipExtLaunchKernelGGL(kern, dim3(nwg), dim3(g.block), g.lds, s, c->launch_e0, c->launch_e1, 0, launch_arg(args)...);
-  else kern<<<nwg, g.block, g.lds, s>>>(launch_arg(args)...);
+  if (g.timed) hipExtLaunchKernelGGL(kern, dim3(nwg), dim3(g.block), g.lds, run.s, std::exchange(run.e0, nullptr), std::exchange(run.e1, nullptr), 0, launch_arg(args)...);
+  else kern<<<nwg, g.block, g.lds, run.s>>>(launch_arg(args)...);
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
 }
@@ -444,26 +462,26 @@ nvdb_status launch_filter_kernel(nvdb_hip_ctx* c, hipStream_t s, void (*kern)(KA
 // the arguments every fp16 build starts with (rows, range, queries, thresholds, log, scatter arguments); rest: what one
 // build adds (the rendezvous arguments, or filter_f16_kernel's aux word)
 template <typename... KA, typename... Rest>
-nvdb_status launch_filter_f16_kernel(nvdb_hip_ctx* c, const FilterCall& f, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, DevBuf* log,
+nvdb_status launch_filter_f16_kernel(nvdb_hip_ctx* c, FilterRun& run, RowRange rows, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, DevBuf* log,
                                      uint32_t trows, Rest... rest) {
-  if (trows && (f.row_hi - f.row_lo) % trows) return fail(c, NVDB_ERR_INTERNAL, "fp16 filter kernel: row range is not a multiple of its tile");
-  return launch_filter_kernel(c, f.s, kern, nwg, g, filter_rows_f16(c), f.row_lo, f.row_hi, static_cast<const _Float16*>(c->q16.p), f.nq, f.QT, f.thr,
-                              static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p), log, scatter_args(c, f.cap, trows), rest...);
+  if (trows && (rows.hi - rows.lo) % trows) return fail(c, NVDB_ERR_INTERNAL, "fp16 filter kernel: row range is not a multiple of its tile");
+  return launch_filter_kernel(c, run, kern, nwg, g, filter_rows_f16(c), rows.lo, rows.hi, static_cast<const _Float16*>(c->q16.p), run.nq, run.QT, run.thr,
+                              static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p), log, scatter_args(c, run, trows), rest...);
 }
 
-// ... every int8 build (rows, scales, range, the two query planes -- the lo plane qlo_off bytes behind the hi plane --, thresholds)
+// ... every int8 build (rows, scales, range, the two query planes -- the lo plane qlo_off bytes behind the hi plane --, thresholds; QT: of THIS build)
 template <typename... KA, typename... Rest>
-nvdb_status launch_filter_i8_kernel(nvdb_hip_ctx* c, const FilterCall& f, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, size_t qlo_off, Rest... rest) {
+nvdb_status launch_filter_i8_kernel(nvdb_hip_ctx* c, FilterRun& run, RowRange rows, uint32_t QT, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, size_t qlo_off, Rest... rest) {
   const signed char* qhi = static_cast<const signed char*>(c->q16.p);
-  return launch_filter_kernel(c, f.s, kern, nwg, g, filter_rows_i8(c), filter_scales_i8(c), f.row_lo, f.row_hi, qhi, qhi + qlo_off, f.nq, f.QT, f.thr,
+  return launch_filter_kernel(c, run, kern, nwg, g, filter_rows_i8(c), filter_scales_i8(c), rows.lo, rows.hi, qhi, qhi + qlo_off, run.nq, QT, run.thr,
                               static_cast<const float*>(c->qscale.p), static_cast<const float*>(c->qinv.p), rest...);
 }
 // ... and what the two-stage builds (filter_i8w / i8p / i8s_kernel) add: qdelta, log, scatter arguments, rendezvous, stage counts (misc[4], [5]: tiles past stage 0 / stage 1)
 template <typename... KA>
-nvdb_status launch_filter_i8w_kernel(nvdb_hip_ctx* c, const FilterCall& f, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, size_t qlo_off,
+nvdb_status launch_filter_i8w_kernel(nvdb_hip_ctx* c, FilterRun& run, RowRange rows, void (*kern)(KA...), uint32_t nwg, const FilterGeom& g, size_t qlo_off,
                                      uint32_t trows, const SyncArgs& sy) {
-  return launch_filter_i8_kernel(c, f, kern, nwg, g, qlo_off, static_cast<const float*>(c->qdelta.p), &c->hitlog, scatter_args(c, f.cap, trows), sy.prog,
-                                 sy.mask, sy.lead, static_cast<uint32_t*>(c->misc.p) + 4);
+  return launch_filter_i8_kernel(c, run, rows, run.QT, kern, nwg, g, qlo_off, static_cast<const float*>(c->qdelta.p), &c->hitlog, scatter_args(c, run, trows),
+                                 sy.prog, sy.mask, sy.lead, static_cast<uint32_t*>(c->misc.p) + 4);
 }
 
 }  // namespace nvdbhip

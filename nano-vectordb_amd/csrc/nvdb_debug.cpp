@@ -77,13 +77,13 @@ nvdb_status nvdb_hip_debug_clock(nvdb_hip_ctx* c, int variant, uint32_t nq, floa
   const size_t prog_bytes = static_cast<size_t>(nwg) * 8 * 4, stamp_bytes = static_cast<size_t>(nwg) * 16;
   if ((st = ensure(c, c->prog, prog_bytes + stamp_bytes))) return st;
   const uint32_t n_al = static_cast<uint32_t>(c->n / FILTER_ROWS * FILTER_ROWS);
-  const FilterCall f{c->stream, 0, n_al, nq, QT, c->last_cap, static_cast<const float*>(inf.p)};
+  FilterRun run{c->stream, FILTER_F16, false, nq, QT, nq_pad, c->last_cap, static_cast<const float*>(inf.p)};
   // 0: the 4-wave build; 20: the 8-wave production build (two waves per SIMD, 32 queries each); tiles in identity order
   const auto kern = variant == 0 ? filter_f16_m16_kernel<768, 6, true, true> : filter_f16_m16_kernel<768, 4, true, true, 2, 2, 8>;
   const uint32_t waves = variant == 0 ? 4 : 8;
   ClockStats cs;
   st = clock_bursts(c, nwg, prog_bytes, seconds, [&] {
-    return launch_filter_f16_kernel(c, f, kern, nwg, FilterGeom{64 * waves, filter_f16_m16_lds_bytes<768>(), waves, false}, &c->hitlog, 0,
+    return launch_filter_f16_kernel(c, run, {0, n_al}, kern, nwg, FilterGeom{64 * waves, filter_f16_m16_lds_bytes<768>(), waves, false}, &c->hitlog, 0,
                                     static_cast<uint32_t*>(c->prog.p), static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead));
   }, [] { return NVDB_OK; }, cs);
   (void)hipFree(inf.p);
@@ -127,12 +127,12 @@ nvdb_status nvdb_hip_debug_clock_i8(nvdb_hip_ctx* c, int variant, uint32_t nq, f
   if ((st = ensure(c, c->prog, std::max(prog_bytes + stamp_bytes, static_cast<size_t>(PROG_SLOTS) * c->num_cu * 8 * 4)))) return st;
   const uint64_t n_dbg = c->dbg_rows > 0 ? std::min<uint64_t>(c->n, static_cast<uint64_t>(c->dbg_rows)) : c->n;
   const uint32_t n_al = static_cast<uint32_t>(n_dbg / I8W_TILE_ROWS * I8W_TILE_ROWS);
-  const FilterCall f{c->stream, 0, n_al, nq, QT, c->last_cap, static_cast<const float*>(c->thr.p)};
+  FilterRun run{c->stream, FILTER_I8, c->last_perm /* ... and its tile order */, nq, QT, nq_pad, c->last_cap, static_cast<const float*>(c->thr.p)};
   const SyncArgs sy{static_cast<uint32_t*>(c->prog.p), static_cast<uint32_t>(c->opt_sync_every - 1), static_cast<uint32_t>(c->opt_sync_lead)};
   uint32_t* counts_dev = static_cast<uint32_t*>(c->misc.p) + 4;   // rare-path entries / lo-plane MFMA blocks: of the timed burst only
   ClockStats cs;
   st = clock_bursts(c, nwg, prog_bytes, seconds, [&] {
-    return launch_filter_i8w_kernel(c, f, kern, nwg, FilterGeom{64 * waves, lds, 8, false}, static_cast<size_t>(nq_pad) * 768, I8W_TILE_ROWS, sy);
+    return launch_filter_i8w_kernel(c, run, {0, n_al}, kern, nwg, FilterGeom{64 * waves, lds, 8, false}, static_cast<size_t>(nq_pad) * 768, I8W_TILE_ROWS, sy);
   }, [&]() -> nvdb_status { HIPCHK(c, hipMemsetAsync(counts_dev, 0, 8, c->stream)); return NVDB_OK; }, cs);
   if (st) return st;
   out4[0] = cs.ms; out4[1] = cs.ghz[0]; out4[2] = cs.ghz[1]; out4[3] = cs.ghz[2];
@@ -195,7 +195,7 @@ nvdb_status nvdb_hip_debug_plan(const nvdb_hip_plan_shape* shape, const nvdb_hip
   SearchPlan p;
   if (nvdb_status st = plan_search(c, nq, k, force_path, cap_override, p)) return failed(st, p.error);
   *out = nvdb_hip_plan{};
-  out->filter_shadow = p.route == ROUTE_FILTER && p.shadow;
+  out->filter_shadow = p.filter && p.kind == FILTER_SHADOW8;
   out->route = p.route; out->prep = p.prep; out->prep_inits = p.prep_inits; out->k_wide = p.k_wide;
   out->k_eff = p.k_eff; out->cap = p.cap; out->QPB = p.QPB; out->QT = p.QT; out->nq_pad = p.nq_pad; out->prog_words = p.prog_words;
   out->head = p.head;
@@ -205,7 +205,7 @@ nvdb_status nvdb_hip_debug_plan(const nvdb_hip_plan_shape* shape, const nvdb_hip
   out->padded = p.padded; out->perm_on = p.perm_on; out->boot = p.boot;
   out->tile_rows = p.tile_rows; out->n_al = p.n_al; out->growth = p.growth; out->boot_tiles = p.boot_tiles; out->boot_rows = p.boot_rows;
   out->r0 = p.r0; out->tail_exact = p.tail_exact;
-  out->helper_tile_rows = filter_tile_rows(&c, nq);
+  out->helper_tile_rows = filter_tile_rows(&c, p.kind, nq);
   out->stat_rows_scanned = p.tail_exact ? (c.n - p.n_al) * p.QT : 0;
   for (uint32_t r = p.r0; r < p.n_al; r = chunk_end(p, r)) {
     if (out->n_chunks == NVDB_PLAN_MAX_CHUNKS) return failed(NVDB_ERR_INTERNAL, "plan: more than NVDB_PLAN_MAX_CHUNKS chunks");

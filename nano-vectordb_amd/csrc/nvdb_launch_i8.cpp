@@ -19,13 +19,13 @@ nvdb_status launch_prep_q8(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, u
 
 #ifdef NVDB_HIP_DEV   // the two-plane int8 kernel (option i8_wide = 0): the reference build the two-stage kernels are compared with
 template <int DIM>
-nvdb_status launch_filter_i8_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t nq_pad) {
-  const uint32_t nwg = filter_grid(c, f.QT);
+nvdb_status launch_filter_i8_dim(nvdb_hip_ctx* c, FilterRun& run, RowRange rows) {
+  const uint32_t nwg = filter_grid(c, run.QT);
   nvdb_status st;
   SyncArgs sy;
-  if ((st = sibling_sync_args(c, f.s, f.QT, nwg, sy))) return st;
-  return launch_filter_i8_kernel(c, f, sy.prog ? filter_i8_kernel<DIM, false, 6, true> : filter_i8_kernel<DIM>, nwg, FilterGeom{256, filter_i8_lds_bytes<DIM>(), 4, true},
-                                 static_cast<size_t>(nq_pad) * DIM, &c->hitlog, scatter_args(c, f.cap, FILTER_ROWS), 0u, sy.prog, sy.mask, sy.lead);
+  if ((st = sibling_sync_args(c, run, nwg, sy))) return st;
+  return launch_filter_i8_kernel(c, run, rows, run.QT, sy.prog ? filter_i8_kernel<DIM, false, 6, true> : filter_i8_kernel<DIM>, nwg, FilterGeom{256, filter_i8_lds_bytes<DIM>(), 4, true},
+                                 static_cast<size_t>(run.nq_pad) * DIM, &c->hitlog, scatter_args(c, run, FILTER_ROWS), 0u, sy.prog, sy.mask, sy.lead);
 }
 #endif  // NVDB_HIP_DEV
 
@@ -42,12 +42,12 @@ template <int DIM, int WPB> auto i8s_build(bool sync) { return sync ? filter_i8s
 //   option i8_defer, signed / huge row scales: the pipelined build with the in-loop second stage (filter_i8p_kernel, DEFER)
 // and the developer library every build at every batch (options i8_pipe, i8_waves8, i8_mfma16, i8_small8).
 template <int DIM, int NB>
-nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t nq_pad) {
+nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, FilterRun& run, RowRange rows) {
   constexpr uint32_t TROWS = i8w_tile_rows(DIM);
   static_assert(TROWS == I8W_TILE_ROWS, "the builds of dims <= 768 stream two 32-row blocks per tile");
-  if ((f.row_hi - f.row_lo) % TROWS) return fail(c, NVDB_ERR_INTERNAL, "int8 two-stage kernel: row range is not a multiple of its 64-row tile");
-  const bool pipe = i8_pipelined(c, NB);                 // (developer build: i8_pipe = 0 runs filter_i8w_kernel at 64 queries per wave, i8_waves8 = 1 the 8-wave pipelined build)
-  const bool defer = i8_stage2_in_loop(c), logs = i8_logs_survivors(c, NB);
+  if ((rows.hi - rows.lo) % TROWS) return fail(c, NVDB_ERR_INTERNAL, "int8 two-stage kernel: row range is not a multiple of its 64-row tile");
+  const bool pipe = i8_pipelined(c, run.kind, NB);       // (developer build: i8_pipe = 0 runs filter_i8w_kernel at 64 queries per wave, i8_waves8 = 1 the 8-wave pipelined build)
+  const bool defer = i8_stage2_in_loop(c), logs = i8_logs_survivors(c, run.kind, NB);
 #ifdef NVDB_HIP_DEV
   const bool w8 = pipe && c->opt_i8_waves8 && DIM != 384;
   constexpr bool HAS_I8W = true, HAS_I8P32 = true, DEV_I8S8_512 = true;
@@ -57,24 +57,24 @@ nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t
   constexpr bool HAS_I8W = (NB == 1);                    // the product runs filter_i8w_kernel for batches <= 128 only
   constexpr bool HAS_I8P32 = (DIM < 384);                // ... and the 32x32x32 logged build only where the 16x16x64 build does not exist
 #endif
-  const uint32_t nwg = filter_grid(c, f.QT);
+  const uint32_t nwg = filter_grid(c, run.QT);
   nvdb_status st;
   SyncArgs sy;
-  if ((st = sibling_sync_args(c, f.s, f.QT, nwg, sy))) return st;
+  if ((st = sibling_sync_args(c, run, nwg, sy))) return st;
   const bool sync = sy.prog != nullptr;
   // (every build's survivor log is sized for 8 waves per workgroup)
   auto launch = [&](auto kern, uint32_t waves, size_t lds) {
-    return launch_filter_i8w_kernel(c, f, kern, nwg, FilterGeom{64 * waves, lds, 8, true}, static_cast<size_t>(nq_pad) * DIM, TROWS, sy);
+    return launch_filter_i8w_kernel(c, run, rows, kern, nwg, FilterGeom{64 * waves, lds, 8, true}, static_cast<size_t>(run.nq_pad) * DIM, TROWS, sy);
   };
   // batches <= 128 at d = 512 / 768: the 16x16x64 logged build on 8 waves of 32 queries (waves without queries only load): its first-stage
   // test rides in the MFMA shadow, so four busy waves stay inside the tile time the HBM stream allows (+6.5 % at batch 128,
   // +2.4 % at 64 over filter_i8w_kernel<768, 1>, profiles/r03_i8_small_batch_ab.txt); signed / huge scales keep the in-loop build.
   // One query tile has no siblings: the SYNC = false instantiation alone.
   if constexpr (NB == 1 && (DIM == 768 || DIM == 512))
-    if (c->opt_i8_small8 && !defer && f.QT == 1 && f.nq > 8)       // (a handful of queries: equal within noise, the old kernel stays)
+    if (c->opt_i8_small8 && !defer && run.QT == 1 && run.nq > 8)   // (a handful of queries: equal within noise, the old kernel stays)
       return launch(filter_i8s_kernel<DIM, false, false, 6, 8>, 8, filter_i8s_lds_bytes<DIM, 8>());
   if constexpr (NB == 1 && DIM == 384)               // d = 384 has no 8-wave schedule: 64 < batch <= 128 on the 4-wave build, two waves without queries (+4 % at 128; equal at 64)
-    if (c->opt_i8_small8 && !defer && f.QT == 1 && f.nq > 64)
+    if (c->opt_i8_small8 && !defer && run.QT == 1 && run.nq > 64)
       return launch(filter_i8s_kernel<DIM, false, false, 6, 4>, 4, filter_i8s_lds_bytes<DIM, 4>());
   if (logs && c->opt_i8_mfma16) {
     // d = 768: on 8 waves of 32 queries, two per SIMD (option i8_dense8).  A flagged block runs rare_log, serial work during which a lone wave's
@@ -101,43 +101,41 @@ nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t
 // int8, 768 < dim <= 1536: the two-stage kernel on 32-row tiles with one 32-query block per wave (128 queries per workgroup);
 // the reference takes any dim (src/simd_dot.cpp:160-213)
 template <int DIM>
-nvdb_status launch_filter_i8w_big_dim(nvdb_hip_ctx* c, const FilterCall& f, uint32_t nq_pad) {
+nvdb_status launch_filter_i8w_big_dim(nvdb_hip_ctx* c, FilterRun& run, RowRange rows) {
   constexpr uint32_t TROWS = i8w_tile_rows(DIM);
   static_assert(TROWS == FILTER_ROWS, "the builds of dims > 768 stream one 32-row block per tile");
-  if ((f.row_hi - f.row_lo) % TROWS) return fail(c, NVDB_ERR_INTERNAL, "int8 kernel: row range is not a multiple of its 32-row tile");
-  const uint32_t nwg = filter_grid(c, f.QT);
+  if ((rows.hi - rows.lo) % TROWS) return fail(c, NVDB_ERR_INTERNAL, "int8 kernel: row range is not a multiple of its 32-row tile");
+  const uint32_t nwg = filter_grid(c, run.QT);
   nvdb_status st;
   SyncArgs sy;
-  if ((st = sibling_sync_args(c, f.s, f.QT, nwg, sy))) return st;
-  return launch_filter_i8w_kernel(c, f, i8w_build<DIM, 1, 1>(sy.prog != nullptr), nwg, FilterGeom{256, filter_i8w_lds_bytes<DIM, 1>(), 4, true},
-                                  static_cast<size_t>(nq_pad) * DIM, TROWS, sy);
+  if ((st = sibling_sync_args(c, run, nwg, sy))) return st;
+  return launch_filter_i8w_kernel(c, run, rows, i8w_build<DIM, 1, 1>(sy.prog != nullptr), nwg, FilterGeom{256, filter_i8w_lds_bytes<DIM, 1>(), 4, true},
+                                  static_cast<size_t>(run.nq_pad) * DIM, TROWS, sy);
 }
 
-// the boot build is the 128-queries-per-workgroup two-plane kernel; QT counts ITS query tiles (the caller multiplies by nb)
+// the boot build is the 128-queries-per-workgroup two-plane kernel: QT counts ITS query tiles, nb per tile of the run (same padded batch)
 template <int DIM>
-nvdb_status launch_boot_i8_dim(nvdb_hip_ctx* c, const FilterCall& f) {
-  return launch_filter_i8_kernel(c, f, filter_i8_kernel<DIM, true>, filter_grid(c, f.QT), FilterGeom{256, filter_i8_lds_bytes<DIM>(), 0, false},
-                                 static_cast<size_t>(f.QT) * 128u * DIM, &c->cand, scatter_args(c, f.cap, FILTER_ROWS), f.cap, static_cast<uint32_t*>(nullptr), 0u, 0u);
+nvdb_status launch_boot_i8_dim(nvdb_hip_ctx* c, FilterRun& run, RowRange rows) {
+  const uint32_t QT = run.nq_pad / 128u;
+  return launch_filter_i8_kernel(c, run, rows, QT, filter_i8_kernel<DIM, true>, filter_grid(c, QT), FilterGeom{256, filter_i8_lds_bytes<DIM>(), 0, false},
+                                 static_cast<size_t>(run.nq_pad) * DIM, &c->cand, scatter_args(c, run, FILTER_ROWS), run.cap, static_cast<uint32_t*>(nullptr), 0u, 0u);
 }
 
-nvdb_status launch_boot_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t n0, uint32_t nq, uint32_t QT, uint32_t cap) {
-  const FilterCall f{s, 0, n0, nq, QT, cap, static_cast<const float*>(c->thr.p)};
+nvdb_status launch_boot_i8(nvdb_hip_ctx* c, FilterRun& run, uint32_t n0) {
   nvdb_status st;
-  if (dispatch_dim(I8Dims{}, c->fdim, st, [&](auto D) { return launch_boot_i8_dim<decltype(D)::value>(c, f); })) return st;
+  if (dispatch_dim(I8Dims{}, c->fdim, st, [&](auto D) { return launch_boot_i8_dim<decltype(D)::value>(c, run, RowRange{0, n0}); })) return st;
   return fail(c, NVDB_ERR_UNSUPPORTED, "int8 boot kernel: unsupported dim");
 }
 
-nvdb_status launch_filter_i8(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint32_t row_hi, uint32_t nq, uint32_t QT, uint32_t cap) {
-  const uint32_t nb = filter_nb(c, nq);
-  const uint32_t nq_pad = QT * filter_qpb(c, nq);
-  const FilterCall f{s, row_lo, row_hi, nq, QT, cap, static_cast<const float*>(c->thr.p)};
+nvdb_status launch_filter_i8(nvdb_hip_ctx* c, FilterRun& run, RowRange rows) {
+  const uint32_t nb = filter_nb(c, run.kind, run.nq);
   nvdb_status st;
-  if (dispatch_dim(I8DimsBig{}, c->fdim, st, [&](auto D) { return launch_filter_i8w_big_dim<decltype(D)::value>(c, f, nq_pad); })) return st;
-  if (i8_two_stage(c) && dispatch_dim(I8Dims{}, c->fdim, st, [&](auto D) {
-        return nb == 2 ? launch_filter_i8w_dim<decltype(D)::value, 2>(c, f, nq_pad) : launch_filter_i8w_dim<decltype(D)::value, 1>(c, f, nq_pad);
+  if (dispatch_dim(I8DimsBig{}, c->fdim, st, [&](auto D) { return launch_filter_i8w_big_dim<decltype(D)::value>(c, run, rows); })) return st;
+  if (i8_two_stage(c, run.kind) && dispatch_dim(I8Dims{}, c->fdim, st, [&](auto D) {
+        return nb == 2 ? launch_filter_i8w_dim<decltype(D)::value, 2>(c, run, rows) : launch_filter_i8w_dim<decltype(D)::value, 1>(c, run, rows);
       })) return st;
 #ifdef NVDB_HIP_DEV
-  if (dispatch_dim(I8Dims{}, c->fdim, st, [&](auto D) { return launch_filter_i8_dim<decltype(D)::value>(c, f, nq_pad); })) return st;
+  if (dispatch_dim(I8Dims{}, c->fdim, st, [&](auto D) { return launch_filter_i8_dim<decltype(D)::value>(c, run, rows); })) return st;
 #endif
   return fail(c, NVDB_ERR_UNSUPPORTED, "int8 filter kernel: unsupported dim");
 }

@@ -138,7 +138,7 @@ nvdb_status parts_call_begin(nvdb_hip_ctx* c, uint32_t path) {
   c->stats.path = path;
   c->stats_lazy = false;
   c->last_nq = 0; c->last_cap = 0; c->last_filter = false;           // (nvdb_hip_search_check describes flat searches)
-  c->last_filter_kind = 0;
+  c->last_filter_kind = FILTER_NONE;
   return NVDB_OK;
 }
 

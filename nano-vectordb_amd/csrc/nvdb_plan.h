@@ -1,8 +1,8 @@
 // nvdb_plan.h -- everything one flat search decides before its first launch (DESIGN.md "pipeline"): route, list capacity,
 // which filter streams, query tiling, bootstrap, chunk boundaries.  plan_search is pure integer arithmetic over corpus facts
-// and options: no HIP call, so tests/test_search_plan_cpu.py pins it without a device (nvdb_hip_debug_plan).  It writes ONE
-// context field, use_shadow (which of a shadow context's two filters streams this search): the shape facts it shares with
-// the launchers (tile rows, queries per workgroup, which int8 build logs; nvdb_ctx.h) are read off the context and follow it.
+// and options: no HIP call and a const context, so tests/test_search_plan_cpu.py pins it without a device (nvdb_hip_debug_plan).
+// Which filter streams is chosen once (filter_kind, nvdb_ctx.h) and carried in the plan: the shape facts plan_search shares with
+// the launchers (tile rows, queries per workgroup, which int8 build logs; nvdb_ctx.h) take it as an argument, here and there.
 #pragma once
 #include "nvdb_ctx.h"
 
@@ -13,23 +13,20 @@ enum Route : uint32_t { ROUTE_EXACT = 1, ROUTE_FILTER = 2, ROUTE_ANYK = 3 };   /
 // rows [0, r0) on the exact kernel, or (64 < k) the k best of rows [0, r0) from the any-k machinery seeding the lists
 enum Boot : uint32_t { BOOT_MFMA = 0, BOOT_EXACT_CHUNK = 1, BOOT_ANYK_SEEDED = 2 };
 
-struct SearchPlan {
+// filter == (route == ROUTE_FILTER); prep without filter: the any-k route when only the bootstrap rules sent a 64 < k search there (its fused init does the per-search resets)
+struct SearchPlan : FilterPlan {
   const char* error = nullptr;          // message of the NVDB_ERR_UNSUPPORTED plan_search returned
   Route route = ROUTE_EXACT;
-  bool prep = false;                    // the filter flow's prep launch runs: the filter route, and the any-k route when only the
-                                        // bootstrap rules sent a 64 < k search there (its fused init does the per-search resets)
-  bool prep_inits = false;              // ... and does the per-search resets itself (option fuse); else init_search_kernel
   bool k_wide = false;                  // k beyond the wavefront lists' 64 entries
-  uint32_t k_eff = 0, cap = 0, QPB = 0, QT = 0, nq_pad = 0, prog_words = 0;
+  uint32_t k_eff = 0;
   uint32_t head = 0;                    // exact route: rows of the prescan (0: one scan)
   // filter route
-  bool padded = false, perm_on = false;
+  bool padded = false;
   Boot boot = BOOT_MFMA;
   uint32_t tile_rows = 0, n_al = 0, growth = 0, boot_tiles = 0, boot_rows = 0;
   uint32_t r0 = 0;                      // rows the exact / seeded bootstrap covers; the chunks tile [r0, n_al)
   uint64_t size0 = 0;                   // rows of the first chunk; every later one covers (growth - 1) x the rows before it
   bool tail_exact = false;              // ragged tail [n_al, n) of an adopted corpus on the exact kernel
-  bool shadow = false;                  // the filter launches stream the int8 shadow of an fp16 / fp32 corpus (else: the kernels of the corpus' own dtype)
 };
 
 // end of the chunk that starts at row r
@@ -38,13 +35,11 @@ inline uint32_t chunk_end(const SearchPlan& p, uint32_t r) {
   return static_cast<uint32_t>(std::min<uint64_t>(p.n_al, r + size));
 }
 
-inline nvdb_status plan_search(nvdb_hip_ctx& ctx, uint32_t nq, uint32_t k, int force_path, uint32_t cap_override, SearchPlan& p) {
-  // a shadow context: the int8 shadow streams unless it was switched off or has overflowed on this corpus (shadow_preferred);
-  // everything below -- tiles, queries per workgroup, growth, bootstrap -- is then that filter's
-  ctx.use_shadow = shadow_preferred(&ctx);
+inline nvdb_status plan_search(const nvdb_hip_ctx& ctx, uint32_t nq, uint32_t k, int force_path, uint32_t cap_override, SearchPlan& p) {
   const nvdb_hip_ctx* c = &ctx;
   p = SearchPlan{};
-  p.shadow = c->use_shadow;
+  // (a shadow context: the shadow unless it was switched off or has overflowed on this corpus); tiles, queries per workgroup, growth, bootstrap below are that filter's
+  const FilterKind kind = p.kind = filter_kind(c);
   const uint32_t n = static_cast<uint32_t>(c->n);
   const uint32_t k_eff = p.k_eff = static_cast<uint32_t>(std::min<uint64_t>(k, c->n));
   int path = force_path ? force_path : static_cast<int>(c->opt_path);
@@ -68,7 +63,7 @@ inline nvdb_status plan_search(nvdb_hip_ctx& ctx, uint32_t nq, uint32_t k, int f
                               c->fdim <= 768 && c->n >= 2ull * FILTER_ROWS * 8 * k_eff);
   if (wide_on_filter) cap = SELECT_MAX_CAP;
   p.cap = cap;
-  p.QPB = filter_qpb(c, nq);
+  p.QPB = filter_qpb(c, kind, nq);
   p.QT = (nq + p.QPB - 1) / p.QPB;
   p.nq_pad = p.QT * p.QPB;
   // one region of sibling-rendezvous counters per filter launch of this search, all reset by the init kernel
@@ -90,16 +85,16 @@ inline nvdb_status plan_search(nvdb_hip_ctx& ctx, uint32_t nq, uint32_t k, int f
   // ---- the filter route ----
   // Whole tiles: the padded rows of a corpus this library allocated are dropped when the wave files its survivors; for an
   // adopted corpus the ragged tail goes to the exact kernel.  Chunk boundaries are whole tiles of the streaming kernel.
-  p.padded = corpus_padded(c);
-  const uint32_t tile_rows = p.tile_rows = filter_tile_rows(c, nq);
+  p.padded = corpus_padded(c, kind);
+  const uint32_t tile_rows = p.tile_rows = filter_tile_rows(c, kind, nq);
   const uint32_t n_al = p.n_al = p.padded ? (n + tile_rows - 1) / tile_rows * tile_rows : n / tile_rows * tile_rows;
   // chunk i covers (growth-1) x the rows seen before it.  fp16: 8 (flat between 4 and 8).  int8 batches > 128: 3 --
   // tighter thresholds earlier mean fewer tiles for which the two-stage kernel needs the lo plane, and a tile costs
   // what its slowest wave costs (profiles/r01d_i8_growth_sweep.txt)
   // (with the first-stage survivors finished after the stream a flagged value costs little: 6 and a 1024-tile bootstrap on big
   // corpora, profiles/r02_i8_boot_growth_sweep.txt; the in-loop second stage wants 3)
-  const bool i8_big = i8_two_stage(c) && nq > 128 && c->fdim <= 768;
-  const bool i8_log = i8_big && i8_logs_survivors(c, filter_nb(c, nq)) && !c->opt_i8_waves8 && c->n >= 64ull * FILTER_ROWS * 1024;
+  const bool i8_big = i8_two_stage(c, kind) && nq > 128 && c->fdim <= 768;
+  const bool i8_log = i8_big && i8_logs_survivors(c, kind, filter_nb(c, kind, nq)) && !c->opt_i8_waves8 && c->n >= 64ull * FILTER_ROWS * 1024;
   uint64_t growth = c->opt_growth > 0 ? static_cast<uint64_t>(c->opt_growth) : (i8_log ? 6u : i8_big ? 3u : 8u);
   if (k_wide) growth = std::max<uint64_t>(2, std::min<uint64_t>(growth, cap / (3ull * k_eff)));     // k * (growth - 1) + k + band <= cap
   p.growth = static_cast<uint32_t>(growth);
@@ -130,7 +125,7 @@ inline nvdb_status plan_search(nvdb_hip_ctx& ctx, uint32_t nq, uint32_t k, int f
   // 64 < k on the filter path needs the MFMA bootstrap (the exact bootstrap chunk's wavefront lists hold 64 entries) or the
   // seeded one; e.g. option boot_tiles larger than the corpus: the any-k path takes the search instead, after the prep launch
   if (k_wide && !mfma_boot && !wide_exact_boot) { p.route = ROUTE_ANYK; return NVDB_OK; }
-  p.route = ROUTE_FILTER;
+  p.route = ROUTE_FILTER; p.filter = true;
   p.boot = mfma_boot ? BOOT_MFMA : k_wide ? BOOT_ANYK_SEEDED : BOOT_EXACT_CHUNK;
   // permuted tile order needs the bootstrap whose entries are discarded (the exact bootstrap chunk keeps rows [0, r0))
   p.perm_on = c->opt_tile_permute && mfma_boot;

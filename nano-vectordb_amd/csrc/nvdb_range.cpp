@@ -15,11 +15,11 @@
 
 namespace nvdbhip {
 
-// Pure arithmetic over corpus facts and options, like plan_search (and like it, it sets use_shadow, which the shape helpers read).
-nvdb_status plan_range(nvdb_hip_ctx& ctx, uint32_t nq, RangePlan& p) {
-  ctx.use_shadow = shadow_preferred(&ctx);
+// Pure arithmetic over corpus facts and options, like plan_search (and like it, it chooses the filter kind once and carries it in the plan).
+nvdb_status plan_range(const nvdb_hip_ctx& ctx, uint32_t nq, RangePlan& p) {
   const nvdb_hip_ctx* c = &ctx;
   p = RangePlan{};
+  const FilterKind kind = p.kind = filter_kind(c);
   int path = static_cast<int>(c->opt_path);
   if (path == 0) path = (filter_supported(c) && nq >= c->opt_min_filter_batch && c->n >= 4ull * c->opt_chunk0) ? 2 : 1;
   if (path == 2 && !filter_supported(c)) {
@@ -27,19 +27,19 @@ nvdb_status plan_range(nvdb_hip_ctx& ctx, uint32_t nq, RangePlan& p) {
     return NVDB_ERR_UNSUPPORTED;
   }
   if (path != 2) return NVDB_OK;
-  p.filter = true;
+  p.filter = p.prep = true;
   // The longest lists the keep kernel orders in LDS: how many rows reach a radius is the caller's choice, not a property of the corpus
   // (even: the pack kernel moves two entries per 16-byte access)
   p.cap = c->opt_cap > 0 ? std::min<uint32_t>(static_cast<uint32_t>(c->opt_cap), SELECT_MAX_CAP) : SELECT_MAX_CAP;
   p.cap = std::max<uint32_t>(2u, (p.cap + 1u) & ~1u);
-  p.QPB = filter_qpb(c, nq);
+  p.QPB = filter_qpb(c, kind, nq);
   p.QT = (nq + p.QPB - 1) / p.QPB;
   p.nq_pad = p.QT * p.QPB;
   p.prog_words = PROG_SLOTS * static_cast<uint32_t>(c->num_cu) * 8u;
   p.prep_inits = c->opt_fuse != 0;
   const uint32_t n = static_cast<uint32_t>(c->n);
-  p.tile_rows = filter_tile_rows(c, nq);
-  p.n_al = corpus_padded(c) ? (n + p.tile_rows - 1) / p.tile_rows * p.tile_rows : n / p.tile_rows * p.tile_rows;
+  p.tile_rows = filter_tile_rows(c, kind, nq);
+  p.n_al = corpus_padded(c, kind) ? (n + p.tile_rows - 1) / p.tile_rows * p.tile_rows : n / p.tile_rows * p.tile_rows;
   p.tail_exact = p.n_al < n;
   // Launches.  A wave logs at most FILTER_LOGCAP survivors per launch, and a range search has no thresholds that tighten from chunk to
   // chunk: what bounds the pressure on a log is the number of launches alone.  Four launches give every wave 4 x 4096 entries -- with
@@ -117,28 +117,14 @@ nvdb_status range_filter_pass(nvdb_hip_ctx* c, hipStream_t s, const RangePlan& p
                               FilterVerdict& v) {
   nvdb_status st;
   const uint32_t n = static_cast<uint32_t>(c->n), cap = p.cap, QT = p.QT;
-  const size_t per_q = static_cast<size_t>(p.nq_pad) * 4;
-  const struct { DevBuf& buf; size_t bytes; } workspace[] = {
-      {c->thr, per_q}, {c->cnt, per_q}, {c->overflow, per_q}, {c->cand, static_cast<size_t>(nq) * cap * sizeof(Cand)}, {c->misc, 64},
-      {c->prog, static_cast<size_t>(p.prog_words) * 4}, {c->tickets, FUSE_TICKETS * 4}, {c->q16, static_cast<size_t>(p.nq_pad) * c->fdim * 2},
-      {c->qscale, per_q}, {c->qinv, per_q}, {c->ebound, per_q}, {c->slack, per_q}, {c->qdelta, per_q}, {c->rg_kept, per_q}};
-  for (const auto& w : workspace)
-    if ((st = ensure(c, w.buf, w.bytes))) return st;
-  c->ev_filter.clear();
-  c->prog_slot = 0;
-  c->perm_on = p.perm_on;
-  c->last_filter_kind = (c->q8shadow && c->use_shadow) ? 2u : c->dtype == NVDB_DTYPE_I8 ? 3u : 1u;
-  if (!p.prep_inits && (st = launch_init_search(c, s, p.nq_pad, QT > 1 ? p.prog_words : 0u))) return st;
-  const PrepInit pinit = p.prep_inits ? PrepInit{static_cast<uint32_t*>(c->cnt.p), static_cast<float*>(c->thr.p), static_cast<uint32_t*>(c->misc.p),
-                                                 static_cast<uint32_t*>(c->prog.p), QT > 1 ? p.prog_words : 0u, static_cast<uint32_t*>(c->tickets.p), nullptr, nullptr}
-                                      : PrepInit{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, nullptr};
-  if ((st = filter_is_i8(c) ? launch_prep_q8(c, s, dq, nq, p.nq_pad, pinit) : launch_prep_q16(c, s, dq, nq, p.nq_pad, pinit))) return st;
+  FilterRun run;
+  if ((st = begin_filter_run(c, s, p, dq, nullptr, nq, &c->rg_kept, run))) return st;
   range_thr_kernel<<<(p.nq_pad + 255) / 256, 256, 0, s>>>(dradius, static_cast<const float*>(c->ebound.p), static_cast<float*>(c->thr.p),
                                                           static_cast<uint32_t*>(c->overflow.p), nq, p.nq_pad);
   HIPCHK(c, hipGetLastError());
   for (uint32_t r = 0; r < p.n_al;) {
     const uint32_t hi = static_cast<uint32_t>(std::min<uint64_t>(p.n_al, static_cast<uint64_t>(r) + p.launch_rows));
-    if ((st = filter_is_i8(c) ? launch_filter_i8(c, s, r, hi, nq, QT, cap) : launch_filter_f16(c, s, r, hi, nq, QT, cap))) return st;
+    if ((st = launch_filter(c, run, {r, hi}))) return st;
     c->stats.chunks++;
     c->stats.rows_scanned += static_cast<uint64_t>(hi - r) * QT;
     r = hi;
@@ -212,7 +198,7 @@ nvdb_status range_search_flat(nvdb_hip_ctx* c, const char* who, const float* que
   c->stats.path = msel ? RANGE_STAT_PARTS : RANGE_STAT_EXACT;
   c->stats_lazy = false;
   c->last_nq = 0; c->last_cap = 0; c->last_filter = false;           // (nvdb_hip_search_check describes flat searches)
-  c->last_filter_kind = 0;
+  c->last_filter_kind = FILTER_NONE;
   bool any_filter = false;
   RangeOut out;
   out.budget_entries = (static_cast<uint64_t>(c->opt_range_max_mb) << 20) / 12;

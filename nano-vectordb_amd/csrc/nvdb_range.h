@@ -107,15 +107,15 @@ nvdb_status range_parts_core(nvdb_hip_ctx* c, hipStream_t s, const char* who, co
 nvdb_status launch_range_parts(nvdb_hip_ctx* c, hipStream_t s, uint32_t qw, bool staged, const float* radius, const ScanArgs& a);
 
 // ---- the flat range search's plan and filter pass (nvdb_range.cpp), as the masked flat top-k (nvdb_masked_flat.cpp) calls them
-struct RangePlan {
+// FilterPlan (nvdb_ctx.h): kind, cap, query tiling, prep_inits, perm_on; filter (== prep): the filter route serves this sub-batch (else: the exact route alone)
+struct RangePlan : FilterPlan {
   const char* error = nullptr;
-  bool filter = false;                  // the filter route serves this call's sub-batches (else: the exact route alone)
-  bool prep_inits = false, perm_on = false, tail_exact = false;
-  uint32_t cap = 0, QPB = 0, QT = 0, nq_pad = 0, prog_words = 0, tile_rows = 0, n_al = 0;
+  bool tail_exact = false;
+  uint32_t tile_rows = 0, n_al = 0;
   uint32_t launch_rows = 0;             // rows per filter launch
 };
 // the route and shapes of one sub-batch of nq queries; p.error: why a forced route is refused
-nvdb_status plan_range(nvdb_hip_ctx& ctx, uint32_t nq, RangePlan& p);
+nvdb_status plan_range(const nvdb_hip_ctx& ctx, uint32_t nq, RangePlan& p);
 
 // what the host reads of one filter pass
 struct FilterVerdict {

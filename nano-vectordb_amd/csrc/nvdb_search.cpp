@@ -45,37 +45,58 @@ nvdb_status zero_q32_pad(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes) {
 
 // rendezvous counters for the next filter launch: a region the init kernel already cleared, or (past PROG_SLOTS
 // launches in one search) a region cleared here
-nvdb_status next_prog_region(nvdb_hip_ctx* c, hipStream_t s, uint32_t nwg, uint32_t** out) {
+nvdb_status next_prog_region(nvdb_hip_ctx* c, FilterRun& run, uint32_t nwg, uint32_t** out) {
   const size_t region_words = static_cast<size_t>(c->num_cu) * 8;
   if (nwg * 8u > region_words) return fail(c, NVDB_ERR_INTERNAL, "rendezvous region too small for this grid");
-  uint32_t* base = static_cast<uint32_t*>(c->prog.p) + static_cast<size_t>(c->prog_slot % PROG_SLOTS) * region_words;
-  if (c->prog_slot >= PROG_SLOTS) HIPCHK(c, hipMemsetAsync(base, 0xFF, region_words * 4, s));
-  ++c->prog_slot;
+  uint32_t* base = static_cast<uint32_t*>(c->prog.p) + static_cast<size_t>(run.prog_slot % PROG_SLOTS) * region_words;
+  if (run.prog_slot >= PROG_SLOTS) HIPCHK(c, hipMemsetAsync(base, 0xFF, region_words * 4, run.s));
+  ++run.prog_slot;
   *out = base;
   return NVDB_OK;
 }
 
 // trows = rows per tile of the kernel being launched (0: identity tile order).  With the permutation on, logical tile g
 // of the corpus' T = ceil-or-floor(n / trows) tiles is streamed from physical tile perm_tile(g) (kernels_filter.h).
-ScatterArgs scatter_args(nvdb_hip_ctx* c, uint32_t cap, uint32_t trows) {
+ScatterArgs scatter_args(nvdb_hip_ctx* c, const FilterRun& run, uint32_t trows) {
   ScatterArgs a{static_cast<Cand*>(c->cand.p), static_cast<uint32_t*>(c->cnt.p), static_cast<uint32_t*>(c->overflow.p),
-                static_cast<uint32_t*>(c->misc.p) + 1, cap, static_cast<uint32_t>(c->n), 1u, 0u, 0u,
+                static_cast<uint32_t*>(c->misc.p) + 1, run.cap, static_cast<uint32_t>(c->n), 1u, 0u, 0u,
                 c->opt_xcd_balance ? static_cast<float*>(c->xcdw.p) : nullptr, static_cast<uint32_t>(c->opt_i8_lo_bits)};
-  if (trows && c->perm_on) {
+  if (trows && run.perm) {
     const uint32_t n = static_cast<uint32_t>(c->n);
-    a.perm_T = corpus_padded(c) ? (n + trows - 1) / trows : n / trows;
+    a.perm_T = corpus_padded(c, run.kind) ? (n + trows - 1) / trows : n / trows;
     perm_params(a.perm_T, a.perm_mul, a.perm_mask);
   }
   return a;
 }
 
-nvdb_status launch_boot(nvdb_hip_ctx* c, hipStream_t s, uint32_t n0, uint32_t nq, uint32_t QT, uint32_t cap, uint32_t nb) {
-  // (int8: the boot build is the 128-queries-per-workgroup kernel; same padded batch)
-  return filter_is_i8(c) ? launch_boot_i8(c, s, n0, nq, QT * nb, cap) : launch_boot_f16(c, s, n0, nq, QT, cap, nb);
-}
+nvdb_status launch_boot(nvdb_hip_ctx* c, FilterRun& run, uint32_t n0) { return filter_is_i8(run.kind) ? launch_boot_i8(c, run, n0) : launch_boot_f16(c, run, n0); }
+nvdb_status launch_filter(nvdb_hip_ctx* c, FilterRun& run, RowRange rows) { return filter_is_i8(run.kind) ? launch_filter_i8(c, run, rows) : launch_filter_f16(c, run, rows); }
 
-nvdb_status launch_filter(nvdb_hip_ctx* c, hipStream_t s, uint32_t row_lo, uint32_t row_hi, uint32_t nq, uint32_t QT, uint32_t cap) {
-  return filter_is_i8(c) ? launch_filter_i8(c, s, row_lo, row_hi, nq, QT, cap) : launch_filter_f16(c, s, row_lo, row_hi, nq, QT, cap);
+nvdb_status begin_filter_run(nvdb_hip_ctx* c, hipStream_t s, const FilterPlan& p, const float* dev_q, const float* host_q, uint32_t nq, DevBuf* extra, FilterRun& run) {
+  nvdb_status st;
+  const size_t per_q = static_cast<size_t>(p.nq_pad) * 4;
+  const struct { DevBuf& buf; size_t bytes; bool filter_flow; } workspace[] = {
+      {c->thr, per_q, false}, {c->cnt, per_q, false}, {c->overflow, per_q, false}, {c->cand, static_cast<size_t>(nq) * p.cap * sizeof(Cand), false},
+      {c->misc, 64, false}, {c->prog, static_cast<size_t>(p.prog_words) * 4, false}, {c->tickets, FUSE_TICKETS * 4, false},
+      {c->q16, static_cast<size_t>(p.nq_pad) * c->fdim * 2, true}, {c->qscale, per_q, true}, {c->qinv, per_q, true},
+      {c->ebound, per_q, true}, {c->slack, per_q, true}, {c->qdelta, per_q, true}};
+  for (const auto& w : workspace)
+    if ((p.prep || !w.filter_flow) && (st = ensure(c, w.buf, w.bytes))) return st;
+  if (extra && (st = ensure(c, *extra, per_q))) return st;
+  // what the last search's filter launches did, from the plan (the rest of "the last search" is the caller's to record)
+  c->ev_filter.clear();
+  c->last_filter_kind = p.filter ? p.kind : FILTER_NONE;
+  if (p.filter) c->last_perm = p.perm_on;
+  run = FilterRun{s, p.kind, p.perm_on, nq, p.QT, p.nq_pad, p.cap, static_cast<const float*>(c->thr.p)};
+  // per-search resets and queries: the prep launch does both itself (option fuse), else init_search_kernel and a copy (one query tile: no siblings, no counters to reset)
+  const uint32_t prog_words = p.QT > 1 ? p.prog_words : 0u;
+  if (host_q && !p.prep_inits) { HIPCHK(c, hipMemcpyAsync(const_cast<float*>(dev_q), host_q, static_cast<size_t>(nq) * c->dim * 4, hipMemcpyDefault, s)); host_q = nullptr; }   // (host_q is the pinned block as the device addresses it)
+  if (!p.prep_inits && (st = launch_init_search(c, s, p.nq_pad, prog_words))) return st;
+  if (!p.prep) return NVDB_OK;
+  PrepInit pinit{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, nullptr};
+  if (p.prep_inits) pinit = PrepInit{static_cast<uint32_t*>(c->cnt.p), static_cast<float*>(c->thr.p), static_cast<uint32_t*>(c->misc.p), static_cast<uint32_t*>(c->prog.p),
+                                     prog_words, static_cast<uint32_t*>(c->tickets.p), host_q, const_cast<float*>(dev_q)};   // (the copy is written only where host_q is read)
+  return filter_is_i8(p.kind) ? launch_prep_q8(c, s, dev_q, nq, p.nq_pad, pinit) : launch_prep_q16(c, s, dev_q, nq, p.nq_pad, pinit);
 }
 
 // Enqueue one whole search of nq (<= 2048) queries resident at dev_q: plan (nvdb_plan.h), workspace, launches.  No host synchronisation.
@@ -92,32 +113,12 @@ nvdb_status search_core(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint
   if (st) return fail(c, st, p.error);
   const int final_mode = sticky ? 1 : 3;          // select_kernel: 3 = final select without folding into the sticky self-check words
   const uint32_t n = static_cast<uint32_t>(c->n), k_eff = p.k_eff, cap = p.cap, QT = p.QT;
-  const size_t per_q = static_cast<size_t>(p.nq_pad) * 4;
-  const struct { DevBuf& buf; size_t bytes; bool filter_flow; } workspace[] = {
-      {c->thr, per_q, false}, {c->cnt, per_q, false}, {c->overflow, per_q, false}, {c->cand, static_cast<size_t>(nq) * cap * sizeof(Cand), false},
-      {c->misc, 64, false}, {c->prog, static_cast<size_t>(p.prog_words) * 4, false}, {c->tickets, FUSE_TICKETS * 4, false},
-      {c->q16, static_cast<size_t>(p.nq_pad) * c->fdim * 2, true}, {c->qscale, per_q, true}, {c->qinv, per_q, true},
-      {c->ebound, per_q, true}, {c->slack, per_q, true}, {c->qdelta, per_q, true}};
-  for (const auto& w : workspace)
-    if ((p.prep || !w.filter_flow) && (st = ensure(c, w.buf, w.bytes))) return st;
-  // the state of "the last search", all of it from the plan
+  // workspace, per-search resets, queries, prep; then the rest of the state of "the last search", all of it from the plan
+  FilterRun run;
+  if ((st = begin_filter_run(c, s, p, dev_q, host_q, nq, nullptr, run))) return st;
   c->stats = nvdb_hip_scan_stats{};
   c->stats.path = p.route;
-  c->last_nq = nq; c->last_cap = cap; c->last_filter = p.route == ROUTE_FILTER;
-  c->ev_filter.clear();
-  c->prog_slot = 0;
-  if (p.route == ROUTE_FILTER) c->perm_on = p.perm_on;
-  c->last_filter_kind = p.route != ROUTE_FILTER ? 0u : p.shadow ? 2u : c->dtype == NVDB_DTYPE_I8 ? 3u : 1u;
-
-  // per-search resets and queries: the prep launch does both itself (option fuse), else init_search_kernel and a copy
-  // (one query tile per stream has no siblings to keep in step: no rendezvous counters to reset)
-  if (host_q && !p.prep_inits) { HIPCHK(c, hipMemcpyAsync(const_cast<float*>(dev_q), host_q, static_cast<size_t>(nq) * c->dim * 4, hipMemcpyDefault, s)); host_q = nullptr; }   // (host_q is the pinned block as the device addresses it)
-  if (!p.prep_inits && (st = launch_init_search(c, s, p.nq_pad, QT > 1 ? p.prog_words : 0u))) return st;
-  const PrepInit pinit = p.prep_inits ? PrepInit{static_cast<uint32_t*>(c->cnt.p), static_cast<float*>(c->thr.p), static_cast<uint32_t*>(c->misc.p),
-                                                 static_cast<uint32_t*>(c->prog.p), QT > 1 ? p.prog_words : 0u, static_cast<uint32_t*>(c->tickets.p), host_q, const_cast<float*>(dev_q)}
-                                      : PrepInit{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, nullptr};
-  if (p.prep && (st = filter_is_i8(c) ? launch_prep_q8(c, s, dev_q, nq, p.nq_pad, pinit) : launch_prep_q16(c, s, dev_q, nq, p.nq_pad, pinit))) return st;
-  const float* thr = static_cast<const float*>(c->thr.p);
+  c->last_nq = nq; c->last_cap = cap; c->last_filter = p.filter;
   const float* slack = static_cast<const float*>(c->slack.p);
 
   if (p.route == ROUTE_ANYK) return search_largek(c, s, dev_q, nq, k, dev_out_ids, dev_out_scores);
@@ -125,7 +126,7 @@ nvdb_status search_core(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint
     // prescan (plan_search): rows [0, head) alone, their exact k-th best score is the bar the rest of the scan starts with
     if (p.head && (st = launch_scan_exact(c, s, 0, p.head, dev_q, nq, k_eff, nullptr, cap, 0))) return st;
     if (p.head && (st = launch_select(c, s, nq, cap, k_eff, nullptr, 0, nullptr, nullptr, 0))) return st;
-    if ((st = launch_scan_exact(c, s, p.head, n, dev_q, nq, k_eff, p.head ? thr : nullptr, cap, p.head ? k_eff : 0))) return st;
+    if ((st = launch_scan_exact(c, s, p.head, n, dev_q, nq, k_eff, p.head ? run.thr : nullptr, cap, p.head ? k_eff : 0))) return st;
     c->stats.chunks = p.head ? 2 : 1;
     c->stats.rows_scanned = c->n;
     return launch_select(c, s, nq, cap, k_eff, nullptr, final_mode, dev_out_ids, dev_out_scores, k);
@@ -134,13 +135,13 @@ nvdb_status search_core(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint
   // ---- the filter route: bootstrap + select, { chunk + select }*, tail, rescore + final select ----
   // MFMA bootstrap: thresholds from the k-th largest of the tile maxima of rows [0, boot_rows); those rows are scanned again by
   // the normal build, so the select discards the bootstrap's entries (mode 2: out_k = list length)
-  if (p.boot == BOOT_MFMA) st = launch_boot(c, s, p.boot_rows, nq, QT, cap, filter_nb(c, nq));
+  if (p.boot == BOOT_MFMA) st = launch_boot(c, run, p.boot_rows);
   else if (p.boot == BOOT_ANYK_SEEDED) st = search_largek(c, s, dev_q, nq, k_eff, nullptr, nullptr, p.r0, static_cast<Cand*>(c->cand.p), static_cast<uint32_t*>(c->cnt.p), cap);
   else st = launch_scan_exact(c, s, 0, p.r0, dev_q, nq, k_eff, nullptr, cap, 0);
   if (st) return st;
   // The int8 shadow's band is its widest term (||q|| x the largest quantisation residual of any row) counted twice under a list
   // score; the thresholding selects of such a search put ONE bound under an exact k-th best score instead (select_body, ExactBar)
-  const float* xthr_q = (p.shadow && k_eff <= WAVE_KMAX && c->opt_shadow_exact_thr) ? dev_q : nullptr;
+  const float* xthr_q = (p.kind == FILTER_SHADOW8 && k_eff <= WAVE_KMAX && c->opt_shadow_exact_thr) ? dev_q : nullptr;
   if ((st = launch_select(c, s, nq, cap, k_eff, slack, p.boot == BOOT_MFMA ? 2 : 0, nullptr, nullptr, p.boot == BOOT_MFMA ? p.boot_tiles : 0, xthr_q))) return st;
   size_t ev = 0;
   for (uint32_t r = p.r0; r < p.n_al;) {
@@ -154,15 +155,13 @@ nvdb_status search_core(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint
         else HIPCHK(c, hipEventCreate(e));
       }
       kl.flops = 2.0 * nq * static_cast<double>(std::min(hi, n) - r) * c->dim;   // algorithmic: real queries, real rows
-      kl.bytes = static_cast<double>(std::min(hi, n) - r) * (filter_is_i8(c) ? c->fdim + 4.0 : c->fdim * 2.0);   // rows streamed once
-      c->launch_e0 = kl.e0; c->launch_e1 = kl.e1;
+      kl.bytes = static_cast<double>(std::min(hi, n) - r) * (filter_is_i8(run.kind) ? c->fdim + 4.0 : c->fdim * 2.0);   // rows streamed once
+      run.e0 = kl.e0; run.e1 = kl.e1;
     } else if (time_filter) {
-      c->launch_e0 = get_event(c, ev); c->launch_e1 = get_event(c, ev + 1);
+      run.e0 = get_event(c, ev); run.e1 = get_event(c, ev + 1);
     }
     if (time_filter && acct) { HIPCHK(c, hipEventRecord(get_event(c, ev), s)); }
-    st = launch_filter(c, s, r, hi, nq, QT, cap);
-    c->launch_e0 = nullptr; c->launch_e1 = nullptr;
-    if (st) return st;
+    if ((st = launch_filter(c, run, {r, hi}))) return st;
     if (time_filter && acct) { HIPCHK(c, hipEventRecord(get_event(c, ev + 1), s)); }
     if (time_filter) { c->ev_filter.emplace_back(ev, ev + 1); ev += 2; }
     if (acct) c->klaunch.push_back(kl);
@@ -173,7 +172,7 @@ nvdb_status search_core(nvdb_hip_ctx* c, hipStream_t s, const float* dev_q, uint
   }
   // ragged tail of an adopted corpus: exact scores, pruned by the current thresholds
   // (fewer than one tile of rows per workgroup: the wavefront lists' 64 entries keep every row that clears the threshold)
-  if (p.tail_exact && (st = launch_scan_exact(c, s, p.n_al, n, dev_q, nq, std::min(k_eff, WAVE_KMAX), thr, cap, 0))) return st;
+  if (p.tail_exact && (st = launch_scan_exact(c, s, p.n_al, n, dev_q, nq, std::min(k_eff, WAVE_KMAX), run.thr, cap, 0))) return st;
   if (p.tail_exact) c->stats.rows_scanned += static_cast<uint64_t>(n - p.n_al) * QT;
   // the final select rides in the rescore launch (one workgroup per query in both); its last workgroup folds the self-check words
   FinalSelect fs{};
@@ -223,19 +222,20 @@ static nvdb_status any_non_finite_query(nvdb_hip_ctx* c, uint32_t nq, bool* any)
 //   rung 2   if that is still not enough, the bound itself was violated, or a query is not finite: the always-correct exact path.
 // (The queries are in the device buffer by then: the retries read them there.)  verdict(rung) waits for the attempt and says
 // NVDB_ERR_INTERNAL when its self-check tripped; at rung 0 it leaves the exact counts in c->stats (search_check_impl).
-// *part: the statistics of the FIRST attempt, the ones that are reported.
+// *part: the statistics of the FIRST attempt, the ones that are reported; *kind: what its filter launches streamed.
 template <typename Verdict>
 static nvdb_status search_sub_batch(nvdb_hip_ctx* c, hipStream_t s, const float* dq, uint32_t nq, uint32_t k, uint64_t* oi, float* os, bool time_filter,
-                                    const float* host_q, uint32_t* st_out, Verdict&& verdict, nvdb_hip_scan_stats* part, bool* tripped = nullptr) {
+                                    const float* host_q, uint32_t* st_out, Verdict&& verdict, nvdb_hip_scan_stats* part, FilterKind* kind, bool* tripped = nullptr) {
   nvdb_status st;
   if ((st = search_core(c, s, dq, nq, k, oi, os, 0, time_filter, 0, false, host_q, st_out))) return st;
+  *kind = c->last_filter_kind;
   nvdb_status chk = verdict(0);
   *part = c->stats;
   if (tripped) *tripped = chk == NVDB_ERR_INTERNAL;
   if (chk != NVDB_ERR_INTERNAL) return chk;
   const uint32_t cap0 = c->last_cap;
   bool retry_filter = part->path == 2 && !part->bound_violations;
-  if (retry_filter && c->last_filter_kind == 2 && f16_beside_shadow(c)) {
+  if (retry_filter && c->last_filter_kind == FILTER_SHADOW8 && f16_beside_shadow(c)) {
     bool non_finite = false;
     if ((st = any_non_finite_query(c, nq, &non_finite))) return st;
     if (non_finite) retry_filter = false;
@@ -259,14 +259,14 @@ static nvdb_status search_sub_batch(nvdb_hip_ctx* c, hipStream_t s, const float*
 }
 
 // (shmem_bytes: the dynamic LDS of the 32x32 filter builds, filter_f16_lds_bytes / filter_i8_lds_bytes at the corpus' dim -- what
-// the ABI's callers have always been told)
-static void fill_timing(const nvdb_hip_ctx* c, nvdb_hip_timing* t, const hipEvent_t (&e)[4], uint32_t k, uint32_t path) {
+// the ABI's callers have always been told; kind: what the reported attempt's filter launches streamed)
+static void fill_timing(const nvdb_hip_ctx* c, nvdb_hip_timing* t, const hipEvent_t (&e)[4], uint32_t k, uint32_t path, FilterKind kind) {
   (void)hipEventElapsedTime(&t->h2d_ms, e[0], e[1]);
   (void)hipEventElapsedTime(&t->kernel_ms, e[1], e[2]);
   (void)hipEventElapsedTime(&t->d2h_ms, e[2], e[3]);
   t->total_ms = t->h2d_ms + t->kernel_ms + t->d2h_ms;
   t->threads = 256; t->nwarps = 4; t->K = k;
-  t->shmem_bytes = path != 2 ? 0 : filter_is_i8(c) ? static_cast<size_t>(FILTER_STAGES_I8) * (FILTER_ROWS * c->fdim + 4096) : static_cast<size_t>(FILTER_STAGES) * FILTER_ROWS * c->fdim * 2;
+  t->shmem_bytes = path != 2 ? 0 : filter_is_i8(kind) ? static_cast<size_t>(FILTER_STAGES_I8) * (FILTER_ROWS * c->fdim + 4096) : static_cast<size_t>(FILTER_STAGES) * FILTER_ROWS * c->fdim * 2;
 }
 
 }  // namespace nvdbhip
@@ -356,6 +356,7 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
   const bool time_filter = timing != nullptr && c->opt_time_launches;
   auto zero_pad = [&]() -> nvdb_status { return zero_q32_pad(c, s, qbytes); };
   nvdb_hip_scan_stats total{};
+  FilterKind kind = FILTER_NONE;
   if (nq <= 1024) {
     // One sub-batch: everything the host needs comes back in ONE synchronisation through pinned staging -- the
     // self-check words (32 B), ids and scores -- instead of five small pageable copies of ~20 us each (a third of
@@ -416,7 +417,7 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
       return (rung == 0 && search_check_impl(c, nullptr, true) == NVDB_ERR_HIP) ? NVDB_ERR_HIP : NVDB_ERR_INTERNAL;
     };
     bool tripped = false;
-    if ((st = search_sub_batch(c, s, dq, nq, k, oi, os, time_filter, host_q, st_out, verdict, &total, &tripped))) return st;
+    if ((st = search_sub_batch(c, s, dq, nq, k, oi, os, time_filter, host_q, st_out, verdict, &total, &kind, &tripped))) return st;
     if (!tripped) {
       total.i8_stage1_tiles = pin_status[4]; total.i8_stage2_blocks = pin_status[5];
       total.filter_kernel_ms = filter_events_ms(c);
@@ -441,7 +442,7 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
       uint64_t* oi = static_cast<uint64_t*>(c->out_ids.p) + static_cast<size_t>(q0) * k;
       float* os = static_cast<float*>(c->out_scores.p) + static_cast<size_t>(q0) * k;
       nvdb_hip_scan_stats part{};
-      if ((st = search_sub_batch(c, s, dq, std::min<uint32_t>(1024, nq - q0), k, oi, os, time_filter, nullptr, nullptr, verdict, &part))) return st;
+      if ((st = search_sub_batch(c, s, dq, std::min<uint32_t>(1024, nq - q0), k, oi, os, time_filter, nullptr, nullptr, verdict, &part, &kind))) return st;
       total.path = std::max(total.path, part.path);
       total.chunks += part.chunks; total.rows_scanned += part.rows_scanned; total.candidates += part.candidates;
       total.overflow_queries += part.overflow_queries; total.bound_violations += part.bound_violations;
@@ -455,7 +456,7 @@ nvdb_status nvdb_hip_search_batch(nvdb_hip_ctx* c, const float* queries, uint32_
     HIPCHK(c, hipStreamSynchronize(s));
     c->stats = total;
   }
-  if (timing) fill_timing(c, timing, e, k, total.path);
+  if (timing) fill_timing(c, timing, e, k, total.path, kind);
   if (total.bound_violations) return fail(c, NVDB_ERR_INTERNAL, "filter error bound violated; results were recomputed on the exact path");
   return NVDB_OK;
 }
