@@ -412,6 +412,71 @@ struct nvdb_hip_ivf;
 nvdb_status nvdb_hip_ivf_compact(struct nvdb_hip_ivf* ivf, uint32_t mask, uint64_t* out_n /* may be NULL */);
 
 /* ---------------------------------------------------------------------------------------------
+ * insertion: the compaction's mirror image.  New rows join the resident corpus on the device, at the END of a partition; the rows
+ * behind them shift up.  After an insertion the context is what a fresh context would be that uploaded the resulting rows with the
+ * same options (and set the resulting table and planes).
+ * Out of scope: the device group; _dev stream forms; updating centroids after an add; giving HBM back; inserting anywhere but at the
+ * end of a partition.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Makes room for at least `rows` rows in every library-owned array of the resident corpus (rows, scales, shadows and their scales),
+ * so that insertions up to that row count move in place.  Never shrinks (rows <= the capacity: NVDB_OK, nothing done); the results
+ * of every search are unchanged.  The arrays are reallocated once and copied: peak HBM is old plus new arrays.
+ *   NVDB_ERR_INVALID ctx == NULL;  NVDB_ERR_NO_CORPUS nothing resident;  NVDB_ERR_UNSUPPORTED an adopted corpus, rows >= 2^32 - 16;
+ *   NVDB_ERR_HIP an allocation or the copy failed: nothing changed. */
+nvdb_status nvdb_hip_reserve_rows(nvdb_hip_ctx* ctx, uint64_t rows);
+
+/* Inserts `m` host rows (the resident corpus' dtype and dim; `scales` iff it is int8) into the resident corpus.
+ * part_of == NULL: the rows go behind the last resident row; with a partition table they join the last partition.
+ * part_of != NULL (needs a partition table): row i goes to the end of partition part_of[i], behind the rows already there; rows that
+ * name the same partition keep the order of i (the move is stable); empty partitions are legal targets.
+ * Old local row r of partition p becomes r + (new rows in partitions < p); global ids stay global_row_base + the NEW local row, as
+ * after a compaction.  out_new_rows[i] = the new local row of inserted row i; *out_n = the new row count.
+ * What moves, all by that one order-preserving map: the rows, the scales of an int8 corpus, the int8 shadow and its scales (the
+ * padded-dim shadow of an int8 corpus as well as the filter shadow of option "q8_shadow"), the fp16 shadow.  The shadow entries of the
+ * new rows are computed from the new rows by the kernels a load runs.  Behind the new end every array reads as zeros again for the
+ * padding rows and the vector-load slack an upload leaves (the call zeroes that region itself).  The norm bounds of the filters become
+ * the maximum of their old values and the new rows' (the sign flag of the int8 scales is ORed): on a corpus that was never compacted
+ * they equal a fresh load's bit for bit.  An insertion never CREATES a shadow: the automatic "q8_shadow" rule is not evaluated again
+ * when n crosses its threshold.  Where a new row holds a value a load would not have built the resident shadow for (a non-finite
+ * element under the q8 shadow, |x| >= 60000 under the fp16 shadow) the rows are placed, the shadows freed and the load's own pass runs
+ * over all rows: slow, rare, correct.  Every resident plane goes through the map and is repacked to W' = ceil(n' / 32) words, tail
+ * bits 0: old rows keep their bit, new rows are live in every plane.  A resident partition table becomes offsets'[p] = offsets[p] +
+ * new rows in partitions < p; the centroids stay.  A held range result is invalidated.  Options, statistics, what the context has
+ * learnt about the corpus (the list capacity it needed, a demoted shadow) and global_row_base are kept.
+ * Capacity: the context records how many rows its arrays have room for -- exactly n after a load, more after nvdb_hip_reserve_rows or
+ * a grown insertion; nvdb_hip_compact_rows keeps it, so an insertion after it reuses that room.  Where n + m fits, the move is in
+ * place: DESCENDING slabs of option "compact_slab_rows" rows from the last row down to the end of the first partition that receives
+ * rows (rows below are neither read nor written); a slab [s0, s1) whose smallest shift carries it to or beyond s1 moves in one launch,
+ * any other goes through the one-slab bounce buffer, so no launch writes bytes that it reads.  Otherwise every array is reallocated
+ * once, to max(n + m, capacity * (100 + option "insert_growth_pct") / 100) rows (default 50; 0: exactly n + m), and old rows are
+ * written straight to their new positions: no bounce, but peak HBM on that path is OLD PLUS NEW arrays.
+ *   NVDB_ERR_INVALID      ctx == NULL; m > 0 and rows == NULL, or scales == NULL on an int8 corpus; part_of without a partition
+ *                         table; an entry of part_of >= nparts: nothing changed, nothing written
+ *   NVDB_ERR_NO_CORPUS    nothing resident
+ *   NVDB_ERR_UNSUPPORTED  an adopted corpus; n + m >= 0xFFFFFFF0; n + m > 0xFFFFFF00 with a table or planes resident: nothing changed
+ *   NVDB_OK               also for m == 0: *out_n = n, nothing launched
+ *   NVDB_ERR_HIP          a HIP error.  One before the first row has moved (allocations, staging): nothing changed.  One after it
+ *                         leaves no half-moved corpus: the context drops its corpus, table and planes, as nvdb_hip_compact_rows does.
+ * Synchronous.  A context is single-owner, as everywhere. */
+nvdb_status nvdb_hip_insert_rows(nvdb_hip_ctx* ctx, const void* rows, const float* scales /* iff int8 */, uint64_t m,
+                                 const uint32_t* part_of /* [m], may be NULL */,
+                                 uint64_t* out_new_rows /* [m], may be NULL */, uint64_t* out_n /* may be NULL */);
+
+/* The same for an index: the new rows get the original ids src_n + i (without the source's row base), src_n = the rows the index
+ * speaks of so far (those it was built from plus those added); src_n grows by m, *out_first_id = the old src_n.  Every row is assigned
+ * by nvdb_hip_assign_rows' rule -- the row as an f32 query against the index's centroids, fp32 reference order, ties to the lowest
+ * centroid -- and joins the end of its list; out_assign returns the lists.  nvdb_hip_ivf_info reports the new n, offsets and perm.
+ * New rows have the largest original ids, so lists stay ordered by original row: on an index that was never compacted the result
+ * equals nvdb_hip_ivf_build of the concatenated source with the same centroids (rows, scales, offsets, perm, every search).  The
+ * centroids are NOT updated.  Planes set with nvdb_hip_ivf_set_row_masks keep speaking of ORIGINAL rows, now src_n + m of them
+ * (ceil((src_n + m) / 32) words); new rows are live.  Statuses as above (ivf == NULL -> NVDB_ERR_INVALID; src_n + m > 0xFFFFFF00 ->
+ * NVDB_ERR_UNSUPPORTED).  As for nvdb_hip_ivf_compact, a failure leaves the index exactly as it was unless its context has dropped
+ * its corpus (a HIP error during the move); then the index holds no rows. */
+nvdb_status nvdb_hip_ivf_add_rows(struct nvdb_hip_ivf* ivf, const void* rows, const float* scales /* iff int8 */, uint64_t m,
+                                  uint64_t* out_first_id /* may be NULL */, uint32_t* out_assign /* [m], may be NULL */);
+
+/* ---------------------------------------------------------------------------------------------
  * range search on the probe path: nvdb_hip_range_search's question -- every row whose score reaches a per-query radius -- asked of
  * a per-query choice of partitions, of an IVF index, and of the rows that are live in a query's mask.  FAISS users know the
  * combination as IndexIVF::range_search with SearchParameters::sel.
@@ -603,7 +668,7 @@ nvdb_status nvdb_hip_ivf_range_results(nvdb_hip_ivf* ivf, uint64_t* out_ids, flo
  * "q8_auto_min_rows", "q8_auto_max_mb" (all set before the upload), "shadow_exact_thr" (1: a search that streams the int8 shadow
  * takes its thresholds from exact scores of its best 2k candidates, one error bound under them; 0: two bounds under the k-th filter score), "exact_mfma" (exact scores on the fp32
  * matrix cores), "exact_lds", "i8_dense8" (int8 filter, d = 768, batches > 128: 1 = 8 waves of 32 queries per workgroup, 0 = 4 of 64; same results), "i8_defer", "i8_lo_bits", "boot_tiles", "xcd_balance", "rescore8", "refine_v2", "refine_pinned" (reference CUDA_PINNED:
- * pinned host staging in nvdb_hip_refine_l2_topk), "largek_budget_mb" (HBM for the any-k path's score matrix), "range_max_mb" (packed results a range search may hold), "compact_slab_rows" (rows per slab of nvdb_hip_compact_rows' walk: a multiple of 64 in [64, 2^24], default 65536), "time_kernels" (1: start /
+ * pinned host staging in nvdb_hip_refine_l2_topk), "largek_budget_mb" (HBM for the any-k path's score matrix), "range_max_mb" (packed results a range search may hold), "compact_slab_rows" (rows per slab of nvdb_hip_compact_rows' walk and of nvdb_hip_insert_rows' -- the same option: a multiple of 64 in [64, 2^24], default 65536), "insert_growth_pct" (an insertion that outgrows the arrays' capacity reallocates them to max(n + m, capacity * (100 + this) / 100) rows: [0, 400], default 50, 0 = exactly n + m), "time_kernels" (1: start /
  * stop events attached to every launch of the dominant kernel, read by nvdb_hip_collect_kernel_times), "time_launches" (the same for one host-API
  * call with a timing struct -> stats.filter_kernel_ms).  "mfma16", "i8_wide", "i8_pipe", "i8_waves8", "i8_mfma16", "i8_small8" select kernel
  * variants that exist in libnvdb_hip_dev.so only: the product accepts their default values (1, 1, 1, 0, 1) and returns

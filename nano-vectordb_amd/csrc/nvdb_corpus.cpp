@@ -2,6 +2,7 @@
 // row-norm pass), options, statistics, host-side helpers of the C ABI (include/nvdb_hip.h).
 #include "nvdb_ctx.h"
 #include "compact_plan.h"
+#include "insert_plan.h"
 #include "kernels_corpus.h"
 
 namespace {
@@ -16,7 +17,7 @@ void free_corpus(nvdb_hip_ctx* c) {
   if (c->shadow16) { (void)hipFree(c->shadow16); c->shadow16 = nullptr; }
   if (c->shadow8) { (void)hipFree(c->shadow8); c->shadow8 = nullptr; }
   if (c->shadow8_scales) { (void)hipFree(c->shadow8_scales); c->shadow8_scales = nullptr; }
-  c->rows = nullptr; c->scales = nullptr; c->owned = false; c->n = 0; c->dim = 0; c->fdim = 0; c->dtype = 0; c->max_norm = 0.f;
+  c->rows = nullptr; c->scales = nullptr; c->owned = false; c->n = 0; c->cap_rows = 0; c->dim = 0; c->fdim = 0; c->dtype = 0; c->max_norm = 0.f;
   c->cap_hint = 0;
   c->q8shadow = false; c->resid_max = 0.f; c->filter_max_norm = 0.f;
   c->shadow_demoted = false; c->last_filter_kind = FILTER_NONE;
@@ -28,6 +29,8 @@ void free_corpus(nvdb_hip_ctx* c) {
 nvdb_status compute_max_norm(nvdb_hip_ctx* c) {
   nvdb_status st = ensure(c, c->misc, 64);
   if (st) return st;
+  if (c->cap_rows < c->n) c->cap_rows = c->n;      // a load: exactly n (free_corpus left 0).  Shadows get room for cap_rows rows, as the rows have
+  const size_t cap = static_cast<size_t>(c->cap_rows);
   HIPCHK(c, hipMemsetAsync(c->misc.p, 0, 64, c->stream));
   uint32_t* bits = static_cast<uint32_t*>(c->misc.p) + 8;
   const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((c->n + 3) / 4, 4096));
@@ -57,10 +60,10 @@ nvdb_status compute_max_norm(nvdb_hip_ctx* c) {
   if (automatic && hipMemGetInfo(&free_hbm, &total_hbm) != hipSuccess) { (void)hipGetLastError(); free_hbm = 0; }
   if (q8_shadow_wanted(c, free_hbm)) {
     const uint32_t sdim = c->dim;
-    const size_t count = static_cast<size_t>(c->n) * sdim, pad = static_cast<size_t>(PAD_ROWS) * sdim + 4096;
-    const size_t n_pad = (static_cast<size_t>(c->n) + PAD_ROWS - 1) / PAD_ROWS * PAD_ROWS + PAD_ROWS;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->shadow8), count + pad);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->shadow8_scales), n_pad * 4);
+    const size_t pad = static_cast<size_t>(PAD_ROWS) * sdim + 4096;
+    const size_t cap_pad = (cap + PAD_ROWS - 1) / PAD_ROWS * PAD_ROWS + PAD_ROWS;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->shadow8), cap * sdim + pad);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->shadow8_scales), cap_pad * 4);
     if (e != hipSuccess) {
       if (c->shadow8) (void)hipFree(c->shadow8);
       c->shadow8 = nullptr; c->shadow8_scales = nullptr;
@@ -101,7 +104,7 @@ nvdb_status compute_max_norm(nvdb_hip_ctx* c) {
     while (!f16_filter_dim(sdim) || sdim < c->dim) sdim += 128;
     const size_t count = static_cast<size_t>(c->n) * sdim;
     const size_t pad = static_cast<size_t>(PAD_ROWS) * sdim * 2 + 4096;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->shadow16), count * 2 + pad));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->shadow16), cap * sdim * 2 + pad));
     HIPCHK(c, hipMemsetAsync(reinterpret_cast<char*>(c->shadow16) + count * 2, 0, pad, c->stream));
     HIPCHK(c, hipMemsetAsync(bits, 0, 4, c->stream));
     if (c->dtype == NVDB_DTYPE_F32) shadow_f16_kernel<float><<<4096, 256, 0, c->stream>>>(static_cast<const float*>(c->rows), c->shadow16, c->n, c->dim, sdim, bits);
@@ -118,8 +121,9 @@ nvdb_status compute_max_norm(nvdb_hip_ctx* c) {
     while (!i8_filter_dim(sdim) || sdim < c->dim) sdim += 128;
     const size_t count = static_cast<size_t>(c->n) * sdim, pad = static_cast<size_t>(PAD_ROWS) * sdim + 4096;
     const size_t n_pad = (static_cast<size_t>(c->n) + PAD_ROWS - 1) / PAD_ROWS * PAD_ROWS + PAD_ROWS;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->shadow8), count + pad));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->shadow8_scales), n_pad * 4));
+    const size_t cap_pad = (cap + PAD_ROWS - 1) / PAD_ROWS * PAD_ROWS + PAD_ROWS;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->shadow8), cap * sdim + pad));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->shadow8_scales), cap_pad * 4));
     HIPCHK(c, hipMemsetAsync(c->shadow8 + count, 0, pad, c->stream));
     HIPCHK(c, hipMemsetAsync(c->shadow8_scales, 0, n_pad * 4, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->shadow8_scales, c->scales, static_cast<size_t>(c->n) * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -233,6 +237,13 @@ nvdb_status corpus_take_ownership(nvdb_hip_ctx* c, void* dev_rows, float* dev_sc
 
 void corpus_drop(nvdb_hip_ctx* c) { free_corpus(c); }
 
+nvdb_status corpus_rederive(nvdb_hip_ctx* c) {
+  if (c->shadow16) { (void)hipFree(c->shadow16); c->shadow16 = nullptr; }
+  if (c->shadow8) { (void)hipFree(c->shadow8); c->shadow8 = nullptr; }
+  if (c->shadow8_scales) { (void)hipFree(c->shadow8_scales); c->shadow8_scales = nullptr; }
+  return compute_max_norm(c);
+}
+
 }  // namespace nvdbhip
 
 extern "C" {
@@ -291,7 +302,7 @@ void nvdb_hip_destroy(nvdb_hip_ctx* c) {
   for (DevBuf* b : {&c->q32, &c->q16, &c->qscale, &c->qinv, &c->ebound, &c->slack, &c->thr, &c->cnt, &c->overflow, &c->cand,
                     &c->out_ids, &c->out_scores, &c->misc, &c->hostblock, &c->hitlog, &c->prog, &c->qdelta, &c->rq, &c->rcand, &c->rout_ids, &c->rout_dist, &c->rdbg, &c->lk_scores, &c->lk_sel, &c->lk_hist, &c->lk_state, &c->xcdw, &c->tickets,
                     &c->rg_radius, &c->rg_kept, &c->rg_off, &c->rg_idx, &c->rg_q, &c->rg_desc, &c->rg_taken, &c->rg_slab, &c->rg_pcnt, &c->rg_maskof, &c->rg_ids, &c->rg_scores, &c->row_masks, &c->mask_rows,
-                    &c->cp_rank, &c->cp_sums, &c->cp_bounce, &c->cp_map, &c->cp_live, &c->row_masks_alt})
+                    &c->cp_rank, &c->cp_sums, &c->cp_bounce, &c->cp_map, &c->cp_live, &c->row_masks_alt, &c->ins_meta, &c->ins_pos})
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   for (auto& k : c->klaunch) { (void)hipEventDestroy(k.e0); (void)hipEventDestroy(k.e1); }
@@ -443,6 +454,7 @@ nvdb_status nvdb_hip_set_option(nvdb_hip_ctx* c, const char* key, int64_t value)
   else if (k == "largek_budget_mb") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "largek_budget_mb must be >= 1"); c->opt_largek_budget_mb = value; }
   else if (k == "range_max_mb") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "range_max_mb must be >= 1"); c->opt_range_max_mb = value; }
   else if (k == "compact_slab_rows") { if (!cp_slab_rows_valid(value)) return fail(c, NVDB_ERR_INVALID, "compact_slab_rows must be a multiple of 64 in [64, 2^24]"); c->opt_compact_slab_rows = value; }
+  else if (k == "insert_growth_pct") { if (!ins_growth_pct_valid(value)) return fail(c, NVDB_ERR_INVALID, "insert_growth_pct must be in [0, 400]"); c->opt_insert_growth_pct = value; }
   else if (k == "chunk_growth") { if (value != 0 && (value < 2 || value > 64)) return fail(c, NVDB_ERR_INVALID, "chunk_growth must be 0 (automatic) or in [2,64]"); c->opt_growth = value; }
   else if (k == "min_filter_batch") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "min_filter_batch must be >= 1"); c->opt_min_filter_batch = value; }
   else return fail(c, NVDB_ERR_INVALID, "unknown option: " + k);

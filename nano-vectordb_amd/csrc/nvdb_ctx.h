@@ -20,6 +20,9 @@
 //                          lists (kernels_masked_topk.h, masked_plan.h)
 //   nvdb_compact.cpp       in-place compaction of tombstoned rows: rank, slab walk (direct / bounce), planes, partition table (kernels_compact.h, compact_plan.h);
 //                          nvdb_hip_compact_rows here, nvdb_hip_ivf_compact beside the index in nvdb_ivf.cpp
+//   nvdb_insert.cpp        insertion at the ends of partitions, in place or into grown buffers: plan, descending slab walk (direct / bounce), scatter of the
+//                          staged rows and their shadows, planes, table (kernels_insert.h, insert_plan.h, nvdb_insert.h); nvdb_hip_reserve_rows and
+//                          nvdb_hip_insert_rows here, nvdb_hip_ivf_add_rows beside the index in nvdb_ivf.cpp
 //   nvdb_ivf.cpp           IVF-Flat build: row assignment, spherical k-means, list layout, the reordered index and its searches (the context's, ids mapped
 //                          back by ivf_map_ids) (kernels_ivf.h, ivf_layout.h)
 //   nvdb_debug.cpp         developer entry points (libnvdb_hip_dev.so only)
@@ -91,6 +94,8 @@ struct nvdb_hip_ctx {
   float* scales = nullptr;
   bool owned = false;
   uint64_t n = 0;
+  uint64_t cap_rows = 0;                           // rows the OWNED arrays (rows, scales, shadows) have room for, their padding aside: n after a load, more after
+                                                   // nvdb_hip_reserve_rows / a grown nvdb_hip_insert_rows; a compaction keeps it
   uint32_t dim = 0, dtype = 0;
   uint64_t row_base = 0;
   float max_norm = 0.f;
@@ -197,7 +202,10 @@ struct nvdb_hip_ctx {
   // compaction (nvdb_compact.cpp): grow-only workspace -- tile ranks, their block sums / bases, one slab of the widest array, the map, the planes' live counts --
   // and the spare the repacked planes are written to before it is swapped with row_masks
   DevBuf cp_rank, cp_sums, cp_bounce, cp_map, cp_live, row_masks_alt;
-  int64_t opt_compact_slab_rows = 65536;           // rows per slab of the walk (a multiple of 64; compact_plan.h): profiles/compact_bench_10M.txt
+  int64_t opt_compact_slab_rows = 65536;           // rows per slab of the walk (a multiple of 64; compact_plan.h): profiles/compact_bench_10M.txt; the insertion's walk too
+  // insertion (nvdb_insert.cpp): grow-only workspace -- [old offsets | shifts | new offsets], the new rows' positions; the staged rows live for one call only
+  DevBuf ins_meta, ins_pos;
+  int64_t opt_insert_growth_pct = 50;              // an insertion that outgrows cap_rows reallocates to max(n + m, cap_rows * (100 + this) / 100) rows; 0: exactly n + m
 };
 
 #define HIPCHK(ctx, call)                                                                        \
@@ -394,6 +402,9 @@ nvdb_status launch_boot_i8(nvdb_hip_ctx* c, FilterRun& run, uint32_t n0);
 nvdb_status corpus_alloc_padded(nvdb_hip_ctx* c, uint64_t n, uint32_t dim, uint32_t dtype, void** rows, float** scales);
 nvdb_status corpus_take_ownership(nvdb_hip_ctx* c, void* dev_rows, float* dev_scales, uint64_t n, uint32_t dim, uint32_t dtype, uint64_t global_row_base);
 void corpus_drop(nvdb_hip_ctx* c);       // the context forgets its corpus, shadows, partition table and planes (what a load does before it loads)
+// the load's own pass over the resident rows again (nvdb_hip_insert_rows, where a new row forbids a resident shadow): the shadows are freed, then norms, flags
+// and whatever shadow a load of these rows would build -- with room for cap_rows rows; table, planes, options and what the context has learnt stay
+nvdb_status corpus_rederive(nvdb_hip_ctx* c);
 // nvdb_partitions.cpp
 void parts_drop(nvdb_hip_ctx* c);        // the corpus changes: forget the partition table and the centroids (the workspace stays)
 void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace

@@ -8,6 +8,9 @@
 // through the child's host API, which retries by itself -- the device group's pattern (nvdb_group.cpp).
 #include "nvdb_ctx.h"
 #include "compact_plan.h"
+#include "insert_plan.h"
+#include "nvdb_insert.h"
+#include "nvdb_parts.h"
 #include "ivf_layout.h"
 #include "row_mask.h"
 #include "kernels_ivf.h"
@@ -64,16 +67,17 @@ struct StreamTimer {
 };
 bool ivf_debug() { return std::getenv("NVDB_IVF_DEBUG") != nullptr; }
 
-// rows of the resident corpus: [row0, row0 + count), or dev_idx[0 .. count) (u32 row numbers in HBM)
-struct RowSel { uint64_t row0; const uint32_t* dev_idx; uint64_t count; };
+// rows of the resident corpus: [row0, row0 + count), or dev_idx[0 .. count) (u32 row numbers in HBM); rows != nullptr: of these
+// device rows (and scales) in the corpus' dtype and dim instead -- the staged rows of nvdb_hip_ivf_add_rows
+struct RowSel { uint64_t row0; const uint32_t* dev_idx; uint64_t count; const void* rows = nullptr; const float* scales = nullptr; };
 
 template <int DT>
-nvdb_status launch_rows_to_f32_dt(nvdb_hip_ctx* c, hipStream_t s, uint64_t row0, const uint32_t* idx, uint32_t count, float* out) {
-  const bool vec = c->dim % ivf_epv<DT>() == 0 && reinterpret_cast<uintptr_t>(c->rows) % 16 == 0;
+nvdb_status launch_rows_to_f32_dt(nvdb_hip_ctx* c, hipStream_t s, const void* rows, const float* scales, uint64_t row0, const uint32_t* idx, uint32_t count, float* out) {
+  const bool vec = c->dim % ivf_epv<DT>() == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0;
   const size_t total = static_cast<size_t>(count) * (vec ? c->dim / ivf_epv<DT>() : c->dim);
   const unsigned grid = static_cast<unsigned>(std::min<size_t>((total + 255) / 256, 65536));
-  if (vec) rows_to_f32_kernel<DT, true><<<grid, 256, 0, s>>>(c->rows, c->scales, c->dim, row0, idx, count, out);
-  else rows_to_f32_kernel<DT, false><<<grid, 256, 0, s>>>(c->rows, c->scales, c->dim, row0, idx, count, out);
+  if (vec) rows_to_f32_kernel<DT, true><<<grid, 256, 0, s>>>(rows, scales, c->dim, row0, idx, count, out);
+  else rows_to_f32_kernel<DT, false><<<grid, 256, 0, s>>>(rows, scales, c->dim, row0, idx, count, out);
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
 }
@@ -81,9 +85,11 @@ nvdb_status launch_rows_to_f32_dt(nvdb_hip_ctx* c, hipStream_t s, uint64_t row0,
 nvdb_status launch_rows_to_f32(nvdb_hip_ctx* c, hipStream_t s, const RowSel& sel, uint64_t first, uint32_t count, float* out) {
   const uint32_t* idx = sel.dev_idx ? sel.dev_idx + first : nullptr;
   const uint64_t row0 = sel.row0 + first;
-  if (c->dtype == NVDB_DTYPE_F32) return launch_rows_to_f32_dt<DT_F32>(c, s, row0, idx, count, out);
-  if (c->dtype == NVDB_DTYPE_F16) return launch_rows_to_f32_dt<DT_F16>(c, s, row0, idx, count, out);
-  return launch_rows_to_f32_dt<DT_I8>(c, s, row0, idx, count, out);
+  const void* rows = sel.rows ? sel.rows : c->rows;
+  const float* scales = sel.rows ? sel.scales : c->scales;
+  if (c->dtype == NVDB_DTYPE_F32) return launch_rows_to_f32_dt<DT_F32>(c, s, rows, scales, row0, idx, count, out);
+  if (c->dtype == NVDB_DTYPE_F16) return launch_rows_to_f32_dt<DT_F16>(c, s, rows, scales, row0, idx, count, out);
+  return launch_rows_to_f32_dt<DT_I8>(c, s, rows, scales, row0, idx, count, out);
 }
 
 // out_assign[i] (host) = best centroid of row i of the selection; the centroids are resident in `child`
@@ -480,6 +486,44 @@ nvdb_status nvdb_hip_ivf_compact(nvdb_hip_ivf* ix, uint32_t mask, uint64_t* out_
   ix->perm.resize(n_new);
   ix->inv.clear();                                   // rebuilt by the next nvdb_hip_ivf_update_row_mask
   if (out_n) *out_n = n_new;
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_ivf_add_rows(nvdb_hip_ivf* ix, const void* rows, const float* scales, uint64_t m, uint64_t* out_first_id, uint32_t* out_assign) {
+  if (!ix) return NVDB_ERR_INVALID;
+  nvdb_hip_ctx* c = ix->ctx;
+  auto ctx_fail = [&](nvdb_status st) {
+    ix->err = c->err;
+    if (!c->rows) {                                  // the context dropped its corpus (a HIP error during the move): an index of no rows
+      ix->perm.clear(); ix->inv.clear();
+      std::fill(ix->offsets.begin(), ix->offsets.end(), 0);
+    }
+    return st;
+  };
+  if (m > IVF_MAX_ROWS || ix->src_n + m > IVF_MAX_ROWS) { ix->err = "ivf_add_rows: too many rows for one index"; return NVDB_ERR_UNSUPPORTED; }
+  InsertStage stage;
+  bool done = false;
+  nvdb_status st = insert_stage(c, "ivf_add_rows", rows, scales, m, true, nullptr, stage, &done);
+  if (st) return ctx_fail(st);
+  if (done) {                                        // m == 0
+    if (out_first_id) *out_first_id = ix->src_n;
+    return NVDB_OK;
+  }
+  // every new row's list: nvdb_hip_assign_rows' rule, over the staged rows, against the index's own centroids
+  PartState* ps = c->parts;
+  if (!ps || !ps->have_centroids || !ps->coarse) return ctx_fail(fail(c, NVDB_ERR_INVALID, "ivf_add_rows: the index has no centroids"));
+  const uint32_t nparts = static_cast<uint32_t>(ix->offsets.size() - 1);
+  std::vector<uint32_t> assign(m);
+  if ((st = assign_core(c, ps->coarse, nparts, RowSel{0, nullptr, m, stage.rows, stage.scales}, assign.data(), "ivf_add_rows"))) return ctx_fail(st);
+  InsPlan pl;                                        // (the context's table is the index's: the plan of the move is the plan of perm)
+  std::vector<uint64_t> new_rows(m);
+  if ((st = insert_staged(c, "ivf_add_rows", stage, m, assign.data(), new_rows.data(), nullptr, &pl))) return ctx_fail(st);
+  // the new rows carry the largest original ids: "ordered by partition, then original row" still holds
+  ins_perm(ix->perm, ix->inv, pl, new_rows.data(), ix->src_n);
+  ix->offsets = pl.off_new;
+  if (out_first_id) *out_first_id = ix->src_n;
+  if (out_assign) std::copy(assign.begin(), assign.end(), out_assign);
+  ix->src_n += m;
   return NVDB_OK;
 }
 

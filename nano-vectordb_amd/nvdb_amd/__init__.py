@@ -41,6 +41,7 @@ EXPORTS = [
     "nvdb_hip_ivf_range_search", "nvdb_hip_ivf_range_results",
     "nvdb_hip_search_partitions_anyk", "nvdb_hip_search_ivf_anyk", "nvdb_hip_ivf_search_anyk",
     "nvdb_hip_compact_rows", "nvdb_hip_ivf_compact",
+    "nvdb_hip_reserve_rows", "nvdb_hip_insert_rows", "nvdb_hip_ivf_add_rows",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -216,6 +217,9 @@ def _bind(L, dev):
     L.nvdb_hip_ivf_search_anyk.argtypes = [vp, vp, u32, u32, u32, vp, C.c_int, vp, vp, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_compact_rows.argtypes = [vp, u32, C.POINTER(u64), vp]
     L.nvdb_hip_ivf_compact.argtypes = [vp, u32, C.POINTER(u64)]
+    L.nvdb_hip_reserve_rows.argtypes = [vp, u64]
+    L.nvdb_hip_insert_rows.argtypes = [vp, vp, vp, u64, vp, vp, C.POINTER(u64)]
+    L.nvdb_hip_ivf_add_rows.argtypes = [vp, vp, vp, u64, C.POINTER(u64), vp]
     for name in EXPORTS:
         getattr(L, name)
     if dev:
@@ -582,6 +586,28 @@ class HipContext:
         self._chk(self.lib.nvdb_hip_compact_rows(self.h, mask, C.byref(n_new), old.ctypes.data))
         return n_new.value, old[:n_new.value].copy()
 
+    def reserve_rows(self, rows):
+        """Make room for at least `rows` rows in the resident corpus' arrays: insertions up to that count move in place."""
+        self._chk(self.lib.nvdb_hip_reserve_rows(self.h, int(rows)))
+
+    def insert_rows(self, rows, scales=None, part_of=None):
+        """Insert host rows ([m, dim] in the corpus' dtype; scales iff int8) at the end of the corpus (part_of None) or at the ends
+        of the partitions part_of [m] names -> (n_new, new_rows [m] u64: the new local row of inserted row i)."""
+        info = self.corpus_info()
+        if info["dtype"] == DT_F16 and getattr(rows, "dtype", None) == np.float16:
+            rows = rows.view(np.uint16)
+        rows = np.ascontiguousarray(rows, dtype=_NP_OF[info["dtype"]]).reshape(-1, info["dim"])
+        m = rows.shape[0]
+        sc = np.ascontiguousarray(scales, dtype=np.float32) if scales is not None else None
+        po = np.ascontiguousarray(part_of, dtype=np.uint32).ravel() if part_of is not None else None
+        if po is not None and po.size != m:
+            raise ValueError("part_of must have one entry per row")
+        new_rows = np.zeros(max(m, 1), dtype=np.uint64)
+        n_new = C.c_uint64(0)
+        self._chk(self.lib.nvdb_hip_insert_rows(self.h, rows.ctypes.data if m else None, sc.ctypes.data if sc is not None else None, m,
+                                                po.ctypes.data if po is not None else None, new_rows.ctypes.data, C.byref(n_new)))
+        return n_new.value, new_rows[:m].copy()
+
     def search_partitions_masked(self, queries, k, probe, mask_of=None, want_timing=False):
         """search_partitions over the rows live in each query's mask: mask_of[q] = plane number (0xFFFFFFFF: none; None: plane 0
         for every query) -> (ids, scores, counts); counts[q] = min(k, live rows in the probed union)."""
@@ -798,6 +824,22 @@ class IvfIndex:
         n_new = C.c_uint64(0)
         self._chk(self.lib.nvdb_hip_ivf_compact(self.h, mask, C.byref(n_new)))
         return n_new.value
+
+    def add_rows(self, rows, scales=None):
+        """Add host rows ([m, dim] in the index's dtype; scales iff int8): each joins the end of the list of its best centroid and
+        gets the original id src_n + i -> (first_id, assign [m] u32).  info() reports the new n, offsets and perm."""
+        info = self.ctx.corpus_info()
+        if info["dtype"] == DT_F16 and getattr(rows, "dtype", None) == np.float16:
+            rows = rows.view(np.uint16)
+        rows = np.ascontiguousarray(rows, dtype=_NP_OF[info["dtype"]]).reshape(-1, info["dim"])
+        m = rows.shape[0]
+        sc = np.ascontiguousarray(scales, dtype=np.float32) if scales is not None else None
+        assign = np.zeros(max(m, 1), dtype=np.uint32)
+        first = C.c_uint64(0)
+        self._chk(self.lib.nvdb_hip_ivf_add_rows(self.h, rows.ctypes.data if m else None, sc.ctypes.data if sc is not None else None, m,
+                                                 C.byref(first), assign.ctypes.data))
+        self.src_n += m
+        return first.value, assign[:m].copy()
 
     def search_masked(self, queries, k, nprobe, mask_of=None, want_probe=False):
         """search() over the rows live in each query's mask (mask_of as HipContext.search_partitions_masked)."""
