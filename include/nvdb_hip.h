@@ -192,6 +192,14 @@ nvdb_status nvdb_hip_range_results(nvdb_hip_ctx* ctx, uint64_t* out_ids, float* 
  * shadow, 3 an int8 corpus.  After a host-API call that retried, out4[3] describes the last attempt. */
 nvdb_status nvdb_hip_shadow_info(const nvdb_hip_ctx* ctx, uint64_t* out4);
 
+/* The scales of a resident int8 filter shadow, read-only (all 0 without one).  A load writes the shadow under ONE common scale -- the
+ * largest per-row reference scale of the corpus, so nothing clips -- where that widens the largest quantisation residual of any row by
+ * at most a quarter (option "shadow_common_scale", set before the load: 0 = always the reference's per-row scales); the flat search then
+ * tests the filter's accumulators without a multiply.  out4[0] = 1 if every scale of the shadow is the common one (an inserted row
+ * above it clears the fact, results stay exact either way), out4[1] = the common scale the load found, out4[2] / out4[3] = the
+ * largest residual the load measured under the per-row rule / under the common scale (0: not measured). */
+nvdb_status nvdb_hip_shadow_scale_info(const nvdb_hip_ctx* ctx, double* out4);
+
 /* Merge per-shard top-k lists (e.g. after an RCCL all-gather): in[s][nq][k] -> out[nq][k] with
  * the same (score desc, id asc) order.  Device buffers, enqueued on hip_stream.  Any k the flat path accepts (the reference
  * bounds k by N only, src/flat_index.cpp:24): up to nshards*k = 4096 the lists of one query are ranked in LDS; longer ones are

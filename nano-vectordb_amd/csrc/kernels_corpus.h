@@ -77,16 +77,20 @@ static __global__ __launch_bounds__(256) void shadow_i8_kernel(const signed char
   }
 }
 
-// int8 FILTER shadow of an fp16 / fp32 corpus (option q8_shadow): the rows quantised per row by the reference's own rule
+// int8 FILTER shadow of an fp16 / fp32 corpus (option q8_shadow): the rows quantised by the reference's own rule
 // (apps/nvdb_quantize_i8.cpp:71-80: scale = max|x| / 127, rint(x / scale), clamp +-127), rows zero-padded to sdim, plus -- what turns
 // a lossy copy into a usable FILTER -- the largest quantisation residual ||x - scale * x_q||_2 over all rows (float bits via atomicMax):
 // |<q, x> - <q, scale * x_q>| <= ||q|| * that, which the query prep adds to the filter's error bound.  One wave per row.
-// out_bits[0] = max residual norm (slightly inflated), out_bits[1] = 1 if a row held a non-finite value (no shadow then).
+// common_scale == 0: every row under its own reference scale.  common_scale > 0: every row under THAT scale, which is also what
+// dst_scales gets (shadow_scale_plan.h; a row whose reference scale is larger clips at +-127 and pays for it in its residual).
+// dst == nullptr: nothing is written -- the reduction pass of a load (the largest reference scale, the per-row rule's residual).
+// out_bits[0] = max residual norm (slightly inflated), out_bits[1] = 1 if a row held a non-finite value (no shadow then),
+// out_bits[2] = the largest reference scale max|x| / 127 of any row (0 for a corpus of zeros).
 template <typename SrcT>
 __global__ __launch_bounds__(256) void shadow_q8_kernel(const SrcT* __restrict__ src, signed char* __restrict__ dst, float* __restrict__ dst_scales,
-                                                        uint64_t n, uint32_t dim, uint32_t sdim, uint32_t* __restrict__ out_bits) {
+                                                        uint64_t n, uint32_t dim, uint32_t sdim, float common_scale, uint32_t* __restrict__ out_bits) {
   const int lane = threadIdx.x & 63;
-  float wres = 0.f;
+  float wres = 0.f, wscale = 0.f;
   bool bad = false;
   for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6); r < n; r += static_cast<uint64_t>(gridDim.x) * 4) {
     const SrcT* row = src + r * dim;
@@ -94,23 +98,24 @@ __global__ __launch_bounds__(256) void shadow_q8_kernel(const SrcT* __restrict__
     for (uint32_t c = lane; c < dim; c += 64) mx = fmaxf(mx, fabsf(static_cast<float>(row[c])));
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     if (!(mx < 3.0e38f)) bad = true;
-    const float scale = mx > 0.f ? mx / 127.f : 1.f;
+    wscale = fmaxf(wscale, mx / 127.f);
+    const float scale = common_scale > 0.f ? common_scale : mx > 0.f ? mx / 127.f : 1.f;
     const float inv = 1.0f / scale;
     float ss = 0.f;
-    signed char* out = dst + r * sdim;
     for (uint32_t c = lane; c < sdim; c += 64) {
       float qv = 0.f, x = 0.f;
       if (c < dim) { x = static_cast<float>(row[c]); qv = fminf(fmaxf(rintf(x * inv), -127.f), 127.f); }
-      out[c] = static_cast<signed char>(static_cast<int>(qv));
+      if (dst) dst[r * sdim + c] = static_cast<signed char>(static_cast<int>(qv));
       const float d = x - qv * scale;
       ss = __builtin_fmaf(d, d, ss);
     }
     for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
     if (!(ss == ss)) bad = true;                       // a NaN element: fmaxf above dropped it, its residual did not
-    if (lane == 0) dst_scales[r] = scale;
+    if (dst && lane == 0) dst_scales[r] = scale;
     wres = fmaxf(wres, sqrtf(ss) * 1.0001f);
   }
   if (lane == 0 && wres > 0.f) atomicMax(out_bits, __builtin_bit_cast(uint32_t, wres));
+  if (lane == 0 && wscale > 0.f && wscale < 3.0e38f) atomicMax(out_bits + 2, __builtin_bit_cast(uint32_t, wscale));
   if (lane == 0 && (bad || !(wres < 3.0e38f))) out_bits[1] = 1u;
 }
 

@@ -19,7 +19,7 @@ void free_corpus(nvdb_hip_ctx* c) {
   if (c->shadow8_scales) { (void)hipFree(c->shadow8_scales); c->shadow8_scales = nullptr; }
   c->rows = nullptr; c->scales = nullptr; c->owned = false; c->n = 0; c->cap_rows = 0; c->dim = 0; c->fdim = 0; c->dtype = 0; c->max_norm = 0.f;
   c->cap_hint = 0;
-  c->q8shadow = false; c->resid_max = 0.f; c->filter_max_norm = 0.f;
+  c->q8shadow = false; c->resid_max = 0.f; c->filter_max_norm = 0.f; c->shadow_cs = ShadowScaleFact{};
   c->shadow_demoted = false; c->last_filter_kind = FILTER_NONE;
   c->range_valid = false; c->range_total = 0;      // the held range results describe the rows they were found in
   parts_drop(c);                                   // a partition table describes the rows it was set for
@@ -49,7 +49,7 @@ nvdb_status compute_max_norm(nvdb_hip_ctx* c) {
   // dim (skipped when values would overflow a half).  int8: its own instantiations, no shadow.
   c->fdim = c->dim;
   c->filter_max_norm = c->max_norm;
-  c->q8shadow = false; c->resid_max = 0.f;
+  c->q8shadow = false; c->resid_max = 0.f; c->shadow_cs = ShadowScaleFact{};
   // Option q8_shadow: an fp16 / fp32 corpus is FILTERED through an int8 copy of itself -- half (a quarter) of the bytes per row and
   // integer MFMAs at twice the fp16 rate; the rows' quantisation residual joins the filter's error bound and every survivor is
   // re-scored from the ORIGINAL rows, so ids and scores stay bit-exact.  Costs n x (dim + 4) bytes of HBM.  1: always; automatic
@@ -77,14 +77,36 @@ nvdb_status compute_max_norm(nvdb_hip_ctx* c) {
     const size_t n_pad = (static_cast<size_t>(c->n) + PAD_ROWS - 1) / PAD_ROWS * PAD_ROWS + PAD_ROWS;
     HIPCHK(c, hipMemsetAsync(c->shadow8 + count, 0, pad, c->stream));
     HIPCHK(c, hipMemsetAsync(c->shadow8_scales, 0, n_pad * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(bits, 0, 8, c->stream));
-    if (c->dtype == NVDB_DTYPE_F32) shadow_q8_kernel<float><<<grid, 256, 0, c->stream>>>(static_cast<const float*>(c->rows), c->shadow8, c->shadow8_scales, c->n, c->dim, sdim, bits);
-    else shadow_q8_kernel<_Float16><<<grid, 256, 0, c->stream>>>(static_cast<const _Float16*>(c->rows), c->shadow8, c->shadow8_scales, c->n, c->dim, sdim, bits);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(hb, bits, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // One pass per rule (shadow_scale_plan.h): the reduction pass writes nothing and finds s_c, the largest reference scale of any row,
+    // and the per-row rule's resid_max; where the option and s_c allow, the rows are written under s_c (every scale entry = s_c) and
+    // kept if that residual stays within the margin; otherwise they are written again under their own scales, as the reference does.
+    uint32_t hb4[4] = {0, 0, 0, 0};
+    auto pass = [&](bool write, float common) -> nvdb_status {
+      HIPCHK(c, hipMemsetAsync(bits, 0, 16, c->stream));
+      signed char* dst = write ? c->shadow8 : nullptr;
+      if (c->dtype == NVDB_DTYPE_F32) shadow_q8_kernel<float><<<grid, 256, 0, c->stream>>>(static_cast<const float*>(c->rows), dst, c->shadow8_scales, c->n, c->dim, sdim, common, bits);
+      else shadow_q8_kernel<_Float16><<<grid, 256, 0, c->stream>>>(static_cast<const _Float16*>(c->rows), dst, c->shadow8_scales, c->n, c->dim, sdim, common, bits);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(hb4, bits, 16, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      return NVDB_OK;
+    };
+    ShadowScaleFact fact;
+    if (c->opt_shadow_common_scale != 0) {
+      if ((st = pass(false, 0.f))) return st;
+      std::memcpy(&fact.resid_row, &hb4[0], 4);
+      std::memcpy(&fact.s_c, &hb4[2], 4);
+      if (shadow_cs_try(c->opt_shadow_common_scale, hb4[1] != 0, fact.s_c)) {
+        if ((st = pass(true, fact.s_c))) return st;
+        std::memcpy(&fact.resid_common, &hb4[0], 4);
+        fact.common = shadow_cs_keep(fact.resid_row, fact.resid_common, hb4[1] != 0);
+      }
+    }
+    if (!fact.common && (st = pass(true, 0.f))) return st;
+    hb[0] = hb4[0]; hb[1] = hb4[1];
     if (hb[1] == 0) {
       std::memcpy(&c->resid_max, &hb[0], 4);
+      c->shadow_cs = fact;
       // row norms of the shadow (what the int8 kernels stream): the query side of the bound and the lo-plane margin are priced with them
       HIPCHK(c, hipMemsetAsync(bits, 0, 8, c->stream));
       row_norm_max_kernel<DT_I8><<<grid, 256, 0, c->stream>>>(c->shadow8, c->shadow8_scales, c->n, sdim, bits);
@@ -410,6 +432,7 @@ nvdb_status nvdb_hip_set_option(nvdb_hip_ctx* c, const char* key, int64_t value)
   else if (k == "sibling_sync") { c->opt_sibling_sync = value ? 1 : 0; }
   else if (k == "f32_shadow") { c->opt_f32_shadow = value ? 1 : 0; }
   else if (k == "q8_shadow") { c->opt_q8_shadow = value < 0 ? -1 : value ? 1 : 0; }
+  else if (k == "shadow_common_scale") { c->opt_shadow_common_scale = value == 0 ? 0 : -1; }
   else if (k == "q8_auto_min_rows") { if (value < 1) return fail(c, NVDB_ERR_INVALID, "q8_auto_min_rows must be >= 1"); c->opt_q8_auto_min_rows = value; }
   else if (k == "q8_auto_max_mb") { if (value < 0 || value > (int64_t(1) << 30)) return fail(c, NVDB_ERR_INVALID, "q8_auto_max_mb out of range"); c->opt_q8_auto_max_mb = value; }
 #ifdef NVDB_HIP_DEV
@@ -467,6 +490,16 @@ nvdb_status nvdb_hip_shadow_info(const nvdb_hip_ctx* c, uint64_t* out4) {
   out4[1] = c->q8shadow ? q8_shadow_bytes(c->n, c->dim) : 0u;
   out4[2] = c->shadow_demoted ? 1u : 0u;
   out4[3] = c->last_filter_kind;
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_shadow_scale_info(const nvdb_hip_ctx* c, double* out4) {
+  if (!c || !out4) return NVDB_ERR_INVALID;
+  const bool on = c->q8shadow;
+  out4[0] = on && c->shadow_cs.common ? 1.0 : 0.0;
+  out4[1] = on ? c->shadow_cs.s_c : 0.0;
+  out4[2] = on ? c->shadow_cs.resid_row : 0.0;
+  out4[3] = on ? c->shadow_cs.resid_common : 0.0;
   return NVDB_OK;
 }
 

@@ -57,6 +57,7 @@
 #include "kernels_exact.h"       // Cand, FinalSelect
 #include "kernels_filter.h"      // Hit, ScatterArgs, PrepInit, tile constants
 #include "nvdb_common.h"
+#include "shadow_scale_plan.h"
 
 using namespace nvdbhip;
 
@@ -105,6 +106,8 @@ struct nvdb_hip_ctx {
   bool shadow_demoted = false;                     // the shadow's lists or wave logs overflowed on this corpus (host API's retry ladder): searches start on the fp16 filter, in the spirit of cap_hint; a reload clears it
   float filter_max_norm = 0.f;                     // max row norm of what the int8 filter streams (== max_norm for an int8 corpus; the shadow's for q8shadow -- max_norm stays the fp16 filter's)
   float resid_max = 0.f;                           // q8shadow: largest ||x - scale * x_q|| over the rows -- the corpus side of the filter's error bound
+  ShadowScaleFact shadow_cs;                       // q8shadow: is the shadow written under ONE scale (shadow_scale_plan.h)?  common: the flat search runs the bits-domain first stage
+  int64_t opt_shadow_common_scale = -1;            // set before the corpus is loaded: 0 = the shadow keeps the reference's per-row scales, otherwise automatic (one common scale where shadow_cs_keep allows it)
   int64_t opt_q8_shadow = -1;                      // set before the corpus is loaded: 1 = build the int8 filter shadow for fp16 / fp32 corpora whose dim the int8 kernels take, 0 = never (set later: also stop
                                                    // streaming a resident one where the fp16 filter stands beside it), -1 = automatic (q8_shadow_wanted below)
   int64_t opt_q8_auto_min_rows = 1 << 20;          // automatic shadow: corpora with at least this many rows (smaller ones are latency-bound: today's chain) ...

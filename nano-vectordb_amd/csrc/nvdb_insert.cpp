@@ -235,15 +235,26 @@ nvdb_status insert_staged(nvdb_hip_ctx* c, const char* who, const InsertStage& s
   float new_filter_norm = 0.f, new_resid = 0.f;
   bool shadow_bad = false;                           // a new row holds a value a load would not have built the resident shadow for
   DevTmp sh8, sh8s, sh16;
+  ShadowScaleFact cs = c->shadow_cs;
   const void* staged_sh8s = nullptr;
   if (c->q8shadow) {
     if ((st = tmp_alloc(c, sh8, m * c->dim)) || (st = tmp_alloc(c, sh8s, m * 4))) return st;
-    HIPCHK(c, hipMemsetAsync(bits, 0, 8, s));
     const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((m + 3) / 4, 4096));
-    if (c->dtype == NVDB_DTYPE_F32) shadow_q8_kernel<float><<<grid, 256, 0, s>>>(static_cast<const float*>(stage.rows), static_cast<signed char*>(sh8.p), static_cast<float*>(sh8s.p), m, c->dim, c->dim, bits);
-    else shadow_q8_kernel<_Float16><<<grid, 256, 0, s>>>(static_cast<const _Float16*>(stage.rows), static_cast<signed char*>(sh8.p), static_cast<float*>(sh8s.p), m, c->dim, c->dim, bits);
-    HIPCHK(c, hipGetLastError());
-    if ((st = read_bits(c, s, bits, hb))) return st;
+    uint32_t hb4[4] = {0, 0, 0, 0};
+    auto quantise = [&](float common) -> nvdb_status {
+      HIPCHK(c, hipMemsetAsync(bits, 0, 16, s));
+      if (c->dtype == NVDB_DTYPE_F32) shadow_q8_kernel<float><<<grid, 256, 0, s>>>(static_cast<const float*>(stage.rows), static_cast<signed char*>(sh8.p), static_cast<float*>(sh8s.p), m, c->dim, c->dim, common, bits);
+      else shadow_q8_kernel<_Float16><<<grid, 256, 0, s>>>(static_cast<const _Float16*>(stage.rows), static_cast<signed char*>(sh8.p), static_cast<float*>(sh8s.p), m, c->dim, c->dim, common, bits);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(hb4, bits, 16, hipMemcpyDeviceToHost, s));
+      HIPCHK(c, hipStreamSynchronize(s));
+      return NVDB_OK;
+    };
+    // a shadow under one common scale takes the new rows under that scale; a new row above it has clipped: the new rows are
+    // quantised again under their own scales and the fact falls (shadow_scale_plan.h) -- applied below, once the move has succeeded
+    if ((st = quantise(cs.common ? cs.s_c : 0.f))) return st;
+    if (cs.common && !shadow_cs_after_write(cs, as_float(hb4[2])) && (st = quantise(0.f))) return st;
+    hb[0] = hb4[0]; hb[1] = hb4[1];
     new_resid = as_float(hb[0]);
     shadow_bad = hb[1] != 0;
     if (!shadow_bad) {
@@ -328,6 +339,7 @@ nvdb_status insert_staged(nvdb_hip_ctx* c, const char* who, const InsertStage& s
     if (c->q8shadow) {
       c->filter_max_norm = std::max(c->filter_max_norm, new_filter_norm);
       c->resid_max = std::max(c->resid_max, new_resid);
+      c->shadow_cs = cs;
     } else {
       c->filter_max_norm = c->max_norm;
       c->i8_scales_signed = c->i8_scales_signed || new_signed;

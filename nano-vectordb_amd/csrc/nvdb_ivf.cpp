@@ -368,6 +368,7 @@ nvdb_status nvdb_hip_ivf_build(nvdb_hip_ctx* src, const float* centroids, uint32
   nvdb_hip_ctx* c = ix->ctx;
   auto ctx_fail = [&](nvdb_status s_) { return bail(s_, "ivf_build: " + c->err); };
   c->opt_f32_shadow = src->opt_f32_shadow;          // (options that act when a corpus becomes resident)
+  c->opt_shadow_common_scale = src->opt_shadow_common_scale;
   c->opt_q8_shadow = src->opt_q8_shadow > 0 ? 1 : 0;   // (the explicit option only: the automatic shadow serves the flat route, which an index's context does not run)
   void* rows = nullptr;
   float* scales = nullptr;

@@ -33,6 +33,7 @@ nvdb_status launch_filter_i8_dim(nvdb_hip_ctx* c, FilterRun& run, RowRange rows)
 template <int DIM, int NB, int MB> auto i8w_build(bool sync) { return sync ? filter_i8w_kernel<DIM, NB, 6, true, MB> : filter_i8w_kernel<DIM, NB, 6, false, MB>; }
 template <int DIM, int WPB, bool DEFER> auto i8p_build(bool sync) { return sync ? filter_i8p_kernel<DIM, true, false, 6, WPB, DEFER> : filter_i8p_kernel<DIM, false, false, 6, WPB, DEFER>; }
 template <int DIM, int WPB> auto i8s_build(bool sync) { return sync ? filter_i8s_kernel<DIM, true, false, 6, WPB> : filter_i8s_kernel<DIM, false, false, 6, WPB>; }
+template <int DIM, int WPB> auto i8c_build(bool sync) { return sync ? shadow_i8c_kernel<DIM, true, 6, WPB> : shadow_i8c_kernel<DIM, false, 6, WPB>; }   // one common scale (shadow_scale_plan.h)
 
 // int8, dims up to 768, 64-row tiles: which build streams which batch.  The product library holds
 //   batches <= 128 (NB = 1)  filter_i8w_kernel at 32 queries per wave; d = 512 / 768 and more than 8 queries (d = 384: more than 64): the
@@ -81,6 +82,16 @@ nvdb_status launch_filter_i8w_dim(nvdb_hip_ctx* c, FilterRun& run, RowRange rows
     // MFMA pipe idles; with two waves per SIMD the partner's MFMAs fill it.  Per launch of the N = 10M ladder the 8-wave build wins 10 / 10 / 5 %
     // where many blocks are flagged and is equal on the last, sparse chunk -- but a 4-wave launch that FOLLOWS 8-wave ones ran 5 % slower than
     // after 4-wave ones, so a search does not mix them (profiles/r07_step0_waves_per_launch.txt, r07_ab_dense8.txt)
+    // a shadow written under one common scale (shadow_scale_plan.h): shadow_i8c_kernel, whose first-stage test compares raw accumulator bits --
+    // same log, same survivors (d = 768, both wave counts; option shadow_common_scale = 0 set AFTER the load keeps the per-row build on it)
+    const bool common = run.kind == FILTER_SHADOW8 && c->q8shadow && c->shadow_cs.common && c->opt_shadow_common_scale != 0;
+    if constexpr (DIM == 768) {
+      if (common) {
+        if (w8 || c->opt_i8_dense8) return launch(i8c_build<DIM, 8>(sync), 8, filter_i8s_lds_bytes<DIM, 8>());
+        return launch(i8c_build<DIM, 4>(sync), 4, filter_i8s_lds_bytes<DIM, 4>());
+      }
+    }
+    (void)common;
     if constexpr (DIM == 768 || (DEV_I8S8_512 && DIM == 512))      // (the developer library also holds the d = 512 build; it runs at d = 768 only)
       if ((w8 || c->opt_i8_dense8) && DIM == 768) return launch(i8s_build<DIM, 8>(sync), 8, filter_i8s_lds_bytes<DIM, 8>());
     if constexpr (DIM >= 384)

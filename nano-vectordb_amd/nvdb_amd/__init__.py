@@ -25,7 +25,7 @@ EXPORTS = [
     "nvdb_hip_abi_version", "nvdb_hip_device_count", "nvdb_hip_create", "nvdb_hip_destroy", "nvdb_hip_last_error",
     "nvdb_hip_upload_corpus", "nvdb_hip_adopt_corpus", "nvdb_hip_generate_corpus", "nvdb_hip_corpus_info",
     "nvdb_hip_download_rows", "nvdb_hip_search_batch", "nvdb_hip_search_batch_dev", "nvdb_hip_search_check",
-    "nvdb_hip_get_stats", "nvdb_hip_range_search", "nvdb_hip_range_results", "nvdb_hip_shadow_info", "nvdb_hip_collect_kernel_times", "nvdb_hip_merge_topk_dev", "nvdb_hip_merge_topk_strided_dev", "nvdb_merge_topk_host", "nvdb_hip_set_option",
+    "nvdb_hip_get_stats", "nvdb_hip_range_search", "nvdb_hip_range_results", "nvdb_hip_shadow_info", "nvdb_hip_shadow_scale_info", "nvdb_hip_collect_kernel_times", "nvdb_hip_merge_topk_dev", "nvdb_hip_merge_topk_strided_dev", "nvdb_merge_topk_host", "nvdb_hip_set_option",
     "nvdb_hip_refine_l2_topk", "nvdb_hip_refine_l2_topk_dev", "nvdb_synth_rows_f32", "nvdb_f32_to_f16",
     "nvdb_quantize_i8_rows",
     "nvdb_hip_group_create", "nvdb_hip_group_destroy", "nvdb_hip_group_last_error", "nvdb_hip_group_size", "nvdb_hip_group_ctx",
@@ -153,6 +153,7 @@ def _bind(L, dev):
     L.nvdb_hip_range_search.argtypes = [vp, vp, u32, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_range_results.argtypes = [vp, vp, vp]
     L.nvdb_hip_shadow_info.argtypes = [vp, C.POINTER(u64)]
+    L.nvdb_hip_shadow_scale_info.argtypes = [vp, C.POINTER(C.c_double)]
     L.nvdb_hip_collect_kernel_times.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double)]
     L.nvdb_hip_merge_topk_dev.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp]
@@ -501,6 +502,14 @@ class HipContext:
         out = (C.c_uint64 * 4)()
         self._chk(self.lib.nvdb_hip_shadow_info(self.h, out))
         return dict(resident=bool(out[0]), bytes=int(out[1]), demoted=bool(out[2]), last_filter=(None, "f16", "shadow", "i8")[out[3]])
+
+    def shadow_scale_info(self):
+        """The scales of the int8 filter shadow: common (every row under one scale: the flat search runs the bits-domain first
+        stage), scale (the common scale the load found), resid_row / resid_common (the largest residual the load measured under the
+        per-row rule / under the common scale; 0: not measured)."""
+        out = (C.c_double * 4)()
+        self._chk(self.lib.nvdb_hip_shadow_scale_info(self.h, out))
+        return dict(common=bool(out[0]), scale=float(out[1]), resid_row=float(out[2]), resid_common=float(out[3]))
 
     def collect_kernel_times(self):
         n, ms, fl, by = C.c_uint32(), C.c_double(), C.c_double(), C.c_double()
