@@ -69,7 +69,7 @@ typedef struct nvdb_hip_timing {
 /* What the last flat search did (for tests, bench.py and the roofline arithmetic). */
 typedef struct nvdb_hip_scan_stats {
   uint32_t path;               /* 1 = exact fp32 scan, 2 = MFMA filter + exact rescore (k <= 1024), 3 = any-k (k > 64 off the filter path), 4 = partitioned probe search,
-                                  5 = range search, filter route, 6 = range search, exact route, 7 = range search, partition scan, 8 = probe search, any k */
+                                  5 = range search, filter route, 6 = range search, exact route, 7 = range search, partition scan, 8 = probe search, any k, 9 = PQ candidate scan */
   uint32_t chunks;             /* corpus chunks (kernel launches of the dominant kernel)          */
   uint64_t rows_scanned;       /* rows x query-tiles streamed by the dominant kernel              */
   uint64_t candidates;         /* (query,row) pairs that reached the exact rescore                */
@@ -707,6 +707,75 @@ nvdb_status nvdb_hip_refine_l2_topk(nvdb_hip_ctx* ctx, const float* queries, con
 nvdb_status nvdb_hip_refine_l2_topk_dev(nvdb_hip_ctx* ctx, const float* dev_queries, const uint32_t* dev_cand_ids,
                                         uint32_t Q, uint32_t R, uint32_t K, uint32_t* dev_out_ids,
                                         float* dev_out_dist, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * PQ candidate generation: the step the refine above follows (reference: FAISS IndexIVFPQ, apps/nvdb_ivfpq_build.cpp -- nlist
+ * 4096, PQ_M 48, 8 bits --, then cuda_l2_topk_batch over R candidates per query, apps/nvdb_ivf_eval.cpp).  A context holds a
+ * PQ SHADOW of its resident corpus (any dtype): M byte codes per row under codebooks the CALLER supplies, as nvdb_hip_ivf_build
+ * is handed its centroids.  The scan walks the probe path's work items, reads M bytes per row instead of the row, and the any-k
+ * select reduces every query's probed union to its R best; nvdb_hip_pq_refine_ivf hands them to the refine without leaving the
+ * device.  The arithmetic, fixed:
+ *   dsub = dim / M; sub-vector m of a row = elements [m * dsub, (m + 1) * dsub) of the row as an f32 query (see the IVF build).
+ *   encode  code[r][m] = the j < 256 that minimises d(j) = sum_t (x[t] - cb[m][j][t])^2, an fp32 sum of squared differences (not
+ *           the expanded x.c - |c|^2 / 2 form); ties go to the lowest j; a NaN distance never wins, a row whose distances are all
+ *           NaN (or +inf) gets code 0.
+ *   tables  L[q][m][j] = sum_t q[m * dsub + t] * cb[m][j][t], fp32.
+ *   score   s(q, r) = sum_m L[q][m][code[r][m]], fp32, m ascending, from 0 (NON-residual dot-product ADC).  A NaN score is no
+ *           candidate: neither returned nor counted, as on the range and any-k paths.
+ *   order   score descending, then local row ascending.
+ * Whatever makes rows resident or moves them -- upload, adopt, generate, nvdb_hip_compact_rows, nvdb_hip_insert_rows and the index
+ * forms of both -- frees the shadow; afterwards the calls below return NVDB_ERR_INVALID ("no PQ codes: nvdb_hip_pq_build").
+ * Cost, plainly: the build is n * dim * 256 fmas on the vector ALUs and n * M bytes of HBM; a search computes M KB of tables per
+ * query, then per work item copies the tables of its <= G queries into LDS (G = 8 up to M = 19, 4 up to 39, 2 up to 78, else 1),
+ * reads M bytes per row once per group and WRITES 8 bytes per (row, query) -- every row of the union is scored and written,
+ * nothing is pruned inside the scan --, then the any-k select: per query one workgroup that reads its block once per radix pass.
+ * Out of scope: training codebooks (the caller trains them; the encode kernel is the assignment step a trainer would reuse),
+ * residual encoding, OPQ rotations, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
+ * pruning inside the scan, the device group, _dev stream forms, the nvdb:: C++ host layer.
+ * ------------------------------------------------------------------------------------------- */
+
+/* codebooks: [M][256][dim / M] f32, host memory.  M >= 4, M % 4 == 0, M <= 128, dim % M == 0, else NVDB_ERR_INVALID; dim / M > 32
+ * -> NVDB_ERR_UNSUPPORTED (the encode kernel's widest build); null pointer -> NVDB_ERR_INVALID; no corpus -> NVDB_ERR_NO_CORPUS.
+ * On any failure nothing has changed: an earlier build stands.  An adopted corpus is fine: the codes are the library's own array.
+ * Replaces an earlier build.  Non-finite rows or codebooks: no fault, no hang. */
+nvdb_status nvdb_hip_pq_build(nvdb_hip_ctx* ctx, const float* codebooks /* [M][256][dim / M] */, uint32_t M);
+/* every output optional; all 0 without codes.  code_bytes = n * M */
+nvdb_status nvdb_hip_pq_info(nvdb_hip_ctx* ctx, uint32_t* M, uint32_t* dsub, uint64_t* code_bytes);
+/* out[nrows][M] (host) = the codes of resident rows [row0, row0 + nrows); row0 + nrows > n -> NVDB_ERR_INVALID; nrows == 0 -> NVDB_OK */
+nvdb_status nvdb_hip_pq_download_codes(nvdb_hip_ctx* ctx, uint64_t row0, uint64_t nrows, uint8_t* out /* [nrows][M] */);
+/* The R best PQ scores of every query's probed union: out_ids[nq][R] global ids, out_scores[nq][R] the PQ scores, out_counts[q]
+ * (optional) = min(R, rows of the union whose score is no NaN); slots beyond the count hold UINT64_MAX / -inf.  R is NOT clamped.
+ * probe[nq][nprobe]: nvdb_hip_search_partitions' rules.  R == 0 or nq == 0 -> NVDB_OK, nothing written; nprobe == 0 -> every
+ * count 0, outputs all padding; null pointers, no partition table, no PQ codes -> NVDB_ERR_INVALID; no corpus ->
+ * NVDB_ERR_NO_CORPUS.  Non-finite queries: no fault, no hang.  The sub-batch cut is nvdb_hip_search_partitions_anyk's, with at
+ * most a quarter of "largek_budget_mb" in tables; the caller does not see it.
+ * nvdb_hip_get_stats afterwards: path = 9, chunks = scan launches, rows_scanned = rows of the work items, candidates =
+ * non-padding entries of the candidate blocks.  timing (optional): as nvdb_hip_search_partitions_anyk. */
+nvdb_status nvdb_hip_pq_search_partitions(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t R,
+                                          const uint32_t* probe /* [nq][nprobe] */, uint32_t nprobe,
+                                          uint64_t* out_ids /* [nq][R] */, float* out_scores /* [nq][R] */,
+                                          uint32_t* out_counts /* [nq], may be NULL */, nvdb_hip_timing* timing /* may be NULL */);
+/* The coarse step (on the full rows' centroids, exact), the clamp of nprobe and out_probe are nvdb_hip_search_ivf's. */
+nvdb_status nvdb_hip_pq_search_ivf(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe,
+                                   uint64_t* out_ids /* [nq][R] */, float* out_scores /* [nq][R] */,
+                                   uint32_t* out_counts /* [nq], may be NULL */, uint32_t* out_probe /* may be NULL */,
+                                   nvdb_hip_timing* timing /* may be NULL */);
+/* nvdb_hip_pq_search_ivf with R, then nvdb_hip_refine_l2_topk over those candidates, per sub-batch on the device: only
+ * out_ids[nq][K] (GLOBAL ids, ascending by squared L2 distance, padding UINT64_MAX) and out_dist[nq][K] (may be NULL; padding
+ * 1e30f) are copied back -- the ids and the distance bits of the two calls composed.  K <= 64, else NVDB_ERR_INVALID; corpus dtype
+ * F16 or F32, as the refine requires (I8 -> NVDB_ERR_UNSUPPORTED); K == 0, R == 0 or nq == 0 -> NVDB_OK, nothing written;
+ * nprobe == 0 -> all padding. */
+nvdb_status nvdb_hip_pq_refine_ivf(nvdb_hip_ctx* ctx, const float* queries, uint32_t nq, uint32_t K, uint32_t R, uint32_t nprobe,
+                                   uint64_t* out_ids /* [nq][K] */, float* out_dist /* [nq][K], may be NULL */,
+                                   uint32_t* out_probe /* may be NULL */, nvdb_hip_timing* timing /* may be NULL */);
+/* The three calls on the index's context (its rows are the list-ordered copy: nvdb_hip_ivf_compact and nvdb_hip_ivf_add_rows free
+ * the shadow), then the id mapping of nvdb_hip_ivf_search_anyk: every id that is not padding becomes src's global_row_base +
+ * perm[id]; equal scores (distances) stand by position in the lists. */
+nvdb_status nvdb_hip_ivf_pq_build(nvdb_hip_ivf* ivf, const float* codebooks, uint32_t M);
+nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe,
+                                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing);
+nvdb_status nvdb_hip_ivf_pq_refine(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t K, uint32_t R, uint32_t nprobe,
+                                   uint64_t* out_ids, float* out_dist, uint32_t* out_probe, nvdb_hip_timing* timing);
 
 /* ---------------------------------------------------------------------------------------------
  * host-side helpers that define the corpus bits (no GPU needed)

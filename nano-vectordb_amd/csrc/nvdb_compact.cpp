@@ -157,6 +157,7 @@ nvdb_status nvdb_hip_compact_rows(nvdb_hip_ctx* c, uint32_t mask, uint64_t* out_
   c->mask_live = live;
   c->n = n_new;
   c->range_valid = false; c->range_total = 0;        // the held range results name rows by their old numbers
+  pq_drop(c);                                        // PQ codes are not carried through the move: nvdb_hip_pq_build again
   if (out_n) *out_n = n_new;
   return NVDB_OK;
 }

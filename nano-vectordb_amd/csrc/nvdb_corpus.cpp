@@ -23,6 +23,7 @@ void free_corpus(nvdb_hip_ctx* c) {
   c->shadow_demoted = false; c->last_filter_kind = FILTER_NONE;
   c->range_valid = false; c->range_total = 0;      // the held range results describe the rows they were found in
   parts_drop(c);                                   // a partition table describes the rows it was set for
+  pq_drop(c);                                      // ... a PQ shadow the rows it was encoded from
   c->nmasks = 0;                                   // ... and so do the row masks
 }
 

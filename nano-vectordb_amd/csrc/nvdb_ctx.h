@@ -16,6 +16,8 @@
 //                          image -> copies -> launches by class), the top-k argument check; row masks and the masked searches (kernels_partitions.h, row_mask.h)
 //   parts_worklist.h       the work list itself and its image's layout, plain C++ with no HIP call (as nvdb_plan.h, range_plan.h, parts_anyk_plan.h, masked_plan.h)
 //   nvdb_parts_anyk.cpp    the probe search for any k: per sub-batch one pass at radius -inf, select, long slabs (kernels_parts_anyk.h, parts_anyk_plan.h)
+//   nvdb_pq.cpp            the PQ candidate scan: the PQ shadow of a corpus (encode), per sub-batch tables, scan over the probe path's work items, the any-k
+//                          select, optionally the refine on the device (kernels_pq.h, pq_plan.h)
 //   nvdb_masked_flat.cpp   the masked flat top-k on the MFMA filter route: prefix rank, bootstrap bar, the range search's filter pass, top-k of the kept
 //                          lists (kernels_masked_topk.h, masked_plan.h)
 //   nvdb_compact.cpp       in-place compaction of tombstoned rows: rank, slab walk (direct / bounce), planes, partition table (kernels_compact.h, compact_plan.h);
@@ -81,6 +83,14 @@ struct DevBuf {
 };
 
 struct PartState;                             // nvdb_partitions.cpp: partition table, centroids and workspace of the probe search
+
+// the PQ shadow of the resident corpus (nvdb_pq.cpp, pq_plan.h): exists from nvdb_hip_pq_build until the rows change
+struct PqState {
+  uint32_t M = 0, dsub = 0;                        // sub-quantisers, elements per sub-vector (dim / M)
+  float* codebooks = nullptr;                      // [M][256][dsub] f32
+  uint8_t* codes = nullptr;                        // [n][M], library-owned, zero-padded by PAD_ROWS rows
+  DevBuf lut;                                      // [queries of a sub-batch][M][256] f32, grow-only
+};
 
 }  // namespace nvdbhip
 
@@ -196,6 +206,7 @@ struct nvdb_hip_ctx {
   int64_t opt_refine_v2 = 2;                       // refine kernel: 0 lane per row, 1 column chunks through LDS, 2 whole rows through LDS (fp16 d = 256/384/512/768; else 1)
   int64_t opt_mfma16 = 1;                          // 1: use the 16x16x32 MFMA build for 256-query tiles
   std::set<const void*> lds_attr_set;              // kernels whose dynamic-LDS limit was raised on this device
+  nvdbhip::PqState* pq = nullptr;                  // PQ shadow (nvdb_hip_pq_build); whatever makes rows resident or moves them frees it (pq_drop)
   nvdbhip::PartState* parts = nullptr;             // partitioned probe search (created by nvdb_hip_set_partitions, or by the first masked flat search)
   DevBuf row_masks, mask_rows;                     // row masks (nvdb_hip_set_row_masks): [nmasks][ceil(n / 32)] words; staging of nvdb_hip_update_row_mask's row list
   uint32_t nmasks = 0;                             // ... planes resident (0: none; any corpus load drops them, the buffer stays)
@@ -411,6 +422,8 @@ nvdb_status corpus_rederive(nvdb_hip_ctx* c);
 // nvdb_partitions.cpp
 void parts_drop(nvdb_hip_ctx* c);        // the corpus changes: forget the partition table and the centroids (the workspace stays)
 void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace
+// nvdb_pq.cpp
+void pq_drop(nvdb_hip_ctx* c);           // the rows change: free the PQ shadow, if there is one
 // nvdb_search.cpp
 nvdb_status ensure_q32(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes);          // the host API's query buffer: qbytes + 8 rows; a new buffer starts all zero
 nvdb_status zero_q32_pad(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes);        // ... and the 8 rows behind this call's queries read as zeros

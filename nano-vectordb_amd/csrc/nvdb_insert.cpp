@@ -351,6 +351,7 @@ nvdb_status insert_staged(nvdb_hip_ctx* c, const char* who, const InsertStage& s
     for (uint64_t& live : c->mask_live) live += m;
   }
   c->range_valid = false; c->range_total = 0;        // the held range results name rows by their old numbers
+  pq_drop(c);                                        // PQ codes are not carried through the move: nvdb_hip_pq_build again
   if (out_new_rows) std::copy(new_rows.begin(), new_rows.end(), out_new_rows);
   if (out_n) *out_n = n_new;
   if (out_plan) *out_plan = std::move(pl);

@@ -544,6 +544,27 @@ nvdb_status nvdb_hip_ivf_search_anyk(nvdb_hip_ivf* ix, const float* queries, uin
   return NVDB_OK;
 }
 
+nvdb_status nvdb_hip_ivf_pq_build(nvdb_hip_ivf* ix, const float* codebooks, uint32_t M) {
+  if (!ix) return NVDB_ERR_INVALID;
+  return ivf_forward(ix, nvdb_hip_pq_build(ix->ctx, codebooks, M));
+}
+
+nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe, uint64_t* out_ids, float* out_scores,
+                                   uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
+  if (!ix) return NVDB_ERR_INVALID;
+  if (nvdb_status st = ivf_forward(ix, nvdb_hip_pq_search_ivf(ix->ctx, queries, nq, R, nprobe, out_ids, out_scores, out_counts, out_probe, timing))) return st;
+  if (nq && R) ivf_map_ids(ix, out_ids, static_cast<uint64_t>(nq) * R);
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_ivf_pq_refine(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t K, uint32_t R, uint32_t nprobe, uint64_t* out_ids, float* out_dist,
+                                   uint32_t* out_probe, nvdb_hip_timing* timing) {
+  if (!ix) return NVDB_ERR_INVALID;
+  if (nvdb_status st = ivf_forward(ix, nvdb_hip_pq_refine_ivf(ix->ctx, queries, nq, K, R, nprobe, out_ids, out_dist, out_probe, timing))) return st;
+  if (nq && R && K) ivf_map_ids(ix, out_ids, static_cast<uint64_t>(nq) * K);
+  return NVDB_OK;
+}
+
 nvdb_status nvdb_hip_ivf_range_search(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, const float* radius, uint32_t nprobe, const uint32_t* mask_of, int masked,
                                       uint64_t* out_lims, uint32_t* out_probe, nvdb_hip_timing* timing) {
   if (!ix) return NVDB_ERR_INVALID;

@@ -114,7 +114,7 @@ nvdb_status parts_stage(nvdb_hip_ctx* c, const PartList& wl, uint32_t nq, const 
 nvdb_status parts_pass(nvdb_hip_ctx* c, hipStream_t s, const char* who, const PartBuild& pb, PartPass& p, const PartPassHook& between) {
   PartState* ps = c->parts;
   nvdb_status st;
-  if (const char* why = pw_worklist(ps->list, p.off, p.nparts, p.q0, p.b, p.nprobe, PART_WAVES * pb.qw_max, p.slot_cap, p.wl))
+  if (const char* why = pw_worklist(ps->list, p.off, p.nparts, p.q0, p.b, p.nprobe, p.qg_max ? p.qg_max : PART_WAVES * pb.qw_max, p.slot_cap, p.wl))
     return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": " + why);
   if (p.skip_empty && !p.wl.total) return NVDB_OK;
   if (between && (st = between(p))) return st;

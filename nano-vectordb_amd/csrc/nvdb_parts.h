@@ -10,6 +10,7 @@
 
 #include "nvdb_ctx.h"
 #include "kernels_partitions.h"
+#include "parts_anyk_plan.h"
 #include "row_mask.h"
 
 namespace nvdbhip {
@@ -111,6 +112,7 @@ struct PartPass {
   const uint64_t* off = nullptr;
   uint32_t nparts = 0, q0 = 0, b = 0, nprobe = 0;
   uint32_t slot_cap = 0;                           // an (item, query) gets min(slot_cap, segment rows) candidate slots
+  uint32_t qg_max = 0;                             // queries per group at most; 0: PART_WAVES * pb.qw_max (a value <= PART_WAVES: every item is class 0)
   const MaskSel* msel = nullptr;                   // the BATCH's (nullptr: unmasked): the pass takes mask_of + q0
   const float* queries = nullptr;                  // the BATCH's, host memory: rows q0 .. go to ps->q; nullptr: they are on the device already
   const uint32_t* extra = nullptr;                 // words behind the work list in the image (the hook may set them)
@@ -122,7 +124,7 @@ struct PartPass {
   PartImage im;
 };
 
-// The set-up of a pass on stream s: build the work list (qg_max = PART_WAVES * pb.qw_max), run `between` (optional: what a caller
+// The set-up of a pass on stream s: build the work list (groups of p.qg_max queries, by default PART_WAVES * pb.qw_max), run `between` (optional: what a caller
 // does between list and image -- grow buffers of its own, rewrite items, set p.extra), grow cand and q, stage the pinned image,
 // enqueue its copy to meta and, where p.queries is given, the queries' copy to ps->q.
 using PartPassHook = std::function<nvdb_status(PartPass&)>;
@@ -145,6 +147,18 @@ nvdb_status parts_scan_classes(nvdb_hip_ctx* c, const PartBuild& pb, const PartI
   }
   return NVDB_OK;
 }
+
+// The any-k tail of a pass with uncapped slots (nvdb_parts_anyk.cpp), shared by the probe search for any k and the PQ candidate
+// scan (nvdb_pq.cpp): once the scan has filled the queries' candidate blocks, the k best of every block.
+struct PaSub { PaPlan plan; std::vector<uint32_t> extra, hcnt, hraw; };          // a sub-batch's plan and host scratch, reused across sub-batches
+// the body of parts_pass' hook: the plan of b queries with these blocks, its words behind the work list (pp.extra: [radius (-inf) b |
+// slab_off 2 b | long lists]), the device output, the counts and the key slabs grown
+nvdb_status pa_sub_plan(nvdb_hip_ctx* c, const char* who, const uint64_t* block, uint32_t b, uint32_t k, PaSub& sub, PartPass& pp);
+// select, long slabs' sorts, emit: ps->out_ids / out_scores ([b][plan.out_k], global ids, padded) and out_counts, c->rg_pcnt (raw counts) on the device
+nvdb_status pa_sub_select(nvdb_hip_ctx* c, hipStream_t s, const PaSub& sub, const PartImage& im, uint32_t b, uint32_t k);
+// the sub-batch's rows into the caller's [b][k] arrays (ids0 == nullptr: they stay on the device), the counts (optional), one
+// synchronisation, the padding beyond plan.out_k, stats.candidates
+nvdb_status pa_sub_finish(nvdb_hip_ctx* c, hipStream_t s, PaSub& sub, uint32_t b, uint32_t k, uint64_t* ids0, float* sc0, uint32_t* counts0);
 
 // The bracket of a call that runs its passes between two events on c->stream (the range scan, the any-k search).  begin: sets
 // the device, records event 60, replaces c->stats by an empty record of `path`, clears what nvdb_hip_search_check reads (it

@@ -15,6 +15,83 @@
 
 namespace nvdbhip {
 
+// ---- the any-k tail of a pass: what parts_anyk_search below and the PQ candidate scan (nvdb_pq.cpp) do alike (nvdb_parts.h) ----
+
+nvdb_status pa_sub_plan(nvdb_hip_ctx* c, const char* who, const uint64_t* block, uint32_t b, uint32_t k, PaSub& sub, PartPass& pp) {
+  PartState* ps = c->parts;
+  PaPlan& plan = sub.plan;
+  if (!pa_plan(block, b, k, plan)) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 results for one query");
+  const uint32_t nlong = static_cast<uint32_t>(plan.longs.size());
+  // behind the work list in the pinned image: [radius (-inf) b | slab_off 2 b | long lists 4 nlong]
+  sub.extra.assign(static_cast<size_t>(b) * 3 + static_cast<size_t>(nlong) * 4, 0xFF800000u);
+  std::copy(plan.slab_off.begin(), plan.slab_off.end(), sub.extra.begin() + b);
+  if (nlong) std::memcpy(sub.extra.data() + static_cast<size_t>(b) * 3, plan.longs.data(), static_cast<size_t>(nlong) * sizeof(PaLong));
+  pp.extra = sub.extra.data(); pp.extra_words = static_cast<uint32_t>(sub.extra.size());
+  const size_t out_entries = static_cast<size_t>(b) * plan.out_k;
+  nvdb_status e;
+  if ((e = ensure(c, ps->out_ids, out_entries * 8))) return e;
+  if ((e = ensure(c, ps->out_scores, out_entries * 4))) return e;
+  if ((e = ensure(c, ps->out_counts, static_cast<size_t>(b) * 4))) return e;
+  if ((e = ensure(c, c->rg_pcnt, static_cast<size_t>(b) * 4))) return e;
+  return ensure(c, c->rg_slab, static_cast<size_t>(plan.slab_keys) * 8);
+}
+
+nvdb_status pa_sub_select(nvdb_hip_ctx* c, hipStream_t s, const PaSub& sub, const PartImage& im, uint32_t b, uint32_t k) {
+  PartState* ps = c->parts;
+  const PaPlan& plan = sub.plan;
+  const uint32_t nlong = static_cast<uint32_t>(plan.longs.size());
+  const uint32_t* d_slab_off = im.extra + b;
+  const PaLong* d_longs = reinterpret_cast<const PaLong*>(im.extra + static_cast<size_t>(b) * 3);
+  const Cand* cand = static_cast<const Cand*>(ps->cand.p);
+  unsigned long long* d_ids = static_cast<unsigned long long*>(ps->out_ids.p);
+  float* d_scores = static_cast<float*>(ps->out_scores.p);
+  uint32_t* d_counts = static_cast<uint32_t*>(ps->out_counts.p);
+  unsigned long long* slab = static_cast<unsigned long long*>(c->rg_slab.p);
+  nvdb_status st;
+  const size_t lds = PA_LDS_HEAD + static_cast<size_t>(plan.lds_keys) * 8;
+  if (lds > 64 * 1024)
+    if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(parts_anyk_select_kernel), PA_LDS_HEAD + static_cast<size_t>(PA_LDS_KEYS) * 8))) return st;
+  parts_anyk_select_kernel<<<b, PA_THREADS, lds, s>>>(cand, im.cbeg, k, plan.out_k, c->row_base, d_slab_off, slab, d_ids, d_scores, d_counts,
+                                                      static_cast<uint32_t*>(c->rg_pcnt.p));
+  HIPCHK(c, hipGetLastError());
+  for (uint32_t a = 0; a < nlong;) {                                 // slabs of one length side by side: one sort per length
+    uint32_t z = a;
+    while (z < nlong && plan.longs[z].K2 == plan.longs[a].K2) ++z;
+    const uint64_t first = (static_cast<uint64_t>(plan.longs[a].off_hi) << 32) | plan.longs[a].off_lo;
+    if ((st = launch_sort_keys(c, s, slab + first, plan.longs[a].K2, z - a))) return st;
+    a = z;
+  }
+  for (uint32_t a = 0; a < nlong; a += 32768u) {                     // (the lists are one grid dimension of the launch)
+    const uint32_t n_l = std::min<uint32_t>(32768u, nlong - a);
+    parts_anyk_emit_kernel<<<dim3((plan.out_k + 255u) / 256u, n_l), 256, 0, s>>>(slab, d_longs + a, cand, im.cbeg, d_counts, plan.out_k, c->row_base, d_ids, d_scores);
+    HIPCHK(c, hipGetLastError());
+  }
+  return NVDB_OK;
+}
+
+nvdb_status pa_sub_finish(nvdb_hip_ctx* c, hipStream_t s, PaSub& sub, uint32_t b, uint32_t k, uint64_t* ids0, float* sc0, uint32_t* counts0) {
+  PartState* ps = c->parts;
+  const PaPlan& plan = sub.plan;
+  const size_t out_entries = static_cast<size_t>(b) * plan.out_k;
+  // the sub-batch's rows into the caller's arrays; what lies beyond the device rows' width is padding
+  if (ids0 && plan.out_k == k) {
+    HIPCHK(c, hipMemcpyAsync(ids0, ps->out_ids.p, out_entries * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(sc0, ps->out_scores.p, out_entries * 4, hipMemcpyDeviceToHost, s));
+  } else if (ids0) {
+    HIPCHK(c, hipMemcpy2DAsync(ids0, static_cast<size_t>(k) * 8, ps->out_ids.p, static_cast<size_t>(plan.out_k) * 8, static_cast<size_t>(plan.out_k) * 8, b, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpy2DAsync(sc0, static_cast<size_t>(k) * 4, ps->out_scores.p, static_cast<size_t>(plan.out_k) * 4, static_cast<size_t>(plan.out_k) * 4, b, hipMemcpyDeviceToHost, s));
+  }
+  sub.hcnt.resize(b);
+  sub.hraw.resize(b);
+  HIPCHK(c, hipMemcpyAsync(sub.hcnt.data(), ps->out_counts.p, static_cast<size_t>(b) * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(sub.hraw.data(), c->rg_pcnt.p, static_cast<size_t>(b) * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));                // (the next sub-batch rewrites the blocks, the image and the device output)
+  if (ids0) pad_rows(b, k, plan.out_k, ids0, sc0);
+  if (counts0) std::copy(sub.hcnt.begin(), sub.hcnt.end(), counts0);
+  for (uint32_t i = 0; i < b; ++i) c->stats.candidates += sub.hraw[i];
+  return NVDB_OK;
+}
+
 namespace {
 
 constexpr uint32_t PARTS_STAT_ANYK = 8;                              // nvdb_hip_scan_stats::path
@@ -36,92 +113,34 @@ nvdb_status parts_anyk_search(nvdb_hip_ctx* c, const char* who, const float* que
   hipStream_t s = c->stream;
 
   const uint64_t budget_entries = (static_cast<uint64_t>(c->opt_largek_budget_mb) << 20) / (2 * sizeof(Cand));
-  std::vector<uint32_t> extra, hcnt, hraw;
-  PaPlan plan;
+  PaSub sub;
   for (uint32_t q0 = 0; q0 < nq;) {
     const uint32_t q1 = pa_cut(block.data(), nq, q0, k, budget_entries);
     if (q1 == q0) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": one query's probed union holds 2^32 rows or more");
     const uint32_t b = q1 - q0;
     uint64_t* ids0 = out_ids + static_cast<size_t>(q0) * k;
     float* sc0 = out_scores + static_cast<size_t>(q0) * k;
-    uint32_t nlong = 0;
-    size_t out_entries = 0;
     PartPass p;
     p.off = off; p.nparts = nparts; p.q0 = q0; p.b = b; p.nprobe = nprobe; p.slot_cap = 0xFFFFFFFFu;
     p.msel = msel; p.queries = queries;
     p.skip_empty = true;
-    st = parts_pass(c, s, who, pb, p, [&](PartPass& pp) -> nvdb_status {
-      if (!pa_plan(block.data() + q0, b, k, plan)) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 results for one query");
-      nlong = static_cast<uint32_t>(plan.longs.size());
-      // behind the work list in the pinned image: [radius (-inf) b | slab_off 2 b | long lists 4 nlong]
-      extra.assign(static_cast<size_t>(b) * 3 + static_cast<size_t>(nlong) * 4, 0xFF800000u);
-      std::copy(plan.slab_off.begin(), plan.slab_off.end(), extra.begin() + b);
-      if (nlong) std::memcpy(extra.data() + static_cast<size_t>(b) * 3, plan.longs.data(), static_cast<size_t>(nlong) * sizeof(PaLong));
-      pp.extra = extra.data(); pp.extra_words = static_cast<uint32_t>(extra.size());
-      out_entries = static_cast<size_t>(b) * plan.out_k;
-      nvdb_status e;
-      if ((e = ensure(c, ps->out_ids, out_entries * 8))) return e;
-      if ((e = ensure(c, ps->out_scores, out_entries * 4))) return e;
-      if ((e = ensure(c, ps->out_counts, static_cast<size_t>(b) * 4))) return e;
-      if ((e = ensure(c, c->rg_pcnt, static_cast<size_t>(b) * 4))) return e;
-      return ensure(c, c->rg_slab, static_cast<size_t>(plan.slab_keys) * 8);
-    });
+    st = parts_pass(c, s, who, pb, p, [&](PartPass& pp) { return pa_sub_plan(c, who, block.data() + q0, b, k, sub, pp); });
     if (st) return st;
-    const PartList& wl = p.wl;
     const PartImage& im = p.im;
-    if (!wl.total) {                                                   // no row in any union of the sub-batch
+    if (!p.wl.total) {                                                 // no row in any union of the sub-batch
       pad_rows(b, k, 0, ids0, sc0, out_counts ? out_counts + q0 : nullptr);
       q0 = q1;
       continue;
     }
     const float* d_radius = reinterpret_cast<const float*>(im.extra);
-    const uint32_t* d_slab_off = im.extra + b;
-    const PaLong* d_longs = reinterpret_cast<const PaLong*>(im.extra + static_cast<size_t>(b) * 3);
-    const Cand* cand = static_cast<const Cand*>(ps->cand.p);
-    unsigned long long* d_ids = static_cast<unsigned long long*>(ps->out_ids.p);
-    float* d_scores = static_cast<float*>(ps->out_scores.p);
-    uint32_t* d_counts = static_cast<uint32_t*>(ps->out_counts.p);
-    unsigned long long* slab = static_cast<unsigned long long*>(c->rg_slab.p);
     uint32_t launches = 0;
     if ((st = parts_scan_classes(c, pb, im, static_cast<const float*>(ps->q.p), launches,
                                  [&](uint32_t qw, const ScanArgs& a) { return launch_range_parts(c, s, qw, pb.staged, d_radius, a); })))
       return st;
     c->stats.chunks += launches;
-    const size_t lds = PA_LDS_HEAD + static_cast<size_t>(plan.lds_keys) * 8;
-    if (lds > 64 * 1024)
-      if ((st = raise_lds_limit(c, reinterpret_cast<const void*>(parts_anyk_select_kernel), PA_LDS_HEAD + static_cast<size_t>(PA_LDS_KEYS) * 8))) return st;
-    parts_anyk_select_kernel<<<b, PA_THREADS, lds, s>>>(cand, im.cbeg, k, plan.out_k, c->row_base, d_slab_off, slab, d_ids, d_scores, d_counts,
-                                                        static_cast<uint32_t*>(c->rg_pcnt.p));
-    HIPCHK(c, hipGetLastError());
-    for (uint32_t a = 0; a < nlong;) {                                 // slabs of one length side by side: one sort per length
-      uint32_t z = a;
-      while (z < nlong && plan.longs[z].K2 == plan.longs[a].K2) ++z;
-      const uint64_t first = (static_cast<uint64_t>(plan.longs[a].off_hi) << 32) | plan.longs[a].off_lo;
-      if ((st = launch_sort_keys(c, s, slab + first, plan.longs[a].K2, z - a))) return st;
-      a = z;
-    }
-    for (uint32_t a = 0; a < nlong; a += 32768u) {                     // (the lists are one grid dimension of the launch)
-      const uint32_t n_l = std::min<uint32_t>(32768u, nlong - a);
-      parts_anyk_emit_kernel<<<dim3((plan.out_k + 255u) / 256u, n_l), 256, 0, s>>>(slab, d_longs + a, cand, im.cbeg, d_counts, plan.out_k, c->row_base, d_ids, d_scores);
-      HIPCHK(c, hipGetLastError());
-    }
-    // the sub-batch's rows into the caller's arrays; what lies beyond the device rows' width is padding
-    if (plan.out_k == k) {
-      HIPCHK(c, hipMemcpyAsync(ids0, d_ids, out_entries * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(c, hipMemcpyAsync(sc0, d_scores, out_entries * 4, hipMemcpyDeviceToHost, s));
-    } else {
-      HIPCHK(c, hipMemcpy2DAsync(ids0, static_cast<size_t>(k) * 8, d_ids, static_cast<size_t>(plan.out_k) * 8, static_cast<size_t>(plan.out_k) * 8, b, hipMemcpyDeviceToHost, s));
-      HIPCHK(c, hipMemcpy2DAsync(sc0, static_cast<size_t>(k) * 4, d_scores, static_cast<size_t>(plan.out_k) * 4, static_cast<size_t>(plan.out_k) * 4, b, hipMemcpyDeviceToHost, s));
-    }
-    hcnt.resize(b);
-    hraw.resize(b);
-    HIPCHK(c, hipMemcpyAsync(hcnt.data(), d_counts, static_cast<size_t>(b) * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(hraw.data(), c->rg_pcnt.p, static_cast<size_t>(b) * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));                // (the next sub-batch rewrites the blocks, the image and the device output)
-    pad_rows(b, k, plan.out_k, ids0, sc0);
-    if (out_counts) std::copy(hcnt.begin(), hcnt.end(), out_counts + q0);
-    for (uint32_t i = 0; i < b; ++i) c->stats.candidates += hraw[i];
-    c->stats.rows_scanned += wl.rows_read;
+    if ((st = pa_sub_select(c, s, sub, im, b, k))) return st;
+    if ((st = pa_sub_finish(c, s, sub, b, k, ids0, sc0, out_counts ? out_counts + q0 : nullptr))) return st;
+    c->stats.rows_scanned += p.wl.rows_read;
     q0 = q1;
   }
   if ((st = parts_call_end(c, timing))) return st;

@@ -1,0 +1,270 @@
+// nvdb_pq.cpp -- the PQ candidate scan (DESIGN.md section 4 "PQ candidate scan"): the step the exact-L2 refine follows.  A context
+// holds a PQ SHADOW of its resident corpus -- M byte codes per row under the caller's codebooks (nvdb_hip_pq_build: pq_encode_kernel)
+// -- and answers a probe search from the codes alone: per sub-batch of queries
+//   pass          parts_pass (nvdb_parts.h) with uncapped slots and groups of G = pq_group(M) queries (every item is class 0);
+//                 between list and image: the any-k plan (pa_sub_plan), the tables' buffer grown
+//   tables        pq_lut_kernel: L[b][M][256] from the sub-batch's queries on the device (ps->q)
+//   scan          pq_scan_kernel<G, W16>: one launch over the work items; every row of a segment -> Cand{score, row} at its place in the slab
+//   select        pa_sub_select: the any-k path's select, long slabs and emit, unchanged, with k = R
+//   copy          the R candidates of every query into the caller's arrays (pa_sub_finish) -- or, fused (nvdb_hip_pq_refine_ivf):
+//                 pq_narrow_ids_kernel, the refine's device launcher on the same stream over ps->q, and only [b][K] results copied back
+// Sub-batches: pa_cut (parts_anyk_plan.h) under largek_budget_mb, and at most a quarter of that budget in tables.
+// Whatever makes rows resident or moves them frees the shadow (pq_drop); the PQ calls then return NVDB_ERR_INVALID.
+// Entry points: nvdb_hip_pq_build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf; the index forms
+// (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them on the index's context and map the ids.
+#include "nvdb_parts.h"
+#include "kernels_pq.h"
+
+namespace nvdbhip {
+
+void pq_drop(nvdb_hip_ctx* c) {
+  PqState* pq = c->pq;
+  if (!pq) return;
+  if (pq->codebooks) (void)hipFree(pq->codebooks);
+  if (pq->codes) (void)hipFree(pq->codes);
+  if (pq->lut.p) (void)hipFree(pq->lut.p);
+  delete pq;
+  c->pq = nullptr;
+}
+
+namespace {
+
+constexpr uint32_t PARTS_STAT_PQ = 9;                                // nvdb_hip_scan_stats::path
+
+template <int DT>
+nvdb_status launch_encode(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq) {
+  const dim3 grid(static_cast<unsigned>((c->n + PQ_ENC_THREADS - 1) / PQ_ENC_THREADS), pq.M / 4u);
+  auto go = [&](auto kernel) {
+    kernel<<<grid, PQ_ENC_THREADS, 0, s>>>(c->rows, c->scales, c->n, c->dim, pq.M, pq.dsub, pq.codebooks, pq.codes);
+  };
+  switch (pq_encode_bound(pq.dsub)) {
+    case 4: go(pq_encode_kernel<DT, 4>); break;
+    case 8: go(pq_encode_kernel<DT, 8>); break;
+    case 16: go(pq_encode_kernel<DT, 16>); break;
+    default: go(pq_encode_kernel<DT, 32>); break;
+  }
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+// the scan's build for M: G tables in LDS, 16-byte or dword code loads
+template <int G>
+nvdb_status launch_scan_g(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, const PartImage& im, uint32_t nitems) {
+  const size_t lds = G * pq_lut_bytes(pq.M);
+  auto go = [&](auto kernel) -> nvdb_status {
+    if (lds > 64 * 1024)
+      if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(kernel), PART_LDS_LIMIT)) return st;
+    kernel<<<nitems, PQ_SCAN_THREADS, lds, s>>>(pq.codes, pq.M, im.items, im.qidx, im.dst, static_cast<const float*>(pq.lut.p), static_cast<Cand*>(c->parts->cand.p));
+    HIPCHK(c, hipGetLastError());
+    return NVDB_OK;
+  };
+  return pq_wide_codes(pq.M) ? go(pq_scan_kernel<G, true>) : go(pq_scan_kernel<G, false>);
+}
+
+nvdb_status launch_scan(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, const PartImage& im, uint32_t nitems) {
+  switch (pq_group(pq.M)) {
+    case 8: return launch_scan_g<8>(c, s, pq, im, nitems);
+    case 4: return launch_scan_g<4>(c, s, pq, im, nitems);
+    case 2: return launch_scan_g<2>(c, s, pq, im, nitems);
+    default: return launch_scan_g<1>(c, s, pq, im, nitems);
+  }
+}
+
+// what a fused call adds to the search: K results per query by exact L2 over the R candidates (out_dist may be nullptr)
+struct PqRefine { uint32_t K; uint64_t* out_ids; float* out_dist; };
+
+// the search proper: the arguments are validated, nq > 0, R > 0 and nprobe > 0.  rf == nullptr: the R candidates go to out_ids /
+// out_scores / out_counts; else they stay on the device and rf's arrays receive the refined results
+nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, uint32_t nq, uint32_t R, const uint32_t* probe, uint32_t nprobe,
+                      uint64_t* out_ids, float* out_scores, uint32_t* out_counts, const PqRefine* rf, nvdb_hip_timing* timing) {
+  PartState* ps = c->parts;
+  PqState& pq = *c->pq;
+  const uint64_t* off = ps->offsets.data();
+  const uint32_t nparts = static_cast<uint32_t>(ps->offsets.size() - 1);
+  const PartBuild pb = parts_build(c);                               // (the pass takes its group size from p.qg_max)
+  nvdb_status st;
+  std::vector<uint64_t> block(nq, 0);
+  if ((st = parts_probes(c, who, off, nparts, nq, probe, nprobe, block.data()))) return st;
+
+  if ((st = parts_call_begin(c, PARTS_STAT_PQ))) return st;
+  hipStream_t s = c->stream;
+
+  const uint64_t budget_bytes = static_cast<uint64_t>(c->opt_largek_budget_mb) << 20;
+  const uint64_t budget_entries = budget_bytes / (2 * sizeof(Cand));
+  const uint32_t lut_batch = pq_lut_batch(pq.M, budget_bytes / 4);
+  PaSub sub;
+  std::vector<uint32_t> h_rid;
+  for (uint32_t q0 = 0; q0 < nq;) {
+    const uint32_t q1 = pa_cut(block.data(), static_cast<uint32_t>(std::min<uint64_t>(nq, static_cast<uint64_t>(q0) + lut_batch)), q0, R, budget_entries);
+    if (q1 == q0) return fail(c, NVDB_ERR_UNSUPPORTED, std::string(who) + ": one query's probed union holds 2^32 rows or more");
+    const uint32_t b = q1 - q0;
+    uint64_t* ids0 = rf ? nullptr : out_ids + static_cast<size_t>(q0) * R;
+    float* sc0 = rf ? nullptr : out_scores + static_cast<size_t>(q0) * R;
+    PartPass p;
+    p.off = off; p.nparts = nparts; p.q0 = q0; p.b = b; p.nprobe = nprobe; p.slot_cap = 0xFFFFFFFFu;
+    p.qg_max = pq_group(pq.M);
+    p.queries = queries;
+    p.skip_empty = true;
+    st = parts_pass(c, s, who, pb, p, [&](PartPass& pp) -> nvdb_status {
+      if (nvdb_status e = pa_sub_plan(c, who, block.data() + q0, b, R, sub, pp)) return e;
+      return ensure(c, pq.lut, b * pq_lut_bytes(pq.M));
+    });
+    if (st) return st;
+    if (!p.wl.total) {                                                 // no row in any union of the sub-batch
+      if (rf) {
+        std::fill(rf->out_ids + static_cast<size_t>(q0) * rf->K, rf->out_ids + static_cast<size_t>(q1) * rf->K, ~0ull);
+        if (rf->out_dist) std::fill(rf->out_dist + static_cast<size_t>(q0) * rf->K, rf->out_dist + static_cast<size_t>(q1) * rf->K, 1e30f);
+      } else {
+        pad_rows(b, R, 0, ids0, sc0, out_counts ? out_counts + q0 : nullptr);
+      }
+      q0 = q1;
+      continue;
+    }
+    pq_lut_kernel<<<dim3(pq.M / 4u, b), 256, 0, s>>>(static_cast<const float*>(ps->q.p), c->dim, pq.M, pq.dsub, pq.codebooks, static_cast<float*>(pq.lut.p));
+    HIPCHK(c, hipGetLastError());
+    if ((st = launch_scan(c, s, pq, p.im, static_cast<uint32_t>(p.wl.nitems)))) return st;
+    c->stats.chunks += 1;
+    if ((st = pa_sub_select(c, s, sub, p.im, b, R))) return st;
+    if (rf) {
+      // the candidates stay on the device: [b][out_k] global ids -> u32 local rows -> the refine over this sub-batch's queries
+      const uint32_t r_dev = sub.plan.out_k;
+      const size_t nc = static_cast<size_t>(b) * r_dev, no = static_cast<size_t>(b) * rf->K;
+      if ((st = ensure(c, c->rcand, nc * 4)) || (st = ensure(c, c->rout_ids, no * 4)) || (st = ensure(c, c->rout_dist, no * 4))) return st;
+      pq_narrow_ids_kernel<<<static_cast<unsigned>((nc + 255) / 256), 256, 0, s>>>(static_cast<const unsigned long long*>(ps->out_ids.p), nc, c->row_base,
+                                                                                static_cast<uint32_t*>(c->rcand.p));
+      HIPCHK(c, hipGetLastError());
+      if ((st = nvdb_hip_refine_l2_topk_dev(c, static_cast<const float*>(ps->q.p), static_cast<const uint32_t*>(c->rcand.p), b, r_dev, rf->K,
+                                            static_cast<uint32_t*>(c->rout_ids.p), rf->out_dist ? static_cast<float*>(c->rout_dist.p) : nullptr, s)))
+        return st;
+      h_rid.resize(no);
+      HIPCHK(c, hipMemcpyAsync(h_rid.data(), c->rout_ids.p, no * 4, hipMemcpyDeviceToHost, s));
+      if (rf->out_dist) HIPCHK(c, hipMemcpyAsync(rf->out_dist + static_cast<size_t>(q0) * rf->K, c->rout_dist.p, no * 4, hipMemcpyDeviceToHost, s));
+    }
+    if ((st = pa_sub_finish(c, s, sub, b, R, ids0, sc0, out_counts ? out_counts + q0 : nullptr))) return st;
+    if (rf)
+      for (size_t i = 0; i < h_rid.size(); ++i) rf->out_ids[static_cast<size_t>(q0) * rf->K + i] = h_rid[i] == 0xFFFFFFFFu ? ~0ull : c->row_base + h_rid[i];
+    c->stats.rows_scanned += p.wl.rows_read;
+    q0 = q1;
+  }
+  if ((st = parts_call_end(c, timing))) return st;
+  if (timing) {
+    timing->K = rf ? rf->K : R; timing->R = R;
+    timing->threads = PQ_SCAN_THREADS; timing->shmem_bytes = pq_group(pq.M) * pq_lut_bytes(pq.M);
+  }
+  return NVDB_OK;
+}
+
+// what every PQ call checks first: a context, a corpus, codes
+nvdb_status pq_args(nvdb_hip_ctx* c, const char* who) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
+  if (!c->pq) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no PQ codes: nvdb_hip_pq_build");
+  return NVDB_OK;
+}
+
+nvdb_status pq_search_args(nvdb_hip_ctx* c, const char* who, bool ivf, const float* queries, uint32_t nq, uint32_t R, const uint32_t* probe, uint32_t nprobe,
+                           uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing, bool* done) {
+  *done = true;
+  if (nvdb_status st = pq_args(c, who)) return st;
+  return parts_topk_args(c, who, ivf, 0, queries, nq, R, probe, nprobe, nullptr, out_ids, out_scores, out_counts, timing, done);
+}
+
+}  // namespace
+}  // namespace nvdbhip
+
+extern "C" {
+
+nvdb_status nvdb_hip_pq_build(nvdb_hip_ctx* c, const float* codebooks, uint32_t M) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
+  if (!codebooks) return fail(c, NVDB_ERR_INVALID, "pq_build: null codebooks");
+  bool unsupported = false;
+  if (const char* why = pq_shape_check(c->dim, M, unsupported)) return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, std::string("pq_build: ") + why);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  PqState fresh;
+  fresh.M = M; fresh.dsub = c->dim / M;
+  const size_t cb_bytes = static_cast<size_t>(M) * PQ_KSUB * fresh.dsub * 4;
+  const size_t code_bytes = static_cast<size_t>(c->n) * M, pad_bytes = static_cast<size_t>(PAD_ROWS) * M;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&fresh.codebooks), cb_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.codes), code_bytes + pad_bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(fresh.codebooks, codebooks, cb_bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(fresh.codes + code_bytes, 0, pad_bytes, s);
+  nvdb_status st = NVDB_OK;
+  if (e != hipSuccess) st = fail(c, NVDB_ERR_HIP, std::string("pq_build: ") + hipGetErrorString(e));
+  if (!st) dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_encode<decltype(dt)::value>(c, s, fresh); });
+  if (!st && (e = hipStreamSynchronize(s)) != hipSuccess) st = fail(c, NVDB_ERR_HIP, std::string("pq_build: ") + hipGetErrorString(e));
+  if (st) {                                                            // nothing changed: an earlier build stands
+    (void)hipGetLastError();
+    if (fresh.codebooks) (void)hipFree(fresh.codebooks);
+    if (fresh.codes) (void)hipFree(fresh.codes);
+    return st;
+  }
+  pq_drop(c);
+  c->pq = new PqState(fresh);
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_pq_info(nvdb_hip_ctx* c, uint32_t* M, uint32_t* dsub, uint64_t* code_bytes) {
+  if (!c) return NVDB_ERR_INVALID;
+  const PqState* pq = c->pq;
+  if (M) *M = pq ? pq->M : 0u;
+  if (dsub) *dsub = pq ? pq->dsub : 0u;
+  if (code_bytes) *code_bytes = pq ? c->n * pq->M : 0ull;
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_pq_download_codes(nvdb_hip_ctx* c, uint64_t row0, uint64_t nrows, uint8_t* out) {
+  if (nvdb_status st = pq_args(c, "pq_download_codes")) return st;
+  if (row0 > c->n || nrows > c->n - row0) return fail(c, NVDB_ERR_INVALID, "pq_download_codes: row0 + nrows > n");
+  if (nrows == 0) return NVDB_OK;
+  if (!out) return fail(c, NVDB_ERR_INVALID, "pq_download_codes: null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(out, c->pq->codes + row0 * c->pq->M, nrows * c->pq->M, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_pq_search_partitions(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t R, const uint32_t* probe, uint32_t nprobe,
+                                          uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing) {
+  const char* who = "pq_search_partitions";
+  bool done;
+  const nvdb_status st = pq_search_args(c, who, false, queries, nq, R, probe, nprobe, out_ids, out_scores, out_counts, timing, &done);
+  if (st || done) return st;
+  return pq_search(c, who, queries, nq, R, probe, nprobe, out_ids, out_scores, out_counts, nullptr, timing);
+}
+
+nvdb_status nvdb_hip_pq_search_ivf(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe, uint64_t* out_ids, float* out_scores,
+                                   uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
+  const char* who = "pq_search_ivf";
+  bool done;
+  nvdb_status st = pq_search_args(c, who, true, queries, nq, R, nullptr, nprobe, out_ids, out_scores, out_counts, timing, &done);
+  if (st || done) return st;
+  uint32_t np = 0;
+  if ((st = parts_coarse(c, who, queries, nq, nprobe, out_probe, timing, np))) return st;
+  return pq_search(c, who, queries, nq, R, c->parts->probe_tmp.data(), np, out_ids, out_scores, out_counts, nullptr, timing);
+}
+
+nvdb_status nvdb_hip_pq_refine_ivf(nvdb_hip_ctx* c, const float* queries, uint32_t nq, uint32_t K, uint32_t R, uint32_t nprobe, uint64_t* out_ids,
+                                   float* out_dist, uint32_t* out_probe, nvdb_hip_timing* timing) {
+  const char* who = "pq_refine_ivf";
+  nvdb_status st = pq_args(c, who);
+  if (st || (st = parts_args(c, who))) return st;
+  if (!c->parts->have_centroids) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no centroids (nvdb_hip_set_centroids)");
+  if (timing) std::memset(timing, 0, sizeof(*timing));
+  if (nq == 0 || R == 0 || K == 0) return NVDB_OK;
+  if (c->dtype != NVDB_DTYPE_F16 && c->dtype != NVDB_DTYPE_F32) return fail(c, NVDB_ERR_UNSUPPORTED, "refine supports base dtype fp16/fp32 only");
+  if (K > NVDB_HIP_REFINE_KMAX) return fail(c, NVDB_ERR_INVALID, "refine: K not supported (K<=64)");
+  if (!queries || !out_ids) return fail(c, NVDB_ERR_INVALID, queries ? "null output" : "Null query");
+  if (nprobe == 0) {
+    std::fill(out_ids, out_ids + static_cast<size_t>(nq) * K, ~0ull);
+    if (out_dist) std::fill(out_dist, out_dist + static_cast<size_t>(nq) * K, 1e30f);
+    return NVDB_OK;
+  }
+  uint32_t np = 0;
+  if ((st = parts_coarse(c, who, queries, nq, nprobe, out_probe, timing, np))) return st;
+  const PqRefine rf{K, out_ids, out_dist};
+  return pq_search(c, who, queries, nq, R, c->parts->probe_tmp.data(), np, nullptr, nullptr, nullptr, &rf, timing);
+}
+
+}  // extern "C"

@@ -1,0 +1,48 @@
+// pq_plan.h -- the host-side arithmetic of the PQ candidate scan (nvdb_pq.cpp, kernels_pq.h; DESIGN.md section 4 "PQ candidate
+// scan"): which shapes a PQ shadow takes, the encode kernel's compile-time sub-vector bound, how many queries' tables a scan
+// workgroup holds in LDS, how its lanes load their codes, and how many queries one sub-batch's tables may serve.  Plain C++ with
+// no HIP in it, like the other plans.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace nvdbhip {
+
+constexpr uint32_t PQ_KSUB = 256;                   // codewords per sub-quantiser: one byte per code
+constexpr uint32_t PQ_M_MAX = 128;                  // sub-quantisers at most: one query's tables are M KB of LDS
+constexpr uint32_t PQ_DSUB_MAX = 32;                // the encode kernel's widest build: a lane holds its sub-vector in 32 registers, 256 codewords x 32 floats = 32 KB of LDS
+constexpr size_t PQ_LDS_BUDGET = 156 * 1024;        // LDS the tables of a scan workgroup may take (of 160 KB)
+
+// 0: fine; else why nvdb_hip_pq_build refuses the shape (unsupported: the arguments are valid, the build does not exist)
+inline const char* pq_shape_check(uint32_t dim, uint32_t M, bool& unsupported) {
+  unsupported = false;
+  if (M < 4 || M % 4 != 0 || M > PQ_M_MAX) return "M must be a multiple of 4 in [4, 128]";
+  if (dim == 0 || dim % M != 0) return "dim must be a multiple of M";
+  if (dim / M > PQ_DSUB_MAX) { unsupported = true; return "dim / M <= 32 (the encode kernel's widest build)"; }
+  return nullptr;
+}
+
+// the encode kernel's build for sub-vectors of dsub elements: the smallest bound of {4, 8, 16, 32} that holds them
+constexpr uint32_t pq_encode_bound(uint32_t dsub) { return dsub <= 4 ? 4u : dsub <= 8 ? 8u : dsub <= 16 ? 16u : 32u; }
+
+// bytes of one query's tables: [M][256] f32
+constexpr size_t pq_lut_bytes(uint32_t M) { return static_cast<size_t>(M) * PQ_KSUB * 4; }
+
+// THE LDS budget rule: queries per scan workgroup = the largest G of {8, 4, 2, 1} whose tables fit (8 up to M = 19, 4 up to 39,
+// 2 up to 78, 1 up to 128)
+constexpr uint32_t pq_group(uint32_t M) {
+  for (uint32_t G = 8; G > 1; G >>= 1)
+    if (G * pq_lut_bytes(M) <= PQ_LDS_BUDGET) return G;
+  return 1;
+}
+
+// a lane reads its row's codes in 16-byte pieces where a row is whole pieces, else in dwords (M % 4 == 0 always)
+constexpr bool pq_wide_codes(uint32_t M) { return M % 16 == 0; }
+
+// queries one sub-batch may hold tables for: budget_bytes of them, at least one
+constexpr uint32_t pq_lut_batch(uint32_t M, uint64_t budget_bytes) {
+  const uint64_t b = budget_bytes / pq_lut_bytes(M);
+  return b < 1 ? 1u : b > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(b);
+}
+
+}  // namespace nvdbhip

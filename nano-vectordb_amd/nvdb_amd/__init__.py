@@ -42,6 +42,8 @@ EXPORTS = [
     "nvdb_hip_search_partitions_anyk", "nvdb_hip_search_ivf_anyk", "nvdb_hip_ivf_search_anyk",
     "nvdb_hip_compact_rows", "nvdb_hip_ivf_compact",
     "nvdb_hip_reserve_rows", "nvdb_hip_insert_rows", "nvdb_hip_ivf_add_rows",
+    "nvdb_hip_pq_build", "nvdb_hip_pq_info", "nvdb_hip_pq_download_codes", "nvdb_hip_pq_search_partitions", "nvdb_hip_pq_search_ivf",
+    "nvdb_hip_pq_refine_ivf", "nvdb_hip_ivf_pq_build", "nvdb_hip_ivf_pq_search", "nvdb_hip_ivf_pq_refine",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -217,6 +219,15 @@ def _bind(L, dev):
     L.nvdb_hip_search_ivf_anyk.argtypes = [vp, vp, u32, u32, u32, vp, C.c_int, vp, vp, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_ivf_search_anyk.argtypes = [vp, vp, u32, u32, u32, vp, C.c_int, vp, vp, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_compact_rows.argtypes = [vp, u32, C.POINTER(u64), vp]
+    L.nvdb_hip_pq_build.argtypes = [vp, vp, u32]
+    L.nvdb_hip_pq_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
+    L.nvdb_hip_pq_download_codes.argtypes = [vp, u64, u64, vp]
+    L.nvdb_hip_pq_search_partitions.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_pq_search_ivf.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_pq_refine_ivf.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_ivf_pq_build.argtypes = [vp, vp, u32]
+    L.nvdb_hip_ivf_pq_search.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, C.POINTER(Timing)]
+    L.nvdb_hip_ivf_pq_refine.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_ivf_compact.argtypes = [vp, u32, C.POINTER(u64)]
     L.nvdb_hip_reserve_rows.argtypes = [vp, u64]
     L.nvdb_hip_insert_rows.argtypes = [vp, vp, vp, u64, vp, vp, C.POINTER(u64)]
@@ -677,6 +688,55 @@ class HipContext:
                                                     probe.ctypes.data if want_probe else None, None))
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
+    # -- PQ candidate scan (a PQ shadow of the resident corpus under the caller's codebooks; stats path 9)
+    def pq_build(self, codebooks):
+        """Encode the resident rows under codebooks [M, 256, dim / M] f32 (nearest codeword by squared L2, ties to the lowest)."""
+        codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
+        if codebooks.ndim != 3 or codebooks.shape[1] != 256:
+            raise ValueError("codebooks must be [M, 256, dim / M]")
+        self._chk(self.lib.nvdb_hip_pq_build(self.h, codebooks.ctypes.data, codebooks.shape[0]))
+
+    def pq_info(self):
+        """dict(M, dsub, code_bytes); all 0 without codes."""
+        M, dsub, nbytes = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._chk(self.lib.nvdb_hip_pq_info(self.h, C.byref(M), C.byref(dsub), C.byref(nbytes)))
+        return dict(M=M.value, dsub=dsub.value, code_bytes=nbytes.value)
+
+    def pq_download_codes(self, row0=0, nrows=None):
+        """The codes of resident rows [row0, row0 + nrows) -> [nrows, M] u8."""
+        if nrows is None:
+            nrows = self.corpus_info()["n"] - row0
+        out = np.zeros((max(nrows, 0), self.pq_info()["M"]), dtype=np.uint8)
+        self._chk(self.lib.nvdb_hip_pq_download_codes(self.h, row0, nrows, out.ctypes.data if out.size else None))
+        return out
+
+    def pq_search_partitions(self, queries, R, probe, want_timing=False):
+        """The R best PQ scores of every query's probed union (probe as search_partitions; R is not clamped) -> (ids, scores, counts)."""
+        queries, nq, ids, scores, counts = self._probe_outputs(queries, R)
+        probe = np.ascontiguousarray(probe, dtype=np.uint32).reshape(nq, -1)
+        t = Timing()
+        self._chk(self.lib.nvdb_hip_pq_search_partitions(self.h, queries.ctypes.data, nq, R, probe.ctypes.data, probe.shape[1], ids.ctypes.data,
+                                                         scores.ctypes.data, counts.ctypes.data, C.byref(t) if want_timing else None))
+        return (ids, scores, counts, t) if want_timing else (ids, scores, counts)
+
+    def pq_search_ivf(self, queries, R, nprobe, want_probe=False):
+        """pq_search_partitions over the nprobe partitions with the best centroids (search_ivf's coarse step); (ids, scores, counts[, probe])."""
+        queries, nq, ids, scores, counts = self._probe_outputs(queries, R)
+        probe = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
+        self._chk(self.lib.nvdb_hip_pq_search_ivf(self.h, queries.ctypes.data, nq, R, nprobe, ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
+                                                  probe.ctypes.data if want_probe else None, None))
+        return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
+
+    def pq_refine_ivf(self, queries, K, R, nprobe, want_dist=True, want_timing=False):
+        """pq_search_ivf with R, then the exact-L2 refine of those candidates on the device -> (ids [nq, K] u64 global, padding
+        UINT64_MAX; dist [nq, K], padding 1e30, or None)."""
+        queries, nq, ids, _, _ = self._probe_outputs(queries, K)
+        dist = np.full((nq, K), 1e30, dtype=np.float32) if want_dist else None
+        t = Timing()
+        self._chk(self.lib.nvdb_hip_pq_refine_ivf(self.h, queries.ctypes.data, nq, K, R, nprobe, ids.ctypes.data,
+                                                  dist.ctypes.data if dist is not None else None, None, C.byref(t) if want_timing else None))
+        return (ids, dist, t) if want_timing else (ids, dist)
+
     # -- range search on the probe path (lims, ids, scores as range_search; over range_max_mb the NvdbError carries `.lims`)
     def _range(self, call, queries, radius, mask_of, masked):
         return _range_call(self, lambda: self.lib.nvdb_hip_last_error(self.h).decode(),
@@ -883,6 +943,31 @@ class IvfIndex:
                                                     1 if masked else 0, ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
                                                     probe.ctypes.data if want_probe else None, None))
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
+
+    # -- PQ candidate scan on the index's context, answered in the source corpus' ids
+    def pq_build(self, codebooks):
+        """HipContext.pq_build over the list-ordered rows; compact() and add_rows() free the codes."""
+        codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
+        if codebooks.ndim != 3 or codebooks.shape[1] != 256:
+            raise ValueError("codebooks must be [M, 256, dim / M]")
+        self._chk(self.lib.nvdb_hip_ivf_pq_build(self.h, codebooks.ctypes.data, codebooks.shape[0]))
+
+    def pq_search(self, queries, R, nprobe, want_probe=False):
+        """The R best PQ scores of the nprobe best lists -> (ids, scores, counts[, probe]); equal scores by (partition, original id)."""
+        queries, nq, ids, scores, counts = self.ctx._probe_outputs(queries, R)
+        probe = np.full((nq, nprobe), 0xFFFFFFFF, dtype=np.uint32)
+        self._chk(self.lib.nvdb_hip_ivf_pq_search(self.h, queries.ctypes.data, nq, R, nprobe, ids.ctypes.data, scores.ctypes.data, counts.ctypes.data,
+                                                  probe.ctypes.data if want_probe else None, None))
+        return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
+
+    def pq_refine(self, queries, K, R, nprobe, want_dist=True, want_timing=False):
+        """pq_search with R, then the exact-L2 refine on the device -> (ids [nq, K] in the source corpus' ids, dist or None)."""
+        queries, nq, ids, _, _ = self.ctx._probe_outputs(queries, K)
+        dist = np.full((nq, K), 1e30, dtype=np.float32) if want_dist else None
+        t = Timing()
+        self._chk(self.lib.nvdb_hip_ivf_pq_refine(self.h, queries.ctypes.data, nq, K, R, nprobe, ids.ctypes.data,
+                                                  dist.ctypes.data if dist is not None else None, None, C.byref(t) if want_timing else None))
+        return (ids, dist, t) if want_timing else (ids, dist)
 
     def range_search(self, queries, radius, nprobe, mask_of=None, masked=None, want_probe=False):
         """Every row of the nprobe best lists whose score reaches the query's radius, optionally restricted to the rows live in its

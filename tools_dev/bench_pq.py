@@ -1,0 +1,124 @@
+"""PQ candidate generation beside the only route to the same candidates without it, on the same index in the same process.
+
+    python tools_dev/bench_pq.py [rows] [dim] [dtype] [nlist] [M] [batch] [calls] [warmup]
+                                 (defaults: 10000000 768 f16 4096 48 1024 10 2)
+
+An IVF index over the synthetic corpus (centroids: two k-means rounds over 262144 rows), codebooks from a few Lloyd rounds per
+sub-quantiser over 20000 sampled rows on the host (training is the caller's: this is a stand-in, not a tuned quantiser).  For
+nprobe in (8, 32) and R in (100, 1024), median wall ms per call, alternating the two routes call by call, of
+  ivf_pq_search R                 PQ scan + select                     | ivf_search_anyk k = R     exact scores of the full rows + select
+  ivf_pq_refine K = 10            the fused pipeline                   | ivf_search_anyk k = R, then refine_l2_topk on the index's rows
+and recall@10 of both refined results against the exact flat top-10 by squared L2 distance over the rows as f32 (the search's
+own score is the dot product, so the flat reference is the refine over every row, taken from a flat scan's 1024 best dot
+products -- stated with the figure).  Prints the build's wall time and one JSON line with all of it."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "nano-vectordb_amd"), os.path.join(ROOT, "oracle")):
+    sys.path.insert(0, p)
+import nvdb_amd  # noqa: E402
+
+U64MAX = np.iinfo(np.uint64).max
+
+
+def train_codebooks(sample, M, rounds, seed):
+    """[M, 256, dsub] f32: per sub-quantiser 256 sampled sub-vectors, then `rounds` Lloyd rounds (nearest by squared L2, mean)."""
+    rs = np.random.RandomState(seed)
+    n, dim = sample.shape
+    dsub = dim // M
+    cb = np.empty((M, 256, dsub), dtype=np.float32)
+    for m in range(M):
+        x = sample[:, m * dsub:(m + 1) * dsub]
+        c = x[rs.choice(n, 256, replace=False)].copy()
+        for _ in range(rounds):
+            d = (x * x).sum(1)[:, None] - 2.0 * x @ c.T + (c * c).sum(1)[None]
+            a = d.argmin(1)
+            for j in range(256):
+                if (a == j).any():
+                    c[j] = x[a == j].mean(0)
+        cb[m] = c
+    return cb
+
+
+def alternate_ms(fa, fb, calls, warmup):
+    for _ in range(warmup):
+        fa(); fb()
+    ta, tb = [], []
+    for _ in range(calls):
+        t0 = time.perf_counter(); fa(); t1 = time.perf_counter(); fb(); t2 = time.perf_counter()
+        ta.append((t1 - t0) * 1e3); tb.append((t2 - t1) * 1e3)
+    return [float(np.median(t)) for t in (ta, tb)] + [float(np.min(ta)), float(np.max(ta)), float(np.min(tb)), float(np.max(tb))]
+
+
+def recall(got, want):
+    return float(np.mean([len(set(g[g != U64MAX].tolist()) & set(w.tolist())) / len(w) for g, w in zip(got, want)]))
+
+
+def main():
+    a = sys.argv[1:]
+    rows = int(a[0]) if len(a) > 0 else 10_000_000
+    dim = int(a[1]) if len(a) > 1 else 768
+    dname = a[2] if len(a) > 2 else "f16"
+    dtype = {"f16": nvdb_amd.DT_F16, "f32": nvdb_amd.DT_F32}[dname]
+    nlist = int(a[3]) if len(a) > 3 else 4096
+    M = int(a[4]) if len(a) > 4 else 48
+    batch = int(a[5]) if len(a) > 5 else 1024
+    calls = int(a[6]) if len(a) > 6 else 10
+    warmup = int(a[7]) if len(a) > 7 else 2
+    seed, K = 20240613, 10
+    out = dict(rows=rows, dim=dim, dtype=dname, nlist=nlist, M=M, batch=batch, calls=calls, warmup=warmup, K=K)
+
+    src = nvdb_amd.HipContext(0)
+    src.generate_corpus(seed, rows, dim, dtype)
+    q = np.ascontiguousarray(nvdb_amd.synth_rows_f32(seed + 1, 0, batch, dim))
+    # the exact flat top-10 by squared L2: the refine over the flat scan's 1024 best dot products
+    fid, _ = src.search_batch(q, 1024)
+    want, _ = src.refine_l2_topk(q, fid.astype(np.uint32), K)
+    want = want.astype(np.uint64)
+    t0 = time.perf_counter()
+    cents = src.train_centroids(nlist, 2, seed, max_train_rows=262144)
+    t1 = time.perf_counter()
+    ix = nvdb_amd.IvfIndex(src, cents)
+    t2 = time.perf_counter()
+    rs = np.random.RandomState(3)
+    pick = np.sort(rs.choice(rows, 20000, replace=False))
+    sample = np.concatenate([src.download_rows(int(r), 1)[0] for r in pick])
+    sample = sample.view(np.float16).astype(np.float32) if dtype == nvdb_amd.DT_F16 else sample
+    src.close()
+    t3 = time.perf_counter()
+    cb = train_codebooks(sample, M, 4, 7)
+    t4 = time.perf_counter()
+    ix.pq_build(cb)
+    t5 = time.perf_counter()
+    out["build"] = dict(train_centroids_s=t1 - t0, ivf_build_s=t2 - t1, codebooks_host_s=t4 - t3, pq_build_s=t5 - t4)
+    print(f"train_centroids {t1 - t0:.2f} s, ivf_build {t2 - t1:.2f} s, host codebooks {t4 - t3:.2f} s, pq_build (upload + encode {rows} rows) {t5 - t4:.3f} s")
+    perm = ix.info()["perm"].astype(np.uint64)
+
+    def exact_then_refine(R, nprobe):
+        ids, _, _ = ix.ctx.search_ivf_anyk(q, R, nprobe)                 # positions in the index's rows, as the refine wants them
+        return ix.ctx.refine_l2_topk(q, np.where(ids == U64MAX, 0xFFFFFFFF, ids).astype(np.uint32), K)
+
+    for nprobe in (8, 32):
+        for R in (100, 1024):
+            key = f"nprobe={nprobe} R={R}"
+            pq, ex, *spread = alternate_ms(lambda: ix.pq_search(q, R, nprobe), lambda: ix.search_anyk(q, R, nprobe), calls, warmup)
+            st = ix.ctx.stats()
+            fpq, fex, *fspread = alternate_ms(lambda: ix.pq_refine(q, K, R, nprobe), lambda: exact_then_refine(R, nprobe), calls, warmup)
+            got_pq, _ = ix.pq_refine(q, K, R, nprobe)
+            rid, _ = exact_then_refine(R, nprobe)
+            got_ex = np.where(rid == 0xFFFFFFFF, U64MAX, perm[np.minimum(rid, rows - 1)])
+            out[key] = dict(pq_search_ms=pq, anyk_ms=ex, search_spread=spread, pq_refine_ms=fpq, anyk_refine_ms=fex, refine_spread=fspread,
+                            recall10_pq=recall(got_pq, want), recall10_exact_route=recall(got_ex, want), rows_scanned_last=st["rows_scanned"])
+            print(f"{key:20s}: ivf_pq_search {pq:8.3f} ms | ivf_search_anyk {ex:8.3f} ms || ivf_pq_refine {fpq:8.3f} ms | anyk + refine {fex:8.3f} ms || "
+                  f"recall@10 pq {out[key]['recall10_pq']:.4f}, exact route {out[key]['recall10_exact_route']:.4f}")
+    print(json.dumps(out))
+    ix.close()
+
+
+if __name__ == "__main__":
+    main()
