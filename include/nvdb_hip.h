@@ -729,8 +729,9 @@ nvdb_status nvdb_hip_refine_l2_topk_dev(nvdb_hip_ctx* ctx, const float* dev_quer
  * query, then per work item copies the tables of its <= G queries into LDS (G = 8 up to M = 19, 4 up to 39, 2 up to 78, else 1),
  * reads M bytes per row once per group and WRITES 8 bytes per (row, query) -- every row of the union is scored and written,
  * nothing is pruned inside the scan --, then the any-k select: per query one workgroup that reads its block once per radix pass.
- * Out of scope: training codebooks (the caller trains them; the encode kernel is the assignment step a trainer would reuse),
- * residual encoding, OPQ rotations, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
+ * Codebooks come from the caller or from nvdb_hip_pq_train below (Lloyd's iteration on the device; training and building stay
+ * separate calls).
+ * Out of scope: cluster splitting and k-means++ starts in the trainer, residual encoding, OPQ rotations, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
  * pruning inside the scan, the device group, _dev stream forms, the nvdb:: C++ host layer.
  * ------------------------------------------------------------------------------------------- */
 
@@ -739,6 +740,32 @@ nvdb_status nvdb_hip_refine_l2_topk_dev(nvdb_hip_ctx* ctx, const float* dev_quer
  * On any failure nothing has changed: an earlier build stands.  An adopted corpus is fine: the codes are the library's own array.
  * Replaces an earlier build.  Non-finite rows or codebooks: no fault, no hang. */
 nvdb_status nvdb_hip_pq_build(nvdb_hip_ctx* ctx, const float* codebooks /* [M][256][dim / M] */, uint32_t M);
+/* Codebooks for nvdb_hip_pq_build by Lloyd's iteration over the resident rows (any dtype, adopted or owned), per sub-quantiser, on
+ * the device.  out_codebooks: [M][256][dim / M] f32, host memory; out_err: [iters] f64, host memory, may be NULL.  Same arguments +
+ * same corpus -> the same bytes (no atomics).  The shape rules are nvdb_hip_pq_build's (dim / M > 32 -> NVDB_ERR_UNSUPPORTED).
+ *   training set: nvdb_hip_train_centroids' rule: every resident row when max_train_rows == 0 or >= n, else the m = max_train_rows
+ *                 rows floor(i * n / m), i < m, each as an f32 query.  m < 256 -> NVDB_ERR_INVALID.
+ *   start:        init ([M][256][dim / M] f32, host) as given; NULL: sub-quantiser mq starts from 256 DISTINCT training rows drawn
+ *                 by nvdb_hip_train_centroids' draw rule with nparts = 256 and the seed `seed ^ (0x9E3779B97F4A7C15 * (mq + 1))`
+ *                 (64-bit, wrapping); codeword j = sub-vector mq of its row as f32, NOT normalised.  iters == 0 returns the start.
+ *   iteration:    assignment: every training row by exactly the encode rule above -- the code is bit for bit what
+ *                 nvdb_hip_pq_build under the same codebooks stores for that row (a row whose distances are all NaN or +inf is a
+ *                 member of codeword 0).  Update: codeword j = the mean of its members' sub-vectors: per column an fp64 sum in
+ *                 ascending training-row order inside chunks of PQ_TRAIN_CHUNK = 4096 training rows (csrc/pq_plan.h), the chunks
+ *                 added in chunk order, divided by the count in fp64, rounded once to f32.  A codeword without members, or with a
+ *                 non-finite sum in any column, keeps its bits: there is NO cluster splitting (as in nvdb_hip_train_centroids), so
+ *                 identical or far-off codewords of `init` stay where they are.
+ *   out_err[i]:   the mean over training rows and sub-quantisers of the winning fp32 distance under the codebooks iteration i
+ *                 STARTED from, in fp64: per (chunk, sub-quantiser) the 256-row tiles' sums added in tile order -- a tile's sum is a
+ *                 fixed tree: a butterfly over each wave's 64 rows, then (w0 + w1) + (w2 + w3) --, the chunks in chunk order, the
+ *                 sub-quantisers in ascending order, one division by m * M.  A row without a winner adds nothing.
+ * Cost: m * dim * 4 bytes of HBM for the rows as f32 and ceil(m / 4096) * 256 * dim * 8 bytes of partial sums (100 MB at 262144
+ * rows of dim 768), both allocated and freed inside the call; per iteration m * dim * 256 fmas and one read of the f32 rows.
+ * Errors: null context / out_codebooks, bad M -> NVDB_ERR_INVALID; no corpus -> NVDB_ERR_NO_CORPUS; on any failure nothing is
+ * written.  Non-finite rows or init: no fault, no hang.  An existing PQ shadow is neither read nor touched. */
+nvdb_status nvdb_hip_pq_train(nvdb_hip_ctx* ctx, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
+                              const float* init /* [M][256][dim / M], may be NULL */,
+                              float* out_codebooks /* [M][256][dim / M] f32, host */, double* out_err /* [iters], may be NULL */);
 /* every output optional; all 0 without codes.  code_bytes = n * M */
 nvdb_status nvdb_hip_pq_info(nvdb_hip_ctx* ctx, uint32_t* M, uint32_t* dsub, uint64_t* code_bytes);
 /* out[nrows][M] (host) = the codes of resident rows [row0, row0 + nrows); row0 + nrows > n -> NVDB_ERR_INVALID; nrows == 0 -> NVDB_OK */
@@ -772,6 +799,9 @@ nvdb_status nvdb_hip_pq_refine_ivf(nvdb_hip_ctx* ctx, const float* queries, uint
  * the shadow), then the id mapping of nvdb_hip_ivf_search_anyk: every id that is not padding becomes src's global_row_base +
  * perm[id]; equal scores (distances) stand by position in the lists. */
 nvdb_status nvdb_hip_ivf_pq_build(nvdb_hip_ivf* ivf, const float* codebooks, uint32_t M);
+/* nvdb_hip_pq_train on the index's context: the training rows are positions of the list-ordered copy */
+nvdb_status nvdb_hip_ivf_pq_train(nvdb_hip_ivf* ivf, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
+                                  const float* init, float* out_codebooks, double* out_err);
 nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe,
                                    uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing);
 nvdb_status nvdb_hip_ivf_pq_refine(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t K, uint32_t R, uint32_t nprobe,

@@ -17,7 +17,7 @@
 //   parts_worklist.h       the work list itself and its image's layout, plain C++ with no HIP call (as nvdb_plan.h, range_plan.h, parts_anyk_plan.h, masked_plan.h)
 //   nvdb_parts_anyk.cpp    the probe search for any k: per sub-batch one pass at radius -inf, select, long slabs (kernels_parts_anyk.h, parts_anyk_plan.h)
 //   nvdb_pq.cpp            the PQ candidate scan: the PQ shadow of a corpus (encode), per sub-batch tables, scan over the probe path's work items, the any-k
-//                          select, optionally the refine on the device (kernels_pq.h, pq_plan.h)
+//                          select, optionally the refine on the device (kernels_pq.h, pq_plan.h); nvdb_hip_pq_train (kernels_pq_train.h)
 //   nvdb_masked_flat.cpp   the masked flat top-k on the MFMA filter route: prefix rank, bootstrap bar, the range search's filter pass, top-k of the kept
 //                          lists (kernels_masked_topk.h, masked_plan.h)
 //   nvdb_compact.cpp       in-place compaction of tombstoned rows: rank, slab walk (direct / bounce), planes, partition table (kernels_compact.h, compact_plan.h);
@@ -424,6 +424,8 @@ void parts_drop(nvdb_hip_ctx* c);        // the corpus changes: forget the parti
 void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace
 // nvdb_pq.cpp
 void pq_drop(nvdb_hip_ctx* c);           // the rows change: free the PQ shadow, if there is one
+// nvdb_ivf.cpp
+void train_pick(uint64_t seed, uint32_t nparts, uint64_t m, uint32_t* pick);   // the trainers' start: nparts distinct rows of m training rows (include/nvdb_hip.h, nvdb_hip_train_centroids)
 // nvdb_search.cpp
 nvdb_status ensure_q32(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes);          // the host API's query buffer: qbytes + 8 rows; a new buffer starts all zero
 nvdb_status zero_q32_pad(nvdb_hip_ctx* c, hipStream_t s, size_t qbytes);        // ... and the 8 rows behind this call's queries read as zeros

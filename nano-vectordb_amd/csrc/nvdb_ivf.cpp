@@ -142,12 +142,6 @@ nvdb_status ivf_args(nvdb_hip_ctx* c, uint32_t nparts, const char* who) {
   return NVDB_OK;
 }
 
-// the draw behind a NULL `init` (include/nvdb_hip.h states the rule): attempt t for centroid j
-uint64_t train_draw(uint64_t seed, uint32_t j, uint32_t t, uint64_t m) {
-  const uint32_t key = synth_row_key(seed, (static_cast<uint64_t>(t) << 32) | j);
-  return ((static_cast<uint64_t>(mix32(key ^ 0x9E3779B9u)) << 32) | mix32(key + 0x85EBCA6Bu)) % m;
-}
-
 template <int DT>
 nvdb_status launch_centroid_sum_dt(nvdb_hip_ctx* c, hipStream_t s, const uint32_t* members, const uint2* chunks, uint32_t nchunks, double* partial) {
   const bool vec = c->dim % 4 == 0 && reinterpret_cast<uintptr_t>(c->rows) % 16 == 0;
@@ -175,6 +169,25 @@ nvdb_status launch_gather_rows(nvdb_hip_ctx* c, hipStream_t s, const nvdb_hip_ct
 }
 
 }  // namespace
+
+// the draw behind a NULL `init` (include/nvdb_hip.h states the rule): attempt t for centroid j
+static uint64_t train_draw(uint64_t seed, uint32_t j, uint32_t t, uint64_t m) {
+  const uint32_t key = synth_row_key(seed, (static_cast<uint64_t>(t) << 32) | j);
+  return ((static_cast<uint64_t>(mix32(key ^ 0x9E3779B9u)) << 32) | mix32(key + 0x85EBCA6Bu)) % m;
+}
+
+// nparts distinct training rows (train_draw; a row already taken is drawn again, after 64 attempts the next free one is taken)
+void train_pick(uint64_t seed, uint32_t nparts, uint64_t m, uint32_t* pick) {
+  std::vector<bool> taken(m, false);
+  for (uint32_t j = 0; j < nparts; ++j) {
+    uint64_t t = train_draw(seed, j, 0, m);
+    for (uint32_t a = 1; taken[t] && a < 64; ++a) t = train_draw(seed, j, a, m);
+    while (taken[t]) t = t + 1 < m ? t + 1 : 0;
+    taken[t] = true;
+    pick[j] = static_cast<uint32_t>(t);
+  }
+}
+
 }  // namespace nvdbhip
 
 struct nvdb_hip_ivf {
@@ -254,16 +267,9 @@ nvdb_status nvdb_hip_train_centroids(nvdb_hip_ctx* c, uint32_t nparts, uint32_t 
   if ((st = dev_alloc(c, d_cen, cen_count * 4))) return st;
   if (init) std::memcpy(cen.data(), init, cen_count * 4);
   else {
-    // nparts distinct training rows (train_draw; a row already taken is drawn again, after 64 attempts the next free one is taken)
-    std::vector<bool> taken(m, false);
     std::vector<uint32_t> pick(nparts);
-    for (uint32_t j = 0; j < nparts; ++j) {
-      uint64_t t = train_draw(seed, j, 0, m);
-      for (uint32_t a = 1; taken[t] && a < 64; ++a) t = train_draw(seed, j, a, m);
-      while (taken[t]) t = t + 1 < m ? t + 1 : 0;
-      taken[t] = true;
-      pick[j] = corpus_row(t);
-    }
+    train_pick(seed, nparts, m, pick.data());
+    for (uint32_t& t : pick) t = corpus_row(t);
     DevMem d_pick;
     if ((st = dev_alloc(c, d_pick, static_cast<size_t>(nparts) * 4))) return st;
     HIPCHK(c, hipMemcpyAsync(d_pick.p, pick.data(), static_cast<size_t>(nparts) * 4, hipMemcpyHostToDevice, s));
@@ -547,6 +553,12 @@ nvdb_status nvdb_hip_ivf_search_anyk(nvdb_hip_ivf* ix, const float* queries, uin
 nvdb_status nvdb_hip_ivf_pq_build(nvdb_hip_ivf* ix, const float* codebooks, uint32_t M) {
   if (!ix) return NVDB_ERR_INVALID;
   return ivf_forward(ix, nvdb_hip_pq_build(ix->ctx, codebooks, M));
+}
+
+nvdb_status nvdb_hip_ivf_pq_train(nvdb_hip_ivf* ix, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init, float* out_codebooks,
+                                  double* out_err) {
+  if (!ix) return NVDB_ERR_INVALID;
+  return ivf_forward(ix, nvdb_hip_pq_train(ix->ctx, M, iters, seed, max_train_rows, init, out_codebooks, out_err));
 }
 
 nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe, uint64_t* out_ids, float* out_scores,

@@ -10,10 +10,16 @@
 //                 pq_narrow_ids_kernel, the refine's device launcher on the same stream over ps->q, and only [b][K] results copied back
 // Sub-batches: pa_cut (parts_anyk_plan.h) under largek_budget_mb, and at most a quarter of that budget in tables.
 // Whatever makes rows resident or moves them frees the shadow (pq_drop); the PQ calls then return NVDB_ERR_INVALID.
-// Entry points: nvdb_hip_pq_build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf; the index forms
+// The codebooks are the caller's or nvdb_hip_pq_train's (kernels_pq_train.h): the training rows gathered once as f32, the start
+// filled on the device, then per iteration pq_train_step_kernel (assignment by the encode's rule and the members' fp64 sums, fused)
+// and pq_train_finish_kernel (the division) with no host step in between; rows, partial sums and codebooks live inside the call, and
+// the context's shadow is not touched.
+// Entry points: nvdb_hip_pq_train / _build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf; the index forms
 // (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them on the index's context and map the ids.
 #include "nvdb_parts.h"
 #include "kernels_pq.h"
+#include "kernels_pq_train.h"
+#include "ivf_layout.h"
 
 namespace nvdbhip {
 
@@ -44,6 +50,117 @@ nvdb_status launch_encode(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq) {
     default: go(pq_encode_kernel<DT, 32>); break;
   }
   HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+// ---- the trainer (nvdb_hip_pq_train): device memory that lives as long as the call
+struct TrainMem {
+  void* p = nullptr;
+  TrainMem() = default;
+  TrainMem(const TrainMem&) = delete;
+  TrainMem& operator=(const TrainMem&) = delete;
+  ~TrainMem() { if (p) (void)hipFree(p); }
+  template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+nvdb_status train_alloc(nvdb_hip_ctx* c, TrainMem& m, size_t bytes) {
+  HIPCHK(c, hipMalloc(&m.p, std::max<size_t>(bytes, 256)));
+  return NVDB_OK;
+}
+
+template <int DT>
+nvdb_status launch_train_gather(nvdb_hip_ctx* c, hipStream_t s, const uint32_t* idx, uint64_t m, float* X) {
+  const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((m * c->dim + 255) / 256, static_cast<uint64_t>(c->num_cu) * 64));
+  pq_train_gather_kernel<DT><<<grid, 256, 0, s>>>(c->rows, c->scales, c->dim, idx, m, X);
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+// one Lloyd iteration of every sub-quantiser: the fused assign-and-sum step, then the division.  err: this iteration's [M] distance sums
+nvdb_status launch_train_iteration(nvdb_hip_ctx* c, hipStream_t s, const float* X, uint64_t m, uint32_t M, uint32_t dsub, float* cb, double* partial,
+                                   uint32_t* count, double* dist, double* err) {
+  const uint32_t chunks = static_cast<uint32_t>(pq_train_chunks(m)), dmax = pq_encode_bound(dsub);
+  const size_t lds = pq_train_lds(dmax);
+  auto go = [&](auto kernel) -> nvdb_status {
+    if (lds > 64 * 1024)
+      if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(kernel), lds)) return st;
+    kernel<<<dim3(chunks, M), PQ_TRAIN_THREADS, lds, s>>>(X, m, c->dim, dsub, cb, partial, count, dist);
+    HIPCHK(c, hipGetLastError());
+    return NVDB_OK;
+  };
+  nvdb_status st;
+  switch (dmax) {
+    case 4: st = go(pq_train_step_kernel<4>); break;
+    case 8: st = go(pq_train_step_kernel<8>); break;
+    case 16: st = go(pq_train_step_kernel<16>); break;
+    default: st = go(pq_train_step_kernel<32>); break;
+  }
+  if (st) return st;
+  pq_train_finish_kernel<<<M, PQ_TRAIN_THREADS, 0, s>>>(partial, count, dist, chunks, dsub, cb, err);
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+// the call proper, the arguments validated: cb (host, [M][256][dsub]) and err (host, [iters]) are this call's own and reach the caller on success only
+nvdb_status pq_train(nvdb_hip_ctx* c, uint32_t M, uint32_t iters, uint64_t seed, uint64_t m, const float* init, std::vector<float>& cb, std::vector<double>& err) {
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const uint64_t n = c->n;
+  const uint32_t dim = c->dim, dsub = dim / M;
+  const size_t cb_bytes = cb.size() * 4;
+  nvdb_status st = NVDB_OK;
+
+  // the training set as f32 rows: every row, or rows floor(i * n / m) (n < 2^32, m < 2^32: the product fits)
+  TrainMem d_idx, d_x, d_cb;
+  if (m < n) {
+    std::vector<uint32_t> idx(m);
+    for (uint64_t i = 0; i < m; ++i) idx[i] = static_cast<uint32_t>(i * n / m);
+    if ((st = train_alloc(c, d_idx, m * 4))) return st;
+    HIPCHK(c, hipMemcpy(d_idx.p, idx.data(), m * 4, hipMemcpyHostToDevice));
+  }
+  if ((st = train_alloc(c, d_x, m * dim * 4)) || (st = train_alloc(c, d_cb, cb_bytes))) return st;
+  dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_train_gather<decltype(dt)::value>(c, s, d_idx.as<uint32_t>(), m, d_x.as<float>()); });
+  if (st) return st;
+
+  if (init) {
+    HIPCHK(c, hipMemcpyAsync(d_cb.p, init, cb_bytes, hipMemcpyHostToDevice, s));
+  } else {
+    // per sub-quantiser 256 distinct training rows, the centroid trainer's draw under the sub-quantiser's own seed
+    std::vector<uint32_t> pick(static_cast<size_t>(M) * PQ_KSUB);
+    for (uint32_t mq = 0; mq < M; ++mq) train_pick(seed ^ (0x9E3779B97F4A7C15ull * (mq + 1)), PQ_KSUB, m, pick.data() + static_cast<size_t>(mq) * PQ_KSUB);
+    TrainMem d_pick;
+    if ((st = train_alloc(c, d_pick, pick.size() * 4))) return st;
+    HIPCHK(c, hipMemcpyAsync(d_pick.p, pick.data(), pick.size() * 4, hipMemcpyHostToDevice, s));
+    pq_train_start_kernel<<<M, PQ_KSUB, 0, s>>>(d_x.as<float>(), dim, dsub, d_pick.as<uint32_t>(), d_cb.as<float>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));                                // (d_pick leaves scope)
+  }
+
+  std::vector<double> err_m(static_cast<size_t>(iters) * M);
+  if (iters) {
+    const uint64_t chunks = pq_train_chunks(m);
+    TrainMem d_partial, d_count, d_dist, d_err;
+    if ((st = train_alloc(c, d_partial, pq_train_partial_bytes(m, dim))) || (st = train_alloc(c, d_count, chunks * M * PQ_KSUB * 4)) ||
+        (st = train_alloc(c, d_dist, chunks * M * 8)) || (st = train_alloc(c, d_err, err_m.size() * 8)))
+      return st;
+    for (uint32_t it = 0; it < iters; ++it)
+      if ((st = launch_train_iteration(c, s, d_x.as<float>(), m, M, dsub, d_cb.as<float>(), d_partial.as<double>(), d_count.as<uint32_t>(), d_dist.as<double>(),
+                                       d_err.as<double>() + static_cast<size_t>(it) * M)))
+        break;
+    if (!st) {
+      HIPCHK(c, hipMemcpyAsync(err_m.data(), d_err.p, err_m.size() * 8, hipMemcpyDeviceToHost, s));
+    }
+    const hipError_t e = hipStreamSynchronize(s);                      // (before the partials leave scope, whatever happened)
+    if (!st && e != hipSuccess) st = fail(c, NVDB_ERR_HIP, std::string("pq_train: ") + hipGetErrorString(e));
+    if (st) return st;
+  }
+  HIPCHK(c, hipMemcpyAsync(cb.data(), d_cb.p, cb_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  // the mean winning distance per iteration: the sub-quantisers' sums added in ascending order, one division
+  for (uint32_t it = 0; it < iters; ++it) {
+    double e = 0.0;
+    for (uint32_t mq = 0; mq < M; ++mq) e += err_m[static_cast<size_t>(it) * M + mq];
+    err[it] = e / (static_cast<double>(m) * M);
+  }
   return NVDB_OK;
 }
 
@@ -202,6 +319,27 @@ nvdb_status nvdb_hip_pq_build(nvdb_hip_ctx* c, const float* codebooks, uint32_t 
   }
   pq_drop(c);
   c->pq = new PqState(fresh);
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_pq_train(nvdb_hip_ctx* c, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init, float* out_codebooks,
+                              double* out_err) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (!out_codebooks) return fail(c, NVDB_ERR_INVALID, "pq_train: null output");
+  if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
+  bool unsupported = false;
+  if (const char* why = pq_shape_check(c->dim, M, unsupported)) return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, std::string("pq_train: ") + why);
+  const uint64_t m = pq_train_rows(c->n, max_train_rows);
+  if (m < PQ_TRAIN_MIN_ROWS) return fail(c, NVDB_ERR_INVALID, "pq_train: fewer than 256 training rows");
+  if (m > IVF_MAX_ROWS) return fail(c, NVDB_ERR_UNSUPPORTED, "pq_train: training set too large (max_train_rows)");
+  std::vector<float> cb(static_cast<size_t>(M) * PQ_KSUB * (c->dim / M));
+  std::vector<double> err(iters);
+  if (nvdb_status st = pq_train(c, M, iters, seed, m, init, cb, err)) {
+    (void)hipGetLastError();
+    return st;
+  }
+  std::memcpy(out_codebooks, cb.data(), cb.size() * 4);
+  if (out_err && iters) std::memcpy(out_err, err.data(), err.size() * 8);
   return NVDB_OK;
 }
 

@@ -1,7 +1,7 @@
 // pq_plan.h -- the host-side arithmetic of the PQ candidate scan (nvdb_pq.cpp, kernels_pq.h; DESIGN.md section 4 "PQ candidate
 // scan"): which shapes a PQ shadow takes, the encode kernel's compile-time sub-vector bound, how many queries' tables a scan
-// workgroup holds in LDS, how its lanes load their codes, and how many queries one sub-batch's tables may serve.  Plain C++ with
-// no HIP in it, like the other plans.
+// workgroup holds in LDS, how its lanes load their codes, how many queries one sub-batch's tables may serve, and the trainer's
+// chunk, LDS and partial-sum sizes (kernels_pq_train.h).  Plain C++ with no HIP in it, like the other plans.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -35,6 +35,18 @@ constexpr uint32_t pq_group(uint32_t M) {
     if (G * pq_lut_bytes(M) <= PQ_LDS_BUDGET) return G;
   return 1;
 }
+
+// ---- the trainer (nvdb_hip_pq_train, kernels_pq_train.h)
+constexpr uint32_t PQ_TRAIN_CHUNK = 4096;           // training rows per workgroup of the step kernel: the unit of the fp64 sums' order (include/nvdb_hip.h names it)
+constexpr uint32_t PQ_TRAIN_MIN_ROWS = PQ_KSUB;     // a start needs 256 distinct training rows
+
+// the training set of max_train_rows over n resident rows: every row (0 or >= n), else that many
+constexpr uint64_t pq_train_rows(uint64_t n, uint64_t max_train_rows) { return (max_train_rows == 0 || max_train_rows >= n) ? n : max_train_rows; }
+constexpr uint64_t pq_train_chunks(uint64_t m) { return (m + PQ_TRAIN_CHUNK - 1) / PQ_TRAIN_CHUNK; }
+// the step kernel's LDS for the build DMAX: codewords [256][DMAX] f32, the tile's sub-vectors [DMAX][256] f32, four fp64 wave sums, 256 code bytes
+constexpr size_t pq_train_lds(uint32_t dmax) { return 2 * static_cast<size_t>(PQ_KSUB) * dmax * 4 + 4 * 8 + 256; }
+// bytes of the per-chunk fp64 partial sums
+constexpr uint64_t pq_train_partial_bytes(uint64_t m, uint32_t dim) { return pq_train_chunks(m) * PQ_KSUB * dim * 8; }
 
 // a lane reads its row's codes in 16-byte pieces where a row is whole pieces, else in dwords (M % 4 == 0 always)
 constexpr bool pq_wide_codes(uint32_t M) { return M % 16 == 0; }

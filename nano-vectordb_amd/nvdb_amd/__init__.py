@@ -44,6 +44,7 @@ EXPORTS = [
     "nvdb_hip_reserve_rows", "nvdb_hip_insert_rows", "nvdb_hip_ivf_add_rows",
     "nvdb_hip_pq_build", "nvdb_hip_pq_info", "nvdb_hip_pq_download_codes", "nvdb_hip_pq_search_partitions", "nvdb_hip_pq_search_ivf",
     "nvdb_hip_pq_refine_ivf", "nvdb_hip_ivf_pq_build", "nvdb_hip_ivf_pq_search", "nvdb_hip_ivf_pq_refine",
+    "nvdb_hip_pq_train", "nvdb_hip_ivf_pq_train",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -220,6 +221,8 @@ def _bind(L, dev):
     L.nvdb_hip_ivf_search_anyk.argtypes = [vp, vp, u32, u32, u32, vp, C.c_int, vp, vp, vp, vp, C.POINTER(Timing)]
     L.nvdb_hip_compact_rows.argtypes = [vp, u32, C.POINTER(u64), vp]
     L.nvdb_hip_pq_build.argtypes = [vp, vp, u32]
+    L.nvdb_hip_pq_train.argtypes = [vp, u32, u32, u64, u64, vp, vp, vp]
+    L.nvdb_hip_ivf_pq_train.argtypes = [vp, u32, u32, u64, u64, vp, vp, vp]
     L.nvdb_hip_pq_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
     L.nvdb_hip_pq_download_codes.argtypes = [vp, u64, u64, vp]
     L.nvdb_hip_pq_search_partitions.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp, C.POINTER(Timing)]
@@ -369,6 +372,18 @@ def _mask_of_arg(mask_of, nq):
     if mask_of is None:
         return None
     return np.ascontiguousarray(np.broadcast_to(np.asarray(mask_of, dtype=np.uint32), (nq,)))
+
+
+def _pq_train(owner, fn, dim, M, iters, seed, max_train_rows, init, want_err):
+    """HipContext.pq_train / IvfIndex.pq_train: fn is the entry point for owner.h.  A bad M reaches the library (dsub 1 stands in)."""
+    dsub = dim // M if M and dim % M == 0 else 1
+    if init is not None:
+        init = np.ascontiguousarray(init, dtype=np.float32).reshape(M, 256, dsub)
+    out = np.zeros((M, 256, dsub), dtype=np.float32)
+    err = np.zeros(iters, dtype=np.float64)
+    owner._chk(fn(owner.h, M, iters, seed, max_train_rows, init.ctypes.data if init is not None else None, out.ctypes.data,
+                  err.ctypes.data if want_err and iters else None))
+    return (out, err) if want_err else out
 
 
 def _range_call(owner, last_error, results, call, queries, radius, mask_of, masked):
@@ -696,6 +711,11 @@ class HipContext:
             raise ValueError("codebooks must be [M, 256, dim / M]")
         self._chk(self.lib.nvdb_hip_pq_build(self.h, codebooks.ctypes.data, codebooks.shape[0]))
 
+    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False):
+        """Codebooks [M, 256, dim / M] f32 by Lloyd's iteration over the resident rows on the device (init None: 256 drawn training
+        rows per sub-quantiser); with want_err also the [iters] f64 mean winning distances.  Does not build: pq_build(result)."""
+        return _pq_train(self, self.lib.nvdb_hip_pq_train, self.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err)
+
     def pq_info(self):
         """dict(M, dsub, code_bytes); all 0 without codes."""
         M, dsub, nbytes = C.c_uint32(), C.c_uint32(), C.c_uint64()
@@ -951,6 +971,10 @@ class IvfIndex:
         if codebooks.ndim != 3 or codebooks.shape[1] != 256:
             raise ValueError("codebooks must be [M, 256, dim / M]")
         self._chk(self.lib.nvdb_hip_ivf_pq_build(self.h, codebooks.ctypes.data, codebooks.shape[0]))
+
+    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False):
+        """HipContext.pq_train over the list-ordered rows."""
+        return _pq_train(self, self.lib.nvdb_hip_ivf_pq_train, self.ctx.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err)
 
     def pq_search(self, queries, R, nprobe, want_probe=False):
         """The R best PQ scores of the nprobe best lists -> (ids, scores, counts[, probe]); equal scores by (partition, original id)."""

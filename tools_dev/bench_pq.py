@@ -3,8 +3,10 @@
     python tools_dev/bench_pq.py [rows] [dim] [dtype] [nlist] [M] [batch] [calls] [warmup]
                                  (defaults: 10000000 768 f16 4096 48 1024 10 2)
 
-An IVF index over the synthetic corpus (centroids: two k-means rounds over 262144 rows), codebooks from a few Lloyd rounds per
-sub-quantiser over 20000 sampled rows on the host (training is the caller's: this is a stand-in, not a tuned quantiser).  For
+An IVF index over the synthetic corpus (centroids: two k-means rounds over 262144 rows), codebooks from four Lloyd rounds per
+sub-quantiser over 20000 sampled rows ON THE DEVICE (pq_train over a context that holds the sample); the numpy trainer stays
+beside it on the same sample, start and rounds: median of 5 after a warm-up of both, and the fp64 quantisation error of both
+codebook sets on the sample (neither is a tuned quantiser).  For
 nprobe in (8, 32) and R in (100, 1024), median wall ms per call, alternating the two routes call by call, of
   ivf_pq_search R                 PQ scan + select                     | ivf_search_anyk k = R     exact scores of the full rows + select
   ivf_pq_refine K = 10            the fused pipeline                   | ivf_search_anyk k = R, then refine_l2_topk on the index's rows
@@ -26,15 +28,15 @@ import nvdb_amd  # noqa: E402
 U64MAX = np.iinfo(np.uint64).max
 
 
-def train_codebooks(sample, M, rounds, seed):
-    """[M, 256, dsub] f32: per sub-quantiser 256 sampled sub-vectors, then `rounds` Lloyd rounds (nearest by squared L2, mean)."""
+def train_codebooks(sample, M, rounds, seed, init=None):
+    """[M, 256, dsub] f32: per sub-quantiser 256 sampled sub-vectors (or init[m]), then `rounds` Lloyd rounds (nearest by squared L2, mean)."""
     rs = np.random.RandomState(seed)
     n, dim = sample.shape
     dsub = dim // M
     cb = np.empty((M, 256, dsub), dtype=np.float32)
     for m in range(M):
         x = sample[:, m * dsub:(m + 1) * dsub]
-        c = x[rs.choice(n, 256, replace=False)].copy()
+        c = x[rs.choice(n, 256, replace=False)].copy() if init is None else init[m].copy()
         for _ in range(rounds):
             d = (x * x).sum(1)[:, None] - 2.0 * x @ c.T + (c * c).sum(1)[None]
             a = d.argmin(1)
@@ -43,6 +45,24 @@ def train_codebooks(sample, M, rounds, seed):
                     c[j] = x[a == j].mean(0)
         cb[m] = c
     return cb
+
+
+def quant_error(sample, cb):
+    """fp64 mean over rows and sub-quantisers of the least squared distance to a codeword."""
+    M, _, dsub = cb.shape
+    total = 0.0
+    for m in range(M):
+        x, c = sample[:, m * dsub:(m + 1) * dsub].astype(np.float64), cb[m].astype(np.float64)
+        total += sum(((x[i:i + 4096, None, :] - c[None]) ** 2).sum(-1).min(1).sum() for i in range(0, len(x), 4096))
+    return total / (len(sample) * M)
+
+
+def median_s(f, reps=5):
+    f()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter(); f(); ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)), ts
 
 
 def alternate_ms(fa, fb, calls, warmup):
@@ -87,16 +107,28 @@ def main():
     t2 = time.perf_counter()
     rs = np.random.RandomState(3)
     pick = np.sort(rs.choice(rows, 20000, replace=False))
-    sample = np.concatenate([src.download_rows(int(r), 1)[0] for r in pick])
-    sample = sample.view(np.float16).astype(np.float32) if dtype == nvdb_amd.DT_F16 else sample
+    raw = np.concatenate([src.download_rows(int(r), 1)[0] for r in pick])
+    sample = raw.view(np.float16).astype(np.float32) if dtype == nvdb_amd.DT_F16 else raw
     src.close()
+    sctx = nvdb_amd.HipContext(0)                                       # the sample as a corpus of its own: both trainers see the same rows
+    sctx.upload_corpus(raw, dtype)
+    rounds = 4
+    start = sctx.pq_train(M, 0, 7)
     t3 = time.perf_counter()
-    cb = train_codebooks(sample, M, 4, 7)
+    cb = sctx.pq_train(M, rounds, 7)                                    # (first call: the code object loads here)
     t4 = time.perf_counter()
     ix.pq_build(cb)
     t5 = time.perf_counter()
-    out["build"] = dict(train_centroids_s=t1 - t0, ivf_build_s=t2 - t1, codebooks_host_s=t4 - t3, pq_build_s=t5 - t4)
-    print(f"train_centroids {t1 - t0:.2f} s, ivf_build {t2 - t1:.2f} s, host codebooks {t4 - t3:.2f} s, pq_build (upload + encode {rows} rows) {t5 - t4:.3f} s")
+    dev_s, dev_all = median_s(lambda: sctx.pq_train(M, rounds, 7))
+    host_s, host_all = median_s(lambda: train_codebooks(sample, M, rounds, 7, start))
+    cb_host = train_codebooks(sample, M, rounds, 7, start)
+    sctx.close()
+    out["build"] = dict(train_centroids_s=t1 - t0, ivf_build_s=t2 - t1, codebooks_device_first_call_s=t4 - t3, pq_build_s=t5 - t4)
+    out["codebooks"] = dict(sample_rows=len(sample), rounds=rounds, device_s=dev_s, device_all_s=dev_all, host_s=host_s, host_all_s=host_all,
+                            err_start=quant_error(sample, start), err_device=quant_error(sample, cb), err_host=quant_error(sample, cb_host))
+    print(f"train_centroids {t1 - t0:.2f} s, ivf_build {t2 - t1:.2f} s, device codebooks (first call) {t4 - t3:.3f} s, pq_build (upload + encode {rows} rows) {t5 - t4:.3f} s")
+    print("codebooks, {sample_rows} rows, {rounds} rounds, same start: device {device_s:.4f} s | numpy {host_s:.3f} s (medians of 5 after a warm-up); "
+          "fp64 quantisation error: start {err_start:.6e}, device {err_device:.6e}, numpy {err_host:.6e}".format(**out["codebooks"]))
     perm = ix.info()["perm"].astype(np.uint64)
 
     def exact_then_refine(R, nprobe):
