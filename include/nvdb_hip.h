@@ -731,7 +731,27 @@ nvdb_status nvdb_hip_refine_l2_topk_dev(nvdb_hip_ctx* ctx, const float* dev_quer
  * nothing is pruned inside the scan --, then the any-k select: per query one workgroup that reads its block once per radix pass.
  * Codebooks come from the caller or from nvdb_hip_pq_train below (Lloyd's iteration on the device; training and building stay
  * separate calls).
- * Out of scope: cluster splitting and k-means++ starts in the trainer, residual encoding, OPQ rotations, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
+ * RESIDUAL shadows (nvdb_hip_pq_build_residual; FAISS IndexIVFPQ's encoding): a row is quantised as its residual to the centroid
+ * of its list, and the score gets the centroid's share back as one base term per (query, probed partition); the tables stay
+ * list-independent.  The arithmetic, fixed:
+ *   list(r)     the partition p with off[p] <= r < off[p + 1], r the local row; an empty partition owns no row.
+ *   c[p]        the centroid of p: [dim] f32, the bits nvdb_hip_set_centroids (or nvdb_hip_ivf_build) was given.
+ *   residual    e[r][t] = x[r][t] - c[list(r)][t], ONE fp32 subtraction; x the row as an f32 query (f16 widened, int8 float(x) *
+ *               scale rounded once, as the encode above).
+ *   encode      the encode rule above applied to e (a NaN or +inf distance never wins; a row without a winner gets code 0).
+ *   tables      L[q][m][j] as above.
+ *   base        b(q, p) = q . c[p] in fp32, in this order whatever the launch: 64 partial sums, sum l of the elements t = l, l + 64,
+ *               l + 128, .. ascending, one fma each, from 0; then six rounds s = 32, 16, 8, 4, 2, 1 in which every partial sum l
+ *               becomes sum[l] + sum[l ^ s] (all 64 at once); b is sum 0.  The same call repeats to the bit.
+ *   score       s(q, r) = b(q, list(r)) + S, S the non-residual sum_m L[q][m][code[r][m]] (m ascending, from 0): one fp32
+ *               addition at the end.  A NaN score is no candidate.
+ *   order       as above.
+ *   reconstruct y[r][t] = c[list(r)][t] + cb[m][code[r][m]][t - m * dsub], m = t / dsub: one fp32 addition.  A non-residual
+ *               shadow gives the codeword alone.
+ * A residual shadow keeps its own device copies of the table and the centroids it was built under; nvdb_hip_set_partitions and
+ * nvdb_hip_set_centroids free it (a non-residual shadow survives them), and so does whatever frees a shadow above.  A search costs
+ * one more small launch per sub-batch (the base terms: dim fmas per (query, probed partition)) and one addition per (row, query).
+ * Out of scope: cluster splitting and k-means++ starts in the trainer, L2 asymmetric-distance tables, OPQ rotations, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
  * pruning inside the scan, the device group, _dev stream forms, the nvdb:: C++ host layer.
  * ------------------------------------------------------------------------------------------- */
 
@@ -766,8 +786,24 @@ nvdb_status nvdb_hip_pq_build(nvdb_hip_ctx* ctx, const float* codebooks /* [M][2
 nvdb_status nvdb_hip_pq_train(nvdb_hip_ctx* ctx, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
                               const float* init /* [M][256][dim / M], may be NULL */,
                               float* out_codebooks /* [M][256][dim / M] f32, host */, double* out_err /* [iters], may be NULL */);
+/* nvdb_hip_pq_build with the rows' residuals to their lists' centroids encoded (RESIDUAL shadows above): the same shape rules and
+ * errors, and the context must hold a partition table and centroids -- else NVDB_ERR_INVALID with a message that names
+ * nvdb_hip_set_partitions or nvdb_hip_set_centroids.  On any failure an earlier shadow, of either kind, stands.  The searches below
+ * answer from whichever shadow the context holds.  Non-finite rows, centroids or codebooks: no fault, no hang. */
+nvdb_status nvdb_hip_pq_build_residual(nvdb_hip_ctx* ctx, const float* codebooks /* [M][256][dim / M] */, uint32_t M);
+/* nvdb_hip_pq_train over the RESIDUALS of the training rows (the same rows, each minus the centroid of its list, one fp32
+ * subtraction): every argument, rule and error of nvdb_hip_pq_train, and nvdb_hip_pq_build_residual's need of a table and
+ * centroids.  The assignment is the residual encode's, bit for bit. */
+nvdb_status nvdb_hip_pq_train_residual(nvdb_hip_ctx* ctx, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
+                                       const float* init /* [M][256][dim / M], may be NULL */,
+                                       float* out_codebooks /* [M][256][dim / M] f32, host */, double* out_err /* [iters], may be NULL */);
 /* every output optional; all 0 without codes.  code_bytes = n * M */
 nvdb_status nvdb_hip_pq_info(nvdb_hip_ctx* ctx, uint32_t* M, uint32_t* dsub, uint64_t* code_bytes);
+/* *residual (optional) = 1 where the context holds a residual shadow, 0 for a non-residual one or none */
+nvdb_status nvdb_hip_pq_kind(nvdb_hip_ctx* ctx, uint32_t* residual);
+/* out[nrows][dim] f32 (host) = resident rows [row0, row0 + nrows) as their codes describe them (reconstruct above), for either
+ * kind of shadow; row0 + nrows > n -> NVDB_ERR_INVALID; nrows == 0 -> NVDB_OK; no codes -> NVDB_ERR_INVALID */
+nvdb_status nvdb_hip_pq_reconstruct(nvdb_hip_ctx* ctx, uint64_t row0, uint64_t nrows, float* out /* [nrows][dim] */);
 /* out[nrows][M] (host) = the codes of resident rows [row0, row0 + nrows); row0 + nrows > n -> NVDB_ERR_INVALID; nrows == 0 -> NVDB_OK */
 nvdb_status nvdb_hip_pq_download_codes(nvdb_hip_ctx* ctx, uint64_t row0, uint64_t nrows, uint8_t* out /* [nrows][M] */);
 /* The R best PQ scores of every query's probed union: out_ids[nq][R] global ids, out_scores[nq][R] the PQ scores, out_counts[q]
@@ -802,6 +838,10 @@ nvdb_status nvdb_hip_ivf_pq_build(nvdb_hip_ivf* ivf, const float* codebooks, uin
 /* nvdb_hip_pq_train on the index's context: the training rows are positions of the list-ordered copy */
 nvdb_status nvdb_hip_ivf_pq_train(nvdb_hip_ivf* ivf, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
                                   const float* init, float* out_codebooks, double* out_err);
+/* nvdb_hip_pq_build_residual / nvdb_hip_pq_train_residual on the index's context: its lists and its centroids */
+nvdb_status nvdb_hip_ivf_pq_build_residual(nvdb_hip_ivf* ivf, const float* codebooks, uint32_t M);
+nvdb_status nvdb_hip_ivf_pq_train_residual(nvdb_hip_ivf* ivf, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
+                                           const float* init, float* out_codebooks, double* out_err);
 nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe,
                                    uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing);
 nvdb_status nvdb_hip_ivf_pq_refine(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t K, uint32_t R, uint32_t nprobe,

@@ -90,6 +90,14 @@ struct PqState {
   float* codebooks = nullptr;                      // [M][256][dsub] f32
   uint8_t* codes = nullptr;                        // [n][M], library-owned, zero-padded by PAD_ROWS rows
   DevBuf lut;                                      // [queries of a sub-batch][M][256] f32, grow-only
+  // a RESIDUAL shadow (nvdb_hip_pq_build_residual; kernels_pq_resid.h): the codes are those of x - centroid of the row's list, under
+  // the table and the centroids the context held at build time -- the shadow's own device copies; nvdb_hip_set_partitions and
+  // nvdb_hip_set_centroids free such a shadow (pq_drop_residual)
+  bool residual = false;
+  uint32_t nparts = 0;
+  float* cent = nullptr;                           // [nparts][dim] f32
+  uint32_t* off = nullptr;                         // [nparts + 1]
+  DevBuf base;                                     // [(probed partition, query) pairs of a sub-batch] f32 base terms, grow-only
 };
 
 }  // namespace nvdbhip
@@ -424,6 +432,7 @@ void parts_drop(nvdb_hip_ctx* c);        // the corpus changes: forget the parti
 void parts_destroy(nvdb_hip_ctx* c);     // ... and free the workspace
 // nvdb_pq.cpp
 void pq_drop(nvdb_hip_ctx* c);           // the rows change: free the PQ shadow, if there is one
+void pq_drop_residual(nvdb_hip_ctx* c);  // the table or the centroids change: free a RESIDUAL shadow (its codes mean nothing under others); another stays
 // nvdb_ivf.cpp
 void train_pick(uint64_t seed, uint32_t nparts, uint64_t m, uint32_t* pick);   // the trainers' start: nparts distinct rows of m training rows (include/nvdb_hip.h, nvdb_hip_train_centroids)
 // nvdb_search.cpp

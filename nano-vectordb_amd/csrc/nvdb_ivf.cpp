@@ -561,6 +561,17 @@ nvdb_status nvdb_hip_ivf_pq_train(nvdb_hip_ivf* ix, uint32_t M, uint32_t iters, 
   return ivf_forward(ix, nvdb_hip_pq_train(ix->ctx, M, iters, seed, max_train_rows, init, out_codebooks, out_err));
 }
 
+nvdb_status nvdb_hip_ivf_pq_build_residual(nvdb_hip_ivf* ix, const float* codebooks, uint32_t M) {
+  if (!ix) return NVDB_ERR_INVALID;
+  return ivf_forward(ix, nvdb_hip_pq_build_residual(ix->ctx, codebooks, M));
+}
+
+nvdb_status nvdb_hip_ivf_pq_train_residual(nvdb_hip_ivf* ix, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init,
+                                           float* out_codebooks, double* out_err) {
+  if (!ix) return NVDB_ERR_INVALID;
+  return ivf_forward(ix, nvdb_hip_pq_train_residual(ix->ctx, M, iters, seed, max_train_rows, init, out_codebooks, out_err));
+}
+
 nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe, uint64_t* out_ids, float* out_scores,
                                    uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
   if (!ix) return NVDB_ERR_INVALID;

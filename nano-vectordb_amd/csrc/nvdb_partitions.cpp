@@ -305,6 +305,7 @@ nvdb_status nvdb_hip_set_partitions(nvdb_hip_ctx* c, const uint64_t* offsets, ui
     if (offsets[p + 1] < offsets[p]) return fail(c, NVDB_ERR_INVALID, "set_partitions: offsets must be non-decreasing");
   HIPCHK(c, hipSetDevice(c->device));
   if (!c->parts) c->parts = new PartState();
+  pq_drop_residual(c);                             // residual PQ codes were formed against the old table's lists
   parts_drop(c);                                   // a new table: the old centroids no longer describe it
   c->parts->offsets.assign(offsets, offsets + nparts + 1);
   return NVDB_OK;
@@ -316,6 +317,7 @@ nvdb_status nvdb_hip_set_centroids(nvdb_hip_ctx* c, const float* centroids) {
   if (!centroids) return fail(c, NVDB_ERR_INVALID, "set_centroids: null centroids");
   PartState* ps = c->parts;
   ps->have_centroids = false;
+  pq_drop_residual(c);                             // ... and residual PQ codes against the old centroids
   if (!ps->coarse) {
     if ((st = nvdb_hip_create(c->device, &ps->coarse))) return fail(c, st, std::string("set_centroids: ") + nvdb_hip_last_error(nullptr));
   }

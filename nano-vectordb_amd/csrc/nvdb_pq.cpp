@@ -14,10 +14,17 @@
 // filled on the device, then per iteration pq_train_step_kernel (assignment by the encode's rule and the members' fp64 sums, fused)
 // and pq_train_finish_kernel (the division) with no host step in between; rows, partial sums and codebooks live inside the call, and
 // the context's shadow is not touched.
-// Entry points: nvdb_hip_pq_train / _build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf; the index forms
-// (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them on the index's context and map the ids.
+// A RESIDUAL shadow (nvdb_hip_pq_build_residual; kernels_pq_resid.h) holds the codes of x - centroid of the row's list, with its own
+// device copies of the table (u32) and the centroids, and a search adds two things: pstart of the pass's work list rides behind
+// the any-k plan's words in the image, pq_base_kernel writes b(q, p) = q . c[p] per (probed partition, query) pair between tables
+// and scan, and pq_scan_resid_kernel adds the pair's term at the sink.  The residual trainer swaps the gather for
+// pq_resid_gather_kernel and shares everything behind it.  nvdb_hip_set_partitions / _set_centroids free such a shadow.
+// Entry points: nvdb_hip_pq_train / _build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf and
+// nvdb_hip_pq_build_residual / _train_residual / _reconstruct / _kind; the index forms (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them
+// on the index's context and map the ids.
 #include "nvdb_parts.h"
 #include "kernels_pq.h"
+#include "kernels_pq_resid.h"
 #include "kernels_pq_train.h"
 #include "ivf_layout.h"
 
@@ -29,8 +36,15 @@ void pq_drop(nvdb_hip_ctx* c) {
   if (pq->codebooks) (void)hipFree(pq->codebooks);
   if (pq->codes) (void)hipFree(pq->codes);
   if (pq->lut.p) (void)hipFree(pq->lut.p);
+  if (pq->cent) (void)hipFree(pq->cent);
+  if (pq->off) (void)hipFree(pq->off);
+  if (pq->base.p) (void)hipFree(pq->base.p);
   delete pq;
   c->pq = nullptr;
+}
+
+void pq_drop_residual(nvdb_hip_ctx* c) {
+  if (c->pq && c->pq->residual) pq_drop(c);
 }
 
 namespace {
@@ -43,14 +57,40 @@ nvdb_status launch_encode(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq) {
   auto go = [&](auto kernel) {
     kernel<<<grid, PQ_ENC_THREADS, 0, s>>>(c->rows, c->scales, c->n, c->dim, pq.M, pq.dsub, pq.codebooks, pq.codes);
   };
-  switch (pq_encode_bound(pq.dsub)) {
-    case 4: go(pq_encode_kernel<DT, 4>); break;
-    case 8: go(pq_encode_kernel<DT, 8>); break;
-    case 16: go(pq_encode_kernel<DT, 16>); break;
-    default: go(pq_encode_kernel<DT, 32>); break;
+  auto go_resid = [&](auto kernel) {
+    kernel<<<grid, PQ_ENC_THREADS, 0, s>>>(c->rows, c->scales, c->n, c->dim, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, pq.cent, pq.codes);
+  };
+  const uint32_t dmax = pq_encode_bound(pq.dsub);
+  if (pq.residual) {
+    switch (dmax) {
+      case 4: go_resid(pq_resid_encode_kernel<DT, 4>); break;
+      case 8: go_resid(pq_resid_encode_kernel<DT, 8>); break;
+      case 16: go_resid(pq_resid_encode_kernel<DT, 16>); break;
+      default: go_resid(pq_resid_encode_kernel<DT, 32>); break;
+    }
+  } else {
+    switch (dmax) {
+      case 4: go(pq_encode_kernel<DT, 4>); break;
+      case 8: go(pq_encode_kernel<DT, 8>); break;
+      case 16: go(pq_encode_kernel<DT, 16>); break;
+      default: go(pq_encode_kernel<DT, 32>); break;
+    }
   }
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
+}
+
+// what the residual calls need of the context: a partition table and centroids; 0: fine
+nvdb_status resid_args(nvdb_hip_ctx* c, const char* who) {
+  if (nvdb_status st = parts_args(c, who)) return st;
+  if (!c->parts->have_centroids || !c->parts->coarse) return fail(c, NVDB_ERR_INVALID, std::string(who) + ": no centroids (nvdb_hip_set_centroids)");
+  return NVDB_OK;
+}
+
+// the context's table as the u32 words the residual kernels search (n <= 0xFFFFFF00: nvdb_hip_set_partitions)
+std::vector<uint32_t> resid_offsets(const nvdb_hip_ctx* c) {
+  const std::vector<uint64_t>& off = c->parts->offsets;
+  return std::vector<uint32_t>(off.begin(), off.end());
 }
 
 // ---- the trainer (nvdb_hip_pq_train): device memory that lives as long as the call
@@ -71,6 +111,15 @@ template <int DT>
 nvdb_status launch_train_gather(nvdb_hip_ctx* c, hipStream_t s, const uint32_t* idx, uint64_t m, float* X) {
   const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((m * c->dim + 255) / 256, static_cast<uint64_t>(c->num_cu) * 64));
   pq_train_gather_kernel<DT><<<grid, 256, 0, s>>>(c->rows, c->scales, c->dim, idx, m, X);
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+// ... and the residual trainer's: off / cent on the device, a wave per training row
+template <int DT>
+nvdb_status launch_resid_gather(nvdb_hip_ctx* c, hipStream_t s, const uint32_t* idx, uint64_t m, const uint32_t* off, uint32_t nparts, const float* cent, float* X) {
+  const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((m + 3) / 4, static_cast<uint64_t>(c->num_cu) * 64));
+  pq_resid_gather_kernel<DT><<<grid, 256, 0, s>>>(c->rows, c->scales, c->dim, idx, m, off, nparts, cent, X);
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
 }
@@ -101,7 +150,9 @@ nvdb_status launch_train_iteration(nvdb_hip_ctx* c, hipStream_t s, const float* 
 }
 
 // the call proper, the arguments validated: cb (host, [M][256][dsub]) and err (host, [iters]) are this call's own and reach the caller on success only
-nvdb_status pq_train(nvdb_hip_ctx* c, uint32_t M, uint32_t iters, uint64_t seed, uint64_t m, const float* init, std::vector<float>& cb, std::vector<double>& err) {
+// residual: the training rows are the residuals to the centroids of their lists (the caller has checked resid_args)
+nvdb_status pq_train(nvdb_hip_ctx* c, bool residual, uint32_t M, uint32_t iters, uint64_t seed, uint64_t m, const float* init, std::vector<float>& cb,
+                     std::vector<double>& err) {
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const uint64_t n = c->n;
@@ -110,7 +161,7 @@ nvdb_status pq_train(nvdb_hip_ctx* c, uint32_t M, uint32_t iters, uint64_t seed,
   nvdb_status st = NVDB_OK;
 
   // the training set as f32 rows: every row, or rows floor(i * n / m) (n < 2^32, m < 2^32: the product fits)
-  TrainMem d_idx, d_x, d_cb;
+  TrainMem d_idx, d_x, d_cb, d_off;
   if (m < n) {
     std::vector<uint32_t> idx(m);
     for (uint64_t i = 0; i < m; ++i) idx[i] = static_cast<uint32_t>(i * n / m);
@@ -118,7 +169,18 @@ nvdb_status pq_train(nvdb_hip_ctx* c, uint32_t M, uint32_t iters, uint64_t seed,
     HIPCHK(c, hipMemcpy(d_idx.p, idx.data(), m * 4, hipMemcpyHostToDevice));
   }
   if ((st = train_alloc(c, d_x, m * dim * 4)) || (st = train_alloc(c, d_cb, cb_bytes))) return st;
-  dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_train_gather<decltype(dt)::value>(c, s, d_idx.as<uint32_t>(), m, d_x.as<float>()); });
+  if (residual) {
+    // the centroids where set_centroids put them (the child context's f32 rows, this device), the table as u32 for the call
+    const std::vector<uint32_t> off = resid_offsets(c);
+    if ((st = train_alloc(c, d_off, off.size() * 4))) return st;
+    HIPCHK(c, hipMemcpy(d_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    dispatch_dtype(c->dtype, st, [&](auto dt) {
+      return launch_resid_gather<decltype(dt)::value>(c, s, d_idx.as<uint32_t>(), m, d_off.as<uint32_t>(), static_cast<uint32_t>(off.size() - 1),
+                                                      static_cast<const float*>(c->parts->coarse->rows), d_x.as<float>());
+    });
+  } else {
+    dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_train_gather<decltype(dt)::value>(c, s, d_idx.as<uint32_t>(), m, d_x.as<float>()); });
+  }
   if (st) return st;
 
   if (init) {
@@ -175,6 +237,15 @@ nvdb_status launch_scan_g(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, con
     HIPCHK(c, hipGetLastError());
     return NVDB_OK;
   };
+  auto go_resid = [&](auto kernel) -> nvdb_status {
+    if (lds > 64 * 1024)
+      if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(kernel), PART_LDS_LIMIT)) return st;
+    kernel<<<nitems, PQ_SCAN_THREADS, lds, s>>>(pq.codes, pq.M, im.items, im.qidx, im.dst, static_cast<const float*>(pq.base.p),
+                                                static_cast<const float*>(pq.lut.p), static_cast<Cand*>(c->parts->cand.p));
+    HIPCHK(c, hipGetLastError());
+    return NVDB_OK;
+  };
+  if (pq.residual) return pq_wide_codes(pq.M) ? go_resid(pq_scan_resid_kernel<G, true>) : go_resid(pq_scan_resid_kernel<G, false>);
   return pq_wide_codes(pq.M) ? go(pq_scan_kernel<G, true>) : go(pq_scan_kernel<G, false>);
 }
 
@@ -222,8 +293,16 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
     p.qg_max = pq_group(pq.M);
     p.queries = queries;
     p.skip_empty = true;
+    size_t pstart_at = 0;                                              // residual: where pstart begins in the image's extra words
     st = parts_pass(c, s, who, pb, p, [&](PartPass& pp) -> nvdb_status {
       if (nvdb_status e = pa_sub_plan(c, who, block.data() + q0, b, R, sub, pp)) return e;
+      if (pq.residual) {
+        // behind the plan's words: pstart[nparts + 1] of this pass's counting sort -- which entries of qidx probe partition p
+        pstart_at = sub.extra.size();
+        sub.extra.insert(sub.extra.end(), ps->list.pstart.begin(), ps->list.pstart.end());
+        pp.extra = sub.extra.data(); pp.extra_words = static_cast<uint32_t>(sub.extra.size());
+        if (nvdb_status e = ensure(c, pq.base, static_cast<size_t>(pp.wl.npairs) * 4)) return e;
+      }
       return ensure(c, pq.lut, b * pq_lut_bytes(pq.M));
     });
     if (st) return st;
@@ -239,6 +318,11 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
     }
     pq_lut_kernel<<<dim3(pq.M / 4u, b), 256, 0, s>>>(static_cast<const float*>(ps->q.p), c->dim, pq.M, pq.dsub, pq.codebooks, static_cast<float*>(pq.lut.p));
     HIPCHK(c, hipGetLastError());
+    if (pq.residual) {
+      pq_base_kernel<<<nparts, PQ_BASE_THREADS, 0, s>>>(static_cast<const float*>(ps->q.p), c->dim, pq.cent, p.im.extra + pstart_at, p.im.qidx,
+                                                        static_cast<float*>(pq.base.p));
+      HIPCHK(c, hipGetLastError());
+    }
     if ((st = launch_scan(c, s, pq, p.im, static_cast<uint32_t>(p.wl.nitems)))) return st;
     c->stats.chunks += 1;
     if ((st = pa_sub_select(c, s, sub, p.im, b, R))) return st;
@@ -286,35 +370,47 @@ nvdb_status pq_search_args(nvdb_hip_ctx* c, const char* who, bool ivf, const flo
   return parts_topk_args(c, who, ivf, 0, queries, nq, R, probe, nprobe, nullptr, out_ids, out_scores, out_counts, timing, done);
 }
 
-}  // namespace
-}  // namespace nvdbhip
-
-extern "C" {
-
-nvdb_status nvdb_hip_pq_build(nvdb_hip_ctx* c, const float* codebooks, uint32_t M) {
+// nvdb_hip_pq_build / nvdb_hip_pq_build_residual: on any failure nothing has changed
+nvdb_status pq_build(nvdb_hip_ctx* c, const char* who, bool residual, const float* codebooks, uint32_t M) {
   if (!c) return NVDB_ERR_INVALID;
+  const std::string w = std::string(who) + ": ";
   if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
-  if (!codebooks) return fail(c, NVDB_ERR_INVALID, "pq_build: null codebooks");
+  if (!codebooks) return fail(c, NVDB_ERR_INVALID, w + "null codebooks");
   bool unsupported = false;
-  if (const char* why = pq_shape_check(c->dim, M, unsupported)) return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, std::string("pq_build: ") + why);
+  if (const char* why = pq_shape_check(c->dim, M, unsupported)) return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, w + why);
+  if (residual)
+    if (nvdb_status st = resid_args(c, who)) return st;
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   PqState fresh;
   fresh.M = M; fresh.dsub = c->dim / M;
+  fresh.residual = residual;
   const size_t cb_bytes = static_cast<size_t>(M) * PQ_KSUB * fresh.dsub * 4;
   const size_t code_bytes = static_cast<size_t>(c->n) * M, pad_bytes = static_cast<size_t>(PAD_ROWS) * M;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&fresh.codebooks), cb_bytes);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.codes), code_bytes + pad_bytes);
   if (e == hipSuccess) e = hipMemcpyAsync(fresh.codebooks, codebooks, cb_bytes, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemsetAsync(fresh.codes + code_bytes, 0, pad_bytes, s);
+  if (residual) {
+    // the shadow's own copies: the table as u32, the centroids from where set_centroids put them (the child context's f32 rows)
+    const std::vector<uint32_t> off = resid_offsets(c);
+    fresh.nparts = static_cast<uint32_t>(off.size() - 1);
+    const size_t cent_bytes = static_cast<size_t>(fresh.nparts) * c->dim * 4;
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.off), off.size() * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.cent), cent_bytes);
+    if (e == hipSuccess) e = hipMemcpy(fresh.off, off.data(), off.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh.cent, c->parts->coarse->rows, cent_bytes, hipMemcpyDeviceToDevice, s);
+  }
   nvdb_status st = NVDB_OK;
-  if (e != hipSuccess) st = fail(c, NVDB_ERR_HIP, std::string("pq_build: ") + hipGetErrorString(e));
+  if (e != hipSuccess) st = fail(c, NVDB_ERR_HIP, w + hipGetErrorString(e));
   if (!st) dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_encode<decltype(dt)::value>(c, s, fresh); });
-  if (!st && (e = hipStreamSynchronize(s)) != hipSuccess) st = fail(c, NVDB_ERR_HIP, std::string("pq_build: ") + hipGetErrorString(e));
+  if (!st && (e = hipStreamSynchronize(s)) != hipSuccess) st = fail(c, NVDB_ERR_HIP, w + hipGetErrorString(e));
   if (st) {                                                            // nothing changed: an earlier build stands
     (void)hipGetLastError();
     if (fresh.codebooks) (void)hipFree(fresh.codebooks);
     if (fresh.codes) (void)hipFree(fresh.codes);
+    if (fresh.off) (void)hipFree(fresh.off);
+    if (fresh.cent) (void)hipFree(fresh.cent);
     return st;
   }
   pq_drop(c);
@@ -322,24 +418,76 @@ nvdb_status nvdb_hip_pq_build(nvdb_hip_ctx* c, const float* codebooks, uint32_t 
   return NVDB_OK;
 }
 
-nvdb_status nvdb_hip_pq_train(nvdb_hip_ctx* c, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init, float* out_codebooks,
-                              double* out_err) {
+// nvdb_hip_pq_train / nvdb_hip_pq_train_residual behind one set of checks
+nvdb_status pq_train_call(nvdb_hip_ctx* c, const char* who, bool residual, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init,
+                          float* out_codebooks, double* out_err) {
   if (!c) return NVDB_ERR_INVALID;
-  if (!out_codebooks) return fail(c, NVDB_ERR_INVALID, "pq_train: null output");
+  const std::string w = std::string(who) + ": ";
+  if (!out_codebooks) return fail(c, NVDB_ERR_INVALID, w + "null output");
   if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
   bool unsupported = false;
-  if (const char* why = pq_shape_check(c->dim, M, unsupported)) return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, std::string("pq_train: ") + why);
+  if (const char* why = pq_shape_check(c->dim, M, unsupported)) return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, w + why);
+  if (residual)
+    if (nvdb_status st = resid_args(c, who)) return st;
   const uint64_t m = pq_train_rows(c->n, max_train_rows);
-  if (m < PQ_TRAIN_MIN_ROWS) return fail(c, NVDB_ERR_INVALID, "pq_train: fewer than 256 training rows");
-  if (m > IVF_MAX_ROWS) return fail(c, NVDB_ERR_UNSUPPORTED, "pq_train: training set too large (max_train_rows)");
+  if (m < PQ_TRAIN_MIN_ROWS) return fail(c, NVDB_ERR_INVALID, w + "fewer than 256 training rows");
+  if (m > IVF_MAX_ROWS) return fail(c, NVDB_ERR_UNSUPPORTED, w + "training set too large (max_train_rows)");
   std::vector<float> cb(static_cast<size_t>(M) * PQ_KSUB * (c->dim / M));
   std::vector<double> err(iters);
-  if (nvdb_status st = pq_train(c, M, iters, seed, m, init, cb, err)) {
+  if (nvdb_status st = pq_train(c, residual, M, iters, seed, m, init, cb, err)) {
     (void)hipGetLastError();
     return st;
   }
   std::memcpy(out_codebooks, cb.data(), cb.size() * 4);
   if (out_err && iters) std::memcpy(out_err, err.data(), err.size() * 8);
+  return NVDB_OK;
+}
+
+}  // namespace
+}  // namespace nvdbhip
+
+extern "C" {
+
+nvdb_status nvdb_hip_pq_build(nvdb_hip_ctx* c, const float* codebooks, uint32_t M) { return pq_build(c, "pq_build", false, codebooks, M); }
+
+nvdb_status nvdb_hip_pq_build_residual(nvdb_hip_ctx* c, const float* codebooks, uint32_t M) { return pq_build(c, "pq_build_residual", true, codebooks, M); }
+
+nvdb_status nvdb_hip_pq_train(nvdb_hip_ctx* c, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init, float* out_codebooks,
+                              double* out_err) {
+  return pq_train_call(c, "pq_train", false, M, iters, seed, max_train_rows, init, out_codebooks, out_err);
+}
+
+nvdb_status nvdb_hip_pq_train_residual(nvdb_hip_ctx* c, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init,
+                                       float* out_codebooks, double* out_err) {
+  return pq_train_call(c, "pq_train_residual", true, M, iters, seed, max_train_rows, init, out_codebooks, out_err);
+}
+
+nvdb_status nvdb_hip_pq_kind(nvdb_hip_ctx* c, uint32_t* residual) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (residual) *residual = (c->pq && c->pq->residual) ? 1u : 0u;
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_pq_reconstruct(nvdb_hip_ctx* c, uint64_t row0, uint64_t nrows, float* out) {
+  if (nvdb_status st = pq_args(c, "pq_reconstruct")) return st;
+  if (row0 > c->n || nrows > c->n - row0) return fail(c, NVDB_ERR_INVALID, "pq_reconstruct: row0 + nrows > n");
+  if (nrows == 0) return NVDB_OK;
+  if (!out) return fail(c, NVDB_ERR_INVALID, "pq_reconstruct: null output");
+  if (c->n > IVF_MAX_ROWS) return fail(c, NVDB_ERR_UNSUPPORTED, "pq_reconstruct: corpus shard too large");
+  HIPCHK(c, hipSetDevice(c->device));
+  const PqState& pq = *c->pq;
+  const uint64_t step = std::min<uint64_t>(nrows, pq_reconstruct_rows(c->dim));
+  TrainMem d_y;
+  if (nvdb_status st = train_alloc(c, d_y, step * c->dim * 4)) return st;
+  for (uint64_t r = 0; r < nrows; r += step) {
+    const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(step, nrows - r));
+    const unsigned grid = std::min<unsigned>((nr + 3u) / 4u, static_cast<unsigned>(c->num_cu) * 64u);
+    pq_reconstruct_kernel<<<grid, 256, 0, c->stream>>>(pq.codes, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, pq.residual ? pq.cent : nullptr,
+                                                       static_cast<uint32_t>(row0 + r), nr, d_y.as<float>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out + r * c->dim, d_y.p, static_cast<size_t>(nr) * c->dim * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
   return NVDB_OK;
 }
 

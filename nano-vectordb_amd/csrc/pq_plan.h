@@ -48,6 +48,13 @@ constexpr size_t pq_train_lds(uint32_t dmax) { return 2 * static_cast<size_t>(PQ
 // bytes of the per-chunk fp64 partial sums
 constexpr uint64_t pq_train_partial_bytes(uint64_t m, uint32_t dim) { return pq_train_chunks(m) * PQ_KSUB * dim * 8; }
 
+// ---- the residual shadow (kernels_pq_resid.h)
+// rows nvdb_hip_pq_reconstruct maps per launch: at most 64 MB of f32 output on the device, at least one row
+constexpr uint64_t pq_reconstruct_rows(uint32_t dim) {
+  const uint64_t r = (64ull << 20) / (static_cast<uint64_t>(dim) * 4);
+  return r < 1 ? 1 : r;
+}
+
 // a lane reads its row's codes in 16-byte pieces where a row is whole pieces, else in dwords (M % 4 == 0 always)
 constexpr bool pq_wide_codes(uint32_t M) { return M % 16 == 0; }
 

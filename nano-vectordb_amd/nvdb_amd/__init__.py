@@ -45,6 +45,8 @@ EXPORTS = [
     "nvdb_hip_pq_build", "nvdb_hip_pq_info", "nvdb_hip_pq_download_codes", "nvdb_hip_pq_search_partitions", "nvdb_hip_pq_search_ivf",
     "nvdb_hip_pq_refine_ivf", "nvdb_hip_ivf_pq_build", "nvdb_hip_ivf_pq_search", "nvdb_hip_ivf_pq_refine",
     "nvdb_hip_pq_train", "nvdb_hip_ivf_pq_train",
+    "nvdb_hip_pq_build_residual", "nvdb_hip_pq_train_residual", "nvdb_hip_pq_kind", "nvdb_hip_pq_reconstruct",
+    "nvdb_hip_ivf_pq_build_residual", "nvdb_hip_ivf_pq_train_residual",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -223,6 +225,12 @@ def _bind(L, dev):
     L.nvdb_hip_pq_build.argtypes = [vp, vp, u32]
     L.nvdb_hip_pq_train.argtypes = [vp, u32, u32, u64, u64, vp, vp, vp]
     L.nvdb_hip_ivf_pq_train.argtypes = [vp, u32, u32, u64, u64, vp, vp, vp]
+    L.nvdb_hip_pq_build_residual.argtypes = [vp, vp, u32]
+    L.nvdb_hip_ivf_pq_build_residual.argtypes = [vp, vp, u32]
+    L.nvdb_hip_pq_train_residual.argtypes = [vp, u32, u32, u64, u64, vp, vp, vp]
+    L.nvdb_hip_ivf_pq_train_residual.argtypes = [vp, u32, u32, u64, u64, vp, vp, vp]
+    L.nvdb_hip_pq_kind.argtypes = [vp, C.POINTER(u32)]
+    L.nvdb_hip_pq_reconstruct.argtypes = [vp, u64, u64, vp]
     L.nvdb_hip_pq_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
     L.nvdb_hip_pq_download_codes.argtypes = [vp, u64, u64, vp]
     L.nvdb_hip_pq_search_partitions.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp, C.POINTER(Timing)]
@@ -704,17 +712,38 @@ class HipContext:
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
     # -- PQ candidate scan (a PQ shadow of the resident corpus under the caller's codebooks; stats path 9)
-    def pq_build(self, codebooks):
-        """Encode the resident rows under codebooks [M, 256, dim / M] f32 (nearest codeword by squared L2, ties to the lowest)."""
+    def pq_build(self, codebooks, residual=False):
+        """Encode the resident rows under codebooks [M, 256, dim / M] f32 (nearest codeword by squared L2, ties to the lowest).
+        residual: encode every row's residual to the centroid of its list (needs set_partitions and set_centroids, which free
+        such a shadow when called again); the searches answer from whichever shadow the context holds."""
         codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
         if codebooks.ndim != 3 or codebooks.shape[1] != 256:
             raise ValueError("codebooks must be [M, 256, dim / M]")
-        self._chk(self.lib.nvdb_hip_pq_build(self.h, codebooks.ctypes.data, codebooks.shape[0]))
+        fn = self.lib.nvdb_hip_pq_build_residual if residual else self.lib.nvdb_hip_pq_build
+        self._chk(fn(self.h, codebooks.ctypes.data, codebooks.shape[0]))
 
-    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False):
+    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False):
         """Codebooks [M, 256, dim / M] f32 by Lloyd's iteration over the resident rows on the device (init None: 256 drawn training
-        rows per sub-quantiser); with want_err also the [iters] f64 mean winning distances.  Does not build: pq_build(result)."""
-        return _pq_train(self, self.lib.nvdb_hip_pq_train, self.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err)
+        rows per sub-quantiser); with want_err also the [iters] f64 mean winning distances.  residual: over the rows' residuals to
+        their lists' centroids.  Does not build: pq_build(result, residual)."""
+        fn = self.lib.nvdb_hip_pq_train_residual if residual else self.lib.nvdb_hip_pq_train
+        return _pq_train(self, fn, self.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err)
+
+    def pq_kind(self):
+        """dict(residual): True where the context holds a residual shadow."""
+        r = C.c_uint32()
+        self._chk(self.lib.nvdb_hip_pq_kind(self.h, C.byref(r)))
+        return dict(residual=bool(r.value))
+
+    def pq_reconstruct(self, row0=0, nrows=None):
+        """Resident rows [row0, row0 + nrows) as their codes describe them -> [nrows, dim] f32: the codeword of every sub-vector,
+        plus the centroid of the row's list under a residual shadow."""
+        info = self.corpus_info()
+        if nrows is None:
+            nrows = info["n"] - row0
+        out = np.zeros((max(nrows, 0), info["dim"]), dtype=np.float32)
+        self._chk(self.lib.nvdb_hip_pq_reconstruct(self.h, row0, nrows, out.ctypes.data if out.size else None))
+        return out
 
     def pq_info(self):
         """dict(M, dsub, code_bytes); all 0 without codes."""
@@ -965,16 +994,27 @@ class IvfIndex:
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
     # -- PQ candidate scan on the index's context, answered in the source corpus' ids
-    def pq_build(self, codebooks):
-        """HipContext.pq_build over the list-ordered rows; compact() and add_rows() free the codes."""
+    def pq_build(self, codebooks, residual=False):
+        """HipContext.pq_build over the list-ordered rows (residual: against the index's lists and centroids); compact() and
+        add_rows() free the codes."""
         codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
         if codebooks.ndim != 3 or codebooks.shape[1] != 256:
             raise ValueError("codebooks must be [M, 256, dim / M]")
-        self._chk(self.lib.nvdb_hip_ivf_pq_build(self.h, codebooks.ctypes.data, codebooks.shape[0]))
+        fn = self.lib.nvdb_hip_ivf_pq_build_residual if residual else self.lib.nvdb_hip_ivf_pq_build
+        self._chk(fn(self.h, codebooks.ctypes.data, codebooks.shape[0]))
 
-    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False):
+    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False):
         """HipContext.pq_train over the list-ordered rows."""
-        return _pq_train(self, self.lib.nvdb_hip_ivf_pq_train, self.ctx.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err)
+        fn = self.lib.nvdb_hip_ivf_pq_train_residual if residual else self.lib.nvdb_hip_ivf_pq_train
+        return _pq_train(self, fn, self.ctx.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err)
+
+    def pq_kind(self):
+        """HipContext.pq_kind of the index's context."""
+        return self.ctx.pq_kind()
+
+    def pq_reconstruct(self, row0=0, nrows=None):
+        """HipContext.pq_reconstruct over the list-ordered rows (positions, not source ids)."""
+        return self.ctx.pq_reconstruct(row0, nrows)
 
     def pq_search(self, queries, R, nprobe, want_probe=False):
         """The R best PQ scores of the nprobe best lists -> (ids, scores, counts[, probe]); equal scores by (partition, original id)."""

@@ -12,7 +12,18 @@ nprobe in (8, 32) and R in (100, 1024), median wall ms per call, alternating the
   ivf_pq_refine K = 10            the fused pipeline                   | ivf_search_anyk k = R, then refine_l2_topk on the index's rows
 and recall@10 of both refined results against the exact flat top-10 by squared L2 distance over the rows as f32 (the search's
 own score is the dot product, so the flat reference is the refine over every row, taken from a flat scan's 1024 best dot
-products -- stated with the figure).  Prints the build's wall time and one JSON line with all of it."""
+products -- stated with the figure).  Prints the build's wall time and one JSON line with all of it.
+
+    python tools_dev/bench_pq.py [the same arguments] --residual [--clustered]
+
+The non-residual shadow beside the RESIDUAL one.  A context holds one shadow, so the process builds the index twice from the same
+rows and centroids -- the same lists, row for row -- and gives each copy one kind: codebooks from pq_train / pq_train(residual=True)
+over the same 20000 list-ordered rows and rounds, then, alternating the two copies call by call, median wall ms of ivf_pq_search
+and ivf_pq_refine at the shapes above, recall@10 of both, the wall time of both builds (median of 3 after a warm-up: codebook
+upload, allocation and the encode kernel) and the fp64 quantisation error of both over 20 blocks of 1000 rows: the mean over rows
+and sub-quantisers of |x - pq_reconstruct(x)|^2.  --clustered replaces the synthetic corpus, which has no cluster structure, by
+seeded centre + noise rows generated on the host (nlist / 4 centres, noise 0.35 of a centre's element scale, every row scaled
+to unit length as the index's spherical k-means expects), labelled as such."""
 import json
 import os
 import sys
@@ -79,8 +90,61 @@ def recall(got, want):
     return float(np.mean([len(set(g[g != U64MAX].tolist()) & set(w.tolist())) / len(w) for g, w in zip(got, want)]))
 
 
+def main_residual(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, clustered):
+    seed, K, rounds = 20240613, 10, 4
+    out = dict(mode="residual", corpus="clustered" if clustered else "synthetic", rows=rows, dim=dim, dtype=dname, nlist=nlist, M=M, batch=batch,
+               calls=calls, warmup=warmup, K=K)
+    src = nvdb_amd.HipContext(0)
+    rs = np.random.RandomState(11)
+    if clustered:
+        centres = rs.standard_normal((max(nlist // 4, 1), dim)).astype(np.float32)
+        x = np.empty((rows, dim), dtype=np.float16 if dtype == nvdb_amd.DT_F16 else np.float32)
+        for i in range(0, rows, 65536):
+            n = min(65536, rows - i)
+            v = centres[rs.randint(len(centres), size=n)] + 0.35 * rs.standard_normal((n, dim)).astype(np.float32)
+            x[i:i + n] = v / np.linalg.norm(v, axis=1, keepdims=True)      # unit rows: the index's centroids are spherical k-means'
+        src.upload_corpus(x.view(np.uint16) if dtype == nvdb_amd.DT_F16 else x, dtype)
+        q = np.ascontiguousarray(x[rs.choice(rows, batch, replace=False)].astype(np.float32) + 0.1 * rs.standard_normal((batch, dim)).astype(np.float32))
+        del x
+    else:
+        src.generate_corpus(seed, rows, dim, dtype)
+        q = np.ascontiguousarray(nvdb_amd.synth_rows_f32(seed + 1, 0, batch, dim))
+    fid, _ = src.search_batch(q, 1024)
+    want, _ = src.refine_l2_topk(q, fid.astype(np.uint32), K)
+    want = want.astype(np.uint64)
+    cents = src.train_centroids(nlist, 2, seed, max_train_rows=262144)
+    ixs = {False: nvdb_amd.IvfIndex(src, cents), True: nvdb_amd.IvfIndex(src, cents)}
+    src.close()
+    blocks = np.sort(rs.choice(rows - 1000, 20, replace=False))
+    for residual, ix in ixs.items():
+        cb = ix.pq_train(M, rounds, 7, max_train_rows=20000, residual=residual)
+        build_s, build_all = median_s(lambda: ix.pq_build(cb, residual=residual), reps=3)
+        err = 0.0
+        for b in blocks:
+            raw = ix.ctx.download_rows(int(b), 1000)[0]
+            xs = (raw.view(np.float16) if dtype == nvdb_amd.DT_F16 else raw).astype(np.float64)
+            err += ((xs - ix.pq_reconstruct(int(b), 1000).astype(np.float64)) ** 2).sum()
+        out["residual" if residual else "plain"] = dict(pq_build_s=build_s, pq_build_all_s=build_all, quant_err=err / (len(blocks) * 1000 * M))
+        print(f"{'residual' if residual else 'plain':8s}: pq_build {build_s:.3f} s (median of 3), fp64 quantisation error {err / (len(blocks) * 1000 * M):.6e}")
+    a, b = ixs[False], ixs[True]
+    for nprobe in (8, 32):
+        for R in (100, 1024):
+            key = f"nprobe={nprobe} R={R}"
+            pa, pb, *spread = alternate_ms(lambda: a.pq_search(q, R, nprobe), lambda: b.pq_search(q, R, nprobe), calls, warmup)
+            fa, fb, *fspread = alternate_ms(lambda: a.pq_refine(q, K, R, nprobe), lambda: b.pq_refine(q, K, R, nprobe), calls, warmup)
+            ra, rb = recall(a.pq_refine(q, K, R, nprobe)[0], want), recall(b.pq_refine(q, K, R, nprobe)[0], want)
+            out[key] = dict(plain_search_ms=pa, residual_search_ms=pb, search_spread=spread, plain_refine_ms=fa, residual_refine_ms=fb, refine_spread=fspread,
+                            recall10_plain=ra, recall10_residual=rb)
+            print(f"{key:20s}: ivf_pq_search plain {pa:8.3f} ms | residual {pb:8.3f} ms || ivf_pq_refine plain {fa:8.3f} ms | residual {fb:8.3f} ms || "
+                  f"recall@10 plain {ra:.4f}, residual {rb:.4f}")
+    print(json.dumps(out))
+    for ix in ixs.values():
+        ix.close()
+
+
 def main():
-    a = sys.argv[1:]
+    flags = [x for x in sys.argv[1:] if x.startswith("--")]
+    a = [x for x in sys.argv[1:] if not x.startswith("--")]
     rows = int(a[0]) if len(a) > 0 else 10_000_000
     dim = int(a[1]) if len(a) > 1 else 768
     dname = a[2] if len(a) > 2 else "f16"
@@ -90,6 +154,8 @@ def main():
     batch = int(a[5]) if len(a) > 5 else 1024
     calls = int(a[6]) if len(a) > 6 else 10
     warmup = int(a[7]) if len(a) > 7 else 2
+    if "--residual" in flags:
+        return main_residual(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, "--clustered" in flags)
     seed, K = 20240613, 10
     out = dict(rows=rows, dim=dim, dtype=dname, nlist=nlist, M=M, batch=batch, calls=calls, warmup=warmup, K=K)
 
