@@ -751,7 +751,26 @@ nvdb_status nvdb_hip_refine_l2_topk_dev(nvdb_hip_ctx* ctx, const float* dev_quer
  * A residual shadow keeps its own device copies of the table and the centroids it was built under; nvdb_hip_set_partitions and
  * nvdb_hip_set_centroids free it (a non-residual shadow survives them), and so does whatever frees a shadow above.  A search costs
  * one more small launch per sub-batch (the base terms: dim fmas per (query, probed partition)) and one addition per (row, query).
- * Out of scope: cluster splitting and k-means++ starts in the trainer, L2 asymmetric-distance tables, OPQ rotations, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
+ * OPQ: shadows under a caller's ROTATION (nvdb_hip_pq_build_opq; FAISS OPQMatrix in front of IndexIVFPQ): the codes are cut from
+ * the rotated row, the codebooks live in the rotated space, the queries are rotated in front of their tables.  Learning the matrix
+ * stays with the caller.  The arithmetic, fixed:
+ *   rotation    A[dim][dim] f32, row-major, host memory.  The library does NOT check that it is orthonormal: the scores approximate
+ *               q . x only where A^T A = I (then (A q) . (A x) = q . x); any other matrix is encoded, scored and reconstructed by the
+ *               same rules and means what the caller makes of it.
+ *   e           the row as an f32 query; under a residual shadow minus the centroid of its list, one fp32 subtraction (residual above).
+ *   y[i]        sum_t A[i][t] * e[t] in fp32: t ascending from 0, one fused multiply-add per element, the accumulator from 0 --
+ *               whatever the launch, the tile or the row's position in it (dim % 4 == 0 follows from the shape rules).  A NaN or
+ *               infinity in one row or in one matrix row reaches only the outputs that read it.
+ *   encode      the encode rule above applied to y.
+ *   queries     q' = A q by the rule of y; tables L[q'][m][j] as above.  Under a residual shadow the base term stays b(q, p) = q . c[p]
+ *               on the UNROTATED query and centroid, bit for bit the one above; the score is b + S as above.  The coarse step and the
+ *               refine use the unrotated queries.
+ *   reconstruct yhat = the codewords side by side; xhat[t] = sum_i A[i][t] * yhat[i] in fp32, i ascending from 0, one fused
+ *               multiply-add each, from 0; under a residual shadow plus c[list(r)][t], one fp32 addition.
+ * The product runs on the fp32 matrix cores (v_mfma_f32_16x16x4_f32 adds its four products to the accumulator as that chain; K is
+ * never split), n * dim * dim multiply-adds per build and nq * dim * dim per search.  The shadow keeps device copies of A and A^T
+ * (2 * dim * dim * 4 bytes), freed with it; a build holds up to 256 MB of rotated f32 rows inside the call.
+ * Out of scope: cluster splitting and k-means++ starts in the trainer, L2 asymmetric-distance tables, learning the rotation, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
  * pruning inside the scan, the device group, _dev stream forms, the nvdb:: C++ host layer.
  * ------------------------------------------------------------------------------------------- */
 
@@ -797,6 +816,27 @@ nvdb_status nvdb_hip_pq_build_residual(nvdb_hip_ctx* ctx, const float* codebooks
 nvdb_status nvdb_hip_pq_train_residual(nvdb_hip_ctx* ctx, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
                                        const float* init /* [M][256][dim / M], may be NULL */,
                                        float* out_codebooks /* [M][256][dim / M] f32, host */, double* out_err /* [iters], may be NULL */);
+/* nvdb_hip_pq_build (residual == 0) or nvdb_hip_pq_build_residual (residual != 0) under a rotation (OPQ above): rotation [dim][dim]
+ * f32, host memory, NULL -> NVDB_ERR_INVALID; every shape rule and error of those builds, and on any failure the earlier shadow, of
+ * any kind, stands.  Replaces an earlier build; a later build without a rotation holds none.  Non-finite matrix: no fault, no hang. */
+nvdb_status nvdb_hip_pq_build_opq(nvdb_hip_ctx* ctx, const float* rotation /* [dim][dim] */, const float* codebooks /* [M][256][dim / M] */,
+                                  uint32_t M, uint32_t residual);
+/* nvdb_hip_pq_train / nvdb_hip_pq_train_residual over the ROTATED training rows: the gathered f32 rows, residual or not, become A e
+ * (OPQ above) before the start is drawn and the Lloyd steps run; everything else -- the draw rule, the sums' order, out_err, "same
+ * arguments -> same bytes" -- is unchanged, and the assignment is the _opq build's, bit for bit.  rotation NULL -> NVDB_ERR_INVALID. */
+nvdb_status nvdb_hip_pq_train_opq(nvdb_hip_ctx* ctx, const float* rotation /* [dim][dim] */, uint32_t M, uint32_t iters, uint64_t seed,
+                                  uint64_t max_train_rows, const float* init /* [M][256][dim / M], may be NULL */,
+                                  float* out_codebooks /* [M][256][dim / M] f32, host */, double* out_err /* [iters], may be NULL */,
+                                  uint32_t residual);
+/* *rotated (optional) = 1 where the context holds a shadow built under a rotation, else 0; out (optional, [dim][dim] f32, host)
+ * then receives the matrix bits it was built under, and is not written otherwise */
+nvdb_status nvdb_hip_pq_rotation(nvdb_hip_ctx* ctx, uint32_t* rotated, float* out /* [dim][dim], may be NULL */);
+/* out[nrows][dim] f32 (host) = y of resident rows [row0, row0 + nrows): exactly what the encode saw (the centroid subtracted under a
+ * residual shadow).  Range errors as nvdb_hip_pq_reconstruct; no codes, or a shadow without a rotation -> NVDB_ERR_INVALID */
+nvdb_status nvdb_hip_pq_rotated_rows(nvdb_hip_ctx* ctx, uint64_t row0, uint64_t nrows, float* out /* [nrows][dim] */);
+/* out[n][dim] f32 (host) = A x for the host vectors x[n][dim] f32: exactly what the searches do to their queries.  n == 0 ->
+ * NVDB_OK; null pointers, no codes, or a shadow without a rotation -> NVDB_ERR_INVALID */
+nvdb_status nvdb_hip_pq_rotate(nvdb_hip_ctx* ctx, const float* x /* [n][dim] */, uint64_t n, float* out /* [n][dim] */);
 /* every output optional; all 0 without codes.  code_bytes = n * M */
 nvdb_status nvdb_hip_pq_info(nvdb_hip_ctx* ctx, uint32_t* M, uint32_t* dsub, uint64_t* code_bytes);
 /* *residual (optional) = 1 where the context holds a residual shadow, 0 for a non-residual one or none */
@@ -842,6 +882,10 @@ nvdb_status nvdb_hip_ivf_pq_train(nvdb_hip_ivf* ivf, uint32_t M, uint32_t iters,
 nvdb_status nvdb_hip_ivf_pq_build_residual(nvdb_hip_ivf* ivf, const float* codebooks, uint32_t M);
 nvdb_status nvdb_hip_ivf_pq_train_residual(nvdb_hip_ivf* ivf, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
                                            const float* init, float* out_codebooks, double* out_err);
+/* nvdb_hip_pq_build_opq / nvdb_hip_pq_train_opq on the index's context */
+nvdb_status nvdb_hip_ivf_pq_build_opq(nvdb_hip_ivf* ivf, const float* rotation, const float* codebooks, uint32_t M, uint32_t residual);
+nvdb_status nvdb_hip_ivf_pq_train_opq(nvdb_hip_ivf* ivf, const float* rotation, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
+                                      const float* init, float* out_codebooks, double* out_err, uint32_t residual);
 nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe,
                                    uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing);
 nvdb_status nvdb_hip_ivf_pq_refine(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t K, uint32_t R, uint32_t nprobe,

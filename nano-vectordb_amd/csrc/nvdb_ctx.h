@@ -98,6 +98,11 @@ struct PqState {
   float* cent = nullptr;                           // [nparts][dim] f32
   uint32_t* off = nullptr;                         // [nparts + 1]
   DevBuf base;                                     // [(probed partition, query) pairs of a sub-batch] f32 base terms, grow-only
+  // a shadow under an OPQ rotation (nvdb_hip_pq_build_opq; kernels_pq_rotate.h): the codes are those of A e, the codebooks live in
+  // the rotated space; the shadow's own device copies of the matrix and its transpose, freed with it
+  float* rot = nullptr;                            // A [dim][dim] f32, nullptr: no rotation
+  float* rot_t = nullptr;                          // A^T [dim][dim] f32 (reconstruction)
+  DevBuf qrot;                                     // [queries of a sub-batch][dim] f32: A q, grow-only
 };
 
 }  // namespace nvdbhip

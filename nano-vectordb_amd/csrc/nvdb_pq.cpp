@@ -19,13 +19,19 @@
 // the any-k plan's words in the image, pq_base_kernel writes b(q, p) = q . c[p] per (probed partition, query) pair between tables
 // and scan, and pq_scan_resid_kernel adds the pair's term at the sink.  The residual trainer swaps the gather for
 // pq_resid_gather_kernel and shares everything behind it.  nvdb_hip_set_partitions / _set_centroids free such a shadow.
-// Entry points: nvdb_hip_pq_train / _build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf and
-// nvdb_hip_pq_build_residual / _train_residual / _reconstruct / _kind; the index forms (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them
-// on the index's context and map the ids.
+// A shadow under an OPQ ROTATION (nvdb_hip_pq_build_opq; kernels_pq_rotate.h) holds the codes of y = A e, e the row or its residual:
+// the build rotates a slab of rows into f32 scratch memory (pq_rotate_kernel<DT, RESID>), runs the f32 non-residual encode over the
+// slab and moves on; the trainer rotates its gathered sample the same way, in place slab by slab; a search rotates each sub-batch's
+// queries (ps->q -> pq.qrot) in front of pq_lut_kernel and nowhere else -- the coarse step, the base terms and the refine keep the
+// caller's queries --; reconstruction multiplies the codewords by A^T.  No rotation: none of these launches.
+// Entry points: nvdb_hip_pq_train / _build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf,
+// nvdb_hip_pq_build_residual / _train_residual / _reconstruct / _kind and nvdb_hip_pq_build_opq / _train_opq / _rotation /
+// _rotated_rows / _rotate; the index forms (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them on the index's context and map the ids.
 #include "nvdb_parts.h"
 #include "kernels_pq.h"
 #include "kernels_pq_resid.h"
 #include "kernels_pq_train.h"
+#include "kernels_pq_rotate.h"
 #include "ivf_layout.h"
 
 namespace nvdbhip {
@@ -39,6 +45,9 @@ void pq_drop(nvdb_hip_ctx* c) {
   if (pq->cent) (void)hipFree(pq->cent);
   if (pq->off) (void)hipFree(pq->off);
   if (pq->base.p) (void)hipFree(pq->base.p);
+  if (pq->rot) (void)hipFree(pq->rot);
+  if (pq->rot_t) (void)hipFree(pq->rot_t);
+  if (pq->qrot.p) (void)hipFree(pq->qrot.p);
   delete pq;
   c->pq = nullptr;
 }
@@ -51,17 +60,18 @@ namespace {
 
 constexpr uint32_t PARTS_STAT_PQ = 9;                                // nvdb_hip_scan_stats::path
 
+// rows / scales / n: the context's corpus, or (residual == false only) a slab of rotated f32 rows; codes: where row 0 of them goes
 template <int DT>
-nvdb_status launch_encode(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq) {
-  const dim3 grid(static_cast<unsigned>((c->n + PQ_ENC_THREADS - 1) / PQ_ENC_THREADS), pq.M / 4u);
+nvdb_status launch_encode(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, bool residual, const void* rows, const float* scales, uint64_t n, uint8_t* codes) {
+  const dim3 grid(static_cast<unsigned>((n + PQ_ENC_THREADS - 1) / PQ_ENC_THREADS), pq.M / 4u);
   auto go = [&](auto kernel) {
-    kernel<<<grid, PQ_ENC_THREADS, 0, s>>>(c->rows, c->scales, c->n, c->dim, pq.M, pq.dsub, pq.codebooks, pq.codes);
+    kernel<<<grid, PQ_ENC_THREADS, 0, s>>>(rows, scales, n, c->dim, pq.M, pq.dsub, pq.codebooks, codes);
   };
   auto go_resid = [&](auto kernel) {
-    kernel<<<grid, PQ_ENC_THREADS, 0, s>>>(c->rows, c->scales, c->n, c->dim, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, pq.cent, pq.codes);
+    kernel<<<grid, PQ_ENC_THREADS, 0, s>>>(rows, scales, n, c->dim, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, pq.cent, codes);
   };
   const uint32_t dmax = pq_encode_bound(pq.dsub);
-  if (pq.residual) {
+  if (residual) {
     switch (dmax) {
       case 4: go_resid(pq_resid_encode_kernel<DT, 4>); break;
       case 8: go_resid(pq_resid_encode_kernel<DT, 8>); break;
@@ -78,6 +88,22 @@ nvdb_status launch_encode(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq) {
   }
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
+}
+
+// Y[nrows][dim] = rows row0 .. row0 + nrows of `rows` (dtype DT; minus their lists' centroids where cent is given) times mat^T
+template <int DT>
+nvdb_status launch_rotate(nvdb_hip_ctx* c, hipStream_t s, const void* rows, const float* scales, uint64_t row0, uint32_t nrows, const float* mat,
+                          const uint32_t* off, uint32_t nparts, const float* cent, float* Y) {
+  const unsigned grid = static_cast<unsigned>(pq_rotate_grid(nrows, c->dim));
+  if (cent) pq_rotate_kernel<DT, true><<<grid, PQ_ROT_THREADS, 0, s>>>(rows, scales, row0, nrows, c->dim, mat, off, nparts, cent, Y);
+  else pq_rotate_kernel<DT, false><<<grid, PQ_ROT_THREADS, 0, s>>>(rows, scales, row0, nrows, c->dim, mat, nullptr, 0u, nullptr, Y);
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+// f32 rows already on the device (queries, a gathered sample, codewords side by side)
+nvdb_status launch_rotate_f32(nvdb_hip_ctx* c, hipStream_t s, const float* X, uint32_t nrows, const float* mat, float* Y) {
+  return launch_rotate<DT_F32>(c, s, X, nullptr, 0, nrows, mat, nullptr, 0u, nullptr, Y);
 }
 
 // what the residual calls need of the context: a partition table and centroids; 0: fine
@@ -151,8 +177,9 @@ nvdb_status launch_train_iteration(nvdb_hip_ctx* c, hipStream_t s, const float* 
 
 // the call proper, the arguments validated: cb (host, [M][256][dsub]) and err (host, [iters]) are this call's own and reach the caller on success only
 // residual: the training rows are the residuals to the centroids of their lists (the caller has checked resid_args)
-nvdb_status pq_train(nvdb_hip_ctx* c, bool residual, uint32_t M, uint32_t iters, uint64_t seed, uint64_t m, const float* init, std::vector<float>& cb,
-                     std::vector<double>& err) {
+// rotation (host, [dim][dim], or nullptr): the gathered rows, residual or not, become A e before anything reads them
+nvdb_status pq_train(nvdb_hip_ctx* c, bool residual, const float* rotation, uint32_t M, uint32_t iters, uint64_t seed, uint64_t m, const float* init,
+                     std::vector<float>& cb, std::vector<double>& err) {
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const uint64_t n = c->n;
@@ -182,6 +209,22 @@ nvdb_status pq_train(nvdb_hip_ctx* c, bool residual, uint32_t M, uint32_t iters,
     dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_train_gather<decltype(dt)::value>(c, s, d_idx.as<uint32_t>(), m, d_x.as<float>()); });
   }
   if (st) return st;
+  if (rotation) {
+    // in place, slab by slab through scratch memory: the f32 build of the product, then the slab copied back over its rows
+    const uint64_t slab = std::min<uint64_t>(m, pq_rotate_slab_rows(dim));
+    TrainMem d_rot, d_y;
+    if ((st = train_alloc(c, d_rot, static_cast<size_t>(dim) * dim * 4)) || (st = train_alloc(c, d_y, slab * dim * 4))) return st;
+    HIPCHK(c, hipMemcpyAsync(d_rot.p, rotation, static_cast<size_t>(dim) * dim * 4, hipMemcpyHostToDevice, s));
+    for (uint64_t r = 0; r < m && !st; r += slab) {
+      const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(slab, m - r));
+      float* x = d_x.as<float>() + r * dim;
+      if ((st = launch_rotate_f32(c, s, x, nr, d_rot.as<float>(), d_y.as<float>()))) break;
+      if (hipMemcpyAsync(x, d_y.p, static_cast<size_t>(nr) * dim * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) st = fail(c, NVDB_ERR_HIP, "pq_train: copy of a rotated slab");
+    }
+    const hipError_t e = hipStreamSynchronize(s);                      // (before the matrix and the slab leave scope, whatever happened)
+    if (!st && e != hipSuccess) st = fail(c, NVDB_ERR_HIP, std::string("pq_train: ") + hipGetErrorString(e));
+    if (st) return st;
+  }
 
   if (init) {
     HIPCHK(c, hipMemcpyAsync(d_cb.p, init, cb_bytes, hipMemcpyHostToDevice, s));
@@ -303,6 +346,8 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
         pp.extra = sub.extra.data(); pp.extra_words = static_cast<uint32_t>(sub.extra.size());
         if (nvdb_status e = ensure(c, pq.base, static_cast<size_t>(pp.wl.npairs) * 4)) return e;
       }
+      if (pq.rot)
+        if (nvdb_status e = ensure(c, pq.qrot, static_cast<size_t>(b) * c->dim * 4)) return e;
       return ensure(c, pq.lut, b * pq_lut_bytes(pq.M));
     });
     if (st) return st;
@@ -316,7 +361,13 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
       q0 = q1;
       continue;
     }
-    pq_lut_kernel<<<dim3(pq.M / 4u, b), 256, 0, s>>>(static_cast<const float*>(ps->q.p), c->dim, pq.M, pq.dsub, pq.codebooks, static_cast<float*>(pq.lut.p));
+    // the tables' queries: the sub-batch's own, or -- a rotated shadow -- A q (the base terms and the refine below keep ps->q)
+    const float* lut_q = static_cast<const float*>(ps->q.p);
+    if (pq.rot) {
+      if ((st = launch_rotate_f32(c, s, lut_q, b, pq.rot, static_cast<float*>(pq.qrot.p)))) return st;
+      lut_q = static_cast<const float*>(pq.qrot.p);
+    }
+    pq_lut_kernel<<<dim3(pq.M / 4u, b), 256, 0, s>>>(lut_q, c->dim, pq.M, pq.dsub, pq.codebooks, static_cast<float*>(pq.lut.p));
     HIPCHK(c, hipGetLastError());
     if (pq.residual) {
       pq_base_kernel<<<nparts, PQ_BASE_THREADS, 0, s>>>(static_cast<const float*>(ps->q.p), c->dim, pq.cent, p.im.extra + pstart_at, p.im.qidx,
@@ -371,10 +422,12 @@ nvdb_status pq_search_args(nvdb_hip_ctx* c, const char* who, bool ivf, const flo
 }
 
 // nvdb_hip_pq_build / nvdb_hip_pq_build_residual: on any failure nothing has changed
-nvdb_status pq_build(nvdb_hip_ctx* c, const char* who, bool residual, const float* codebooks, uint32_t M) {
+// opq: the codes are cut from A e (rotation: host, [dim][dim]); else rotation is not looked at
+nvdb_status pq_build(nvdb_hip_ctx* c, const char* who, bool residual, const float* codebooks, uint32_t M, bool opq = false, const float* rotation = nullptr) {
   if (!c) return NVDB_ERR_INVALID;
   const std::string w = std::string(who) + ": ";
   if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
+  if (opq && !rotation) return fail(c, NVDB_ERR_INVALID, w + "null rotation");
   if (!codebooks) return fail(c, NVDB_ERR_INVALID, w + "null codebooks");
   bool unsupported = false;
   if (const char* why = pq_shape_check(c->dim, M, unsupported)) return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, w + why);
@@ -401,16 +454,42 @@ nvdb_status pq_build(nvdb_hip_ctx* c, const char* who, bool residual, const floa
     if (e == hipSuccess) e = hipMemcpy(fresh.off, off.data(), off.size() * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpyAsync(fresh.cent, c->parts->coarse->rows, cent_bytes, hipMemcpyDeviceToDevice, s);
   }
+  TrainMem d_slab;                                                     // a rotated build's f32 rows, a slab at a time; lives as long as the call
+  const uint64_t slab = std::min<uint64_t>(c->n, pq_rotate_slab_rows(c->dim));
+  if (opq) {
+    // the shadow's own copies of A and of A^T (transposed here, once)
+    const size_t d = c->dim, rot_bytes = d * d * 4;
+    std::vector<float> at(d * d);
+    for (size_t i = 0; i < d; ++i)
+      for (size_t t = 0; t < d; ++t) at[t * d + i] = rotation[i * d + t];
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.rot), rot_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.rot_t), rot_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_slab.p, slab * d * 4);
+    if (e == hipSuccess) e = hipMemcpy(fresh.rot, rotation, rot_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(fresh.rot_t, at.data(), rot_bytes, hipMemcpyHostToDevice);
+  }
   nvdb_status st = NVDB_OK;
   if (e != hipSuccess) st = fail(c, NVDB_ERR_HIP, w + hipGetErrorString(e));
-  if (!st) dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_encode<decltype(dt)::value>(c, s, fresh); });
+  if (!st && !opq)
+    dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_encode<decltype(dt)::value>(c, s, fresh, residual, c->rows, c->scales, c->n, fresh.codes); });
+  // rotated: per slab the product into the scratch rows, then the f32 non-residual encode over them (the centroid is gone already)
+  for (uint64_t r = 0; opq && !st && r < c->n; r += slab) {
+    const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(slab, c->n - r));
+    dispatch_dtype(c->dtype, st, [&](auto dt) {
+      return launch_rotate<decltype(dt)::value>(c, s, c->rows, c->scales, r, nr, fresh.rot, fresh.off, fresh.nparts, residual ? fresh.cent : nullptr, d_slab.as<float>());
+    });
+    if (!st) st = launch_encode<DT_F32>(c, s, fresh, false, d_slab.p, nullptr, nr, fresh.codes + r * M);
+  }
   if (!st && (e = hipStreamSynchronize(s)) != hipSuccess) st = fail(c, NVDB_ERR_HIP, w + hipGetErrorString(e));
   if (st) {                                                            // nothing changed: an earlier build stands
+    if (opq) (void)hipStreamSynchronize(s);                            // (before the slab leaves scope)
     (void)hipGetLastError();
     if (fresh.codebooks) (void)hipFree(fresh.codebooks);
     if (fresh.codes) (void)hipFree(fresh.codes);
     if (fresh.off) (void)hipFree(fresh.off);
     if (fresh.cent) (void)hipFree(fresh.cent);
+    if (fresh.rot) (void)hipFree(fresh.rot);
+    if (fresh.rot_t) (void)hipFree(fresh.rot_t);
     return st;
   }
   pq_drop(c);
@@ -420,9 +499,10 @@ nvdb_status pq_build(nvdb_hip_ctx* c, const char* who, bool residual, const floa
 
 // nvdb_hip_pq_train / nvdb_hip_pq_train_residual behind one set of checks
 nvdb_status pq_train_call(nvdb_hip_ctx* c, const char* who, bool residual, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init,
-                          float* out_codebooks, double* out_err) {
+                          float* out_codebooks, double* out_err, bool opq = false, const float* rotation = nullptr) {
   if (!c) return NVDB_ERR_INVALID;
   const std::string w = std::string(who) + ": ";
+  if (opq && !rotation) return fail(c, NVDB_ERR_INVALID, w + "null rotation");
   if (!out_codebooks) return fail(c, NVDB_ERR_INVALID, w + "null output");
   if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
   bool unsupported = false;
@@ -434,7 +514,7 @@ nvdb_status pq_train_call(nvdb_hip_ctx* c, const char* who, bool residual, uint3
   if (m > IVF_MAX_ROWS) return fail(c, NVDB_ERR_UNSUPPORTED, w + "training set too large (max_train_rows)");
   std::vector<float> cb(static_cast<size_t>(M) * PQ_KSUB * (c->dim / M));
   std::vector<double> err(iters);
-  if (nvdb_status st = pq_train(c, residual, M, iters, seed, m, init, cb, err)) {
+  if (nvdb_status st = pq_train(c, residual, opq ? rotation : nullptr, M, iters, seed, m, init, cb, err)) {
     (void)hipGetLastError();
     return st;
   }
@@ -462,6 +542,72 @@ nvdb_status nvdb_hip_pq_train_residual(nvdb_hip_ctx* c, uint32_t M, uint32_t ite
   return pq_train_call(c, "pq_train_residual", true, M, iters, seed, max_train_rows, init, out_codebooks, out_err);
 }
 
+nvdb_status nvdb_hip_pq_build_opq(nvdb_hip_ctx* c, const float* rotation, const float* codebooks, uint32_t M, uint32_t residual) {
+  return pq_build(c, "pq_build_opq", residual != 0, codebooks, M, true, rotation);
+}
+
+nvdb_status nvdb_hip_pq_train_opq(nvdb_hip_ctx* c, const float* rotation, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init,
+                                  float* out_codebooks, double* out_err, uint32_t residual) {
+  return pq_train_call(c, "pq_train_opq", residual != 0, M, iters, seed, max_train_rows, init, out_codebooks, out_err, true, rotation);
+}
+
+nvdb_status nvdb_hip_pq_rotation(nvdb_hip_ctx* c, uint32_t* rotated, float* out) {
+  if (!c) return NVDB_ERR_INVALID;
+  const bool have = c->pq && c->pq->rot;
+  if (rotated) *rotated = have ? 1u : 0u;
+  if (have && out) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->pq->rot, static_cast<size_t>(c->dim) * c->dim * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_pq_rotated_rows(nvdb_hip_ctx* c, uint64_t row0, uint64_t nrows, float* out) {
+  if (nvdb_status st = pq_args(c, "pq_rotated_rows")) return st;
+  if (!c->pq->rot) return fail(c, NVDB_ERR_INVALID, "pq_rotated_rows: the shadow has no rotation: nvdb_hip_pq_build_opq");
+  if (row0 > c->n || nrows > c->n - row0) return fail(c, NVDB_ERR_INVALID, "pq_rotated_rows: row0 + nrows > n");
+  if (nrows == 0) return NVDB_OK;
+  if (!out) return fail(c, NVDB_ERR_INVALID, "pq_rotated_rows: null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  const PqState& pq = *c->pq;
+  const uint64_t step = std::min<uint64_t>(nrows, pq_reconstruct_rows(c->dim));
+  TrainMem d_y;
+  if (nvdb_status st = train_alloc(c, d_y, step * c->dim * 4)) return st;
+  for (uint64_t r = 0; r < nrows; r += step) {
+    const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(step, nrows - r));
+    nvdb_status st = NVDB_OK;
+    dispatch_dtype(c->dtype, st, [&](auto dt) {
+      return launch_rotate<decltype(dt)::value>(c, c->stream, c->rows, c->scales, row0 + r, nr, pq.rot, pq.off, pq.nparts, pq.residual ? pq.cent : nullptr, d_y.as<float>());
+    });
+    if (st) return st;
+    HIPCHK(c, hipMemcpyAsync(out + r * c->dim, d_y.p, static_cast<size_t>(nr) * c->dim * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_pq_rotate(nvdb_hip_ctx* c, const float* x, uint64_t n, float* out) {
+  if (nvdb_status st = pq_args(c, "pq_rotate")) return st;
+  if (!c->pq->rot) return fail(c, NVDB_ERR_INVALID, "pq_rotate: the shadow has no rotation: nvdb_hip_pq_build_opq");
+  if (n == 0) return NVDB_OK;
+  if (!x || !out) return fail(c, NVDB_ERR_INVALID, x ? "pq_rotate: null output" : "pq_rotate: null vectors");
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t step = std::min<uint64_t>(n, pq_reconstruct_rows(c->dim));
+  const size_t bytes = step * c->dim * 4;
+  TrainMem d_x, d_y;
+  nvdb_status st;
+  if ((st = train_alloc(c, d_x, bytes)) || (st = train_alloc(c, d_y, bytes))) return st;
+  for (uint64_t r = 0; r < n; r += step) {
+    const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(step, n - r));
+    HIPCHK(c, hipMemcpyAsync(d_x.p, x + r * c->dim, static_cast<size_t>(nr) * c->dim * 4, hipMemcpyHostToDevice, c->stream));
+    if ((st = launch_rotate_f32(c, c->stream, d_x.as<float>(), nr, c->pq->rot, d_y.as<float>()))) return st;
+    HIPCHK(c, hipMemcpyAsync(out + r * c->dim, d_y.p, static_cast<size_t>(nr) * c->dim * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return NVDB_OK;
+}
+
 nvdb_status nvdb_hip_pq_kind(nvdb_hip_ctx* c, uint32_t* residual) {
   if (!c) return NVDB_ERR_INVALID;
   if (residual) *residual = (c->pq && c->pq->residual) ? 1u : 0u;
@@ -477,15 +623,25 @@ nvdb_status nvdb_hip_pq_reconstruct(nvdb_hip_ctx* c, uint64_t row0, uint64_t nro
   HIPCHK(c, hipSetDevice(c->device));
   const PqState& pq = *c->pq;
   const uint64_t step = std::min<uint64_t>(nrows, pq_reconstruct_rows(c->dim));
-  TrainMem d_y;
+  TrainMem d_y, d_x;                                                   // d_x: a rotated shadow's rows back in the corpus' space
   if (nvdb_status st = train_alloc(c, d_y, step * c->dim * 4)) return st;
+  if (pq.rot)
+    if (nvdb_status st = train_alloc(c, d_x, step * c->dim * 4)) return st;
   for (uint64_t r = 0; r < nrows; r += step) {
     const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(step, nrows - r));
     const unsigned grid = std::min<unsigned>((nr + 3u) / 4u, static_cast<unsigned>(c->num_cu) * 64u);
-    pq_reconstruct_kernel<<<grid, 256, 0, c->stream>>>(pq.codes, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, pq.residual ? pq.cent : nullptr,
+    // a rotated shadow: the codewords side by side, times A^T, and only then the centroid
+    pq_reconstruct_kernel<<<grid, 256, 0, c->stream>>>(pq.codes, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, pq.residual && !pq.rot ? pq.cent : nullptr,
                                                        static_cast<uint32_t>(row0 + r), nr, d_y.as<float>());
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out + r * c->dim, d_y.p, static_cast<size_t>(nr) * c->dim * 4, hipMemcpyDeviceToHost, c->stream));
+    if (pq.rot) {
+      if (nvdb_status st = launch_rotate_f32(c, c->stream, d_y.as<float>(), nr, pq.rot_t, d_x.as<float>())) return st;
+      if (pq.residual) {
+        pq_rotate_add_cent_kernel<<<grid, 256, 0, c->stream>>>(d_x.as<float>(), static_cast<uint32_t>(row0 + r), nr, c->dim, pq.off, pq.nparts, pq.cent);
+        HIPCHK(c, hipGetLastError());
+      }
+    }
+    HIPCHK(c, hipMemcpyAsync(out + r * c->dim, pq.rot ? d_x.p : d_y.p, static_cast<size_t>(nr) * c->dim * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return NVDB_OK;

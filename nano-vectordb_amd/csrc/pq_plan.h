@@ -55,6 +55,26 @@ constexpr uint64_t pq_reconstruct_rows(uint32_t dim) {
   return r < 1 ? 1 : r;
 }
 
+// ---- OPQ rotations (kernels_pq_rotate.h): Y[rows][dim] = E[rows][dim] . A^T on the fp32 matrix cores
+// THE tile cut: a workgroup of 8 waves owns 256 rows x 128 output columns (a wave: 64 x 64, 16 accumulator tiles), K in slices of
+// 16 through LDS.  Operand traffic through L2 and LDS is n * dim^2 * 4 * (1 / 256 + 1 / 128) bytes: 277 GB at 10M x 768, against
+// 737 GB at 64 x 64; the MFMA time of 2 * n * dim^2 flop at 157 TFLOP/s is 75 ms there, so the tile has to stage 3.7 TB/s over 256
+// CUs to hide under it: 6 bytes per CU and clock at 2.4 GHz (64 x 64: 16), where a CU's LDS takes 128.
+constexpr uint32_t PQ_ROT_TR = 256;                 // rows per workgroup tile
+constexpr uint32_t PQ_ROT_TC = 128;                 // output columns per workgroup tile (a column panel of the matrix)
+constexpr uint32_t PQ_ROT_KS = 16;                  // K elements per LDS slice: four MFMA K-steps
+
+// workgroups of one launch over nrows rows: row tiles x column panels, the panel varying fastest
+constexpr uint64_t pq_rotate_grid(uint64_t nrows, uint32_t dim) {
+  return ((nrows + PQ_ROT_TR - 1) / PQ_ROT_TR) * ((dim + PQ_ROT_TC - 1) / PQ_ROT_TC);
+}
+// rows one slab of rotated f32 rows holds (the build and the trainer rotate slab by slab into scratch memory that lives inside the
+// call): at most 256 MB, whole row tiles, at least one; at dim >= 4 a slab's grid stays below 2^17 workgroups
+constexpr uint64_t pq_rotate_slab_rows(uint32_t dim) {
+  const uint64_t r = (256ull << 20) / (static_cast<uint64_t>(dim) * 4) / PQ_ROT_TR * PQ_ROT_TR;
+  return r < PQ_ROT_TR ? PQ_ROT_TR : r;
+}
+
 // a lane reads its row's codes in 16-byte pieces where a row is whole pieces, else in dwords (M % 4 == 0 always)
 constexpr bool pq_wide_codes(uint32_t M) { return M % 16 == 0; }
 

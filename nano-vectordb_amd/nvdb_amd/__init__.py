@@ -47,6 +47,8 @@ EXPORTS = [
     "nvdb_hip_pq_train", "nvdb_hip_ivf_pq_train",
     "nvdb_hip_pq_build_residual", "nvdb_hip_pq_train_residual", "nvdb_hip_pq_kind", "nvdb_hip_pq_reconstruct",
     "nvdb_hip_ivf_pq_build_residual", "nvdb_hip_ivf_pq_train_residual",
+    "nvdb_hip_pq_build_opq", "nvdb_hip_pq_train_opq", "nvdb_hip_pq_rotation", "nvdb_hip_pq_rotated_rows", "nvdb_hip_pq_rotate",
+    "nvdb_hip_ivf_pq_build_opq", "nvdb_hip_ivf_pq_train_opq",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -229,6 +231,13 @@ def _bind(L, dev):
     L.nvdb_hip_ivf_pq_build_residual.argtypes = [vp, vp, u32]
     L.nvdb_hip_pq_train_residual.argtypes = [vp, u32, u32, u64, u64, vp, vp, vp]
     L.nvdb_hip_ivf_pq_train_residual.argtypes = [vp, u32, u32, u64, u64, vp, vp, vp]
+    L.nvdb_hip_pq_build_opq.argtypes = [vp, vp, vp, u32, u32]
+    L.nvdb_hip_ivf_pq_build_opq.argtypes = [vp, vp, vp, u32, u32]
+    L.nvdb_hip_pq_train_opq.argtypes = [vp, vp, u32, u32, u64, u64, vp, vp, vp, u32]
+    L.nvdb_hip_ivf_pq_train_opq.argtypes = [vp, vp, u32, u32, u64, u64, vp, vp, vp, u32]
+    L.nvdb_hip_pq_rotation.argtypes = [vp, C.POINTER(u32), vp]
+    L.nvdb_hip_pq_rotated_rows.argtypes = [vp, u64, u64, vp]
+    L.nvdb_hip_pq_rotate.argtypes = [vp, vp, u64, vp]
     L.nvdb_hip_pq_kind.argtypes = [vp, C.POINTER(u32)]
     L.nvdb_hip_pq_reconstruct.argtypes = [vp, u64, u64, vp]
     L.nvdb_hip_pq_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
@@ -382,15 +391,39 @@ def _mask_of_arg(mask_of, nq):
     return np.ascontiguousarray(np.broadcast_to(np.asarray(mask_of, dtype=np.uint32), (nq,)))
 
 
-def _pq_train(owner, fn, dim, M, iters, seed, max_train_rows, init, want_err):
-    """HipContext.pq_train / IvfIndex.pq_train: fn is the entry point for owner.h.  A bad M reaches the library (dsub 1 stands in)."""
+def _rotation_arg(rotation, dim):
+    rotation = np.ascontiguousarray(rotation, dtype=np.float32)
+    if rotation.shape != (dim, dim):
+        raise ValueError("rotation must be [dim, dim]")
+    return rotation
+
+
+def _pq_build(owner, plain, resid, opq, dim, codebooks, residual, rotation):
+    """HipContext.pq_build / IvfIndex.pq_build: the entry points for owner.h without and with a rotation."""
+    codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
+    if codebooks.ndim != 3 or codebooks.shape[1] != 256:
+        raise ValueError("codebooks must be [M, 256, dim / M]")
+    if rotation is None:
+        owner._chk((resid if residual else plain)(owner.h, codebooks.ctypes.data, codebooks.shape[0]))
+    else:
+        rotation = _rotation_arg(rotation, dim)
+        owner._chk(opq(owner.h, rotation.ctypes.data, codebooks.ctypes.data, codebooks.shape[0], 1 if residual else 0))
+
+
+def _pq_train(owner, fn, dim, M, iters, seed, max_train_rows, init, want_err, rotation=None, residual=False):
+    """HipContext.pq_train / IvfIndex.pq_train: fn is the entry point for owner.h (the _opq one where rotation is given).  A bad M
+    reaches the library (dsub 1 stands in)."""
     dsub = dim // M if M and dim % M == 0 else 1
     if init is not None:
         init = np.ascontiguousarray(init, dtype=np.float32).reshape(M, 256, dsub)
     out = np.zeros((M, 256, dsub), dtype=np.float32)
     err = np.zeros(iters, dtype=np.float64)
-    owner._chk(fn(owner.h, M, iters, seed, max_train_rows, init.ctypes.data if init is not None else None, out.ctypes.data,
-                  err.ctypes.data if want_err and iters else None))
+    args = (M, iters, seed, max_train_rows, init.ctypes.data if init is not None else None, out.ctypes.data,
+            err.ctypes.data if want_err and iters else None)
+    if rotation is None:
+        owner._chk(fn(owner.h, *args))
+    else:
+        owner._chk(fn(owner.h, _rotation_arg(rotation, dim).ctypes.data, *args, 1 if residual else 0))
     return (out, err) if want_err else out
 
 
@@ -712,22 +745,50 @@ class HipContext:
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
     # -- PQ candidate scan (a PQ shadow of the resident corpus under the caller's codebooks; stats path 9)
-    def pq_build(self, codebooks, residual=False):
+    def pq_build(self, codebooks, residual=False, rotation=None):
         """Encode the resident rows under codebooks [M, 256, dim / M] f32 (nearest codeword by squared L2, ties to the lowest).
         residual: encode every row's residual to the centroid of its list (needs set_partitions and set_centroids, which free
-        such a shadow when called again); the searches answer from whichever shadow the context holds."""
-        codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
-        if codebooks.ndim != 3 or codebooks.shape[1] != 256:
-            raise ValueError("codebooks must be [M, 256, dim / M]")
-        fn = self.lib.nvdb_hip_pq_build_residual if residual else self.lib.nvdb_hip_pq_build
-        self._chk(fn(self.h, codebooks.ctypes.data, codebooks.shape[0]))
+        such a shadow when called again); the searches answer from whichever shadow the context holds.
+        rotation: an OPQ matrix A [dim, dim] f32 -- the codes are cut from A e, the codebooks live in the rotated space, and the
+        searches rotate their queries; the scores approximate q . x only where A^T A = I (not checked)."""
+        _pq_build(self, self.lib.nvdb_hip_pq_build, self.lib.nvdb_hip_pq_build_residual, self.lib.nvdb_hip_pq_build_opq,
+                  self.corpus_info()["dim"] if rotation is not None else 0, codebooks, residual, rotation)
 
-    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False):
+    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False, rotation=None):
         """Codebooks [M, 256, dim / M] f32 by Lloyd's iteration over the resident rows on the device (init None: 256 drawn training
         rows per sub-quantiser); with want_err also the [iters] f64 mean winning distances.  residual: over the rows' residuals to
-        their lists' centroids.  Does not build: pq_build(result, residual)."""
-        fn = self.lib.nvdb_hip_pq_train_residual if residual else self.lib.nvdb_hip_pq_train
-        return _pq_train(self, fn, self.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err)
+        their lists' centroids.  rotation: over the rotated training rows.  Does not build: pq_build(result, residual, rotation)."""
+        fn = self.lib.nvdb_hip_pq_train_opq if rotation is not None else self.lib.nvdb_hip_pq_train_residual if residual else self.lib.nvdb_hip_pq_train
+        return _pq_train(self, fn, self.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err, rotation, residual)
+
+    def pq_rotation(self):
+        """The matrix [dim, dim] f32 the shadow was built under, or None (no shadow, or one without a rotation)."""
+        r = C.c_uint32()
+        self._chk(self.lib.nvdb_hip_pq_rotation(self.h, C.byref(r), None))
+        if not r.value:
+            return None
+        dim = self.corpus_info()["dim"]
+        out = np.zeros((dim, dim), dtype=np.float32)
+        self._chk(self.lib.nvdb_hip_pq_rotation(self.h, None, out.ctypes.data))
+        return out
+
+    def pq_rotate(self, x):
+        """A x for host vectors [n, dim] f32 -> [n, dim] f32: exactly what the searches do to their queries."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        out = np.zeros_like(x)
+        self._chk(self.lib.nvdb_hip_pq_rotate(self.h, x.ctypes.data if x.size else None, x.shape[0], out.ctypes.data if x.size else None))
+        return out
+
+    def pq_rotated_rows(self, row0=0, nrows=None):
+        """Resident rows [row0, row0 + nrows) as the rotated shadow's encode saw them -> [nrows, dim] f32: A e, e the row or its residual."""
+        info = self.corpus_info()
+        if nrows is None:
+            nrows = info["n"] - row0
+        out = np.zeros((max(nrows, 0), info["dim"]), dtype=np.float32)
+        self._chk(self.lib.nvdb_hip_pq_rotated_rows(self.h, row0, nrows, out.ctypes.data if out.size else None))
+        return out
 
     def pq_kind(self):
         """dict(residual): True where the context holds a residual shadow."""
@@ -994,19 +1055,29 @@ class IvfIndex:
         return (ids, scores, counts, probe) if want_probe else (ids, scores, counts)
 
     # -- PQ candidate scan on the index's context, answered in the source corpus' ids
-    def pq_build(self, codebooks, residual=False):
+    def pq_build(self, codebooks, residual=False, rotation=None):
         """HipContext.pq_build over the list-ordered rows (residual: against the index's lists and centroids); compact() and
         add_rows() free the codes."""
-        codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
-        if codebooks.ndim != 3 or codebooks.shape[1] != 256:
-            raise ValueError("codebooks must be [M, 256, dim / M]")
-        fn = self.lib.nvdb_hip_ivf_pq_build_residual if residual else self.lib.nvdb_hip_ivf_pq_build
-        self._chk(fn(self.h, codebooks.ctypes.data, codebooks.shape[0]))
+        _pq_build(self, self.lib.nvdb_hip_ivf_pq_build, self.lib.nvdb_hip_ivf_pq_build_residual, self.lib.nvdb_hip_ivf_pq_build_opq,
+                  self.ctx.corpus_info()["dim"] if rotation is not None else 0, codebooks, residual, rotation)
 
-    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False):
+    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False, rotation=None):
         """HipContext.pq_train over the list-ordered rows."""
-        fn = self.lib.nvdb_hip_ivf_pq_train_residual if residual else self.lib.nvdb_hip_ivf_pq_train
-        return _pq_train(self, fn, self.ctx.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err)
+        lib = self.lib
+        fn = lib.nvdb_hip_ivf_pq_train_opq if rotation is not None else lib.nvdb_hip_ivf_pq_train_residual if residual else lib.nvdb_hip_ivf_pq_train
+        return _pq_train(self, fn, self.ctx.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err, rotation, residual)
+
+    def pq_rotation(self):
+        """HipContext.pq_rotation of the index's context."""
+        return self.ctx.pq_rotation()
+
+    def pq_rotate(self, x):
+        """HipContext.pq_rotate of the index's context."""
+        return self.ctx.pq_rotate(x)
+
+    def pq_rotated_rows(self, row0=0, nrows=None):
+        """HipContext.pq_rotated_rows over the list-ordered rows (positions, not source ids)."""
+        return self.ctx.pq_rotated_rows(row0, nrows)
 
     def pq_kind(self):
         """HipContext.pq_kind of the index's context."""

@@ -23,7 +23,16 @@ and ivf_pq_refine at the shapes above, recall@10 of both, the wall time of both 
 upload, allocation and the encode kernel) and the fp64 quantisation error of both over 20 blocks of 1000 rows: the mean over rows
 and sub-quantisers of |x - pq_reconstruct(x)|^2.  --clustered replaces the synthetic corpus, which has no cluster structure, by
 seeded centre + noise rows generated on the host (nlist / 4 centres, noise 0.35 of a centre's element scale, every row scaled
-to unit length as the index's spherical k-means expects), labelled as such."""
+to unit length as the index's spherical k-means expects), labelled as such.
+
+    python tools_dev/bench_pq.py [the same arguments] --opq [--clustered | --decay]
+
+A shadow without a rotation beside one under an OPQ ROTATION, two copies of the same index as above.  The rotation is learnt here,
+in numpy, over 20000 rows sampled through the library: four alternations of pq_train(rotation=A) and pq_build(rotation=A) on the
+device, yhat from the codes, A <- U V^T of the SVD of sum yhat x^T (learn_rotation).  Reports the wall time of both builds, their
+difference against 2 n dim^2 flop at the 157 TFLOP/s of the fp32 matrix cores, the fp64 quantisation error of both, and, alternating
+the two copies call by call, ivf_pq_search / ivf_pq_refine times and recall@10.  --decay: unit rows of one Gaussian whose
+per-dimension deviation falls as 1 / sqrt(1 + t / 8), t the dimension."""
 import json
 import os
 import sys
@@ -142,6 +151,95 @@ def main_residual(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, clust
         ix.close()
 
 
+def learn_rotation(sctx, sample, M, rounds, alternations, residual=False):
+    """OPQ's alternation in numpy over a sample context: codebooks and codes under A on the device (pq_train / pq_build with
+    rotation=A), yhat from the codes, A <- U V^T of the SVD of sum yhat x^T (orthonormal by construction).  Starts from I."""
+    dim = sample.shape[1]
+    A = np.eye(dim, dtype=np.float32)
+    x64 = sample.astype(np.float64)
+    for _ in range(alternations):
+        cb = sctx.pq_train(M, rounds, 7, rotation=A, residual=residual)
+        sctx.pq_build(cb, rotation=A, residual=residual)
+        yhat = cb[np.arange(M), sctx.pq_download_codes()].reshape(len(sample), dim).astype(np.float64)
+        u, _, vt = np.linalg.svd(yhat.T @ x64)
+        A = np.ascontiguousarray((u @ vt).astype(np.float32))
+    return A
+
+
+def main_opq(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, corpus):
+    seed, K, rounds = 20240613, 10, 4
+    out = dict(mode="opq", corpus=corpus, rows=rows, dim=dim, dtype=dname, nlist=nlist, M=M, batch=batch, calls=calls, warmup=warmup, K=K)
+    src = nvdb_amd.HipContext(0)
+    rs = np.random.RandomState(11)
+    if corpus == "synthetic":
+        src.generate_corpus(seed, rows, dim, dtype)
+        q = np.ascontiguousarray(nvdb_amd.synth_rows_f32(seed + 1, 0, batch, dim))
+    else:
+        # clustered: main_residual's centre + noise rows; decay: one Gaussian whose per-dimension deviation falls as 1 / sqrt(1 + t / 8),
+        # t the dimension -- the first sub-vectors carry most of the variance, which is what a rotation can balance
+        centres = rs.standard_normal((max(nlist // 4, 1), dim)).astype(np.float32)
+        sigma = (1.0 / np.sqrt(1.0 + np.arange(dim) / 8.0)).astype(np.float32)
+        x = np.empty((rows, dim), dtype=np.float16 if dtype == nvdb_amd.DT_F16 else np.float32)
+        for i in range(0, rows, 65536):
+            n = min(65536, rows - i)
+            g = rs.standard_normal((n, dim)).astype(np.float32)
+            v = centres[rs.randint(len(centres), size=n)] + 0.35 * g if corpus == "clustered" else g * sigma
+            x[i:i + n] = v / np.linalg.norm(v, axis=1, keepdims=True)
+        src.upload_corpus(x.view(np.uint16) if dtype == nvdb_amd.DT_F16 else x, dtype)
+        q = np.ascontiguousarray(x[rs.choice(rows, batch, replace=False)].astype(np.float32) + 0.1 * rs.standard_normal((batch, dim)).astype(np.float32))
+        del x
+    fid, _ = src.search_batch(q, 1024)
+    want, _ = src.refine_l2_topk(q, fid.astype(np.uint32), K)
+    want = want.astype(np.uint64)
+    cents = src.train_centroids(nlist, 2, seed, max_train_rows=262144)
+    ixs = {False: nvdb_amd.IvfIndex(src, cents), True: nvdb_amd.IvfIndex(src, cents)}
+    src.close()
+    ix = ixs[True]
+    # the rotation: learnt over 20000 list-ordered rows sampled through the library
+    pick = np.arange(20000, dtype=np.int64) * rows // 20000
+    raw = np.concatenate([ix.ctx.download_rows(int(r), 1)[0] for r in pick])
+    sample = (raw.view(np.float16) if dtype == nvdb_amd.DT_F16 else raw).astype(np.float32)
+    sctx = nvdb_amd.HipContext(0)
+    sctx.upload_corpus(raw, dtype)
+    t0 = time.perf_counter()
+    A = learn_rotation(sctx, sample, M, rounds, 4)
+    out["learn_rotation_s"] = time.perf_counter() - t0
+    sctx.close()
+    out["orthonormality"] = float(np.abs(A.astype(np.float64) @ A.astype(np.float64).T - np.eye(dim)).max())
+    blocks = np.sort(rs.choice(rows - 1000, 20, replace=False))
+    for rotated, ix in ixs.items():
+        rot = A if rotated else None
+        cb = ix.pq_train(M, rounds, 7, max_train_rows=20000, rotation=rot)
+        build_s, build_all = median_s(lambda: ix.pq_build(cb, rotation=rot), reps=3)
+        err = 0.0
+        for b in blocks:
+            raw = ix.ctx.download_rows(int(b), 1000)[0]
+            xs = (raw.view(np.float16) if dtype == nvdb_amd.DT_F16 else raw).astype(np.float64)
+            err += ((xs - ix.pq_reconstruct(int(b), 1000).astype(np.float64)) ** 2).sum()
+        name = "opq" if rotated else "plain"
+        out[name] = dict(pq_build_s=build_s, pq_build_all_s=build_all, quant_err=err / (len(blocks) * 1000 * M))
+        print(f"{name:5s}: pq_build {build_s:.3f} s (median of 3), fp64 quantisation error {err / (len(blocks) * 1000 * M):.6e}")
+    ideal = 2.0 * rows * dim * dim / 157e12
+    extra = out["opq"]["pq_build_s"] - out["plain"]["pq_build_s"]
+    out["rotate"] = dict(mfma_bound_s=ideal, build_difference_s=extra, bound_over_difference=ideal / extra if extra > 0 else None)
+    print(f"rotation inside the build: opq - plain = {extra:.3f} s (the product, the slab, and an encode that reads f32 rows) against "
+          f"2 n dim^2 / 157 TFLOP/s = {ideal:.3f} s: {ideal / extra if extra > 0 else float('nan'):.3f} of the matrix cores' peak")
+    a, b = ixs[False], ixs[True]
+    for nprobe in (8, 32):
+        for R in (100, 1024):
+            key = f"nprobe={nprobe} R={R}"
+            pa, pb, *spread = alternate_ms(lambda: a.pq_search(q, R, nprobe), lambda: b.pq_search(q, R, nprobe), calls, warmup)
+            fa, fb, *fspread = alternate_ms(lambda: a.pq_refine(q, K, R, nprobe), lambda: b.pq_refine(q, K, R, nprobe), calls, warmup)
+            ra, rb = recall(a.pq_refine(q, K, R, nprobe)[0], want), recall(b.pq_refine(q, K, R, nprobe)[0], want)
+            out[key] = dict(plain_search_ms=pa, opq_search_ms=pb, search_spread=spread, plain_refine_ms=fa, opq_refine_ms=fb, refine_spread=fspread,
+                            recall10_plain=ra, recall10_opq=rb)
+            print(f"{key:20s}: ivf_pq_search plain {pa:8.3f} ms | opq {pb:8.3f} ms || ivf_pq_refine plain {fa:8.3f} ms | opq {fb:8.3f} ms || "
+                  f"recall@10 plain {ra:.4f}, opq {rb:.4f}")
+    print(json.dumps(out))
+    for ix in ixs.values():
+        ix.close()
+
+
 def main():
     flags = [x for x in sys.argv[1:] if x.startswith("--")]
     a = [x for x in sys.argv[1:] if not x.startswith("--")]
@@ -154,6 +252,9 @@ def main():
     batch = int(a[5]) if len(a) > 5 else 1024
     calls = int(a[6]) if len(a) > 6 else 10
     warmup = int(a[7]) if len(a) > 7 else 2
+    if "--opq" in flags:
+        corpus = "clustered" if "--clustered" in flags else "decay" if "--decay" in flags else "synthetic"
+        return main_opq(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, corpus)
     if "--residual" in flags:
         return main_residual(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, "--clustered" in flags)
     seed, K = 20240613, 10
