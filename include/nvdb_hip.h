@@ -770,8 +770,31 @@ nvdb_status nvdb_hip_refine_l2_topk_dev(nvdb_hip_ctx* ctx, const float* dev_quer
  * The product runs on the fp32 matrix cores (v_mfma_f32_16x16x4_f32 adds its four products to the accumulator as that chain; K is
  * never split), n * dim * dim multiply-adds per build and nq * dim * dim per search.  The shadow keeps device copies of A and A^T
  * (2 * dim * dim * 4 bytes), freed with it; a build holds up to 256 MB of rotated f32 rows inside the call.
+ * 4-BIT shadows (nvdb_hip_pq4_build; the reference's PQ_BITS handed to faiss::IndexIVFPQ, FAISS "PQ96x4" beside "PQ48x8"): 16
+ * codewords per sub-quantiser, two codes to a byte.  Somewhat worse codes at equal bytes, a much cheaper scan: a table row is 16
+ * consecutive dwords, so the scan's LDS gather cannot conflict, and one query's tables are 64 * M bytes instead of M KB, so a
+ * workgroup serves 8 to 32 queries per read of a list's codes.  The arithmetic differs from the rules above only here:
+ *   shape       K = 16 codewords; M % 8 == 0, 8 <= M <= 256, dim % M == 0, else NVDB_ERR_INVALID; dim / M > 32 -> NVDB_ERR_UNSUPPORTED;
+ *               a residual shadow also needs dim <= 4096 (the base terms' kernel stages one centroid), else NVDB_ERR_UNSUPPORTED.
+ *   codes       code[r][m] < 16 by the encode rule above (fp32 sum of squared differences, t ascending; ties to the lowest j; a NaN
+ *               or +inf distance never wins; a row without a winner gets code 0), applied to the row, its residual or its rotated form.
+ *               Packed two to a byte: byte i of row r = code[r][2 * i] | code[r][2 * i + 1] << 4.  A row is M / 2 bytes, the array
+ *               [n][M / 2], row-major.
+ *   tables      L[q][m][j] for j < 16, by the fma chain above.
+ *   score       s(q, r) = sum_m L[q][m][code[r][m]], fp32, m ascending from 0; under a residual shadow the base term b(q, list(r))
+ *               by the butterfly rule above, added with one fp32 addition at the end.  A NaN score is no candidate.
+ *   rotation    rows, queries and reconstruction are rotated by the OPQ rule above.
+ *   order       score descending, then local row ascending.
+ *   reconstruct the codewords side by side; then the residual and rotation rules above.
+ * Every call that serves a shadow serves a 4-bit one: nvdb_hip_pq_info (code_bytes = n * M / 2), _download_codes ([nrows][M / 2]
+ * packed), _kind, _reconstruct, _rotation, _rotated_rows, _rotate, the searches, the fused refine and the index forms;
+ * nvdb_hip_pq_bits tells the width.  Cost: the build is n * dim * 16 fmas, a streaming kernel bounded by the rows' bytes; a search
+ * computes 64 * M bytes of tables per query, copies the tables of <= G queries per work item into LDS interleaved (G = 32 up to
+ * M = 32, 16 up to M = 72, else 8), reads M / 2 bytes per row once per group and writes 8 bytes per (row, query) as above.
  * Out of scope: cluster splitting and k-means++ starts in the trainer, L2 asymmetric-distance tables, learning the rotation, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
- * pruning inside the scan, the device group, _dev stream forms, the nvdb:: C++ host layer.
+ * pruning inside the scan, the device group, _dev stream forms, the nvdb:: C++ host layer, a 16-codeword trainer on the device
+ * (nvdb_hip_pq_train* train 256 codewords), u8-quantised tables and in-register shuffles for the 4-bit scan, code widths other
+ * than 4 and 8.
  * ------------------------------------------------------------------------------------------- */
 
 /* codebooks: [M][256][dim / M] f32, host memory.  M >= 4, M % 4 == 0, M <= 128, dim % M == 0, else NVDB_ERR_INVALID; dim / M > 32
@@ -837,15 +860,24 @@ nvdb_status nvdb_hip_pq_rotated_rows(nvdb_hip_ctx* ctx, uint64_t row0, uint64_t 
 /* out[n][dim] f32 (host) = A x for the host vectors x[n][dim] f32: exactly what the searches do to their queries.  n == 0 ->
  * NVDB_OK; null pointers, no codes, or a shadow without a rotation -> NVDB_ERR_INVALID */
 nvdb_status nvdb_hip_pq_rotate(nvdb_hip_ctx* ctx, const float* x /* [n][dim] */, uint64_t n, float* out /* [n][dim] */);
-/* every output optional; all 0 without codes.  code_bytes = n * M */
+/* One build call for every kind of 4-BIT shadow (4-BIT shadows above): codebooks [M][16][dim / M] f32 (host); rotation [dim][dim]
+ * f32 (host) or NULL: none; residual != 0: the rows' residuals are encoded, with nvdb_hip_pq_build_residual's preconditions (a
+ * partition table and centroids, else NVDB_ERR_INVALID).  Shape errors as listed above; null codebooks -> NVDB_ERR_INVALID; no
+ * corpus -> NVDB_ERR_NO_CORPUS.  Replaces an earlier shadow of either width; on any failure the earlier shadow stands. */
+nvdb_status nvdb_hip_pq4_build(nvdb_hip_ctx* ctx, const float* rotation /* [dim][dim], NULL: none */, const float* codebooks /* [M][16][dim / M] */,
+                               uint32_t M, uint32_t residual);
+/* *nbits (optional) = 0 without a shadow, otherwise its code width: 8 or 4 */
+nvdb_status nvdb_hip_pq_bits(nvdb_hip_ctx* ctx, uint32_t* nbits);
+/* every output optional; all 0 without codes.  code_bytes = n * M (a 4-bit shadow: n * M / 2) */
 nvdb_status nvdb_hip_pq_info(nvdb_hip_ctx* ctx, uint32_t* M, uint32_t* dsub, uint64_t* code_bytes);
 /* *residual (optional) = 1 where the context holds a residual shadow, 0 for a non-residual one or none */
 nvdb_status nvdb_hip_pq_kind(nvdb_hip_ctx* ctx, uint32_t* residual);
 /* out[nrows][dim] f32 (host) = resident rows [row0, row0 + nrows) as their codes describe them (reconstruct above), for either
  * kind of shadow; row0 + nrows > n -> NVDB_ERR_INVALID; nrows == 0 -> NVDB_OK; no codes -> NVDB_ERR_INVALID */
 nvdb_status nvdb_hip_pq_reconstruct(nvdb_hip_ctx* ctx, uint64_t row0, uint64_t nrows, float* out /* [nrows][dim] */);
-/* out[nrows][M] (host) = the codes of resident rows [row0, row0 + nrows); row0 + nrows > n -> NVDB_ERR_INVALID; nrows == 0 -> NVDB_OK */
-nvdb_status nvdb_hip_pq_download_codes(nvdb_hip_ctx* ctx, uint64_t row0, uint64_t nrows, uint8_t* out /* [nrows][M] */);
+/* out[nrows][M] (host; a 4-bit shadow: [nrows][M / 2], packed) = the codes of resident rows [row0, row0 + nrows); row0 + nrows > n
+ * -> NVDB_ERR_INVALID; nrows == 0 -> NVDB_OK */
+nvdb_status nvdb_hip_pq_download_codes(nvdb_hip_ctx* ctx, uint64_t row0, uint64_t nrows, uint8_t* out /* [nrows][M] or [nrows][M / 2] */);
 /* The R best PQ scores of every query's probed union: out_ids[nq][R] global ids, out_scores[nq][R] the PQ scores, out_counts[q]
  * (optional) = min(R, rows of the union whose score is no NaN); slots beyond the count hold UINT64_MAX / -inf.  R is NOT clamped.
  * probe[nq][nprobe]: nvdb_hip_search_partitions' rules.  R == 0 or nq == 0 -> NVDB_OK, nothing written; nprobe == 0 -> every
@@ -886,6 +918,8 @@ nvdb_status nvdb_hip_ivf_pq_train_residual(nvdb_hip_ivf* ivf, uint32_t M, uint32
 nvdb_status nvdb_hip_ivf_pq_build_opq(nvdb_hip_ivf* ivf, const float* rotation, const float* codebooks, uint32_t M, uint32_t residual);
 nvdb_status nvdb_hip_ivf_pq_train_opq(nvdb_hip_ivf* ivf, const float* rotation, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
                                       const float* init, float* out_codebooks, double* out_err, uint32_t residual);
+/* nvdb_hip_pq4_build on the index's context: its list-ordered rows, its lists and its centroids */
+nvdb_status nvdb_hip_ivf_pq4_build(nvdb_hip_ivf* ivf, const float* rotation, const float* codebooks, uint32_t M, uint32_t residual);
 nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe,
                                    uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing);
 nvdb_status nvdb_hip_ivf_pq_refine(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t K, uint32_t R, uint32_t nprobe,

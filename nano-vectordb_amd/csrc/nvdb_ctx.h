@@ -87,9 +87,10 @@ struct PartState;                             // nvdb_partitions.cpp: partition 
 // the PQ shadow of the resident corpus (nvdb_pq.cpp, pq_plan.h): exists from nvdb_hip_pq_build until the rows change
 struct PqState {
   uint32_t M = 0, dsub = 0;                        // sub-quantisers, elements per sub-vector (dim / M)
-  float* codebooks = nullptr;                      // [M][256][dsub] f32
-  uint8_t* codes = nullptr;                        // [n][M], library-owned, zero-padded by PAD_ROWS rows
-  DevBuf lut;                                      // [queries of a sub-batch][M][256] f32, grow-only
+  uint32_t nbits = 8;                              // code width: 8 (256 codewords, a byte per code) or 4 (nvdb_hip_pq4_build: 16 codewords, two codes to a byte; kernels_pq4.h)
+  float* codebooks = nullptr;                      // [M][256 or 16][dsub] f32
+  uint8_t* codes = nullptr;                        // [n][M or M / 2], library-owned, zero-padded by PAD_ROWS rows
+  DevBuf lut;                                      // [queries of a sub-batch][M][256 or 16] f32, grow-only
   // a RESIDUAL shadow (nvdb_hip_pq_build_residual; kernels_pq_resid.h): the codes are those of x - centroid of the row's list, under
   // the table and the centroids the context held at build time -- the shadow's own device copies; nvdb_hip_set_partitions and
   // nvdb_hip_set_centroids free such a shadow (pq_drop_residual)

@@ -583,6 +583,11 @@ nvdb_status nvdb_hip_ivf_pq_train_opq(nvdb_hip_ivf* ix, const float* rotation, u
   return ivf_forward(ix, nvdb_hip_pq_train_opq(ix->ctx, rotation, M, iters, seed, max_train_rows, init, out_codebooks, out_err, residual));
 }
 
+nvdb_status nvdb_hip_ivf_pq4_build(nvdb_hip_ivf* ix, const float* rotation, const float* codebooks, uint32_t M, uint32_t residual) {
+  if (!ix) return NVDB_ERR_INVALID;
+  return ivf_forward(ix, nvdb_hip_pq4_build(ix->ctx, rotation, codebooks, M, residual));
+}
+
 nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe, uint64_t* out_ids, float* out_scores,
                                    uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
   if (!ix) return NVDB_ERR_INVALID;

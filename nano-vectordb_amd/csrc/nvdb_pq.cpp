@@ -24,14 +24,19 @@
 // slab and moves on; the trainer rotates its gathered sample the same way, in place slab by slab; a search rotates each sub-batch's
 // queries (ps->q -> pq.qrot) in front of pq_lut_kernel and nowhere else -- the coarse step, the base terms and the refine keep the
 // caller's queries --; reconstruction multiplies the codewords by A^T.  No rotation: none of these launches.
+// A 4-BIT shadow (nvdb_hip_pq4_build; kernels_pq4.h) holds two codes to a byte under 16 codewords per sub-quantiser: PqState::nbits
+// says which of the two sets of kernels (encode, tables, scan, reconstruct) every call above launches -- groups of pq4_group(M)
+// queries, which fill the work list's classes 1 and 2 as well: the items of all three are contiguous in the image and one launch
+// takes them --; the pass, the base terms, the rotation, the select and the refine do not know the width.
 // Entry points: nvdb_hip_pq_train / _build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf,
 // nvdb_hip_pq_build_residual / _train_residual / _reconstruct / _kind and nvdb_hip_pq_build_opq / _train_opq / _rotation /
-// _rotated_rows / _rotate; the index forms (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them on the index's context and map the ids.
+// _rotated_rows / _rotate, nvdb_hip_pq4_build / _pq_bits; the index forms (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them on the index's context and map the ids.
 #include "nvdb_parts.h"
 #include "kernels_pq.h"
 #include "kernels_pq_resid.h"
 #include "kernels_pq_train.h"
 #include "kernels_pq_rotate.h"
+#include "kernels_pq4.h"
 #include "ivf_layout.h"
 
 namespace nvdbhip {
@@ -85,6 +90,27 @@ nvdb_status launch_encode(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, boo
       case 16: go(pq_encode_kernel<DT, 16>); break;
       default: go(pq_encode_kernel<DT, 32>); break;
     }
+  }
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+// ... and of a 4-bit shadow: one kernel for both kinds
+template <int DT>
+nvdb_status launch_encode4(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, bool residual, const void* rows, const float* scales, uint64_t n, uint8_t* codes) {
+  const unsigned grid = static_cast<unsigned>((n + PQ_ENC_THREADS - 1) / PQ_ENC_THREADS);
+  auto go = [&](auto kernel) {
+    kernel<<<grid, PQ_ENC_THREADS, 0, s>>>(rows, scales, n, c->dim, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, pq.cent, codes);
+  };
+  auto with_kind = [&](auto dmax) {
+    if (residual) go(pq4_encode_kernel<DT, decltype(dmax)::value, true>);
+    else go(pq4_encode_kernel<DT, decltype(dmax)::value, false>);
+  };
+  switch (pq_encode_bound(pq.dsub)) {
+    case 4: with_kind(std::integral_constant<int, 4>{}); break;
+    case 8: with_kind(std::integral_constant<int, 8>{}); break;
+    case 16: with_kind(std::integral_constant<int, 16>{}); break;
+    default: with_kind(std::integral_constant<int, 32>{}); break;
   }
   HIPCHK(c, hipGetLastError());
   return NVDB_OK;
@@ -292,7 +318,30 @@ nvdb_status launch_scan_g(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, con
   return pq_wide_codes(pq.M) ? go(pq_scan_kernel<G, true>) : go(pq_scan_kernel<G, false>);
 }
 
+// the 4-bit scan's build for M: G interleaved tables in LDS; nitems: the items of every class (im.items: classes 2, 1, 0, contiguous)
+template <int G>
+nvdb_status launch_scan4_g(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, const PartImage& im, uint32_t nitems) {
+  const size_t lds = pq4_scan_lds(pq.M, G);
+  auto go = [&](auto kernel) -> nvdb_status {
+    if (lds > 64 * 1024)
+      if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(kernel), PART_LDS_LIMIT)) return st;
+    kernel<<<nitems, PQ_SCAN_THREADS, lds, s>>>(pq.codes, pq.M, im.items, im.qidx, im.dst, static_cast<const float*>(pq.base.p),
+                                                static_cast<const float*>(pq.lut.p), static_cast<Cand*>(c->parts->cand.p));
+    HIPCHK(c, hipGetLastError());
+    return NVDB_OK;
+  };
+  if (pq.residual) return pq4_wide_codes(pq.M) ? go(pq4_scan_kernel<G, true, true>) : go(pq4_scan_kernel<G, false, true>);
+  return pq4_wide_codes(pq.M) ? go(pq4_scan_kernel<G, true, false>) : go(pq4_scan_kernel<G, false, false>);
+}
+
 nvdb_status launch_scan(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, const PartImage& im, uint32_t nitems) {
+  if (pq.nbits == 4) {
+    switch (pq4_group(pq.M)) {
+      case 32: return launch_scan4_g<32>(c, s, pq, im, nitems);
+      case 16: return launch_scan4_g<16>(c, s, pq, im, nitems);
+      default: return launch_scan4_g<8>(c, s, pq, im, nitems);
+    }
+  }
   switch (pq_group(pq.M)) {
     case 8: return launch_scan_g<8>(c, s, pq, im, nitems);
     case 4: return launch_scan_g<4>(c, s, pq, im, nitems);
@@ -322,7 +371,10 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
 
   const uint64_t budget_bytes = static_cast<uint64_t>(c->opt_largek_budget_mb) << 20;
   const uint64_t budget_entries = budget_bytes / (2 * sizeof(Cand));
-  const uint32_t lut_batch = pq_lut_batch(pq.M, budget_bytes / 4);
+  const bool b4 = pq.nbits == 4;
+  const uint32_t group = b4 ? pq4_group(pq.M) : pq_group(pq.M);
+  const size_t lut_bytes = b4 ? pq4_lut_bytes(pq.M) : pq_lut_bytes(pq.M);
+  const uint32_t lut_batch = b4 ? pq4_lut_batch(pq.M, budget_bytes / 4) : pq_lut_batch(pq.M, budget_bytes / 4);
   PaSub sub;
   std::vector<uint32_t> h_rid;
   for (uint32_t q0 = 0; q0 < nq;) {
@@ -333,7 +385,7 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
     float* sc0 = rf ? nullptr : out_scores + static_cast<size_t>(q0) * R;
     PartPass p;
     p.off = off; p.nparts = nparts; p.q0 = q0; p.b = b; p.nprobe = nprobe; p.slot_cap = 0xFFFFFFFFu;
-    p.qg_max = pq_group(pq.M);
+    p.qg_max = group;
     p.queries = queries;
     p.skip_empty = true;
     size_t pstart_at = 0;                                              // residual: where pstart begins in the image's extra words
@@ -348,7 +400,7 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
       }
       if (pq.rot)
         if (nvdb_status e = ensure(c, pq.qrot, static_cast<size_t>(b) * c->dim * 4)) return e;
-      return ensure(c, pq.lut, b * pq_lut_bytes(pq.M));
+      return ensure(c, pq.lut, b * lut_bytes);
     });
     if (st) return st;
     if (!p.wl.total) {                                                 // no row in any union of the sub-batch
@@ -367,7 +419,8 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
       if ((st = launch_rotate_f32(c, s, lut_q, b, pq.rot, static_cast<float*>(pq.qrot.p)))) return st;
       lut_q = static_cast<const float*>(pq.qrot.p);
     }
-    pq_lut_kernel<<<dim3(pq.M / 4u, b), 256, 0, s>>>(lut_q, c->dim, pq.M, pq.dsub, pq.codebooks, static_cast<float*>(pq.lut.p));
+    if (b4) pq4_lut_kernel<<<dim3((pq.M + 15u) / 16u, b), 256, 0, s>>>(lut_q, c->dim, pq.M, pq.dsub, pq.codebooks, static_cast<float*>(pq.lut.p));
+    else pq_lut_kernel<<<dim3(pq.M / 4u, b), 256, 0, s>>>(lut_q, c->dim, pq.M, pq.dsub, pq.codebooks, static_cast<float*>(pq.lut.p));
     HIPCHK(c, hipGetLastError());
     if (pq.residual) {
       pq_base_kernel<<<nparts, PQ_BASE_THREADS, 0, s>>>(static_cast<const float*>(ps->q.p), c->dim, pq.cent, p.im.extra + pstart_at, p.im.qidx,
@@ -401,7 +454,7 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
   if ((st = parts_call_end(c, timing))) return st;
   if (timing) {
     timing->K = rf ? rf->K : R; timing->R = R;
-    timing->threads = PQ_SCAN_THREADS; timing->shmem_bytes = pq_group(pq.M) * pq_lut_bytes(pq.M);
+    timing->threads = PQ_SCAN_THREADS; timing->shmem_bytes = b4 ? pq4_scan_lds(pq.M, group) : group * lut_bytes;
   }
   return NVDB_OK;
 }
@@ -422,24 +475,28 @@ nvdb_status pq_search_args(nvdb_hip_ctx* c, const char* who, bool ivf, const flo
 }
 
 // nvdb_hip_pq_build / nvdb_hip_pq_build_residual: on any failure nothing has changed
-// opq: the codes are cut from A e (rotation: host, [dim][dim]); else rotation is not looked at
-nvdb_status pq_build(nvdb_hip_ctx* c, const char* who, bool residual, const float* codebooks, uint32_t M, bool opq = false, const float* rotation = nullptr) {
+// opq: the codes are cut from A e (rotation: host, [dim][dim]); else rotation is not looked at.  nbits: 8, or 4 (nvdb_hip_pq4_build)
+nvdb_status pq_build(nvdb_hip_ctx* c, const char* who, bool residual, const float* codebooks, uint32_t M, bool opq = false, const float* rotation = nullptr,
+                     uint32_t nbits = 8) {
   if (!c) return NVDB_ERR_INVALID;
   const std::string w = std::string(who) + ": ";
   if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
   if (opq && !rotation) return fail(c, NVDB_ERR_INVALID, w + "null rotation");
   if (!codebooks) return fail(c, NVDB_ERR_INVALID, w + "null codebooks");
   bool unsupported = false;
-  if (const char* why = pq_shape_check(c->dim, M, unsupported)) return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, w + why);
+  if (const char* why = nbits == 4 ? pq4_shape_check(c->dim, M, residual, unsupported) : pq_shape_check(c->dim, M, unsupported))
+    return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, w + why);
   if (residual)
     if (nvdb_status st = resid_args(c, who)) return st;
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   PqState fresh;
   fresh.M = M; fresh.dsub = c->dim / M;
+  fresh.nbits = nbits;
   fresh.residual = residual;
-  const size_t cb_bytes = static_cast<size_t>(M) * PQ_KSUB * fresh.dsub * 4;
-  const size_t code_bytes = static_cast<size_t>(c->n) * M, pad_bytes = static_cast<size_t>(PAD_ROWS) * M;
+  const size_t row_bytes = pq_row_bytes(M, nbits);
+  const size_t cb_bytes = static_cast<size_t>(M) * (nbits == 4 ? PQ4_KSUB : PQ_KSUB) * fresh.dsub * 4;
+  const size_t code_bytes = static_cast<size_t>(c->n) * row_bytes, pad_bytes = static_cast<size_t>(PAD_ROWS) * row_bytes;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&fresh.codebooks), cb_bytes);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.codes), code_bytes + pad_bytes);
   if (e == hipSuccess) e = hipMemcpyAsync(fresh.codebooks, codebooks, cb_bytes, hipMemcpyHostToDevice, s);
@@ -471,14 +528,19 @@ nvdb_status pq_build(nvdb_hip_ctx* c, const char* who, bool residual, const floa
   nvdb_status st = NVDB_OK;
   if (e != hipSuccess) st = fail(c, NVDB_ERR_HIP, w + hipGetErrorString(e));
   if (!st && !opq)
-    dispatch_dtype(c->dtype, st, [&](auto dt) { return launch_encode<decltype(dt)::value>(c, s, fresh, residual, c->rows, c->scales, c->n, fresh.codes); });
+    dispatch_dtype(c->dtype, st, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      return nbits == 4 ? launch_encode4<DT>(c, s, fresh, residual, c->rows, c->scales, c->n, fresh.codes)
+                        : launch_encode<DT>(c, s, fresh, residual, c->rows, c->scales, c->n, fresh.codes);
+    });
   // rotated: per slab the product into the scratch rows, then the f32 non-residual encode over them (the centroid is gone already)
   for (uint64_t r = 0; opq && !st && r < c->n; r += slab) {
     const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(slab, c->n - r));
     dispatch_dtype(c->dtype, st, [&](auto dt) {
       return launch_rotate<decltype(dt)::value>(c, s, c->rows, c->scales, r, nr, fresh.rot, fresh.off, fresh.nparts, residual ? fresh.cent : nullptr, d_slab.as<float>());
     });
-    if (!st) st = launch_encode<DT_F32>(c, s, fresh, false, d_slab.p, nullptr, nr, fresh.codes + r * M);
+    if (!st) st = nbits == 4 ? launch_encode4<DT_F32>(c, s, fresh, false, d_slab.p, nullptr, nr, fresh.codes + r * row_bytes)
+                             : launch_encode<DT_F32>(c, s, fresh, false, d_slab.p, nullptr, nr, fresh.codes + r * row_bytes);
   }
   if (!st && (e = hipStreamSynchronize(s)) != hipSuccess) st = fail(c, NVDB_ERR_HIP, w + hipGetErrorString(e));
   if (st) {                                                            // nothing changed: an earlier build stands
@@ -549,6 +611,16 @@ nvdb_status nvdb_hip_pq_build_opq(nvdb_hip_ctx* c, const float* rotation, const 
 nvdb_status nvdb_hip_pq_train_opq(nvdb_hip_ctx* c, const float* rotation, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init,
                                   float* out_codebooks, double* out_err, uint32_t residual) {
   return pq_train_call(c, "pq_train_opq", residual != 0, M, iters, seed, max_train_rows, init, out_codebooks, out_err, true, rotation);
+}
+
+nvdb_status nvdb_hip_pq4_build(nvdb_hip_ctx* c, const float* rotation, const float* codebooks, uint32_t M, uint32_t residual) {
+  return pq_build(c, "pq4_build", residual != 0, codebooks, M, rotation != nullptr, rotation, 4);
+}
+
+nvdb_status nvdb_hip_pq_bits(nvdb_hip_ctx* c, uint32_t* nbits) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (nbits) *nbits = c->pq ? c->pq->nbits : 0u;
+  return NVDB_OK;
 }
 
 nvdb_status nvdb_hip_pq_rotation(nvdb_hip_ctx* c, uint32_t* rotated, float* out) {
@@ -631,8 +703,11 @@ nvdb_status nvdb_hip_pq_reconstruct(nvdb_hip_ctx* c, uint64_t row0, uint64_t nro
     const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(step, nrows - r));
     const unsigned grid = std::min<unsigned>((nr + 3u) / 4u, static_cast<unsigned>(c->num_cu) * 64u);
     // a rotated shadow: the codewords side by side, times A^T, and only then the centroid
-    pq_reconstruct_kernel<<<grid, 256, 0, c->stream>>>(pq.codes, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, pq.residual && !pq.rot ? pq.cent : nullptr,
-                                                       static_cast<uint32_t>(row0 + r), nr, d_y.as<float>());
+    const float* cent = pq.residual && !pq.rot ? pq.cent : nullptr;
+    if (pq.nbits == 4)
+      pq4_reconstruct_kernel<<<grid, 256, 0, c->stream>>>(pq.codes, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, cent, static_cast<uint32_t>(row0 + r), nr, d_y.as<float>());
+    else
+      pq_reconstruct_kernel<<<grid, 256, 0, c->stream>>>(pq.codes, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, cent, static_cast<uint32_t>(row0 + r), nr, d_y.as<float>());
     HIPCHK(c, hipGetLastError());
     if (pq.rot) {
       if (nvdb_status st = launch_rotate_f32(c, c->stream, d_y.as<float>(), nr, pq.rot_t, d_x.as<float>())) return st;
@@ -652,7 +727,7 @@ nvdb_status nvdb_hip_pq_info(nvdb_hip_ctx* c, uint32_t* M, uint32_t* dsub, uint6
   const PqState* pq = c->pq;
   if (M) *M = pq ? pq->M : 0u;
   if (dsub) *dsub = pq ? pq->dsub : 0u;
-  if (code_bytes) *code_bytes = pq ? c->n * pq->M : 0ull;
+  if (code_bytes) *code_bytes = pq ? c->n * pq_row_bytes(pq->M, pq->nbits) : 0ull;
   return NVDB_OK;
 }
 
@@ -662,7 +737,8 @@ nvdb_status nvdb_hip_pq_download_codes(nvdb_hip_ctx* c, uint64_t row0, uint64_t 
   if (nrows == 0) return NVDB_OK;
   if (!out) return fail(c, NVDB_ERR_INVALID, "pq_download_codes: null output");
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(out, c->pq->codes + row0 * c->pq->M, nrows * c->pq->M, hipMemcpyDeviceToHost, c->stream));
+  const uint64_t row_bytes = pq_row_bytes(c->pq->M, c->pq->nbits);
+  HIPCHK(c, hipMemcpyAsync(out, c->pq->codes + row0 * row_bytes, nrows * row_bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return NVDB_OK;
 }

@@ -84,4 +84,50 @@ constexpr uint32_t pq_lut_batch(uint32_t M, uint64_t budget_bytes) {
   return b < 1 ? 1u : b > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(b);
 }
 
+// ---- 4-bit shadows (nvdb_hip_pq4_build, kernels_pq4.h): 16 codewords per sub-quantiser, two codes to a byte
+constexpr uint32_t PQ4_KSUB = 16;                   // codewords per sub-quantiser: one table row is 16 consecutive dwords
+constexpr uint32_t PQ4_M_MAX = 256;                 // sub-quantisers at most: one query's tables are 64 M bytes, 16 KB here
+constexpr uint32_t PQ4_ENC_SQ = 8;                  // sub-quantisers per encode step: a thread leaves one dword of packed codes
+constexpr uint32_t PQ_BASE_DIM_MAX = PQ_M_MAX * PQ_DSUB_MAX;   // pq_base_kernel stages one centroid in a static array of this many floats
+
+// 0: fine; else why nvdb_hip_pq4_build refuses the shape.  residual: the search's base terms go through pq_base_kernel as it is,
+// whose centroid array bounds dim (an 8-bit shape never exceeds it; a 4-bit one can, at M > 128 with dsub 32)
+inline const char* pq4_shape_check(uint32_t dim, uint32_t M, bool residual, bool& unsupported) {
+  unsupported = false;
+  if (M < 8 || M % 8 != 0 || M > PQ4_M_MAX) return "M must be a multiple of 8 in [8, 256] (4-bit codes)";
+  if (dim == 0 || dim % M != 0) return "dim must be a multiple of M";
+  if (dim / M > PQ_DSUB_MAX) { unsupported = true; return "dim / M <= 32 (the encode kernel's widest build)"; }
+  if (residual && dim > PQ_BASE_DIM_MAX) { unsupported = true; return "dim <= 4096 for a residual 4-bit shadow (the base terms' centroid stage)"; }
+  return nullptr;
+}
+
+// bytes of one row's codes and of one query's tables ([M][16] f32) under either width
+constexpr uint32_t pq_row_bytes(uint32_t M, uint32_t nbits) { return nbits == 4 ? M / 2 : M; }
+constexpr size_t pq4_lut_bytes(uint32_t M) { return static_cast<size_t>(M) * PQ4_KSUB * 4; }
+
+// THE group rule of the 4-bit scan: G = the largest of {32, 16, 8} whose interleaved tables (G * 64 M bytes) leave room for TWO
+// workgroups per CU, i.e. fit half the LDS budget; 8 where none does (8 * 64 * 256 = 128 KB still fits one).  Why two: a wave's
+// work per nibble is one ds_read_b128 and four dependent-free adds per quad, with nothing else to overlap a code load's latency
+// than other waves -- 16 waves per CU (4 per SIMD) are what the 8-bit scan runs with at its best group sizes, and a second
+// workgroup also covers the first one's table copy and barrier.  Why not smaller than that: every doubling of G halves the
+// re-reads of a list's codes and the table stream through L2.  32 up to M = 32, 16 up to M = 72, 8 above (M = 96: 48 KB, three
+// workgroups per CU).  PART_WAVES * PART_QW_MAX = 32 is the work list's widest group.
+constexpr uint32_t pq4_group(uint32_t M) {
+  for (uint32_t G = 32; G > 8; G >>= 1)
+    if (G * pq4_lut_bytes(M) <= PQ_LDS_BUDGET / 2) return G;
+  return 8;
+}
+
+// the 4-bit scan's LDS: the G tables and, behind them, G slab offsets and G base terms
+constexpr size_t pq4_scan_lds(uint32_t M, uint32_t G) { return G * pq4_lut_bytes(M) + G * 8u; }
+
+// a lane reads its row's M / 2 code bytes in 16-byte pieces where a row is whole pieces, else in dwords (M % 8 == 0 always)
+constexpr bool pq4_wide_codes(uint32_t M) { return (M / 2) % 16 == 0; }
+
+// queries one sub-batch may hold 4-bit tables for: budget_bytes of them, at least one
+constexpr uint32_t pq4_lut_batch(uint32_t M, uint64_t budget_bytes) {
+  const uint64_t b = budget_bytes / pq4_lut_bytes(M);
+  return b < 1 ? 1u : b > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(b);
+}
+
 }  // namespace nvdbhip

@@ -49,6 +49,7 @@ EXPORTS = [
     "nvdb_hip_ivf_pq_build_residual", "nvdb_hip_ivf_pq_train_residual",
     "nvdb_hip_pq_build_opq", "nvdb_hip_pq_train_opq", "nvdb_hip_pq_rotation", "nvdb_hip_pq_rotated_rows", "nvdb_hip_pq_rotate",
     "nvdb_hip_ivf_pq_build_opq", "nvdb_hip_ivf_pq_train_opq",
+    "nvdb_hip_pq4_build", "nvdb_hip_ivf_pq4_build", "nvdb_hip_pq_bits",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -239,6 +240,9 @@ def _bind(L, dev):
     L.nvdb_hip_pq_rotated_rows.argtypes = [vp, u64, u64, vp]
     L.nvdb_hip_pq_rotate.argtypes = [vp, vp, u64, vp]
     L.nvdb_hip_pq_kind.argtypes = [vp, C.POINTER(u32)]
+    L.nvdb_hip_pq4_build.argtypes = [vp, vp, vp, u32, u32]
+    L.nvdb_hip_ivf_pq4_build.argtypes = [vp, vp, vp, u32, u32]
+    L.nvdb_hip_pq_bits.argtypes = [vp, C.POINTER(u32)]
     L.nvdb_hip_pq_reconstruct.argtypes = [vp, u64, u64, vp]
     L.nvdb_hip_pq_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
     L.nvdb_hip_pq_download_codes.argtypes = [vp, u64, u64, vp]
@@ -398,12 +402,16 @@ def _rotation_arg(rotation, dim):
     return rotation
 
 
-def _pq_build(owner, plain, resid, opq, dim, codebooks, residual, rotation):
-    """HipContext.pq_build / IvfIndex.pq_build: the entry points for owner.h without and with a rotation."""
+def _pq_build(owner, plain, resid, opq, pq4, dim, codebooks, residual, rotation):
+    """HipContext.pq_build / IvfIndex.pq_build: the entry points for owner.h without and with a rotation; pq4: the one call for
+    16-codeword codebooks (the width comes from shape[1])."""
     codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
-    if codebooks.ndim != 3 or codebooks.shape[1] != 256:
-        raise ValueError("codebooks must be [M, 256, dim / M]")
-    if rotation is None:
+    if codebooks.ndim != 3 or codebooks.shape[1] not in (16, 256):
+        raise ValueError("codebooks must be [M, 256, dim / M] (or [M, 16, dim / M]: 4-bit codes)")
+    if codebooks.shape[1] == 16:
+        rotation = None if rotation is None else _rotation_arg(rotation, dim)
+        owner._chk(pq4(owner.h, None if rotation is None else rotation.ctypes.data, codebooks.ctypes.data, codebooks.shape[0], 1 if residual else 0))
+    elif rotation is None:
         owner._chk((resid if residual else plain)(owner.h, codebooks.ctypes.data, codebooks.shape[0]))
     else:
         rotation = _rotation_arg(rotation, dim)
@@ -746,12 +754,13 @@ class HipContext:
 
     # -- PQ candidate scan (a PQ shadow of the resident corpus under the caller's codebooks; stats path 9)
     def pq_build(self, codebooks, residual=False, rotation=None):
-        """Encode the resident rows under codebooks [M, 256, dim / M] f32 (nearest codeword by squared L2, ties to the lowest).
+        """Encode the resident rows under codebooks [M, 256, dim / M] f32 (nearest codeword by squared L2, ties to the lowest);
+        codebooks [M, 16, dim / M] build a 4-bit shadow (two codes to a byte, M % 8 == 0), served by every call below.
         residual: encode every row's residual to the centroid of its list (needs set_partitions and set_centroids, which free
         such a shadow when called again); the searches answer from whichever shadow the context holds.
         rotation: an OPQ matrix A [dim, dim] f32 -- the codes are cut from A e, the codebooks live in the rotated space, and the
         searches rotate their queries; the scores approximate q . x only where A^T A = I (not checked)."""
-        _pq_build(self, self.lib.nvdb_hip_pq_build, self.lib.nvdb_hip_pq_build_residual, self.lib.nvdb_hip_pq_build_opq,
+        _pq_build(self, self.lib.nvdb_hip_pq_build, self.lib.nvdb_hip_pq_build_residual, self.lib.nvdb_hip_pq_build_opq, self.lib.nvdb_hip_pq4_build,
                   self.corpus_info()["dim"] if rotation is not None else 0, codebooks, residual, rotation)
 
     def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False, rotation=None):
@@ -796,6 +805,12 @@ class HipContext:
         self._chk(self.lib.nvdb_hip_pq_kind(self.h, C.byref(r)))
         return dict(residual=bool(r.value))
 
+    def pq_bits(self):
+        """The shadow's code width: 8 or 4; 0 without a shadow."""
+        r = C.c_uint32()
+        self._chk(self.lib.nvdb_hip_pq_bits(self.h, C.byref(r)))
+        return r.value
+
     def pq_reconstruct(self, row0=0, nrows=None):
         """Resident rows [row0, row0 + nrows) as their codes describe them -> [nrows, dim] f32: the codeword of every sub-vector,
         plus the centroid of the row's list under a residual shadow."""
@@ -813,10 +828,12 @@ class HipContext:
         return dict(M=M.value, dsub=dsub.value, code_bytes=nbytes.value)
 
     def pq_download_codes(self, row0=0, nrows=None):
-        """The codes of resident rows [row0, row0 + nrows) -> [nrows, M] u8."""
+        """The codes of resident rows [row0, row0 + nrows) -> [nrows, M] u8; a 4-bit shadow: [nrows, M // 2], two codes to a byte
+        (the even sub-quantiser in the low nibble)."""
         if nrows is None:
             nrows = self.corpus_info()["n"] - row0
-        out = np.zeros((max(nrows, 0), self.pq_info()["M"]), dtype=np.uint8)
+        M = self.pq_info()["M"]
+        out = np.zeros((max(nrows, 0), M // 2 if self.pq_bits() == 4 else M), dtype=np.uint8)
         self._chk(self.lib.nvdb_hip_pq_download_codes(self.h, row0, nrows, out.ctypes.data if out.size else None))
         return out
 
@@ -1058,7 +1075,7 @@ class IvfIndex:
     def pq_build(self, codebooks, residual=False, rotation=None):
         """HipContext.pq_build over the list-ordered rows (residual: against the index's lists and centroids); compact() and
         add_rows() free the codes."""
-        _pq_build(self, self.lib.nvdb_hip_ivf_pq_build, self.lib.nvdb_hip_ivf_pq_build_residual, self.lib.nvdb_hip_ivf_pq_build_opq,
+        _pq_build(self, self.lib.nvdb_hip_ivf_pq_build, self.lib.nvdb_hip_ivf_pq_build_residual, self.lib.nvdb_hip_ivf_pq_build_opq, self.lib.nvdb_hip_ivf_pq4_build,
                   self.ctx.corpus_info()["dim"] if rotation is not None else 0, codebooks, residual, rotation)
 
     def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False, rotation=None):
@@ -1082,6 +1099,10 @@ class IvfIndex:
     def pq_kind(self):
         """HipContext.pq_kind of the index's context."""
         return self.ctx.pq_kind()
+
+    def pq_bits(self):
+        """HipContext.pq_bits of the index's context."""
+        return self.ctx.pq_bits()
 
     def pq_reconstruct(self, row0=0, nrows=None):
         """HipContext.pq_reconstruct over the list-ordered rows (positions, not source ids)."""

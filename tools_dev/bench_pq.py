@@ -32,7 +32,15 @@ in numpy, over 20000 rows sampled through the library: four alternations of pq_t
 device, yhat from the codes, A <- U V^T of the SVD of sum yhat x^T (learn_rotation).  Reports the wall time of both builds, their
 difference against 2 n dim^2 flop at the 157 TFLOP/s of the fp32 matrix cores, the fp64 quantisation error of both, and, alternating
 the two copies call by call, ivf_pq_search / ivf_pq_refine times and recall@10.  --decay: unit rows of one Gaussian whose
-per-dimension deviation falls as 1 / sqrt(1 + t / 8), t the dimension."""
+per-dimension deviation falls as 1 / sqrt(1 + t / 8), t the dimension.
+
+    python tools_dev/bench_pq.py [the same arguments] --bits 4 [--clustered]
+
+The 8-bit shadow at M beside 4-BIT shadows at 2 M (equal bytes per row) and at M (half the bytes), two copies of the same index as
+above: copy a keeps the 8-bit shadow, copy b takes the two 4-bit ones in turn.  All codebooks are trained here in numpy on the same
+20000 list-ordered rows (train_codebooks with 256 or 16 codewords, four rounds; the device trainer has no 16-codeword build).
+Reports the wall time of the builds, the fp64 quantisation error, and, alternating the two copies call by call, ivf_pq_search /
+ivf_pq_refine times and recall@10."""
 import json
 import os
 import sys
@@ -48,19 +56,19 @@ import nvdb_amd  # noqa: E402
 U64MAX = np.iinfo(np.uint64).max
 
 
-def train_codebooks(sample, M, rounds, seed, init=None):
-    """[M, 256, dsub] f32: per sub-quantiser 256 sampled sub-vectors (or init[m]), then `rounds` Lloyd rounds (nearest by squared L2, mean)."""
+def train_codebooks(sample, M, rounds, seed, init=None, ksub=256):
+    """[M, ksub, dsub] f32: per sub-quantiser ksub sampled sub-vectors (or init[m]), then `rounds` Lloyd rounds (nearest by squared L2, mean)."""
     rs = np.random.RandomState(seed)
     n, dim = sample.shape
     dsub = dim // M
-    cb = np.empty((M, 256, dsub), dtype=np.float32)
+    cb = np.empty((M, ksub, dsub), dtype=np.float32)
     for m in range(M):
         x = sample[:, m * dsub:(m + 1) * dsub]
-        c = x[rs.choice(n, 256, replace=False)].copy() if init is None else init[m].copy()
+        c = x[rs.choice(n, ksub, replace=False)].copy() if init is None else init[m].copy()
         for _ in range(rounds):
             d = (x * x).sum(1)[:, None] - 2.0 * x @ c.T + (c * c).sum(1)[None]
             a = d.argmin(1)
-            for j in range(256):
+            for j in range(ksub):
                 if (a == j).any():
                     c[j] = x[a == j].mean(0)
         cb[m] = c
@@ -240,9 +248,74 @@ def main_opq(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, corpus):
         ix.close()
 
 
+def main_bits(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, clustered):
+    seed, K, rounds = 20240613, 10, 4
+    out = dict(mode="bits4", corpus="clustered" if clustered else "synthetic", rows=rows, dim=dim, dtype=dname, nlist=nlist, M=M, batch=batch,
+               calls=calls, warmup=warmup, K=K)
+    src = nvdb_amd.HipContext(0)
+    rs = np.random.RandomState(11)
+    if clustered:                                                       # main_residual's centre + noise rows
+        centres = rs.standard_normal((max(nlist // 4, 1), dim)).astype(np.float32)
+        x = np.empty((rows, dim), dtype=np.float16 if dtype == nvdb_amd.DT_F16 else np.float32)
+        for i in range(0, rows, 65536):
+            n = min(65536, rows - i)
+            v = centres[rs.randint(len(centres), size=n)] + 0.35 * rs.standard_normal((n, dim)).astype(np.float32)
+            x[i:i + n] = v / np.linalg.norm(v, axis=1, keepdims=True)
+        src.upload_corpus(x.view(np.uint16) if dtype == nvdb_amd.DT_F16 else x, dtype)
+        q = np.ascontiguousarray(x[rs.choice(rows, batch, replace=False)].astype(np.float32) + 0.1 * rs.standard_normal((batch, dim)).astype(np.float32))
+        del x
+    else:
+        src.generate_corpus(seed, rows, dim, dtype)
+        q = np.ascontiguousarray(nvdb_amd.synth_rows_f32(seed + 1, 0, batch, dim))
+    fid, _ = src.search_batch(q, 1024)
+    want, _ = src.refine_l2_topk(q, fid.astype(np.uint32), K)
+    want = want.astype(np.uint64)
+    cents = src.train_centroids(nlist, 2, seed, max_train_rows=262144)
+    a, b = nvdb_amd.IvfIndex(src, cents), nvdb_amd.IvfIndex(src, cents)
+    src.close()
+    pick = np.arange(20000, dtype=np.int64) * rows // 20000
+    raw = np.concatenate([a.ctx.download_rows(int(r), 1)[0] for r in pick])
+    sample = (raw.view(np.float16) if dtype == nvdb_amd.DT_F16 else raw).astype(np.float32)
+    blocks = np.sort(rs.choice(rows - 1000, 20, replace=False))
+
+    def shadow(ix, m, ksub):
+        cb = train_codebooks(sample, m, rounds, 7, ksub=ksub)
+        build_s, build_all = median_s(lambda: ix.pq_build(cb), reps=3)
+        err = 0.0
+        for blk in blocks:
+            r = ix.ctx.download_rows(int(blk), 1000)[0]
+            xs = (r.view(np.float16) if dtype == nvdb_amd.DT_F16 else r).astype(np.float64)
+            err += ((xs - ix.pq_reconstruct(int(blk), 1000).astype(np.float64)) ** 2).sum()
+        d = dict(M=m, bits=ix.pq_bits(), bytes_per_row=ix.ctx.pq_info()["code_bytes"] // rows, pq_build_s=build_s, pq_build_all_s=build_all,
+                 quant_err_per_row=err / (len(blocks) * 1000))
+        print(f"{d['bits']}-bit M={m}: {d['bytes_per_row']} bytes per row, pq_build {build_s:.3f} s (median of 3), fp64 |x - xhat|^2 per row {d['quant_err_per_row']:.6e}")
+        return d
+
+    out["pq8"] = shadow(a, M, 256)
+    for m4 in (2 * M, M):
+        tag = f"pq4_M{m4}"
+        out[tag] = shadow(b, m4, 16)
+        for nprobe in (8, 32):
+            for R in (100, 1024):
+                key = f"{tag} nprobe={nprobe} R={R}"
+                pa, pb, *spread = alternate_ms(lambda: a.pq_search(q, R, nprobe), lambda: b.pq_search(q, R, nprobe), calls, warmup)
+                fa, fb, *fspread = alternate_ms(lambda: a.pq_refine(q, K, R, nprobe), lambda: b.pq_refine(q, K, R, nprobe), calls, warmup)
+                ra, rb = recall(a.pq_refine(q, K, R, nprobe)[0], want), recall(b.pq_refine(q, K, R, nprobe)[0], want)
+                out[key] = dict(pq8_search_ms=pa, pq4_search_ms=pb, search_spread=spread, pq8_refine_ms=fa, pq4_refine_ms=fb, refine_spread=fspread,
+                                recall10_pq8=ra, recall10_pq4=rb)
+                print(f"{key:32s}: ivf_pq_search 8-bit {pa:8.3f} ms | 4-bit {pb:8.3f} ms || ivf_pq_refine 8-bit {fa:8.3f} ms | 4-bit {fb:8.3f} ms || "
+                      f"recall@10 8-bit {ra:.4f}, 4-bit {rb:.4f}")
+    print(json.dumps(out))
+    a.close()
+    b.close()
+
+
 def main():
-    flags = [x for x in sys.argv[1:] if x.startswith("--")]
-    a = [x for x in sys.argv[1:] if not x.startswith("--")]
+    argv = [x for i, x in enumerate(sys.argv[1:]) if not (i and sys.argv[i] == "--bits")]       # (--bits takes a value)
+    if "--bits" in sys.argv and sys.argv[sys.argv.index("--bits") + 1:][:1] != ["4"]:
+        raise SystemExit("--bits 4 is the only width beside the default")
+    flags = [x for x in argv if x.startswith("--")]
+    a = [x for x in argv if not x.startswith("--")]
     rows = int(a[0]) if len(a) > 0 else 10_000_000
     dim = int(a[1]) if len(a) > 1 else 768
     dname = a[2] if len(a) > 2 else "f16"
@@ -252,6 +325,8 @@ def main():
     batch = int(a[5]) if len(a) > 5 else 1024
     calls = int(a[6]) if len(a) > 6 else 10
     warmup = int(a[7]) if len(a) > 7 else 2
+    if "--bits" in flags:
+        return main_bits(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, "--clustered" in flags)
     if "--opq" in flags:
         corpus = "clustered" if "--clustered" in flags else "decay" if "--decay" in flags else "synthetic"
         return main_opq(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, corpus)
