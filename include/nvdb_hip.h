@@ -791,10 +791,26 @@ nvdb_status nvdb_hip_refine_l2_topk_dev(nvdb_hip_ctx* ctx, const float* dev_quer
  * nvdb_hip_pq_bits tells the width.  Cost: the build is n * dim * 16 fmas, a streaming kernel bounded by the rows' bytes; a search
  * computes 64 * M bytes of tables per query, copies the tables of <= G queries per work item into LDS interleaved (G = 32 up to
  * M = 32, 16 up to M = 72, else 8), reads M / 2 bytes per row once per group and writes 8 bytes per (row, query) as above.
- * Out of scope: cluster splitting and k-means++ starts in the trainer, L2 asymmetric-distance tables, learning the rotation, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
- * pruning inside the scan, the device group, _dev stream forms, the nvdb:: C++ host layer, a 16-codeword trainer on the device
- * (nvdb_hip_pq_train* train 256 codewords), u8-quantised tables and in-register shuffles for the 4-bit scan, code widths other
- * than 4 and 8.
+ * Their codebooks come from the caller or from nvdb_hip_pq4_train below, a 16-codeword trainer on the device: nvdb_hip_pq_train's
+ * arithmetic with 16 in place of 256.
+ *   shape       exactly what nvdb_hip_pq4_build accepts (the shape rule above, the residual bound included), the same status codes;
+ *               residual != 0 needs a partition table and centroids, as nvdb_hip_pq_train_residual does.
+ *   training set nvdb_hip_pq_train's rule; fewer than 16 training rows -> NVDB_ERR_INVALID.
+ *   start       init ([M][16][dim / M]) as given; NULL: sub-quantiser mq starts from 16 DISTINCT training rows by the same draw rule
+ *               with nparts = 16 and the seed `seed ^ (0x9E3779B97F4A7C15 * (mq + 1))`.  iters == 0 returns the start.
+ *   rows        gathered as f32, then minus the centroid of the row's list where residual is set (one fp32 subtraction), then
+ *               rotated where a rotation is given (the OPQ rule above): what nvdb_hip_pq4_build of the same kind encodes.
+ *   assignment  the 4-bit encode rule above, bit for bit: the code nvdb_hip_pq4_build of the same kind stores for that row under
+ *               the same codebooks (a row without a winner is a member of codeword 0).
+ *   update      nvdb_hip_pq_train's: per (codeword, column) an fp64 sum in ascending training-row order inside chunks of
+ *               PQ_TRAIN_CHUNK rows, the chunks added in chunk order, divided by the count in fp64, rounded once to f32; a codeword
+ *               without members, or with a non-finite sum in any column, keeps its bits.
+ *   out_err[i]  nvdb_hip_pq_train's rule unchanged: the tile tree, the tiles, chunks and sub-quantisers in order, one division.
+ * Same arguments + same corpus -> the same bytes (no atomics).  Cost: m * dim * 4 bytes for the rows as f32 and ceil(m / 4096) * 16 *
+ * dim * 8 bytes of partial sums; per iteration m * dim * 16 fmas and one read of the f32 rows, a line of a row fetched once.
+ * Out of scope: cluster splitting and k-means++ starts in the trainers, L2 asymmetric-distance tables, learning the rotation, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
+ * pruning inside the scan, the device group, _dev stream forms, the nvdb:: C++ host layer, u8-quantised tables and in-register
+ * shuffles for the 4-bit scan, code widths other than 4 and 8.
  * ------------------------------------------------------------------------------------------- */
 
 /* codebooks: [M][256][dim / M] f32, host memory.  M >= 4, M % 4 == 0, M <= 128, dim % M == 0, else NVDB_ERR_INVALID; dim / M > 32
@@ -866,6 +882,16 @@ nvdb_status nvdb_hip_pq_rotate(nvdb_hip_ctx* ctx, const float* x /* [n][dim] */,
  * corpus -> NVDB_ERR_NO_CORPUS.  Replaces an earlier shadow of either width; on any failure the earlier shadow stands. */
 nvdb_status nvdb_hip_pq4_build(nvdb_hip_ctx* ctx, const float* rotation /* [dim][dim], NULL: none */, const float* codebooks /* [M][16][dim / M] */,
                                uint32_t M, uint32_t residual);
+/* Codebooks for nvdb_hip_pq4_build of the same kind by Lloyd's iteration on the device, one call for every kind (4-BIT shadows
+ * above): rotation [dim][dim] f32 (host) or NULL: none; residual != 0: over the rows' residuals.  Every other argument as
+ * nvdb_hip_pq_train's, with 16 codewords per sub-quantiser.  Errors: null context / out_codebooks, a bad shape, fewer than 16
+ * training rows, residual without a table and centroids -> NVDB_ERR_INVALID (dim / M > 32 -> NVDB_ERR_UNSUPPORTED); no corpus ->
+ * NVDB_ERR_NO_CORPUS; on any failure nothing is written.  Non-finite rows or init: no fault, no hang.  An existing PQ shadow is
+ * neither read nor touched. */
+nvdb_status nvdb_hip_pq4_train(nvdb_hip_ctx* ctx, const float* rotation /* [dim][dim], NULL: none */, uint32_t M, uint32_t iters,
+                               uint64_t seed, uint64_t max_train_rows, const float* init /* [M][16][dim / M], may be NULL */,
+                               float* out_codebooks /* [M][16][dim / M] f32, host */, double* out_err /* [iters], may be NULL */,
+                               uint32_t residual);
 /* *nbits (optional) = 0 without a shadow, otherwise its code width: 8 or 4 */
 nvdb_status nvdb_hip_pq_bits(nvdb_hip_ctx* ctx, uint32_t* nbits);
 /* every output optional; all 0 without codes.  code_bytes = n * M (a 4-bit shadow: n * M / 2) */
@@ -920,6 +946,9 @@ nvdb_status nvdb_hip_ivf_pq_train_opq(nvdb_hip_ivf* ivf, const float* rotation, 
                                       const float* init, float* out_codebooks, double* out_err, uint32_t residual);
 /* nvdb_hip_pq4_build on the index's context: its list-ordered rows, its lists and its centroids */
 nvdb_status nvdb_hip_ivf_pq4_build(nvdb_hip_ivf* ivf, const float* rotation, const float* codebooks, uint32_t M, uint32_t residual);
+/* nvdb_hip_pq4_train on the index's context: the training rows are positions of the list-ordered copy */
+nvdb_status nvdb_hip_ivf_pq4_train(nvdb_hip_ivf* ivf, const float* rotation, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
+                                   const float* init, float* out_codebooks, double* out_err, uint32_t residual);
 nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe,
                                    uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing);
 nvdb_status nvdb_hip_ivf_pq_refine(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t K, uint32_t R, uint32_t nprobe,

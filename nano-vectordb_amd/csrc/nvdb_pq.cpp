@@ -13,7 +13,8 @@
 // The codebooks are the caller's or nvdb_hip_pq_train's (kernels_pq_train.h): the training rows gathered once as f32, the start
 // filled on the device, then per iteration pq_train_step_kernel (assignment by the encode's rule and the members' fp64 sums, fused)
 // and pq_train_finish_kernel (the division) with no host step in between; rows, partial sums and codebooks live inside the call, and
-// the context's shadow is not touched.
+// the context's shadow is not touched.  nvdb_hip_pq4_train (kernels_pq4_train.h) is the same call with 16 codewords: its own start,
+// step and finish kernels behind the shared gather, residual and rotation stages.
 // A RESIDUAL shadow (nvdb_hip_pq_build_residual; kernels_pq_resid.h) holds the codes of x - centroid of the row's list, with its own
 // device copies of the table (u32) and the centroids, and a search adds two things: pstart of the pass's work list rides behind
 // the any-k plan's words in the image, pq_base_kernel writes b(q, p) = q . c[p] per (probed partition, query) pair between tables
@@ -30,13 +31,14 @@
 // takes them --; the pass, the base terms, the rotation, the select and the refine do not know the width.
 // Entry points: nvdb_hip_pq_train / _build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf,
 // nvdb_hip_pq_build_residual / _train_residual / _reconstruct / _kind and nvdb_hip_pq_build_opq / _train_opq / _rotation /
-// _rotated_rows / _rotate, nvdb_hip_pq4_build / _pq_bits; the index forms (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them on the index's context and map the ids.
+// _rotated_rows / _rotate, nvdb_hip_pq4_build / _pq4_train / _pq_bits; the index forms (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them on the index's context and map the ids.
 #include "nvdb_parts.h"
 #include "kernels_pq.h"
 #include "kernels_pq_resid.h"
 #include "kernels_pq_train.h"
 #include "kernels_pq_rotate.h"
 #include "kernels_pq4.h"
+#include "kernels_pq4_train.h"
 #include "ivf_layout.h"
 
 namespace nvdbhip {
@@ -201,15 +203,41 @@ nvdb_status launch_train_iteration(nvdb_hip_ctx* c, hipStream_t s, const float* 
   return NVDB_OK;
 }
 
-// the call proper, the arguments validated: cb (host, [M][256][dsub]) and err (host, [iters]) are this call's own and reach the caller on success only
+// ... of the 16-codeword trainer (nvdb_hip_pq4_train): a workgroup per (chunk, group of pq4_train_sq sub-quantisers)
+nvdb_status launch_train4_iteration(nvdb_hip_ctx* c, hipStream_t s, const float* X, uint64_t m, uint32_t M, uint32_t dsub, float* cb, double* partial,
+                                    uint32_t* count, double* dist, double* err) {
+  const uint32_t chunks = static_cast<uint32_t>(pq_train_chunks(m)), dmax = pq_encode_bound(dsub);
+  const size_t lds = pq4_train_lds(dmax);
+  auto go = [&](auto kernel) -> nvdb_status {
+    if (lds > 64 * 1024)
+      if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(kernel), lds)) return st;
+    kernel<<<dim3(chunks, M / pq4_train_sq(dmax)), PQ_TRAIN_THREADS, lds, s>>>(X, m, c->dim, M, dsub, cb, partial, count, dist);
+    HIPCHK(c, hipGetLastError());
+    return NVDB_OK;
+  };
+  nvdb_status st;
+  switch (dmax) {
+    case 4: st = go(pq4_train_step_kernel<4>); break;
+    case 8: st = go(pq4_train_step_kernel<8>); break;
+    case 16: st = go(pq4_train_step_kernel<16>); break;
+    default: st = go(pq4_train_step_kernel<32>); break;
+  }
+  if (st) return st;
+  pq4_train_finish_kernel<<<(M * PQ4_KSUB + 255u) / 256u, 256, 0, s>>>(partial, count, dist, chunks, M, dsub, cb, err);
+  HIPCHK(c, hipGetLastError());
+  return NVDB_OK;
+}
+
+// the call proper, the arguments validated: cb (host, [M][256][dsub]; nbits 4: [M][16][dsub]) and err (host, [iters]) are this call's own and reach the caller on success only
 // residual: the training rows are the residuals to the centroids of their lists (the caller has checked resid_args)
 // rotation (host, [dim][dim], or nullptr): the gathered rows, residual or not, become A e before anything reads them
+// nbits: 8, or 4 (nvdb_hip_pq4_train): the codewords per sub-quantiser, the pick, the partial sums and the iteration's kernels
 nvdb_status pq_train(nvdb_hip_ctx* c, bool residual, const float* rotation, uint32_t M, uint32_t iters, uint64_t seed, uint64_t m, const float* init,
-                     std::vector<float>& cb, std::vector<double>& err) {
+                     std::vector<float>& cb, std::vector<double>& err, uint32_t nbits) {
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const uint64_t n = c->n;
-  const uint32_t dim = c->dim, dsub = dim / M;
+  const uint32_t dim = c->dim, dsub = dim / M, ksub = nbits == 4 ? PQ4_KSUB : PQ_KSUB;
   const size_t cb_bytes = cb.size() * 4;
   nvdb_status st = NVDB_OK;
 
@@ -255,13 +283,14 @@ nvdb_status pq_train(nvdb_hip_ctx* c, bool residual, const float* rotation, uint
   if (init) {
     HIPCHK(c, hipMemcpyAsync(d_cb.p, init, cb_bytes, hipMemcpyHostToDevice, s));
   } else {
-    // per sub-quantiser 256 distinct training rows, the centroid trainer's draw under the sub-quantiser's own seed
-    std::vector<uint32_t> pick(static_cast<size_t>(M) * PQ_KSUB);
-    for (uint32_t mq = 0; mq < M; ++mq) train_pick(seed ^ (0x9E3779B97F4A7C15ull * (mq + 1)), PQ_KSUB, m, pick.data() + static_cast<size_t>(mq) * PQ_KSUB);
+    // per sub-quantiser 256 (16) distinct training rows, the centroid trainer's draw under the sub-quantiser's own seed
+    std::vector<uint32_t> pick(static_cast<size_t>(M) * ksub);
+    for (uint32_t mq = 0; mq < M; ++mq) train_pick(seed ^ (0x9E3779B97F4A7C15ull * (mq + 1)), ksub, m, pick.data() + static_cast<size_t>(mq) * ksub);
     TrainMem d_pick;
     if ((st = train_alloc(c, d_pick, pick.size() * 4))) return st;
     HIPCHK(c, hipMemcpyAsync(d_pick.p, pick.data(), pick.size() * 4, hipMemcpyHostToDevice, s));
-    pq_train_start_kernel<<<M, PQ_KSUB, 0, s>>>(d_x.as<float>(), dim, dsub, d_pick.as<uint32_t>(), d_cb.as<float>());
+    if (nbits == 4) pq4_train_start_kernel<<<(M * PQ4_KSUB + 255u) / 256u, 256, 0, s>>>(d_x.as<float>(), dim, M, dsub, d_pick.as<uint32_t>(), d_cb.as<float>());
+    else pq_train_start_kernel<<<M, PQ_KSUB, 0, s>>>(d_x.as<float>(), dim, dsub, d_pick.as<uint32_t>(), d_cb.as<float>());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));                                // (d_pick leaves scope)
   }
@@ -270,12 +299,13 @@ nvdb_status pq_train(nvdb_hip_ctx* c, bool residual, const float* rotation, uint
   if (iters) {
     const uint64_t chunks = pq_train_chunks(m);
     TrainMem d_partial, d_count, d_dist, d_err;
-    if ((st = train_alloc(c, d_partial, pq_train_partial_bytes(m, dim))) || (st = train_alloc(c, d_count, chunks * M * PQ_KSUB * 4)) ||
+    if ((st = train_alloc(c, d_partial, nbits == 4 ? pq4_train_partial_bytes(m, dim) : pq_train_partial_bytes(m, dim))) || (st = train_alloc(c, d_count, chunks * M * ksub * 4)) ||
         (st = train_alloc(c, d_dist, chunks * M * 8)) || (st = train_alloc(c, d_err, err_m.size() * 8)))
       return st;
+    const auto iteration = nbits == 4 ? launch_train4_iteration : launch_train_iteration;
     for (uint32_t it = 0; it < iters; ++it)
-      if ((st = launch_train_iteration(c, s, d_x.as<float>(), m, M, dsub, d_cb.as<float>(), d_partial.as<double>(), d_count.as<uint32_t>(), d_dist.as<double>(),
-                                       d_err.as<double>() + static_cast<size_t>(it) * M)))
+      if ((st = iteration(c, s, d_x.as<float>(), m, M, dsub, d_cb.as<float>(), d_partial.as<double>(), d_count.as<uint32_t>(), d_dist.as<double>(),
+                          d_err.as<double>() + static_cast<size_t>(it) * M)))
         break;
     if (!st) {
       HIPCHK(c, hipMemcpyAsync(err_m.data(), d_err.p, err_m.size() * 8, hipMemcpyDeviceToHost, s));
@@ -559,24 +589,25 @@ nvdb_status pq_build(nvdb_hip_ctx* c, const char* who, bool residual, const floa
   return NVDB_OK;
 }
 
-// nvdb_hip_pq_train / nvdb_hip_pq_train_residual behind one set of checks
+// every training entry point behind one set of checks.  nbits: 8, or 4 (nvdb_hip_pq4_train: pq4_shape_check, 16 codewords)
 nvdb_status pq_train_call(nvdb_hip_ctx* c, const char* who, bool residual, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init,
-                          float* out_codebooks, double* out_err, bool opq = false, const float* rotation = nullptr) {
+                          float* out_codebooks, double* out_err, bool opq = false, const float* rotation = nullptr, uint32_t nbits = 8) {
   if (!c) return NVDB_ERR_INVALID;
   const std::string w = std::string(who) + ": ";
   if (opq && !rotation) return fail(c, NVDB_ERR_INVALID, w + "null rotation");
   if (!out_codebooks) return fail(c, NVDB_ERR_INVALID, w + "null output");
   if (!c->rows || c->n == 0) return fail(c, NVDB_ERR_NO_CORPUS, "Empty base");
   bool unsupported = false;
-  if (const char* why = pq_shape_check(c->dim, M, unsupported)) return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, w + why);
+  if (const char* why = nbits == 4 ? pq4_shape_check(c->dim, M, residual, unsupported) : pq_shape_check(c->dim, M, unsupported))
+    return fail(c, unsupported ? NVDB_ERR_UNSUPPORTED : NVDB_ERR_INVALID, w + why);
   if (residual)
     if (nvdb_status st = resid_args(c, who)) return st;
   const uint64_t m = pq_train_rows(c->n, max_train_rows);
-  if (m < PQ_TRAIN_MIN_ROWS) return fail(c, NVDB_ERR_INVALID, w + "fewer than 256 training rows");
+  if (m < (nbits == 4 ? PQ4_TRAIN_MIN_ROWS : PQ_TRAIN_MIN_ROWS)) return fail(c, NVDB_ERR_INVALID, w + (nbits == 4 ? "fewer than 16 training rows" : "fewer than 256 training rows"));
   if (m > IVF_MAX_ROWS) return fail(c, NVDB_ERR_UNSUPPORTED, w + "training set too large (max_train_rows)");
-  std::vector<float> cb(static_cast<size_t>(M) * PQ_KSUB * (c->dim / M));
+  std::vector<float> cb(static_cast<size_t>(M) * (nbits == 4 ? PQ4_KSUB : PQ_KSUB) * (c->dim / M));
   std::vector<double> err(iters);
-  if (nvdb_status st = pq_train(c, residual, opq ? rotation : nullptr, M, iters, seed, m, init, cb, err)) {
+  if (nvdb_status st = pq_train(c, residual, opq ? rotation : nullptr, M, iters, seed, m, init, cb, err, nbits)) {
     (void)hipGetLastError();
     return st;
   }
@@ -615,6 +646,11 @@ nvdb_status nvdb_hip_pq_train_opq(nvdb_hip_ctx* c, const float* rotation, uint32
 
 nvdb_status nvdb_hip_pq4_build(nvdb_hip_ctx* c, const float* rotation, const float* codebooks, uint32_t M, uint32_t residual) {
   return pq_build(c, "pq4_build", residual != 0, codebooks, M, rotation != nullptr, rotation, 4);
+}
+
+nvdb_status nvdb_hip_pq4_train(nvdb_hip_ctx* c, const float* rotation, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows, const float* init,
+                               float* out_codebooks, double* out_err, uint32_t residual) {
+  return pq_train_call(c, "pq4_train", residual != 0, M, iters, seed, max_train_rows, init, out_codebooks, out_err, rotation != nullptr, rotation, 4);
 }
 
 nvdb_status nvdb_hip_pq_bits(nvdb_hip_ctx* c, uint32_t* nbits) {

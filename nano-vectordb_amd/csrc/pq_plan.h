@@ -1,7 +1,8 @@
 // pq_plan.h -- the host-side arithmetic of the PQ candidate scan (nvdb_pq.cpp, kernels_pq.h; DESIGN.md section 4 "PQ candidate
 // scan"): which shapes a PQ shadow takes, the encode kernel's compile-time sub-vector bound, how many queries' tables a scan
 // workgroup holds in LDS, how its lanes load their codes, how many queries one sub-batch's tables may serve, and the trainer's
-// chunk, LDS and partial-sum sizes (kernels_pq_train.h).  Plain C++ with no HIP in it, like the other plans.
+// chunk, LDS and partial-sum sizes (kernels_pq_train.h; kernels_pq4_train.h for 16 codewords).  Plain C++ with no HIP in it, like the
+// other plans.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -100,6 +101,26 @@ inline const char* pq4_shape_check(uint32_t dim, uint32_t M, bool residual, bool
   if (residual && dim > PQ_BASE_DIM_MAX) { unsupported = true; return "dim <= 4096 for a residual 4-bit shadow (the base terms' centroid stage)"; }
   return nullptr;
 }
+
+// ---- the 16-codeword trainer (nvdb_hip_pq4_train, kernels_pq4_train.h): the 8-bit trainer's chunk and training-set rules
+constexpr uint32_t PQ4_TRAIN_MIN_ROWS = PQ4_KSUB;   // a start needs 16 distinct training rows
+// sub-quantisers a step workgroup owns for the build dmax: a row contributes at most 64 f32 elements (8, 8, 4, 2 at dmax 4, 8, 16,
+// 32; M % 8 == 0 makes each divide M)
+constexpr uint32_t pq4_train_sq(uint32_t dmax) { return dmax <= 8 ? 8u : 64u / dmax; }
+// dwords between two rows of the tile's sub-vectors in LDS: the group's elements plus one, ODD -- phase 1 writes with lane = row,
+// phase 2 reads with lane = column, and neither hits a bank twice whichever power of two the bank count is
+constexpr uint32_t pq4_train_stride(uint32_t dmax) { return pq4_train_sq(dmax) * dmax + 1; }
+// the step kernel's LDS for the build dmax: fp64 wave sums [4][sq], codewords [sq][16][dmax] f32, 256 code dwords, the tile's
+// sub-vectors [256][stride] f32 -- at most 71936 bytes (dmax 8; 37120 at dmax 4): two workgroups in a CU's 160 KB
+constexpr size_t pq4_train_lds(uint32_t dmax) {
+  return 4 * static_cast<size_t>(pq4_train_sq(dmax)) * 8 + static_cast<size_t>(pq4_train_sq(dmax)) * PQ4_KSUB * dmax * 4 + 256 * 4 +
+         256 * static_cast<size_t>(pq4_train_stride(dmax)) * 4;
+}
+static_assert(2 * pq4_train_lds(4) <= 160 * 1024 && 2 * pq4_train_lds(8) <= 160 * 1024 && 2 * pq4_train_lds(16) <= 160 * 1024 &&
+                  2 * pq4_train_lds(32) <= 160 * 1024,
+              "two step workgroups per CU");
+// bytes of the per-chunk fp64 partial sums
+constexpr uint64_t pq4_train_partial_bytes(uint64_t m, uint32_t dim) { return pq_train_chunks(m) * PQ4_KSUB * dim * 8; }
 
 // bytes of one row's codes and of one query's tables ([M][16] f32) under either width
 constexpr uint32_t pq_row_bytes(uint32_t M, uint32_t nbits) { return nbits == 4 ? M / 2 : M; }

@@ -50,6 +50,7 @@ EXPORTS = [
     "nvdb_hip_pq_build_opq", "nvdb_hip_pq_train_opq", "nvdb_hip_pq_rotation", "nvdb_hip_pq_rotated_rows", "nvdb_hip_pq_rotate",
     "nvdb_hip_ivf_pq_build_opq", "nvdb_hip_ivf_pq_train_opq",
     "nvdb_hip_pq4_build", "nvdb_hip_ivf_pq4_build", "nvdb_hip_pq_bits",
+    "nvdb_hip_pq4_train", "nvdb_hip_ivf_pq4_train",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -242,6 +243,8 @@ def _bind(L, dev):
     L.nvdb_hip_pq_kind.argtypes = [vp, C.POINTER(u32)]
     L.nvdb_hip_pq4_build.argtypes = [vp, vp, vp, u32, u32]
     L.nvdb_hip_ivf_pq4_build.argtypes = [vp, vp, vp, u32, u32]
+    L.nvdb_hip_pq4_train.argtypes = [vp, vp, u32, u32, u64, u64, vp, vp, vp, u32]
+    L.nvdb_hip_ivf_pq4_train.argtypes = [vp, vp, u32, u32, u64, u64, vp, vp, vp, u32]
     L.nvdb_hip_pq_bits.argtypes = [vp, C.POINTER(u32)]
     L.nvdb_hip_pq_reconstruct.argtypes = [vp, u64, u64, vp]
     L.nvdb_hip_pq_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
@@ -418,17 +421,21 @@ def _pq_build(owner, plain, resid, opq, pq4, dim, codebooks, residual, rotation)
         owner._chk(opq(owner.h, rotation.ctypes.data, codebooks.ctypes.data, codebooks.shape[0], 1 if residual else 0))
 
 
-def _pq_train(owner, fn, dim, M, iters, seed, max_train_rows, init, want_err, rotation=None, residual=False):
-    """HipContext.pq_train / IvfIndex.pq_train: fn is the entry point for owner.h (the _opq one where rotation is given).  A bad M
-    reaches the library (dsub 1 stands in)."""
-    dsub = dim // M if M and dim % M == 0 else 1
+def _pq_train(owner, fn, dim, M, iters, seed, max_train_rows, init, want_err, rotation=None, residual=False, pq4=None, bits=8):
+    """HipContext.pq_train / IvfIndex.pq_train: fn is the entry point for owner.h (the _opq one where rotation is given); pq4: the
+    one call for 16-codeword codebooks (bits=4).  A bad M reaches the library (dsub 1 stands in)."""
+    if bits not in (4, 8):
+        raise ValueError("bits must be 8 or 4")
+    dsub, ksub = dim // M if M and dim % M == 0 else 1, 16 if bits == 4 else 256
     if init is not None:
-        init = np.ascontiguousarray(init, dtype=np.float32).reshape(M, 256, dsub)
-    out = np.zeros((M, 256, dsub), dtype=np.float32)
+        init = np.ascontiguousarray(init, dtype=np.float32).reshape(M, ksub, dsub)
+    out = np.zeros((M, ksub, dsub), dtype=np.float32)
     err = np.zeros(iters, dtype=np.float64)
     args = (M, iters, seed, max_train_rows, init.ctypes.data if init is not None else None, out.ctypes.data,
             err.ctypes.data if want_err and iters else None)
-    if rotation is None:
+    if bits == 4:
+        owner._chk(pq4(owner.h, None if rotation is None else _rotation_arg(rotation, dim).ctypes.data, *args, 1 if residual else 0))
+    elif rotation is None:
         owner._chk(fn(owner.h, *args))
     else:
         owner._chk(fn(owner.h, _rotation_arg(rotation, dim).ctypes.data, *args, 1 if residual else 0))
@@ -763,12 +770,14 @@ class HipContext:
         _pq_build(self, self.lib.nvdb_hip_pq_build, self.lib.nvdb_hip_pq_build_residual, self.lib.nvdb_hip_pq_build_opq, self.lib.nvdb_hip_pq4_build,
                   self.corpus_info()["dim"] if rotation is not None else 0, codebooks, residual, rotation)
 
-    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False, rotation=None):
+    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False, rotation=None, bits=8):
         """Codebooks [M, 256, dim / M] f32 by Lloyd's iteration over the resident rows on the device (init None: 256 drawn training
         rows per sub-quantiser); with want_err also the [iters] f64 mean winning distances.  residual: over the rows' residuals to
-        their lists' centroids.  rotation: over the rotated training rows.  Does not build: pq_build(result, residual, rotation)."""
+        their lists' centroids.  rotation: over the rotated training rows.  bits=4: [M, 16, dim / M] for a 4-bit shadow (init
+        likewise; M % 8 == 0); any other width raises ValueError.  Does not build: pq_build(result, residual, rotation)."""
         fn = self.lib.nvdb_hip_pq_train_opq if rotation is not None else self.lib.nvdb_hip_pq_train_residual if residual else self.lib.nvdb_hip_pq_train
-        return _pq_train(self, fn, self.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err, rotation, residual)
+        return _pq_train(self, fn, self.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err, rotation, residual,
+                         self.lib.nvdb_hip_pq4_train, bits)
 
     def pq_rotation(self):
         """The matrix [dim, dim] f32 the shadow was built under, or None (no shadow, or one without a rotation)."""
@@ -1078,11 +1087,12 @@ class IvfIndex:
         _pq_build(self, self.lib.nvdb_hip_ivf_pq_build, self.lib.nvdb_hip_ivf_pq_build_residual, self.lib.nvdb_hip_ivf_pq_build_opq, self.lib.nvdb_hip_ivf_pq4_build,
                   self.ctx.corpus_info()["dim"] if rotation is not None else 0, codebooks, residual, rotation)
 
-    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False, rotation=None):
+    def pq_train(self, M, iters, seed, max_train_rows=0, init=None, want_err=False, residual=False, rotation=None, bits=8):
         """HipContext.pq_train over the list-ordered rows."""
         lib = self.lib
         fn = lib.nvdb_hip_ivf_pq_train_opq if rotation is not None else lib.nvdb_hip_ivf_pq_train_residual if residual else lib.nvdb_hip_ivf_pq_train
-        return _pq_train(self, fn, self.ctx.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err, rotation, residual)
+        return _pq_train(self, fn, self.ctx.corpus_info()["dim"], M, iters, seed, max_train_rows, init, want_err, rotation, residual,
+                         lib.nvdb_hip_ivf_pq4_train, bits)
 
     def pq_rotation(self):
         """HipContext.pq_rotation of the index's context."""

@@ -37,10 +37,16 @@ per-dimension deviation falls as 1 / sqrt(1 + t / 8), t the dimension.
     python tools_dev/bench_pq.py [the same arguments] --bits 4 [--clustered]
 
 The 8-bit shadow at M beside 4-BIT shadows at 2 M (equal bytes per row) and at M (half the bytes), two copies of the same index as
-above: copy a keeps the 8-bit shadow, copy b takes the two 4-bit ones in turn.  All codebooks are trained here in numpy on the same
-20000 list-ordered rows (train_codebooks with 256 or 16 codewords, four rounds; the device trainer has no 16-codeword build).
-Reports the wall time of the builds, the fp64 quantisation error, and, alternating the two copies call by call, ivf_pq_search /
-ivf_pq_refine times and recall@10."""
+above: copy a keeps the 8-bit shadow, copy b takes the two 4-bit ones in turn.  All codebooks are trained on the device over the same
+262144 list-ordered rows (pq_train with bits=8 or bits=4, four rounds).  Reports seconds per Lloyd iteration of each training, the
+wall time of the builds, the fp64 quantisation error, and, alternating the two copies call by call, ivf_pq_search / ivf_pq_refine
+times and recall@10.
+
+    python tools_dev/bench_pq.py <rows> <dim> <f16|f32> 0 <M> --train
+
+The trainers alone over every one of <rows> synthetic rows: seconds per Lloyd iteration of pq_train(bits=4) and pq_train(bits=8) at
+the same M, alternating the widths run by run (lloyd_seconds), and one round of the numpy trainer over 20000 of the rows with 16
+codewords."""
 import json
 import os
 import sys
@@ -91,6 +97,38 @@ def median_s(f, reps=5):
     for _ in range(reps):
         t0 = time.perf_counter(); f(); ts.append(time.perf_counter() - t0)
     return float(np.median(ts)), ts
+
+
+def lloyd_seconds(owner, M, bits, rounds, max_train_rows=0, reps=7):
+    """Seconds per Lloyd iteration of owner.pq_train: wall time of a call with `rounds` iterations minus that of one with none (the
+    gather, the start and the copies are in both), over rounds; reps pairs after one warm-up pair -> (median, all)."""
+    def call(iters):
+        t0 = time.perf_counter(); owner.pq_train(M, iters, 7, max_train_rows=max_train_rows, bits=bits); return time.perf_counter() - t0
+    call(rounds), call(0)
+    ts = [(call(rounds) - call(0)) / rounds for _ in range(reps)]
+    return float(np.median(ts)), ts
+
+
+def main_train(rows, dim, dname, dtype, M):
+    rounds = 4
+    ctx = nvdb_amd.HipContext(0)
+    ctx.generate_corpus(20240613, rows, dim, dtype)
+    out = dict(mode="train", rows=rows, dim=dim, dtype=dname, M=M, rounds=rounds)
+    for rep in range(2):                                                # the widths alternate; the second pass is the record
+        for bits in (4, 8):
+            s, every = lloyd_seconds(ctx, M, bits, rounds)
+            out[f"pq{bits}"] = dict(s_per_iteration=s, all_s=every, out_err=ctx.pq_train(M, rounds, 7, bits=bits, want_err=True)[1].tolist())
+    pick = np.arange(20000, dtype=np.int64) * rows // 20000
+    raw = np.concatenate([ctx.download_rows(int(r), 1)[0] for r in pick])
+    sample = (raw.view(np.float16) if dtype == nvdb_amd.DT_F16 else raw).astype(np.float32)
+    host_s, host_all = median_s(lambda: train_codebooks(sample, M, 1, 7, ksub=16), reps=3)
+    out["numpy_20000_rows_16_codewords"] = dict(s_per_iteration=host_s, all_s=host_all)
+    for bits in (4, 8):
+        d = out[f"pq{bits}"]
+        print(f"pq_train(bits={bits}) M={M}, {rows} rows: {d['s_per_iteration'] * 1e3:.3f} ms per Lloyd iteration (median of 7; min {min(d['all_s']) * 1e3:.3f}, max {max(d['all_s']) * 1e3:.3f})")
+    print(f"numpy, 16 codewords, 20000 rows: {host_s:.3f} s per round (median of 3; min {min(host_all):.3f}, max {max(host_all):.3f})")
+    print(json.dumps(out))
+    ctx.close()
 
 
 def alternate_ms(fa, fb, calls, warmup):
@@ -273,20 +311,21 @@ def main_bits(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, clustered
     cents = src.train_centroids(nlist, 2, seed, max_train_rows=262144)
     a, b = nvdb_amd.IvfIndex(src, cents), nvdb_amd.IvfIndex(src, cents)
     src.close()
-    pick = np.arange(20000, dtype=np.int64) * rows // 20000
-    raw = np.concatenate([a.ctx.download_rows(int(r), 1)[0] for r in pick])
-    sample = (raw.view(np.float16) if dtype == nvdb_amd.DT_F16 else raw).astype(np.float32)
     blocks = np.sort(rs.choice(rows - 1000, 20, replace=False))
 
     def shadow(ix, m, ksub):
-        cb = train_codebooks(sample, m, rounds, 7, ksub=ksub)
+        bits = 4 if ksub == 16 else 8
+        cb = ix.pq_train(m, rounds, 7, max_train_rows=262144, bits=bits)
+        it_s, it_all = lloyd_seconds(ix, m, bits, rounds, max_train_rows=262144, reps=3)
+        print(f"{bits}-bit M={m}: pq_train over {min(rows, 262144)} rows {it_s * 1e3:.3f} ms per Lloyd iteration (median of 3: {' '.join(f'{t * 1e3:.3f}' for t in it_all)})")
         build_s, build_all = median_s(lambda: ix.pq_build(cb), reps=3)
         err = 0.0
         for blk in blocks:
             r = ix.ctx.download_rows(int(blk), 1000)[0]
             xs = (r.view(np.float16) if dtype == nvdb_amd.DT_F16 else r).astype(np.float64)
             err += ((xs - ix.pq_reconstruct(int(blk), 1000).astype(np.float64)) ** 2).sum()
-        d = dict(M=m, bits=ix.pq_bits(), bytes_per_row=ix.ctx.pq_info()["code_bytes"] // rows, pq_build_s=build_s, pq_build_all_s=build_all,
+        d = dict(M=m, bits=ix.pq_bits(), bytes_per_row=ix.ctx.pq_info()["code_bytes"] // rows, pq_train_s_per_iteration=it_s, pq_train_all_s=it_all,
+                 pq_build_s=build_s, pq_build_all_s=build_all,
                  quant_err_per_row=err / (len(blocks) * 1000))
         print(f"{d['bits']}-bit M={m}: {d['bytes_per_row']} bytes per row, pq_build {build_s:.3f} s (median of 3), fp64 |x - xhat|^2 per row {d['quant_err_per_row']:.6e}")
         return d
@@ -325,6 +364,8 @@ def main():
     batch = int(a[5]) if len(a) > 5 else 1024
     calls = int(a[6]) if len(a) > 6 else 10
     warmup = int(a[7]) if len(a) > 7 else 2
+    if "--train" in flags:
+        return main_train(rows, dim, dname, dtype, M)
     if "--bits" in flags:
         return main_bits(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, "--clustered" in flags)
     if "--opq" in flags:
