@@ -808,7 +808,29 @@ nvdb_status nvdb_hip_refine_l2_topk_dev(nvdb_hip_ctx* ctx, const float* dev_quer
  *   out_err[i]  nvdb_hip_pq_train's rule unchanged: the tile tree, the tiles, chunks and sub-quantisers in order, one division.
  * Same arguments + same corpus -> the same bytes (no atomics).  Cost: m * dim * 4 bytes for the rows as f32 and ceil(m / 4096) * 16 *
  * dim * 8 bytes of partial sums; per iteration m * dim * 16 fmas and one read of the f32 rows, a line of a row fetched once.
- * Out of scope: cluster splitting and k-means++ starts in the trainers, L2 asymmetric-distance tables, learning the rotation, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
+ * The L2 METRIC (nvdb_hip_pq_set_metric; FAISS IndexIVFPQ under METRIC_L2, what the reference builds): the scan ranks by the squared
+ * L2 distance to the row's reconstruction instead of the dot product.  |q - xhat|^2 = |q|^2 - 2 q.xhat + |xhat|^2 and q.xhat is the
+ * score above, base term included, for every kind of shadow: the L2 scan is the dot scan plus ONE f32 per row, h[r], computed once
+ * per shadow and subtracted at the scan's sink; no per-list tables.  The arithmetic, fixed:
+ *   xhat[r][t]  the bits nvdb_hip_pq_reconstruct returns for row r (the codewords side by side; the transpose product under a
+ *               rotation; plus the centroid under a residual shadow).
+ *   n[r]        sum_t xhat[r][t]^2 in fp32: t ascending from 0, one fma per element (acc = fma(x, x, acc)), the accumulator from 0 --
+ *               whatever the launch, the tile or the row's place in it.
+ *   h[r]        0.5f * n[r].
+ *   z(q, r)     s(q, r) - h[r], ONE fp32 subtraction; s the dot metric's score bits for this shadow (the sum over m, then the base
+ *               term under a residual shadow).  A NaN z is no candidate: neither returned nor counted.  -inf is a candidate.
+ *   order       z descending, then local row ascending: the select above, unchanged.
+ *   qq[q]       |q|^2 of the UNROTATED query by the base term's rule: 64 partial sums over t = l, l + 64, .., one fma each, from 0;
+ *               then the six-round butterfly.
+ *   distance    dist(q, r) = fma(-2, z, qq[q]), one fma: non-decreasing along the order above; equal distances of different z keep
+ *               the order of z.  Padding is UINT64_MAX / +inf.
+ *   fused       nvdb_hip_pq_refine_ivf and nvdb_hip_ivf_pq_refine take the R candidates by the order above, then refine as before;
+ *               the distance above is not formed.
+ * The metric belongs to the shadow: 0 (dot product) after every build, and whatever frees or replaces a shadow frees h and returns
+ * it to 0, so every call sequence without nvdb_hip_pq_set_metric behaves bit for bit as before.  Cost: 4 bytes per row of HBM (40 MB
+ * at 10M rows), read once per (row, group of queries) beside the M or M / 2 code bytes; nvdb_hip_pq_set_metric(1) is one pass over
+ * the codes (a rotated shadow: reconstruction slab by slab, n * dim * dim multiply-adds).
+ * Out of scope: cluster splitting and k-means++ starts in the trainers, per-list or precomputed L2 tables, an L2 coarse step, norms carried through insertion and compaction, learning the rotation, row masks on the PQ scan, codes carried through compaction and insertion, fp16 tables,
  * pruning inside the scan, the device group, _dev stream forms, the nvdb:: C++ host layer, u8-quantised tables and in-register
  * shuffles for the 4-bit scan, code widths other than 4 and 8.
  * ------------------------------------------------------------------------------------------- */
@@ -894,6 +916,17 @@ nvdb_status nvdb_hip_pq4_train(nvdb_hip_ctx* ctx, const float* rotation /* [dim]
                                uint32_t residual);
 /* *nbits (optional) = 0 without a shadow, otherwise its code width: 8 or 4 */
 nvdb_status nvdb_hip_pq_bits(nvdb_hip_ctx* ctx, uint32_t* nbits);
+/* The metric the PQ searches below rank by (the L2 METRIC above): 0 = dot product, the default after every build; 1 = squared L2.
+ * 1 computes h for the shadow the context holds (no shadow -> NVDB_ERR_INVALID, "no PQ codes"; no corpus -> NVDB_ERR_NO_CORPUS); 0
+ * frees it (and is NVDB_OK without a shadow); any other value -> NVDB_ERR_INVALID.  On any failure nothing has changed.  Under
+ * metric 1 nvdb_hip_pq_search_partitions, _search_ivf and the index form return in out_scores the distances, ASCENDING, padding
+ * +inf; ids, counts, stats, the sub-batch cut and timing are as under metric 0. */
+nvdb_status nvdb_hip_pq_set_metric(nvdb_hip_ctx* ctx, uint32_t metric);
+/* *metric = the metric in force (0 without a shadow); a null pointer -> NVDB_ERR_INVALID */
+nvdb_status nvdb_hip_pq_metric(nvdb_hip_ctx* ctx, uint32_t* metric);
+/* out[nrows] f32 (host) = n[r] of resident rows [row0, row0 + nrows) (the L2 METRIC above; returned as h + h).  Range errors as
+ * nvdb_hip_pq_reconstruct; NVDB_ERR_INVALID unless the metric is 1 */
+nvdb_status nvdb_hip_pq_norms(nvdb_hip_ctx* ctx, uint64_t row0, uint64_t nrows, float* out /* [nrows] */);
 /* every output optional; all 0 without codes.  code_bytes = n * M (a 4-bit shadow: n * M / 2) */
 nvdb_status nvdb_hip_pq_info(nvdb_hip_ctx* ctx, uint32_t* M, uint32_t* dsub, uint64_t* code_bytes);
 /* *residual (optional) = 1 where the context holds a residual shadow, 0 for a non-residual one or none */
@@ -949,6 +982,8 @@ nvdb_status nvdb_hip_ivf_pq4_build(nvdb_hip_ivf* ivf, const float* rotation, con
 /* nvdb_hip_pq4_train on the index's context: the training rows are positions of the list-ordered copy */
 nvdb_status nvdb_hip_ivf_pq4_train(nvdb_hip_ivf* ivf, const float* rotation, uint32_t M, uint32_t iters, uint64_t seed, uint64_t max_train_rows,
                                    const float* init, float* out_codebooks, double* out_err, uint32_t residual);
+/* nvdb_hip_pq_set_metric on the index's context */
+nvdb_status nvdb_hip_ivf_pq_set_metric(nvdb_hip_ivf* ivf, uint32_t metric);
 nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe,
                                    uint64_t* out_ids, float* out_scores, uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing);
 nvdb_status nvdb_hip_ivf_pq_refine(nvdb_hip_ivf* ivf, const float* queries, uint32_t nq, uint32_t K, uint32_t R, uint32_t nprobe,

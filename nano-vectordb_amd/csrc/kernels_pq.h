@@ -130,10 +130,12 @@ __device__ __forceinline__ void pq_lookup4(uint32_t w, const char* lutm, uint32_
 template <bool W16> struct PqPiece { using T = uint32_t; };
 template <> struct PqPiece<true> { using T = uint4; };
 
-// the tile loop of one wave for an item of at most NG queries (its tables are in LDS)
-template <int NG, bool W16>
+// the tile loop of one wave for an item of at most NG queries (its tables are in LDS).  L2 (kernels_pq_l2.h; false: no instruction
+// of it): hn[row], half the squared norm of the row's reconstruction, rides with the first piece of the row's codes and leaves the
+// score at the sink, one fp32 subtraction
+template <int NG, bool W16, bool L2 = false>
 __device__ __forceinline__ void pq_scan_tiles(const uint8_t* __restrict__ codes, uint32_t M, const PartItem& it, const uint32_t* __restrict__ dst,
-                                              const char* lut, Cand* __restrict__ cand, uint32_t wave, uint32_t lane) {
+                                              const char* lut, Cand* __restrict__ cand, uint32_t wave, uint32_t lane, const float* __restrict__ hn = nullptr) {
   using Piece = typename PqPiece<W16>::T;
   constexpr uint32_t PB = sizeof(Piece);
   const uint32_t np = M / PB, qstride = M * (PQ_KSUB * 4);
@@ -143,13 +145,17 @@ __device__ __forceinline__ void pq_scan_tiles(const uint8_t* __restrict__ codes,
   for (int g = 0; g < NG; ++g) dbase[g] = static_cast<uint32_t>(g) < it.nqg ? dst[it.doff + g] : 0u;
   auto load = [&](uint32_t row, uint32_t p) { return *reinterpret_cast<const Piece*>(codes + static_cast<uint64_t>(row) * M + p * PB); };
   Piece nxt{};
+  [[maybe_unused]] float hnxt = 0.f;
   if (wave < ntiles && lo + wave * 64u + lane < hi) nxt = load(lo + wave * 64u + lane, 0u);
+  if constexpr (L2) { if (wave < ntiles && lo + wave * 64u + lane < hi) hnxt = hn[lo + wave * 64u + lane]; }
   for (uint32_t tile = wave; tile < ntiles; tile += PART_WAVES) {
     const uint32_t row = lo + tile * 64u + lane;
     const bool valid = row < hi;                                       // (a lane beyond the segment looks code 0 up and stores nothing)
     Piece cur = nxt;
     nxt = Piece{};
+    [[maybe_unused]] const float hrow = hnxt;
     if (tile + PART_WAVES < ntiles && row + 64u * PART_WAVES < hi) nxt = load(row + 64u * PART_WAVES, 0u);
+    if constexpr (L2) { if (tile + PART_WAVES < ntiles && row + 64u * PART_WAVES < hi) hnxt = hn[row + 64u * PART_WAVES]; }
     float acc[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) acc[g] = 0.f;
@@ -170,8 +176,10 @@ __device__ __forceinline__ void pq_scan_tiles(const uint8_t* __restrict__ codes,
     if (valid) {
 #pragma unroll
       for (int g = 0; g < NG; ++g)
-        if (static_cast<uint32_t>(g) < it.nqg)
+        if (static_cast<uint32_t>(g) < it.nqg) {
+          if constexpr (L2) acc[g] = acc[g] - hrow;                    // z = s - h
           cand[static_cast<uint64_t>(dbase[g]) + (row - lo)] = acc[g] == acc[g] ? Cand{acc[g], row} : Cand{NEG_INF, 0xFFFFFFFFu};
+        }
     }
   }
 }

@@ -193,11 +193,11 @@ __device__ __forceinline__ void pq4_lookup8(uint32_t w, const char* lutm, uint32
 }
 
 // one work item of at most NG queries: its tables into the image [NG / W][M][16][W] (queries beyond nqg: zeros), behind them the
-// queries' slab offsets [NG] u32 and base terms [NG] f32; then the tile loop of pq_scan_tiles over rows of M / 2 bytes
-template <int NG, bool W16, bool RESID>
+// queries' slab offsets [NG] u32 and base terms [NG] f32; then the tile loop of pq_scan_tiles over rows of M / 2 bytes (L2 / hn as there)
+template <int NG, bool W16, bool RESID, bool L2 = false>
 __device__ __forceinline__ void pq4_scan_item(const uint8_t* __restrict__ codes, uint32_t M, const PartItem& it, const uint32_t* __restrict__ qidx,
                                               const uint32_t* __restrict__ dst, const float* __restrict__ base, const float* __restrict__ lut,
-                                              char* lds, Cand* __restrict__ cand, uint32_t tid) {
+                                              char* lds, Cand* __restrict__ cand, uint32_t tid, const float* __restrict__ hn = nullptr) {
   constexpr int W = NG >= 4 ? 4 : NG, NS = NG / W;
   using Slot = typename Pq4Slot<W>::T;
   using Piece = typename PqPiece<W16>::T;
@@ -236,13 +236,17 @@ __device__ __forceinline__ void pq4_scan_item(const uint8_t* __restrict__ codes,
   const uint32_t lo = it.row_lo, hi = it.row_hi, ntiles = (hi - lo + 63u) / 64u;
   auto load = [&](uint32_t row, uint32_t p) { return *reinterpret_cast<const Piece*>(codes + static_cast<uint64_t>(row) * rb + p * PB); };
   Piece nxt{};
+  [[maybe_unused]] float hnxt = 0.f;
   if (wave < ntiles && lo + wave * 64u + lane < hi) nxt = load(lo + wave * 64u + lane, 0u);
+  if constexpr (L2) { if (wave < ntiles && lo + wave * 64u + lane < hi) hnxt = hn[lo + wave * 64u + lane]; }
   for (uint32_t tile = wave; tile < ntiles; tile += PART_WAVES) {
     const uint32_t row = lo + tile * 64u + lane;
     const bool valid = row < hi;                                       // (a lane beyond the segment looks code 0 up and stores nothing)
     Piece cur = nxt;
     nxt = Piece{};
+    [[maybe_unused]] const float hrow = hnxt;
     if (tile + PART_WAVES < ntiles && row + 64u * PART_WAVES < hi) nxt = load(row + 64u * PART_WAVES, 0u);
+    if constexpr (L2) { if (tile + PART_WAVES < ntiles && row + 64u * PART_WAVES < hi) hnxt = hn[row + 64u * PART_WAVES]; }
     float acc[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) acc[g] = 0.f;
@@ -269,6 +273,7 @@ __device__ __forceinline__ void pq4_scan_item(const uint8_t* __restrict__ codes,
         if (static_cast<uint32_t>(g) < it.nqg) {
           float sc = acc[g];
           if constexpr (RESID) sc = reinterpret_cast<const float*>(sd)[NG + g] + acc[g];   // (the one addition the residual form adds)
+          if constexpr (L2) sc = sc - hrow;                                                 // z = s - h
           cand[static_cast<uint64_t>(sd[g]) + (row - lo)] = sc == sc ? Cand{sc, row} : Cand{NEG_INF, 0xFFFFFFFFu};
         }
     }

@@ -142,10 +142,11 @@ static __global__ __launch_bounds__(PQ_BASE_THREADS) void pq_base_kernel(const f
   }
 }
 
-// pq_scan_tiles (kernels_pq.h) restated with the base terms: base[it.qoff + g] is b(query g of the group, the item's partition)
-template <int NG, bool W16>
+// pq_scan_tiles (kernels_pq.h) restated with the base terms: base[it.qoff + g] is b(query g of the group, the item's partition); L2 / hn as there
+template <int NG, bool W16, bool L2 = false>
 __device__ __forceinline__ void pq_scan_resid_tiles(const uint8_t* __restrict__ codes, uint32_t M, const PartItem& it, const uint32_t* __restrict__ dst,
-                                                    const float* __restrict__ base, const char* lut, Cand* __restrict__ cand, uint32_t wave, uint32_t lane) {
+                                                    const float* __restrict__ base, const char* lut, Cand* __restrict__ cand, uint32_t wave, uint32_t lane,
+                                                    const float* __restrict__ hn = nullptr) {
   using Piece = typename PqPiece<W16>::T;
   constexpr uint32_t PB = sizeof(Piece);
   const uint32_t np = M / PB, qstride = M * (PQ_KSUB * 4);
@@ -160,13 +161,17 @@ __device__ __forceinline__ void pq_scan_resid_tiles(const uint8_t* __restrict__ 
   }
   auto load = [&](uint32_t row, uint32_t p) { return *reinterpret_cast<const Piece*>(codes + static_cast<uint64_t>(row) * M + p * PB); };
   Piece nxt{};
+  [[maybe_unused]] float hnxt = 0.f;
   if (wave < ntiles && lo + wave * 64u + lane < hi) nxt = load(lo + wave * 64u + lane, 0u);
+  if constexpr (L2) { if (wave < ntiles && lo + wave * 64u + lane < hi) hnxt = hn[lo + wave * 64u + lane]; }
   for (uint32_t tile = wave; tile < ntiles; tile += PART_WAVES) {
     const uint32_t row = lo + tile * 64u + lane;
     const bool valid = row < hi;                                       // (a lane beyond the segment looks code 0 up and stores nothing)
     Piece cur = nxt;
     nxt = Piece{};
+    [[maybe_unused]] const float hrow = hnxt;
     if (tile + PART_WAVES < ntiles && row + 64u * PART_WAVES < hi) nxt = load(row + 64u * PART_WAVES, 0u);
+    if constexpr (L2) { if (tile + PART_WAVES < ntiles && row + 64u * PART_WAVES < hi) hnxt = hn[row + 64u * PART_WAVES]; }
     float acc[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) acc[g] = 0.f;
@@ -188,7 +193,8 @@ __device__ __forceinline__ void pq_scan_resid_tiles(const uint8_t* __restrict__ 
 #pragma unroll
       for (int g = 0; g < NG; ++g)
         if (static_cast<uint32_t>(g) < it.nqg) {
-          const float sc = bterm[g] + acc[g];                          // (the one addition the residual form adds)
+          float sc = bterm[g] + acc[g];                                // (the one addition the residual form adds)
+          if constexpr (L2) sc = sc - hrow;                            // z = s - h
           cand[static_cast<uint64_t>(dbase[g]) + (row - lo)] = sc == sc ? Cand{sc, row} : Cand{NEG_INF, 0xFFFFFFFFu};
         }
     }

@@ -104,6 +104,12 @@ struct PqState {
   float* rot = nullptr;                            // A [dim][dim] f32, nullptr: no rotation
   float* rot_t = nullptr;                          // A^T [dim][dim] f32 (reconstruction)
   DevBuf qrot;                                     // [queries of a sub-batch][dim] f32: A q, grow-only
+  // the metric the searches rank by (nvdb_hip_pq_set_metric; kernels_pq_l2.h): 0 dot product, 1 squared L2 -- then half_norm holds
+  // h[r] = |xhat_r|^2 / 2 of every row's reconstruction, subtracted at the scan's sink.  Lives and dies with the shadow: whatever
+  // replaces or frees it (pq_drop) returns the metric to 0
+  uint32_t metric = 0;
+  float* half_norm = nullptr;                      // [n] f32, nullptr under the dot metric
+  DevBuf qq;                                       // [queries of a sub-batch] f32: |q|^2, grow-only
 };
 
 }  // namespace nvdbhip

@@ -594,6 +594,11 @@ nvdb_status nvdb_hip_ivf_pq4_train(nvdb_hip_ivf* ix, const float* rotation, uint
   return ivf_forward(ix, nvdb_hip_pq4_train(ix->ctx, rotation, M, iters, seed, max_train_rows, init, out_codebooks, out_err, residual));
 }
 
+nvdb_status nvdb_hip_ivf_pq_set_metric(nvdb_hip_ivf* ix, uint32_t metric) {
+  if (!ix) return NVDB_ERR_INVALID;
+  return ivf_forward(ix, nvdb_hip_pq_set_metric(ix->ctx, metric));
+}
+
 nvdb_status nvdb_hip_ivf_pq_search(nvdb_hip_ivf* ix, const float* queries, uint32_t nq, uint32_t R, uint32_t nprobe, uint64_t* out_ids, float* out_scores,
                                    uint32_t* out_counts, uint32_t* out_probe, nvdb_hip_timing* timing) {
   if (!ix) return NVDB_ERR_INVALID;

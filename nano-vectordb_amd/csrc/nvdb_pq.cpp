@@ -29,7 +29,11 @@
 // says which of the two sets of kernels (encode, tables, scan, reconstruct) every call above launches -- groups of pq4_group(M)
 // queries, which fill the work list's classes 1 and 2 as well: the items of all three are contiguous in the image and one launch
 // takes them --; the pass, the base terms, the rotation, the select and the refine do not know the width.
-// Entry points: nvdb_hip_pq_train / _build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf,
+// Under the L2 METRIC (nvdb_hip_pq_set_metric(1); kernels_pq_l2.h) the shadow also holds h[r] = |xhat_r|^2 / 2 -- pq_norms_kernel
+// straight from the codes, or, under a rotation, pq_rownorm_kernel over reconstruct_slab's rows slab by slab -- and a search
+// launches the L2 builds of the scans (z = s - h at the sink), pq_qnorm_kernel beside the tables and pq_l2_emit_kernel behind the
+// select (z -> fma(-2, z, |q|^2), padding +inf); the fused call only takes the order.  PqState::metric dies with the shadow.
+// Entry points: nvdb_hip_pq_set_metric / _metric / _norms (nvdb_hip_ivf_pq_set_metric), nvdb_hip_pq_train / _build / _info / _download_codes / _search_partitions / _search_ivf / _refine_ivf,
 // nvdb_hip_pq_build_residual / _train_residual / _reconstruct / _kind and nvdb_hip_pq_build_opq / _train_opq / _rotation /
 // _rotated_rows / _rotate, nvdb_hip_pq4_build / _pq4_train / _pq_bits; the index forms (nvdb_hip_ivf_pq_*, nvdb_ivf.cpp) call them on the index's context and map the ids.
 #include "nvdb_parts.h"
@@ -39,6 +43,7 @@
 #include "kernels_pq_rotate.h"
 #include "kernels_pq4.h"
 #include "kernels_pq4_train.h"
+#include "kernels_pq_l2.h"
 #include "ivf_layout.h"
 
 namespace nvdbhip {
@@ -55,6 +60,8 @@ void pq_drop(nvdb_hip_ctx* c) {
   if (pq->rot) (void)hipFree(pq->rot);
   if (pq->rot_t) (void)hipFree(pq->rot_t);
   if (pq->qrot.p) (void)hipFree(pq->qrot.p);
+  if (pq->half_norm) (void)hipFree(pq->half_norm);
+  if (pq->qq.p) (void)hipFree(pq->qq.p);
   delete pq;
   c->pq = nullptr;
 }
@@ -344,6 +351,18 @@ nvdb_status launch_scan_g(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, con
     HIPCHK(c, hipGetLastError());
     return NVDB_OK;
   };
+  auto go_l2 = [&](auto kernel) -> nvdb_status {                       // the L2 builds: one signature for both kinds, h behind the tables
+    if (lds > 64 * 1024)
+      if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(kernel), PART_LDS_LIMIT)) return st;
+    kernel<<<nitems, PQ_SCAN_THREADS, lds, s>>>(pq.codes, pq.M, im.items, im.qidx, im.dst, static_cast<const float*>(pq.base.p),
+                                                static_cast<const float*>(pq.lut.p), pq.half_norm, static_cast<Cand*>(c->parts->cand.p));
+    HIPCHK(c, hipGetLastError());
+    return NVDB_OK;
+  };
+  if (pq.metric) {
+    if (pq.residual) return pq_wide_codes(pq.M) ? go_l2(pq_scan_l2_kernel<G, true, true>) : go_l2(pq_scan_l2_kernel<G, false, true>);
+    return pq_wide_codes(pq.M) ? go_l2(pq_scan_l2_kernel<G, true, false>) : go_l2(pq_scan_l2_kernel<G, false, false>);
+  }
   if (pq.residual) return pq_wide_codes(pq.M) ? go_resid(pq_scan_resid_kernel<G, true>) : go_resid(pq_scan_resid_kernel<G, false>);
   return pq_wide_codes(pq.M) ? go(pq_scan_kernel<G, true>) : go(pq_scan_kernel<G, false>);
 }
@@ -360,6 +379,18 @@ nvdb_status launch_scan4_g(nvdb_hip_ctx* c, hipStream_t s, const PqState& pq, co
     HIPCHK(c, hipGetLastError());
     return NVDB_OK;
   };
+  auto go_l2 = [&](auto kernel) -> nvdb_status {
+    if (lds > 64 * 1024)
+      if (nvdb_status st = raise_lds_limit(c, reinterpret_cast<const void*>(kernel), PART_LDS_LIMIT)) return st;
+    kernel<<<nitems, PQ_SCAN_THREADS, lds, s>>>(pq.codes, pq.M, im.items, im.qidx, im.dst, static_cast<const float*>(pq.base.p),
+                                                static_cast<const float*>(pq.lut.p), pq.half_norm, static_cast<Cand*>(c->parts->cand.p));
+    HIPCHK(c, hipGetLastError());
+    return NVDB_OK;
+  };
+  if (pq.metric) {
+    if (pq.residual) return pq4_wide_codes(pq.M) ? go_l2(pq4_scan_l2_kernel<G, true, true>) : go_l2(pq4_scan_l2_kernel<G, false, true>);
+    return pq4_wide_codes(pq.M) ? go_l2(pq4_scan_l2_kernel<G, true, false>) : go_l2(pq4_scan_l2_kernel<G, false, false>);
+  }
   if (pq.residual) return pq4_wide_codes(pq.M) ? go(pq4_scan_kernel<G, true, true>) : go(pq4_scan_kernel<G, false, true>);
   return pq4_wide_codes(pq.M) ? go(pq4_scan_kernel<G, true, false>) : go(pq4_scan_kernel<G, false, false>);
 }
@@ -402,6 +433,8 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
   const uint64_t budget_bytes = static_cast<uint64_t>(c->opt_largek_budget_mb) << 20;
   const uint64_t budget_entries = budget_bytes / (2 * sizeof(Cand));
   const bool b4 = pq.nbits == 4;
+  const bool l2_out = pq.metric != 0 && !rf;                           // the L2 metric with scores to report: |q|^2 and the emit (fused: z orders, no distance is formed)
+  const float pos_inf = __builtin_huge_valf();
   const uint32_t group = b4 ? pq4_group(pq.M) : pq_group(pq.M);
   const size_t lut_bytes = b4 ? pq4_lut_bytes(pq.M) : pq_lut_bytes(pq.M);
   const uint32_t lut_batch = b4 ? pq4_lut_batch(pq.M, budget_bytes / 4) : pq_lut_batch(pq.M, budget_bytes / 4);
@@ -430,6 +463,8 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
       }
       if (pq.rot)
         if (nvdb_status e = ensure(c, pq.qrot, static_cast<size_t>(b) * c->dim * 4)) return e;
+      if (l2_out)
+        if (nvdb_status e = ensure(c, pq.qq, static_cast<size_t>(b) * 4)) return e;
       return ensure(c, pq.lut, b * lut_bytes);
     });
     if (st) return st;
@@ -439,6 +474,7 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
         if (rf->out_dist) std::fill(rf->out_dist + static_cast<size_t>(q0) * rf->K, rf->out_dist + static_cast<size_t>(q1) * rf->K, 1e30f);
       } else {
         pad_rows(b, R, 0, ids0, sc0, out_counts ? out_counts + q0 : nullptr);
+        if (l2_out) std::fill(sc0, sc0 + static_cast<size_t>(b) * R, pos_inf);
       }
       q0 = q1;
       continue;
@@ -452,6 +488,10 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
     if (b4) pq4_lut_kernel<<<dim3((pq.M + 15u) / 16u, b), 256, 0, s>>>(lut_q, c->dim, pq.M, pq.dsub, pq.codebooks, static_cast<float*>(pq.lut.p));
     else pq_lut_kernel<<<dim3(pq.M / 4u, b), 256, 0, s>>>(lut_q, c->dim, pq.M, pq.dsub, pq.codebooks, static_cast<float*>(pq.lut.p));
     HIPCHK(c, hipGetLastError());
+    if (l2_out) {
+      pq_qnorm_kernel<<<(b + 3u) / 4u, 256, 0, s>>>(static_cast<const float*>(ps->q.p), c->dim, b, static_cast<float*>(pq.qq.p));
+      HIPCHK(c, hipGetLastError());
+    }
     if (pq.residual) {
       pq_base_kernel<<<nparts, PQ_BASE_THREADS, 0, s>>>(static_cast<const float*>(ps->q.p), c->dim, pq.cent, p.im.extra + pstart_at, p.im.qidx,
                                                         static_cast<float*>(pq.base.p));
@@ -460,6 +500,13 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
     if ((st = launch_scan(c, s, pq, p.im, static_cast<uint32_t>(p.wl.nitems)))) return st;
     c->stats.chunks += 1;
     if ((st = pa_sub_select(c, s, sub, p.im, b, R))) return st;
+    if (l2_out) {                                                      // z -> distances where the select left them, padding -> +inf
+      const uint64_t ne = static_cast<uint64_t>(b) * sub.plan.out_k;
+      pq_l2_emit_kernel<<<static_cast<unsigned>((ne + 255) / 256), 256, 0, s>>>(static_cast<const unsigned long long*>(ps->out_ids.p),
+                                                                               static_cast<float*>(ps->out_scores.p), ne, sub.plan.out_k,
+                                                                               static_cast<const float*>(pq.qq.p));
+      HIPCHK(c, hipGetLastError());
+    }
     if (rf) {
       // the candidates stay on the device: [b][out_k] global ids -> u32 local rows -> the refine over this sub-batch's queries
       const uint32_t r_dev = sub.plan.out_k;
@@ -476,6 +523,8 @@ nvdb_status pq_search(nvdb_hip_ctx* c, const char* who, const float* queries, ui
       if (rf->out_dist) HIPCHK(c, hipMemcpyAsync(rf->out_dist + static_cast<size_t>(q0) * rf->K, c->rout_dist.p, no * 4, hipMemcpyDeviceToHost, s));
     }
     if ((st = pa_sub_finish(c, s, sub, b, R, ids0, sc0, out_counts ? out_counts + q0 : nullptr))) return st;
+    for (uint32_t q = 0; l2_out && sub.plan.out_k < R && q < b; ++q)   // (the host's padding beyond the device rows' width)
+      std::fill(sc0 + static_cast<size_t>(q) * R + sub.plan.out_k, sc0 + static_cast<size_t>(q + 1) * R, pos_inf);
     if (rf)
       for (size_t i = 0; i < h_rid.size(); ++i) rf->out_ids[static_cast<size_t>(q0) * rf->K + i] = h_rid[i] == 0xFFFFFFFFu ? ~0ull : c->row_base + h_rid[i];
     c->stats.rows_scanned += p.wl.rows_read;
@@ -501,7 +550,9 @@ nvdb_status pq_search_args(nvdb_hip_ctx* c, const char* who, bool ivf, const flo
                            uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nvdb_hip_timing* timing, bool* done) {
   *done = true;
   if (nvdb_status st = pq_args(c, who)) return st;
-  return parts_topk_args(c, who, ivf, 0, queries, nq, R, probe, nprobe, nullptr, out_ids, out_scores, out_counts, timing, done);
+  const nvdb_status st = parts_topk_args(c, who, ivf, 0, queries, nq, R, probe, nprobe, nullptr, out_ids, out_scores, out_counts, timing, done);
+  if (!st && *done && c->pq->metric && nq && R && nprobe == 0) std::fill(out_scores, out_scores + static_cast<size_t>(nq) * R, __builtin_huge_valf());   // all padding: +inf under L2
+  return st;
 }
 
 // nvdb_hip_pq_build / nvdb_hip_pq_build_residual: on any failure nothing has changed
@@ -586,6 +637,64 @@ nvdb_status pq_build(nvdb_hip_ctx* c, const char* who, bool residual, const floa
   }
   pq_drop(c);
   c->pq = new PqState(fresh);
+  return NVDB_OK;
+}
+
+// the device part of nvdb_hip_pq_reconstruct: rows row0 .. row0 + nr as their codes describe them, enqueued on the context's stream.
+// d_y / d_x: [nr][dim] f32 (d_x: a rotated shadow's rows back in the corpus' space, else not looked at); *xhat: which of the two holds them
+nvdb_status reconstruct_slab(nvdb_hip_ctx* c, const PqState& pq, uint32_t row0, uint32_t nr, float* d_y, float* d_x, const float** xhat) {
+  const unsigned grid = std::min<unsigned>((nr + 3u) / 4u, static_cast<unsigned>(c->num_cu) * 64u);
+  // a rotated shadow: the codewords side by side, times A^T, and only then the centroid
+  const float* cent = pq.residual && !pq.rot ? pq.cent : nullptr;
+  if (pq.nbits == 4) pq4_reconstruct_kernel<<<grid, 256, 0, c->stream>>>(pq.codes, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, cent, row0, nr, d_y);
+  else pq_reconstruct_kernel<<<grid, 256, 0, c->stream>>>(pq.codes, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, cent, row0, nr, d_y);
+  HIPCHK(c, hipGetLastError());
+  *xhat = d_y;
+  if (pq.rot) {
+    if (nvdb_status st = launch_rotate_f32(c, c->stream, d_y, nr, pq.rot_t, d_x)) return st;
+    if (pq.residual) {
+      pq_rotate_add_cent_kernel<<<grid, 256, 0, c->stream>>>(d_x, row0, nr, c->dim, pq.off, pq.nparts, pq.cent);
+      HIPCHK(c, hipGetLastError());
+    }
+    *xhat = d_x;
+  }
+  return NVDB_OK;
+}
+
+// nvdb_hip_pq_set_metric(1): h[r] for the shadow the context holds, into memory of its own; on any failure nothing has changed
+nvdb_status pq_half_norms(nvdb_hip_ctx* c, const char* who, float** out) {
+  const PqState& pq = *c->pq;
+  const std::string w = std::string(who) + ": ";
+  if (c->n > IVF_MAX_ROWS) return fail(c, NVDB_ERR_UNSUPPORTED, w + "corpus shard too large");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const uint32_t n = static_cast<uint32_t>(c->n);
+  TrainMem d_h, d_y, d_x;                                              // d_y / d_x: a rotated shadow's slabs
+  nvdb_status st = train_alloc(c, d_h, pq_norm_bytes(n));
+  if (!st && !pq.rot) {
+    // the codewords' squares straight from the codes: no f32 rows in HBM
+    const unsigned grid = (n + PQ_NORM_TILE - 1u) / PQ_NORM_TILE;
+    auto go = [&](auto kernel) { kernel<<<grid, PQ_NORM_THREADS, 0, s>>>(pq.codes, n, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, pq.cent, d_h.as<float>()); };
+    if (pq.nbits == 4) { if (pq.residual) go(pq_norms_kernel<4, true>); else go(pq_norms_kernel<4, false>); }
+    else { if (pq.residual) go(pq_norms_kernel<8, true>); else go(pq_norms_kernel<8, false>); }
+    if (hipGetLastError() != hipSuccess) st = fail(c, NVDB_ERR_HIP, w + "launch of the norms kernel");
+  } else if (!st) {
+    // a rotation: xhat is the full transpose product -- reconstruct's device part slab by slab, the chain over each f32 slab
+    const uint32_t step = static_cast<uint32_t>(std::min<uint64_t>(n, pq_reconstruct_rows(c->dim)));
+    if (!(st = train_alloc(c, d_y, static_cast<size_t>(step) * c->dim * 4))) st = train_alloc(c, d_x, static_cast<size_t>(step) * c->dim * 4);
+    for (uint32_t r = 0; !st && r < n; r += step) {
+      const uint32_t nr = std::min<uint32_t>(step, n - r);
+      const float* xhat = nullptr;
+      if ((st = reconstruct_slab(c, pq, r, nr, d_y.as<float>(), d_x.as<float>(), &xhat))) break;
+      pq_rownorm_kernel<<<(nr + PQ_NORM_THREADS - 1u) / PQ_NORM_THREADS, PQ_NORM_THREADS, 0, s>>>(xhat, nr, c->dim, d_h.as<float>() + r);
+      if (hipGetLastError() != hipSuccess) st = fail(c, NVDB_ERR_HIP, w + "launch of the row-norm kernel");
+    }
+  }
+  const hipError_t e = hipStreamSynchronize(s);                        // (before the slabs leave scope, whatever happened)
+  if (!st && e != hipSuccess) st = fail(c, NVDB_ERR_HIP, w + hipGetErrorString(e));
+  if (st) { (void)hipGetLastError(); return st; }
+  *out = d_h.as<float>();
+  d_h.p = nullptr;                                                     // (the shadow's from here on)
   return NVDB_OK;
 }
 
@@ -737,24 +846,53 @@ nvdb_status nvdb_hip_pq_reconstruct(nvdb_hip_ctx* c, uint64_t row0, uint64_t nro
     if (nvdb_status st = train_alloc(c, d_x, step * c->dim * 4)) return st;
   for (uint64_t r = 0; r < nrows; r += step) {
     const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(step, nrows - r));
-    const unsigned grid = std::min<unsigned>((nr + 3u) / 4u, static_cast<unsigned>(c->num_cu) * 64u);
-    // a rotated shadow: the codewords side by side, times A^T, and only then the centroid
-    const float* cent = pq.residual && !pq.rot ? pq.cent : nullptr;
-    if (pq.nbits == 4)
-      pq4_reconstruct_kernel<<<grid, 256, 0, c->stream>>>(pq.codes, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, cent, static_cast<uint32_t>(row0 + r), nr, d_y.as<float>());
-    else
-      pq_reconstruct_kernel<<<grid, 256, 0, c->stream>>>(pq.codes, pq.M, pq.dsub, pq.codebooks, pq.off, pq.nparts, cent, static_cast<uint32_t>(row0 + r), nr, d_y.as<float>());
-    HIPCHK(c, hipGetLastError());
-    if (pq.rot) {
-      if (nvdb_status st = launch_rotate_f32(c, c->stream, d_y.as<float>(), nr, pq.rot_t, d_x.as<float>())) return st;
-      if (pq.residual) {
-        pq_rotate_add_cent_kernel<<<grid, 256, 0, c->stream>>>(d_x.as<float>(), static_cast<uint32_t>(row0 + r), nr, c->dim, pq.off, pq.nparts, pq.cent);
-        HIPCHK(c, hipGetLastError());
-      }
-    }
-    HIPCHK(c, hipMemcpyAsync(out + r * c->dim, pq.rot ? d_x.p : d_y.p, static_cast<size_t>(nr) * c->dim * 4, hipMemcpyDeviceToHost, c->stream));
+    const float* xhat = nullptr;
+    if (nvdb_status st = reconstruct_slab(c, pq, static_cast<uint32_t>(row0 + r), nr, d_y.as<float>(), d_x.as<float>(), &xhat)) return st;
+    HIPCHK(c, hipMemcpyAsync(out + r * c->dim, xhat, static_cast<size_t>(nr) * c->dim * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_pq_set_metric(nvdb_hip_ctx* c, uint32_t metric) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (metric > 1u) return fail(c, NVDB_ERR_INVALID, "pq_set_metric: metric must be 0 (dot product) or 1 (squared L2)");
+  if (metric == 0u && !c->pq) return NVDB_OK;                          // (the default already)
+  if (nvdb_status st = pq_args(c, "pq_set_metric")) return st;
+  PqState& pq = *c->pq;
+  if (metric == pq.metric) return NVDB_OK;
+  if (metric == 0u) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(pq.half_norm);
+    pq.half_norm = nullptr;
+    pq.metric = 0u;
+    return NVDB_OK;
+  }
+  float* h = nullptr;
+  if (nvdb_status st = pq_half_norms(c, "pq_set_metric", &h)) return st;
+  pq.half_norm = h;
+  pq.metric = 1u;
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_pq_metric(nvdb_hip_ctx* c, uint32_t* metric) {
+  if (!c) return NVDB_ERR_INVALID;
+  if (!metric) return fail(c, NVDB_ERR_INVALID, "pq_metric: null output");
+  *metric = c->pq ? c->pq->metric : 0u;
+  return NVDB_OK;
+}
+
+nvdb_status nvdb_hip_pq_norms(nvdb_hip_ctx* c, uint64_t row0, uint64_t nrows, float* out) {
+  if (nvdb_status st = pq_args(c, "pq_norms")) return st;
+  if (!c->pq->metric) return fail(c, NVDB_ERR_INVALID, "pq_norms: the metric is not squared L2: nvdb_hip_pq_set_metric");
+  if (row0 > c->n || nrows > c->n - row0) return fail(c, NVDB_ERR_INVALID, "pq_norms: row0 + nrows > n");
+  if (nrows == 0) return NVDB_OK;
+  if (!out) return fail(c, NVDB_ERR_INVALID, "pq_norms: null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(out, c->pq->half_norm + row0, nrows * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (uint64_t i = 0; i < nrows; ++i) out[i] = out[i] + out[i];       // n = h + h: the halving is undone exactly (short of a subnormal n)
   return NVDB_OK;
 }
 

@@ -151,4 +151,20 @@ constexpr uint32_t pq4_lut_batch(uint32_t M, uint64_t budget_bytes) {
   return b < 1 ? 1u : b > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(b);
 }
 
+// ---- the L2 metric (nvdb_hip_pq_set_metric, kernels_pq_l2.h): h[r] = |xhat_r|^2 / 2, one f32 per row beside the codes
+// h is allocated as the codes are -- one hipMalloc outside every budget option, a failure leaves the metric where it was --: 4
+// bytes per row beside M or M / 2 of codes, 40 MB at 10M rows
+constexpr uint64_t pq_norm_bytes(uint64_t n) { return n * 4; }
+constexpr uint32_t PQ_NORM_THREADS = 256;
+// rows a lane of pq_norms_kernel owns (so many accumulators): a tile stages the whole codebook, dim KB, through LDS, so its cost
+// per row falls with the tile -- at 4 a tile is 1024 rows and the staging 0.75 KB per row at dim 768, a third of pq_encode's
+// (its tiles are 256 rows); 8 would halve it again but leaves 10M rows only 1221 tiles for 256 CUs and doubles the tail
+constexpr uint32_t PQ_NORM_ROWS_PER_LANE = 4;
+constexpr uint32_t PQ_NORM_TILE = PQ_NORM_THREADS * PQ_NORM_ROWS_PER_LANE;
+// floats between two codewords of the LDS image: ODD, so that 64 lanes on 64 different codewords hit 64 different banks
+constexpr uint32_t pq_norm_stride(uint32_t dsub) { return dsub | 1u; }
+// columns per LDS chunk of pq_rownorm_kernel and the floats between two of its rows (odd again: lane = row walks its row)
+constexpr uint32_t PQ_ROWNORM_COLS = 32;
+constexpr uint32_t PQ_ROWNORM_LD = PQ_ROWNORM_COLS + 1;
+
 }  // namespace nvdbhip

@@ -51,6 +51,7 @@ EXPORTS = [
     "nvdb_hip_ivf_pq_build_opq", "nvdb_hip_ivf_pq_train_opq",
     "nvdb_hip_pq4_build", "nvdb_hip_ivf_pq4_build", "nvdb_hip_pq_bits",
     "nvdb_hip_pq4_train", "nvdb_hip_ivf_pq4_train",
+    "nvdb_hip_pq_set_metric", "nvdb_hip_pq_metric", "nvdb_hip_pq_norms", "nvdb_hip_ivf_pq_set_metric",
 ]
 # only in libnvdb_hip_dev.so; the product library must NOT export them (tests/test_cabi_cpu.py)
 DEV_EXPORTS = ["nvdb_hip_debug_clock", "nvdb_hip_debug_clock_i8", "nvdb_permuted_tile", "nvdb_hip_debug_tile_ranges",
@@ -247,6 +248,10 @@ def _bind(L, dev):
     L.nvdb_hip_ivf_pq4_train.argtypes = [vp, vp, u32, u32, u64, u64, vp, vp, vp, u32]
     L.nvdb_hip_pq_bits.argtypes = [vp, C.POINTER(u32)]
     L.nvdb_hip_pq_reconstruct.argtypes = [vp, u64, u64, vp]
+    L.nvdb_hip_pq_set_metric.argtypes = [vp, u32]
+    L.nvdb_hip_ivf_pq_set_metric.argtypes = [vp, u32]
+    L.nvdb_hip_pq_metric.argtypes = [vp, C.POINTER(u32)]
+    L.nvdb_hip_pq_norms.argtypes = [vp, u64, u64, vp]
     L.nvdb_hip_pq_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
     L.nvdb_hip_pq_download_codes.argtypes = [vp, u64, u64, vp]
     L.nvdb_hip_pq_search_partitions.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp, C.POINTER(Timing)]
@@ -403,6 +408,9 @@ def _rotation_arg(rotation, dim):
     if rotation.shape != (dim, dim):
         raise ValueError("rotation must be [dim, dim]")
     return rotation
+
+
+_PQ_METRICS = ("dot", "l2")                         # nvdb_hip_pq_set_metric's values by index (another name: ValueError)
 
 
 def _pq_build(owner, plain, resid, opq, pq4, dim, codebooks, residual, rotation):
@@ -830,6 +838,26 @@ class HipContext:
         self._chk(self.lib.nvdb_hip_pq_reconstruct(self.h, row0, nrows, out.ctypes.data if out.size else None))
         return out
 
+    def pq_set_metric(self, metric):
+        """What the PQ searches rank by: "dot" (the default after every build) or "l2" -- the squared L2 distance to the row's
+        reconstruction; the searches then return distances, ascending, padding +inf.  "l2" computes half the squared norm of every
+        row's reconstruction once; whatever frees or replaces the shadow returns the metric to "dot"."""
+        self._chk(self.lib.nvdb_hip_pq_set_metric(self.h, _PQ_METRICS.index(metric)))
+
+    def pq_metric(self):
+        """The metric in force: "dot" or "l2"."""
+        r = C.c_uint32()
+        self._chk(self.lib.nvdb_hip_pq_metric(self.h, C.byref(r)))
+        return _PQ_METRICS[r.value]
+
+    def pq_norms(self, row0=0, nrows=None):
+        """|xhat_r|^2 of resident rows [row0, row0 + nrows) as the L2 scan uses them -> [nrows] f32; needs the "l2" metric."""
+        if nrows is None:
+            nrows = self.corpus_info()["n"] - row0
+        out = np.zeros(max(nrows, 0), dtype=np.float32)
+        self._chk(self.lib.nvdb_hip_pq_norms(self.h, row0, nrows, out.ctypes.data if out.size else None))
+        return out
+
     def pq_info(self):
         """dict(M, dsub, code_bytes); all 0 without codes."""
         M, dsub, nbytes = C.c_uint32(), C.c_uint32(), C.c_uint64()
@@ -1117,6 +1145,18 @@ class IvfIndex:
     def pq_reconstruct(self, row0=0, nrows=None):
         """HipContext.pq_reconstruct over the list-ordered rows (positions, not source ids)."""
         return self.ctx.pq_reconstruct(row0, nrows)
+
+    def pq_set_metric(self, metric):
+        """HipContext.pq_set_metric on the index's context."""
+        self._chk(self.lib.nvdb_hip_ivf_pq_set_metric(self.h, _PQ_METRICS.index(metric)))
+
+    def pq_metric(self):
+        """HipContext.pq_metric of the index's context."""
+        return self.ctx.pq_metric()
+
+    def pq_norms(self, row0=0, nrows=None):
+        """HipContext.pq_norms over the list-ordered rows (positions, not source ids)."""
+        return self.ctx.pq_norms(row0, nrows)
 
     def pq_search(self, queries, R, nprobe, want_probe=False):
         """The R best PQ scores of the nprobe best lists -> (ids, scores, counts[, probe]); equal scores by (partition, original id)."""

@@ -42,6 +42,15 @@ above: copy a keeps the 8-bit shadow, copy b takes the two 4-bit ones in turn.  
 wall time of the builds, the fp64 quantisation error, and, alternating the two copies call by call, ivf_pq_search / ivf_pq_refine
 times and recall@10.
 
+    python tools_dev/bench_pq.py [the same arguments] --l2 [--clustered] [--scaled]
+
+The SAME shadow under both metrics (pq_set_metric), one index, alternating "dot" and "l2" call by call in one process: 8-bit at M,
+4-bit at 2 M and at M.  Reports ivf_pq_search / ivf_pq_refine times and recall@10 of the fused refine under both, against the exact
+L2 top-10 (--scaled: computed here in numpy over the rows as f32 -- on rows of unequal length a dot-product shortlist would miss --,
+else the refine over the flat scan's 1024 best dot products as above), and the
+wall time of pq_set_metric("l2") beside pq_build for the plain, residual and rotated (a random orthonormal matrix) kinds at M.
+--scaled multiplies row r by 0.5 + (r % 7) / 4 (the rows are then generated on the host).
+
     python tools_dev/bench_pq.py <rows> <dim> <f16|f32> 0 <M> --train
 
 The trainers alone over every one of <rows> synthetic rows: seconds per Lloyd iteration of pq_train(bits=4) and pq_train(bits=8) at
@@ -349,6 +358,83 @@ def main_bits(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, clustered
     b.close()
 
 
+def main_l2(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, clustered, scaled):
+    seed, K, rounds = 20240613, 10, 4
+    out = dict(mode="l2", corpus=("clustered" if clustered else "synthetic") + (" scaled" if scaled else ""), rows=rows, dim=dim, dtype=dname, nlist=nlist,
+               M=M, batch=batch, calls=calls, warmup=warmup, K=K)
+    src = nvdb_amd.HipContext(0)
+    rs = np.random.RandomState(11)
+    if clustered or scaled:                                             # rows made on the host
+        centres = rs.standard_normal((max(nlist // 4, 1), dim)).astype(np.float32)
+        x = np.empty((rows, dim), dtype=np.float16 if dtype == nvdb_amd.DT_F16 else np.float32)
+        for i in range(0, rows, 65536):
+            n = min(65536, rows - i)
+            if clustered:                                               # main_residual's centre + noise rows, unit length
+                v = centres[rs.randint(len(centres), size=n)] + 0.35 * rs.standard_normal((n, dim)).astype(np.float32)
+                v /= np.linalg.norm(v, axis=1, keepdims=True)
+            else:
+                v = nvdb_amd.synth_rows_f32(seed, i, n, dim)
+            x[i:i + n] = v * (0.5 + (np.arange(i, i + n) % 7) / 4).astype(np.float32)[:, None] if scaled else v
+        src.upload_corpus(x.view(np.uint16) if dtype == nvdb_amd.DT_F16 else x, dtype)
+    else:
+        src.generate_corpus(seed, rows, dim, dtype)
+    q = np.ascontiguousarray(x[rs.choice(rows, batch, replace=False)].astype(np.float32) + 0.1 * rs.standard_normal((batch, dim)).astype(np.float32)) if clustered \
+        else np.ascontiguousarray(nvdb_amd.synth_rows_f32(seed + 1, 0, batch, dim))
+    if scaled:
+        # exact L2 top-K in numpy, |x|^2 - 2 q.x block by block (|q|^2 orders nothing): rows of unequal length, so no dot-product shortlist
+        best_d, best_i = np.full((batch, K), np.inf, dtype=np.float32), np.zeros((batch, K), dtype=np.int64)
+        for i in range(0, rows, 65536):
+            xb = x[i:i + 65536].astype(np.float32)
+            d = np.concatenate([best_d, (xb * xb).sum(1)[None] - 2.0 * q @ xb.T], axis=1)
+            ids = np.concatenate([best_i, np.broadcast_to(np.arange(i, i + len(xb)), (batch, len(xb)))], axis=1)
+            keep = np.argpartition(d, K - 1, axis=1)[:, :K]
+            best_d, best_i = np.take_along_axis(d, keep, 1), np.take_along_axis(ids, keep, 1)
+        want = best_i.astype(np.uint64)
+    else:                                                               # rows of one length: the refine over the flat scan's 1024 best dot products, as above
+        fid, _ = src.search_batch(q, 1024)
+        want = src.refine_l2_topk(q, fid.astype(np.uint32), K)[0].astype(np.uint64)
+    x = None
+    cents = src.train_centroids(nlist, 2, seed, max_train_rows=262144)
+    ix = nvdb_amd.IvfIndex(src, cents)
+    src.close()
+    A = np.ascontiguousarray(np.linalg.qr(rs.standard_normal((dim, dim)))[0].astype(np.float32))
+    for kind, residual, rot in (("plain", False, None), ("residual", True, None), ("rotated", False, A)):
+        cb = ix.pq_train(M, rounds, 7, max_train_rows=20000, residual=residual, rotation=rot)
+        build_s, build_all = median_s(lambda: ix.pq_build(cb, residual=residual, rotation=rot), reps=3)
+
+        def to_l2():
+            ix.pq_set_metric("dot"); t0 = time.perf_counter(); ix.pq_set_metric("l2"); return time.perf_counter() - t0
+        to_l2()
+        ts = [to_l2() for _ in range(3)]
+        out[f"set_metric {kind}"] = dict(pq_build_s=build_s, pq_build_all_s=build_all, set_metric_l2_s=float(np.median(ts)), set_metric_l2_all_s=ts)
+        print(f"{kind:8s} 8-bit M={M}: pq_build {build_s:.3f} s | pq_set_metric('l2') {np.median(ts):.4f} s (medians of 3: {' '.join(f'{t:.4f}' for t in ts)})")
+
+    def under(metric, f):
+        def call():
+            ix.pq_set_metric(metric)                                    # (timed apart from f: see set_metric above; the toggle is not what a user repeats)
+            t0 = time.perf_counter(); r = f(); return time.perf_counter() - t0, r
+        return call
+
+    for bits, m in ((8, M), (4, 2 * M), (4, M)):
+        ix.pq_build(ix.pq_train(m, rounds, 7, max_train_rows=262144, bits=bits))
+        for nprobe in (8, 32):
+            for R in (100, 1024):
+                key, row = f"pq{bits}_M{m} nprobe={nprobe} R={R}", {}
+                for name, f in (("search", lambda: ix.pq_search(q, R, nprobe)), ("refine", lambda: ix.pq_refine(q, K, R, nprobe))):
+                    dot, l2 = under("dot", f), under("l2", f)
+                    for _ in range(warmup):
+                        dot(); l2()
+                    td, tl = zip(*[(dot()[0] * 1e3, l2()[0] * 1e3) for _ in range(calls)])
+                    row.update({f"dot_{name}_ms": float(np.median(td)), f"l2_{name}_ms": float(np.median(tl)), f"{name}_spread": [min(td), max(td), min(tl), max(tl)]})
+                row.update(recall10_dot=recall(under("dot", lambda: ix.pq_refine(q, K, R, nprobe))()[1][0], want),
+                           recall10_l2=recall(under("l2", lambda: ix.pq_refine(q, K, R, nprobe))()[1][0], want))
+                out[key] = row
+                print(f"{key:32s}: ivf_pq_search dot {row['dot_search_ms']:8.3f} ms | l2 {row['l2_search_ms']:8.3f} ms || ivf_pq_refine dot {row['dot_refine_ms']:8.3f} ms | "
+                      f"l2 {row['l2_refine_ms']:8.3f} ms || recall@10 dot {row['recall10_dot']:.4f}, l2 {row['recall10_l2']:.4f}")
+    print(json.dumps(out))
+    ix.close()
+
+
 def main():
     argv = [x for i, x in enumerate(sys.argv[1:]) if not (i and sys.argv[i] == "--bits")]       # (--bits takes a value)
     if "--bits" in sys.argv and sys.argv[sys.argv.index("--bits") + 1:][:1] != ["4"]:
@@ -366,6 +452,8 @@ def main():
     warmup = int(a[7]) if len(a) > 7 else 2
     if "--train" in flags:
         return main_train(rows, dim, dname, dtype, M)
+    if "--l2" in flags:
+        return main_l2(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, "--clustered" in flags, "--scaled" in flags)
     if "--bits" in flags:
         return main_bits(rows, dim, dname, dtype, nlist, M, batch, calls, warmup, "--clustered" in flags)
     if "--opq" in flags:
